@@ -11,9 +11,15 @@ of frames, inputs already resident in HBM.  ``--gpus N``:
 
 Weak scaling is the headline (every rank analyses its own 1000 frames per step); with more than one
 rank every step ends with the path's only collective, the RCCL all-gather of the result records,
-read straight from the engine's device buffer, inside the timed region.  The same run then times
+read straight from the engine's device buffer, inside the timed region.  With ``--full`` the same run then times
 strong scaling (ONE 1000-frame trajectory split over the ranks) and reports it beside the headline.
 Prints ONE JSON line on rank 0.
+
+A plain run measures the headline only: set-up, the W warm-up steps, the K timed steps (``ms_per_step``) and the
+line.  ``--full`` adds everything else the line can carry, each measured after the headline: the CPU baselines
+(before the GPU starts), strong scaling and BASELINE configs 4 and 5 across the ranks, the roofline with its kernel
+timings and committed profile summaries, the one-GPU strong-scaling model and the secondary shapes and end-to-end
+figures.  ``--dump-outputs DIR`` writes the records of the last timed step (see ``dump_outputs``).
 """
 from __future__ import annotations
 
@@ -30,8 +36,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 # the pipeline keeps several kernels in flight on separate streams: ask the HIP runtime for enough
-# hardware queues BEFORE anything (torch included) initialises it
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
+# hardware queues BEFORE anything (torch included) initialises it -- a smaller value already in the
+# environment is raised, or the headline would time single launches instead of the pipeline
+BENCH_HW_QUEUES = 12
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+except ValueError:
+    _queues = 0
+if _queues < BENCH_HW_QUEUES:
+    os.environ["GPU_MAX_HW_QUEUES"] = str(BENCH_HW_QUEUES)
 
 FRAMES = 1000
 N_ATOMS = 168
@@ -599,6 +612,27 @@ def _serial_kernel_ms():
     return None, None
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+DUMP_SEED = 0              # ... and the seed of the sample of units it keeps when the records are larger
+
+
+def dump_outputs(directory, records, budget=DUMP_BYTES, seed=DUMP_SEED):
+    """The records of the timed path's last step -- what ``Resident.download`` hands a caller (on N > 1 ranks: the
+    gathered records of every rank, rank order) -- as ``directory/<field>.npy`` in float64, one file per field of
+    ``UNIT_OUT_DTYPE`` (integer fields converted exactly), plus ``unit_index.npy``: the units the rows belong to.
+    Past ``budget`` bytes a fixed, seeded sample of units is kept, in unit order."""
+    names = records.dtype.names
+    per_unit = 8 * (1 + sum(int(np.prod(records.dtype[n].shape, dtype=np.int64)) for n in names))
+    keep = np.arange(len(records))
+    if len(records) * per_unit > budget:
+        rng = np.random.default_rng(seed)
+        keep = np.sort(rng.choice(len(records), size=budget // per_unit, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "unit_index.npy"), keep.astype(np.float64))
+    for name in names:
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(records[name][keep], dtype=np.float64))
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -628,6 +662,12 @@ def main():
     ap.add_argument("--multi-frames", type=int, default=10000,
                     help="N > 1: frames of the config-4 periodic trajectory, all ranks together (BASELINE: 10k frames x 8 cages)")
     ap.add_argument("--no-strong", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: CPU baselines, strong scaling, configs 4 and 5 across the ranks, the "
+                         "roofline and kernel timings, the secondary shapes and end-to-end figures (the --no-* "
+                         "options above leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step as DIR/<field>.npy (float64)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -638,7 +678,7 @@ def main():
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
 
     cpu = None
-    if rank == 0 and world_env == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_env == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline()              # before the GPU is initialised (see above)
 
     import torch
@@ -793,6 +833,8 @@ def main():
             mine = allrec[: args.frames]
             gather_ok = bool(len(allrec) == world * args.frames and mine.tobytes() == out.tobytes()
                              and (allrec["status"] == 0).all() and (allrec["n_atoms"] == N_ATOMS).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out if gather is None else allrec)
 
     def max_over_ranks(seconds):
         if dist is None:
@@ -803,7 +845,7 @@ def main():
 
     # ---- strong scaling: ONE trajectory of `frames` frames split over the ranks -----------------------
     strong = None
-    if dist is not None and not args.no_strong:
+    if args.full and dist is not None and not args.no_strong:
         per = -(-args.frames // world)
         lo, hi = T.shard_range(args.frames, rank, world)
         # the same decision on EVERY rank (a short last block would leave its rank out of the collectives
@@ -822,7 +864,7 @@ def main():
 
     # ---- BASELINE configs 4 and 5 across the ranks (N > 1 only; every rank takes part) ------------------
     multi = None
-    if dist is not None and world > 1 and not args.no_secondary:
+    if args.full and dist is not None and world > 1 and not args.no_secondary:
         res.sync()
         try:
             multi = secondary_multi(ctx, vdw, mass, dist, rank, world, local_rank, backend, tdev, barrier,
@@ -833,87 +875,6 @@ def main():
     if rank == 0:
         ms_step = 1e3 * elapsed / args.steps
         value = world * args.frames * args.steps / elapsed
-        # kernel duration measured with HIP events on the launch stream
-        k_ms = res.time_launches(max(3, args.steps))
-        # one launch on its own (no overlap with a neighbour): the latency of a single batch
-        lat = []
-        for _ in range(5):
-            res.sync()
-            t1 = time.perf_counter()
-            res.launch()
-            res.sync()
-            lat.append(1e3 * (time.perf_counter() - t1))
-        single_ms = float(np.median(lat))
-        units_per_s = args.frames / (k_ms * 1e-3)
-        achieved_gbs = units_per_s * ALGO_BYTES_PER_UNIT / 1e9
-        achieved_tf = units_per_s * ALGO_FLOP_PER_UNIT / 1e12
-        tj, tname = _load_profile(TRAFFIC_FILES)
-        traffic = None
-        if tj is not None:
-            try:
-                traffic = tj["per_launch_bytes"] * (args.frames / tj["units_per_launch"])
-            except (KeyError, TypeError, ZeroDivisionError):
-                traffic = None
-        # VALU issue utilisation from the profiled wave-level instruction count (committed summary) and
-        # the kernel time measured in this run: instructions x 4 SIMD cycles / (SIMDs x clock x time)
-        cj, cname = _load_profile(COUNTER_FILES)
-        valu_issue = None
-        if cj is not None:
-            try:
-                per_unit = cj["per_launch"]["SQ_INSTS_VALU"] / cj["units_per_launch"]
-                vi = cj["valu_issue"]
-                valu_issue = {"wave_instructions_per_launch": per_unit * args.frames,
-                              "frac": per_unit * args.frames * vi["simd_cycles_per_wave_instruction"]
-                                      / (vi["simds"] * vi["clock_ghz"] * 1e9 * k_ms * 1e-3),
-                              "source": f"static: profiles/{cname} (rocprofv3 --pmc SQ_INSTS_VALU), not measured by this run",
-                              "provenance": _provenance_of(cname, cj)}
-            except (KeyError, TypeError, ZeroDivisionError):
-                valu_issue = None
-        # what the vector ALUs really execute in double precision (rocprofv3 --pmc SQ_INSTS_VALU_{FMA,MUL,ADD,TRANS}_F64, a
-        # committed summary like the two above): executed flop per launch and the fraction of the FP64 vector peak that is,
-        # at the kernel time measured in this run -- beside `frac`, which prices the ALGORITHMIC 2e7 flop per unit
-        fj, fname = _load_profile(FP64_FILES)
-        executed = None
-        if fj is not None:
-            try:
-                ex_launch = fj["executed_fp64_flop_per_unit"] * args.frames
-                executed = {"executed_fp64_flop_per_launch": ex_launch,
-                            "frac_executed": ex_launch / (k_ms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
-                            "executed_over_algorithmic": ex_launch / (ALGO_FLOP_PER_UNIT * args.frames),
-                            "by_kernel": {k: {"executed_fp64_flop": v["executed_fp64_flop"] * args.frames / fj["units_per_launch"],
-                                              "fp64_share_of_valu": v.get("fp64_share_of_valu")} for k, v in fj["kernels"].items()},
-                            "what": "(2 FMA + MUL + ADD + TRANS) F64 wave instructions x 64 lanes (inactive lanes included): what the "
-                                    "ALUs are occupied with in double precision -- pruned evaluations do not appear, address "
-                                    "arithmetic, integer work and the single-precision screens are not counted",
-                            "source": f"static: profiles/{fname} (rocprofv3 --pmc), not measured by this run",
-                            "provenance": _provenance_of(fname, fj)}
-            except (KeyError, TypeError, ZeroDivisionError):
-                executed = None
-        # per launch of the pipeline, each on its own (no other launch in flight): HIP events on the
-        # stream the kernel runs on; profiles/r02_serial_kernel_stats.csv is rocprofv3's view of the same
-        # Two clocks per launch: `ms` = rocprofv3's average kernel duration of ONE analysis at a time (committed summary,
-        # static: first wave to last wave of the kernel -- the figure the fractions use); `ms_events_live` = HIP events
-        # on the launch's own stream in THIS run, which also contain the time the launch sits behind its gate and waits
-        # for SIMD slots.
-        per_kernel = None
-        try:
-            st = res.stage_times()
-            prof, prof_name = _serial_kernel_ms()
-            per_kernel = []
-            if "average" not in st:           # (the average diameter ran inside the window teams)
-                st = {("windows+average" if k == "windows" else k): v for k, v in st.items()}
-            for name, ms_live in st.items():
-                fl = ALGO_FLOP_BY_KERNEL[name] * args.frames
-                ms = prof.get(name) if (prof and args.frames == FRAMES) else None
-                entry = {"kernel": name, "ms": ms if ms is not None else ms_live, "ms_events_live": ms_live,
-                         "ms_source": (f"static: profiles/{prof_name} (rocprofv3 --kernel-trace --stats, one analysis at a time)"
-                                       if ms is not None else "HIP events of this run (no committed profile for this shape)"),
-                         "algorithmic_flop_per_launch": fl}
-                entry["achieved_tflops"] = fl / (entry["ms"] * 1e-3) / 1e12
-                entry["frac_fp64_valu"] = entry["achieved_tflops"] / FP64_VECTOR_PEAK_TFLOPS
-                per_kernel.append(entry)
-        except Exception:  # noqa: BLE001 - e.g. a context that runs single launches has no per-launch times
-            per_kernel = None
         line = {
             "metric": "trajectory frames/sec full_analysis (pore+windows), CC3 1k-frame",
             "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -931,7 +892,6 @@ def main():
                        "retries": {"this_context": ctx.retries, "process": _lib.retries_total(),
                                    "what": "analyses repeated after PW_E_TIMEOUT (a launch gave up waiting for another); 0 on a healthy device"},
                        "successive_steps_overlap": bool(ctx.pipelined), "pipelined": bool(ctx.pipelined), "gate_timeouts": ctx.gate_timeouts,
-                       "single_step_latency_ms": single_ms,
                        "windows_eq_4": int((out["n_windows"] == 4).sum()),
                        "ms_per_step_by_rank": {"min": 1e3 * min(weak_per_rank) / args.steps,
                                                "max": 1e3 * max(weak_per_rank) / args.steps},
@@ -941,35 +901,119 @@ def main():
                        "world_size_env": world_env,
                        "ranks": ranks_info,
                        "distinct_gpus": len({(r["host"], r["pci_bus_id"]) for r in ranks_info})},
-            "roofline": {"bound": "fp64_valu", "achieved": achieved_tf, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved_tf / FP64_VECTOR_PEAK_TFLOPS,
-                         "algorithmic_flop_per_launch": ALGO_FLOP_PER_UNIT * args.frames,
-                         "executed_fp64_flop_per_launch": None if executed is None else executed["executed_fp64_flop_per_launch"],
-                         "frac_executed": None if executed is None else executed["frac_executed"],
-                         "executed": executed,
-                         "kernel": "pw_analyse_kernel x 2 (one analysis = optimiser chains | window search with the average-diameter stage, concurrent)",
-                         "kernel_ms": k_ms,
-                         "kernel_ms_note": "HIP events on the launch streams around back-to-back analyses / their number: the steady-state "
-                                           "period (successive analyses overlap); config.single_step_latency_ms is one analysis on its own",
-                         "frac_single_analysis": (args.frames * ALGO_FLOP_PER_UNIT / (single_ms * 1e-3) / 1e12) / FP64_VECTOR_PEAK_TFLOPS,
-                         "per_kernel": per_kernel,
-                         "hbm": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": achieved_gbs / HBM_PEAK_GBS,
-                                 "algorithmic_bytes_per_launch": ALGO_BYTES_PER_UNIT * args.frames},
-                         "traffic": traffic,
-                         "traffic_note": None if tname is None else
-                         f"static: fabric bytes per launch from rocprofv3 PMC (profiles/{tname}), not measured by this run; "
-                         "includes Infinity-Cache hits on the re-used per-team workspaces",
-                         "traffic_provenance": _provenance_of(tname, tj),
-                         "valu_issue_measured": valu_issue,
-                         "profile_inputs": {
-                             "what": "the static inputs of this line (traffic, VALU issue, per_kernel[*].ms) and the tree they were "
-                                     "measured on; stale = the sources under pywindow_amd/csrc have changed since",
-                             "csrc_sha16_now": _csrc_sha16(),
-                             "traffic": _provenance_of(tname, tj), "counters": _provenance_of(cname, cj),
-                             "fp64_counters": _provenance_of(fname, fj),
-                             "serial_kernel_stats": _provenance_of(prof_name if per_kernel else None)}},
         }
+        if args.full:
+            # kernel duration measured with HIP events on the launch stream
+            k_ms = res.time_launches(max(3, args.steps))
+            # one launch on its own (no overlap with a neighbour): the latency of a single batch
+            lat = []
+            for _ in range(5):
+                res.sync()
+                t1 = time.perf_counter()
+                res.launch()
+                res.sync()
+                lat.append(1e3 * (time.perf_counter() - t1))
+            single_ms = float(np.median(lat))
+            units_per_s = args.frames / (k_ms * 1e-3)
+            achieved_gbs = units_per_s * ALGO_BYTES_PER_UNIT / 1e9
+            achieved_tf = units_per_s * ALGO_FLOP_PER_UNIT / 1e12
+            tj, tname = _load_profile(TRAFFIC_FILES)
+            traffic = None
+            if tj is not None:
+                try:
+                    traffic = tj["per_launch_bytes"] * (args.frames / tj["units_per_launch"])
+                except (KeyError, TypeError, ZeroDivisionError):
+                    traffic = None
+            # VALU issue utilisation from the profiled wave-level instruction count (committed summary) and
+            # the kernel time measured in this run: instructions x 4 SIMD cycles / (SIMDs x clock x time)
+            cj, cname = _load_profile(COUNTER_FILES)
+            valu_issue = None
+            if cj is not None:
+                try:
+                    per_unit = cj["per_launch"]["SQ_INSTS_VALU"] / cj["units_per_launch"]
+                    vi = cj["valu_issue"]
+                    valu_issue = {"wave_instructions_per_launch": per_unit * args.frames,
+                                  "frac": per_unit * args.frames * vi["simd_cycles_per_wave_instruction"]
+                                          / (vi["simds"] * vi["clock_ghz"] * 1e9 * k_ms * 1e-3),
+                                  "source": f"static: profiles/{cname} (rocprofv3 --pmc SQ_INSTS_VALU), not measured by this run",
+                                  "provenance": _provenance_of(cname, cj)}
+                except (KeyError, TypeError, ZeroDivisionError):
+                    valu_issue = None
+            # what the vector ALUs really execute in double precision (rocprofv3 --pmc SQ_INSTS_VALU_{FMA,MUL,ADD,TRANS}_F64, a
+            # committed summary like the two above): executed flop per launch and the fraction of the FP64 vector peak that is,
+            # at the kernel time measured in this run -- beside `frac`, which prices the ALGORITHMIC 2e7 flop per unit
+            fj, fname = _load_profile(FP64_FILES)
+            executed = None
+            if fj is not None:
+                try:
+                    ex_launch = fj["executed_fp64_flop_per_unit"] * args.frames
+                    executed = {"executed_fp64_flop_per_launch": ex_launch,
+                                "frac_executed": ex_launch / (k_ms * 1e-3) / 1e12 / FP64_VECTOR_PEAK_TFLOPS,
+                                "executed_over_algorithmic": ex_launch / (ALGO_FLOP_PER_UNIT * args.frames),
+                                "by_kernel": {k: {"executed_fp64_flop": v["executed_fp64_flop"] * args.frames / fj["units_per_launch"],
+                                                  "fp64_share_of_valu": v.get("fp64_share_of_valu")} for k, v in fj["kernels"].items()},
+                                "what": "(2 FMA + MUL + ADD + TRANS) F64 wave instructions x 64 lanes (inactive lanes included): what the "
+                                        "ALUs are occupied with in double precision -- pruned evaluations do not appear, address "
+                                        "arithmetic, integer work and the single-precision screens are not counted",
+                                "source": f"static: profiles/{fname} (rocprofv3 --pmc), not measured by this run",
+                                "provenance": _provenance_of(fname, fj)}
+                except (KeyError, TypeError, ZeroDivisionError):
+                    executed = None
+            # per launch of the pipeline, each on its own (no other launch in flight): HIP events on the
+            # stream the kernel runs on; profiles/r02_serial_kernel_stats.csv is rocprofv3's view of the same
+            # Two clocks per launch: `ms` = rocprofv3's average kernel duration of ONE analysis at a time (committed summary,
+            # static: first wave to last wave of the kernel -- the figure the fractions use); `ms_events_live` = HIP events
+            # on the launch's own stream in THIS run, which also contain the time the launch sits behind its gate and waits
+            # for SIMD slots.
+            per_kernel = None
+            try:
+                st = res.stage_times()
+                prof, prof_name = _serial_kernel_ms()
+                per_kernel = []
+                if "average" not in st:           # (the average diameter ran inside the window teams)
+                    st = {("windows+average" if k == "windows" else k): v for k, v in st.items()}
+                for name, ms_live in st.items():
+                    fl = ALGO_FLOP_BY_KERNEL[name] * args.frames
+                    ms = prof.get(name) if (prof and args.frames == FRAMES) else None
+                    entry = {"kernel": name, "ms": ms if ms is not None else ms_live, "ms_events_live": ms_live,
+                             "ms_source": (f"static: profiles/{prof_name} (rocprofv3 --kernel-trace --stats, one analysis at a time)"
+                                           if ms is not None else "HIP events of this run (no committed profile for this shape)"),
+                             "algorithmic_flop_per_launch": fl}
+                    entry["achieved_tflops"] = fl / (entry["ms"] * 1e-3) / 1e12
+                    entry["frac_fp64_valu"] = entry["achieved_tflops"] / FP64_VECTOR_PEAK_TFLOPS
+                    per_kernel.append(entry)
+            except Exception:  # noqa: BLE001 - e.g. a context that runs single launches has no per-launch times
+                per_kernel = None
+            line["config"]["single_step_latency_ms"] = single_ms
+            roofline = {"bound": "fp64_valu", "achieved": achieved_tf, "peak": FP64_VECTOR_PEAK_TFLOPS, "unit": "TFLOP/s",
+                        "frac": achieved_tf / FP64_VECTOR_PEAK_TFLOPS,
+                        "algorithmic_flop_per_launch": ALGO_FLOP_PER_UNIT * args.frames,
+                        "executed_fp64_flop_per_launch": None if executed is None else executed["executed_fp64_flop_per_launch"],
+                        "frac_executed": None if executed is None else executed["frac_executed"],
+                        "executed": executed,
+                        "kernel": "pw_analyse_kernel x 2 (one analysis = optimiser chains | window search with the average-diameter stage, concurrent)",
+                        "kernel_ms": k_ms,
+                        "kernel_ms_note": "HIP events on the launch streams around back-to-back analyses / their number: the steady-state "
+                                          "period (successive analyses overlap); config.single_step_latency_ms is one analysis on its own",
+                        "frac_single_analysis": (args.frames * ALGO_FLOP_PER_UNIT / (single_ms * 1e-3) / 1e12) / FP64_VECTOR_PEAK_TFLOPS,
+                        "per_kernel": per_kernel,
+                        "hbm": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                "frac": achieved_gbs / HBM_PEAK_GBS,
+                                "algorithmic_bytes_per_launch": ALGO_BYTES_PER_UNIT * args.frames},
+                        "traffic": traffic,
+                        "traffic_note": None if tname is None else
+                        f"static: fabric bytes per launch from rocprofv3 PMC (profiles/{tname}), not measured by this run; "
+                        "includes Infinity-Cache hits on the re-used per-team workspaces",
+                        "traffic_provenance": _provenance_of(tname, tj),
+                        "valu_issue_measured": valu_issue,
+                        "profile_inputs": {
+                            "what": "the static inputs of this line (traffic, VALU issue, per_kernel[*].ms) and the tree they were "
+                                    "measured on; stale = the sources under pywindow_amd/csrc have changed since",
+                            "csrc_sha16_now": _csrc_sha16(),
+                            "traffic": _provenance_of(tname, tj), "counters": _provenance_of(cname, cj),
+                            "fp64_counters": _provenance_of(fname, fj),
+                            "serial_kernel_stats": _provenance_of(prof_name if per_kernel else None)}}
+            line["roofline"] = roofline
         if strong is not None:
             if "value" in strong:
                 # against `world` GPUs each as fast as this one analysing the whole trajectory on its own
@@ -986,7 +1030,7 @@ def main():
                 "is `value_strong` / `efficiency_strong` (`strong`: the same trajectory split into %d contiguous shards, the "
                 "gather of the records included).  A shard of a few hundred frames is bound by the latency of its slowest "
                 "optimiser chain, not by throughput (DESIGN.md section 5), so value_strong stays far below value." % (args.frames, world))
-        if world == 1:
+        if args.full and world == 1:
             # what strong scaling of the 1000-frame trajectory can reach: a rank's share analysed on this
             # GPU (ranks are independent; the gather is not in these numbers)
             model = {}
@@ -1007,7 +1051,7 @@ def main():
             line["strong_scaling_model_1gpu"] = model
         if multi is not None:
             line["secondary_multi"] = multi
-        if not args.no_secondary and world == 1:
+        if args.full and not args.no_secondary and world == 1:
             # (the headline above stands on its own: a secondary figure that fails is reported as such, not fatal)
             try:
                 line["secondary"] = secondary(ctx, vdw, mass)

@@ -1,3 +1,4 @@
+import os
 import pathlib
 import sys
 
@@ -6,6 +7,18 @@ import pytest
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 if str(ROOT) not in sys.path:
     sys.path.insert(0, str(ROOT))
+
+# The GPU tests assert the overlapped pipeline, whose ten streams need a hardware queue each (GPU_MAX_HW_QUEUES >= 10,
+# read when HIP starts).  The package only sets its 12 when the variable is absent, so a smaller value already in the
+# environment would leave every context on single launches: raise it here, before anything starts HIP.  The child
+# processes the tests start inherit it.
+PW_HW_QUEUES = 12
+try:
+    _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+except ValueError:
+    _queues = 0
+if _queues < PW_HW_QUEUES:
+    os.environ["GPU_MAX_HW_QUEUES"] = str(PW_HW_QUEUES)
 
 
 def pytest_configure(config):

@@ -207,7 +207,7 @@ def _run_bench_child(extra_env, gpus=2, frames=240, multi=None):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", str(gpus), "--steps", "3", "--warmup", "1",
-           "--frames", str(frames), "--no-cpu-baseline"]
+           "--frames", str(frames), "--full", "--no-cpu-baseline"]
     # multi = (units, frames): BASELINE configs 5 and 4 across the ranks at reduced size (bench.py: secondary_multi)
     cmd += ["--no-secondary"] if multi is None else ["--multi-units", str(multi[0]), "--multi-frames", str(multi[1])]
     proc = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)

@@ -5,7 +5,7 @@ o=gpurun_out/$tag
 mkdir -p $o
 timeout 1200 python -m pytest tests/test_gpu_distributed.py tests/test_gpu_api.py tests/test_zz_no_retries.py -m gpu -x -q > $o/gputest.log 2>&1
 grep -a "passed\|failed\|Error" $o/gputest.log | tail -5
-timeout 600 python bench.py --no-cpu-baseline > $o/bench.json 2> $o/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline > $o/bench.json 2> $o/bench.err
 python - <<P
 import json
 d = json.loads(open("$o/bench.json").read().strip().splitlines()[-1])
