@@ -25,9 +25,9 @@
 #include "../../include/pywindow_amd.h"
 #include "pw_host.hpp"
 #include <vector>
-// (no PW_TEAM_STATE_IN_LDS here: this file's stage functions serve kernels that keep their team state in LDS -- chains,
-// average diameter -- AND kernels that keep it on the stack -- the window search, whose out-of-line stage
-// function spills five times as much when its table of pointers is an LDS object: 269 against 55 scratch stores)
+// (the stage functions do not assume where the team state is: the chains keep it in LDS, the window search on its
+// stack -- its out-of-line stage function spills five times as much when its table of pointers is an LDS object: 269
+// against 55 scratch stores)
 #include "pw_unit.hpp"
 #include "pw_launch.hpp"
 
@@ -76,7 +76,6 @@ constexpr size_t PW_KERNEL_STATIC_LDS = 1024;
 
 constexpr unsigned MASK_ANY = 0xffffffffu;
 constexpr unsigned MASK_CHAINS = PW_STAGE_BASIC | PW_STAGE_OPT | PW_STAGE_MERGE;
-constexpr unsigned MASK_AVERAGE = PW_STAGE_AVG | PW_STAGE_MERGE | PW_STAGE_COM_ONLY;
 constexpr unsigned MASK_WINDOWS = PW_STAGE_WINDOWS | PW_STAGE_REUSE_OPT | PW_STAGE_MERGE | PW_STAGE_COM_ONLY;
 // ... and the window launch that runs the average-diameter stage as well (round 6: the pipeline's default)
 constexpr unsigned MASK_WINDOWS_AVG = MASK_WINDOWS | PW_STAGE_AVG;
@@ -106,27 +105,15 @@ __global__ void __launch_bounds__(256) pw_nb_build_kernel(unsigned* __restrict__
 
 // MASK: the stage bits this instantiation can execute (the run-time mask is ANDed with it), so
 // the launches of the pipeline carry only the code -- and the registers -- of their own stages
-// Register budget: two waves per SIMD (three for the average-diameter launch).  A one-wave-per-SIMD
+// Register budget: two waves per SIMD.  A one-wave-per-SIMD
 // build (amdgpu_waves_per_eu(1, 1): 256 VGPRs + AGPRs, no VGPR spills) was tried for the optimiser
 // chains and rejected: such a wave owns more than half of its SIMD's register file, so no wave of the
 // window launch (256 VGPRs) can share the SIMD with it, and sharing SIMDs between the launches is
 // what the pipeline lives on.  The spills that remain are outside the hot loops (0.2 % of the
 // chains' instructions, profiles/r02_*).
-#ifndef PW_A_PRIO
-#define PW_A_PRIO 3
-#endif
-#ifndef PW_OCC
-#define PW_OCC 2
-#endif
-#ifndef PW_OCC8
-#define PW_OCC8 1
-#endif
-#ifndef PW_OCC_A
-#define PW_OCC_A PW_OCC
-#endif
 // A batch whose coordinates are still arriving (pw_resident_stream_*): `ready` counts the units whose
 // coordinates are on the device.  The launches that read coordinates without going through the hand-off queue --
-// optimiser chains, average diameter -- take units in index order and wait (bounded) until theirs is there, so the
+// optimiser chains -- take units in index order and wait (bounded) until theirs is there, so the
 // analysis can be launched before the reader has decoded the first frame.  ready == nullptr: everything is there.
 __device__ inline bool wait_for_unit(const unsigned long long* ready, long u, int* error_flag, long long limit) {
     if (!ready) return true;
@@ -150,7 +137,7 @@ __device__ inline bool wait_for_unit(const unsigned long long* ready, long u, in
     return true;
 }
 template <int NW, unsigned MASK>
-__global__ void __launch_bounds__(NW * 64, NW == 8 ? PW_OCC8 : (MASK == PW_KERNEL_AVERAGE ? 3 : (MASK == MASK_CHAINS ? PW_OCC_A : PW_OCC)))
+__global__ void __launch_bounds__(NW * 64, 2)
 pw_analyse_kernel(long n_units, const long* __restrict__ atom_offset, const double* __restrict__ xyz,
                   const double* __restrict__ vdw, const double* __restrict__ mass, unsigned stages,
                   int nmax, int nrot, int nlb, int nframes, int lean, PwWsArgs wsa, unsigned long long* counter,
@@ -159,9 +146,8 @@ pw_analyse_kernel(long n_units, const long* __restrict__ atom_offset, const doub
                   const unsigned long long* __restrict__ ready, const unsigned char* __restrict__ tmpl) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     __shared__ long s_unit;
-    // the team's table of pointers and its parameters live in LDS (PW_TEAM_STATE_IN_LDS, pw_unit.hpp): the stage
-    // functions are out of line and take them by reference -- on the stack they were 600 bytes of scratch per
-    // lane that every look-up went through
+    // the chains' table of pointers and parameters live in LDS: the stage functions are out of line and take them by
+    // reference -- on the stack they were 600 bytes of scratch per lane that every look-up went through
     __shared__ UnitShared s_sh;
     __shared__ pw_params s_prm;
     static_assert(sizeof(UnitShared) + sizeof(pw_params) + 16 <= PW_KERNEL_STATIC_LDS, "static LDS of the analysis kernels");
@@ -169,7 +155,7 @@ pw_analyse_kernel(long n_units, const long* __restrict__ atom_offset, const doub
     // the optimiser chains are latency-bound and on the critical path: when one shares a SIMD
     // with a bulk wave of another launch it must win the issue arbitration
     if (role == PW_ROLE_PRODUCER) {
-        __builtin_amdgcn_s_setprio(PW_A_PRIO);
+        __builtin_amdgcn_s_setprio(3);
         if (threadIdx.x == 0) atomicAdd(&queue->started, 1);
     }
     TeamWorkspace* ws = (TeamWorkspace*)wsa.ws + blockIdx.x;
@@ -185,8 +171,8 @@ pw_analyse_kernel(long n_units, const long* __restrict__ atom_offset, const doub
         bind_workspace(ws, wsa, blockIdx.x, rsq_tab, team_slab_bytes(wsa.p_cap), team_adj_words(wsa.p_cap));
     }
     __syncthreads();
-    // chains and average diameter look their pointers up in LDS; the window search keeps them on its stack (see above)
-    constexpr bool STATE_IN_LDS = MASK == MASK_CHAINS || MASK == PW_KERNEL_AVERAGE;
+    // the chains look their pointers up in LDS; the window search keeps them on its stack (see above)
+    constexpr bool STATE_IN_LDS = MASK == MASK_CHAINS;
     UnitShared sh_stack;
     if (!STATE_IN_LDS) sh_stack.carve(lds, nmax, nrot, nlb, nframes, lean, wsa.p_cap);
     UnitShared& sh = STATE_IN_LDS ? (UnitShared&)s_sh : sh_stack;
@@ -215,9 +201,7 @@ pw_analyse_kernel(long n_units, const long* __restrict__ atom_offset, const doub
                         }
                         __builtin_amdgcn_s_sleep(32);
                         // (the producer gave up -- its units never arrived: nothing more will be published)
-#ifndef PW_NO_CONSUMER_ERROR_CHECK
                         if (__hip_atomic_load(&queue->error, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) break;
-#endif
                         // The limit is on time WITHOUT A PUBLICATION by the optimiser launch (250 ms by default; a chain
                         // publishes every few microseconds, the slowest takes 2 ms): a wait during which the producers
                         // keep coming in -- a device shared with another tenant, a batch of long chains -- is never cut
@@ -253,7 +237,7 @@ pw_analyse_kernel(long n_units, const long* __restrict__ atom_offset, const doub
         const long v0 = a0 * vstride;
         if (threadIdx.x == 0) ws->unit = u;     // (read by the debug capture only; ordered by load_unit's barrier)
         // (tmpl: the radius groups of a one-molecule-type batch, worked out once on the host -- pw_unit.hpp: load_unit)
-        analyse_unit<T, MASK>(sh, ws, n, xyz + 3 * a0, vdw + v0, mass + v0, stages & MASK, out + u, prm, vstride == 0 ? tmpl : nullptr);
+        analyse_unit<T>(sh, ws, n, xyz + 3 * a0, vdw + v0, mass + v0, stages & MASK, out + u, prm, vstride == 0 ? tmpl : nullptr);
         if (role == PW_ROLE_PRODUCER) {
             // analyse_unit ended with a team barrier; thread 0 wrote the record
             if (threadIdx.x == 0) {
@@ -287,7 +271,8 @@ __global__ void pw_gate_kernel(UnitQueue* queue, int expected, unsigned long lon
         if (wall_clock64() - t0 > limit) {
             // Counted either way.  Teams HAVE started and then none for a whole limit: the device is busy with something
             // else (another tenant, earlier analyses' chains); the launches behind the gate may go -- the window teams are
-            // capped at five per four CUs (launch_pipeline), so the optimiser teams that are still to come always find
+            // capped (pw_resident_launch: five per four CUs, eleven per eight above 6 x n_cu units when the average
+            // diameter runs in them; PW_C_TEAMS can raise the cap), so the optimiser teams that are still to come find
             // wave slots and LDS, and the consumers' own limit watches the publications from here on.  NOT ONE team has
             // started: the optimiser launch is not running at all -- its stream is behind something that does not move --
             // and consumers would only wait for it: the analysis is given up (cause 4, PW_E_TIMEOUT).
@@ -489,7 +474,7 @@ struct pw_context {
     int timeout_repeats;              // PW_TIMEOUT_REPEATS (default 2): how often pw_analysis_batch repeats an analysis after PW_E_TIMEOUT
     int device;
     hipStream_t stream;      // main stream (launch order, timing events)
-    hipStream_t aux;         // second stream: stages that do not depend on the optimiser
+    hipStream_t aux;         // second stream: no launch uses it, but the stream probe counts it (pw_context_create)
     int n_cu;
     size_t lds_per_cu;
     TeamWorkspace* ws;
@@ -508,7 +493,7 @@ struct pw_context {
     hipStream_t prods[PW_SETS];
     // successive pipeline launches alternate between two sets of (result buffer, queue,
     // slots, events), so the optimiser chains of launch k+1 run beside the window tail of k
-    hipEvent_t ev_reset[PW_SETS], ev_prod[PW_SETS], ev_gate[PW_SETS], ev_join[PW_SETS], ev_done[PW_SETS];
+    hipEvent_t ev_reset[PW_SETS], ev_prod[PW_SETS], ev_gate[PW_SETS], ev_done[PW_SETS];
     int done_valid[PW_SETS];
     hipStream_t cons[PW_SETS];   // gate + window launch of the pipeline, one stream per buffer set
     hipEvent_t ev_head[PW_SETS]; // head gate of the launch using set b has run
@@ -531,22 +516,20 @@ struct pw_context {
                              // streams of the pipeline do not run concurrently, see pw_context_create)
     int host_threads;        // device == -1 (the explicit host path, pw_hostpath.cpp): threads over the units
     int concurrent_streams;  // how many of the pipeline's 2 + 2 x PW_SETS streams ran at the same time in the probe
-    int c_waves;             // waves per team in the window launch (PW_C_WAVES, default 4)
     pw_params prm;           // knobs of find_windows / find_average_diameter
     unsigned* rsq_tab;       // VRSQRT14PD table on the device (numpy's arccos, pw_math.hpp)
     unsigned* nb_off;        // neighbour tables of the sampling sphere for P = PW_NB_PMIN .. PW_NB_PMAX (pw_unit.hpp)
     unsigned short* nb_idx;
     double* nb_bound;
     double* nb_unit;         // the unit vectors of every tabulated P (50 MB)
-    // team workspaces of the pipeline: C0 | A0 | B | A1 | C1, each region sized for the largest grid
+    // team workspaces of the pipeline: C[0..n) | A[0..n), each region sized for the largest grid
     // any launch on this context has asked for so far.  The layout only changes when a maximum
     // grows, and growing synchronises the device first, so two launches in flight -- which may have
     // different plans (other batch size, other stage mask) -- never share a team workspace.
-    int max_a, max_b, max_c;
+    int max_a, max_c;
     hipEvent_t ev_ext;       // ordering against a caller's stream (pw_resident_results_ready)
-    hipEvent_t ev_t[3][2];   // pw_resident_stage_times: start / stop of the chains, average and window launches
+    hipEvent_t ev_t[2][2];   // pw_resident_stage_times: start / stop of the chains and window launches
     int timing;              // record them during the next pipeline launch
-    int timed_avg;           // ... and whether that launch had an average-diameter launch of its own (else the stage ran in the window teams)
     pw_unit_debug* dbg;      // per-unit stage capture of the current debug analysis, else null
     hipStream_t rb_stream;   // the periodic re-assembly's own stream, highest priority (pw_internal_rebuild_stream), created on first use
     void* pool;              // device scratch kept between calls (the team slabs of the periodic re-assembly)
@@ -762,11 +745,6 @@ static int plan_launch(pw_context* c, long n_units, int nmax, int want_nw, bool 
     return PW_OK;
 }
 
-// PW_TEMPLATE_GROUPS=0: every unit works its radius groups out itself, as until round 5 (A/B comparisons)
-static bool template_groups_on() {
-    static const bool on = !(getenv("PW_TEMPLATE_GROUPS") && getenv("PW_TEMPLATE_GROUPS")[0] == '0');
-    return on;
-}
 template <int NW, unsigned MASK>
 static int launch_nw(pw_context* c, pw_resident* r, unsigned stages, const LaunchPlan& p, hipStream_t st,
                      int ws_first, int adj_first, int counter_slot, int role, bool reset_counter) {
@@ -800,18 +778,16 @@ static int launch_nw(pw_context* c, pw_resident* r, unsigned stages, const Launc
     hipLaunchKernelGGL(kern, dim3(p.grid), dim3(NW * 64), p.lds, st, r->n_units, r->d_offset,
                        r->d_xyz, r->d_vdw, r->d_mass, stages, r->nmax, p.nrot, p.nlb, p.nframes, p.lean, wsa,
                        c->counter + counter_slot, r->d_out, role, c->cur_queue, c->cur_slots, c->prm, c->rsq_tab,
-                       r->vstride, (const unsigned long long*)r->d_ready, (const unsigned char*)(template_groups_on() ? r->d_tmpl : nullptr));
+                       r->vstride, (const unsigned long long*)r->d_ready, (const unsigned char*)r->d_tmpl);
     HIP_TRY(hipGetLastError());
     return PW_OK;
 }
 static int launch_plan(pw_context* c, pw_resident* r, unsigned stages, const LaunchPlan& p, hipStream_t st,
                        int ws_first, int adj_first, int counter_slot, int role = PW_ROLE_PLAIN,
                        bool reset_counter = true) {
-    // the three launches of the pipeline have kernels of their own
+    // the launches of the pipeline have kernels of their own
     if (stages == MASK_CHAINS && p.nw == 1)
         return launch_nw<1, MASK_CHAINS>(c, r, stages, p, st, ws_first, adj_first, counter_slot, role, reset_counter);
-    if (stages == MASK_AVERAGE && p.nw == 4)
-        return launch_nw<4, MASK_AVERAGE>(c, r, stages, p, st, ws_first, adj_first, counter_slot, role, reset_counter);
     if (stages == MASK_WINDOWS && p.nw == 4)
         return launch_nw<4, MASK_WINDOWS>(c, r, stages, p, st, ws_first, adj_first, counter_slot, role, reset_counter);
     if (stages == MASK_WINDOWS_AVG && p.nw == 4)
@@ -951,7 +927,7 @@ int pw_context_create(int device, pw_context** out) {
     c->lds_per_cu = 160 * 1024;
     ct_mark("properties");
     CTX_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    CTX_TRY(hipMalloc((void**)&c->counter, (4 * PW_SETS + 3) * sizeof(unsigned long long)));      // per set: chains | windows | average | basic; + 2 for single launches; + the gates' time-outs
+    CTX_TRY(hipMalloc((void**)&c->counter, (4 * PW_SETS + 3) * sizeof(unsigned long long)));      // per set: chains | windows | (unused) | basic; + 2 for single launches; + the gates' time-outs
     CTX_TRY(hipMemset(c->counter, 0, (4 * PW_SETS + 3) * sizeof(unsigned long long)));
     CTX_TRY(hipMalloc((void**)&c->queue, PW_SETS * sizeof(UnitQueue)));
     CTX_TRY(hipMemset(c->queue, 0, PW_SETS * sizeof(UnitQueue)));
@@ -970,7 +946,7 @@ int pw_context_create(int device, pw_context** out) {
     c->cur_queue = c->queue;
     {
         // the optimiser chains are the critical path: their launch gets the highest priority,
-        // the average-diameter launch the lowest
+        // the idle second stream the lowest
         int lo = 0, hi = 0;
         CTX_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
         for (int b = 0; b < PW_SETS; ++b)
@@ -982,7 +958,6 @@ int pw_context_create(int device, pw_context** out) {
         CTX_TRY(hipEventCreateWithFlags(&c->ev_reset[b], hipEventDisableTiming));
         CTX_TRY(hipEventCreateWithFlags(&c->ev_prod[b], hipEventDisableTiming));
         CTX_TRY(hipEventCreateWithFlags(&c->ev_gate[b], hipEventDisableTiming));
-        CTX_TRY(hipEventCreateWithFlags(&c->ev_join[b], hipEventDisableTiming));
         CTX_TRY(hipEventCreateWithFlags(&c->ev_done[b], hipEventDisableTiming));
         CTX_TRY(hipEventCreateWithFlags(&c->ev_tail[b], hipEventDisableTiming));
         CTX_TRY(hipEventCreateWithFlags(&c->ev_head[b], hipEventDisableTiming));
@@ -1006,7 +981,6 @@ int pw_context_create(int device, pw_context** out) {
     CTX_TRY(hipEventCreateWithFlags(&c->ev_ext, hipEventDisableTiming));
     const char* fz = getenv("PW_FUSED");
     c->fused = (fz && fz[0] == '1') ? 1 : 0;
-    c->c_waves = 4;
     c->prm = default_params();
     {
         auto ms_env = [](const char* name, long dflt) { const char* e = getenv(name); long v = e ? atol(e) : dflt; return v > 0 ? v : dflt; };
@@ -1112,7 +1086,7 @@ void pw_context_destroy(pw_context* c) {
     if (c->bigmem) (void)hipFree(c->bigmem);
     delete c->extra;
     if (c->ev_ext) (void)hipEventDestroy(c->ev_ext);
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < 2; ++k)
         for (int e = 0; e < 2; ++e)
             if (c->ev_t[k][e]) (void)hipEventDestroy(c->ev_t[k][e]);
     if (c->counter) (void)hipFree(c->counter);
@@ -1123,7 +1097,6 @@ void pw_context_destroy(pw_context* c) {
         if (c->ev_reset[b]) (void)hipEventDestroy(c->ev_reset[b]);
         if (c->ev_prod[b]) (void)hipEventDestroy(c->ev_prod[b]);
         if (c->ev_gate[b]) (void)hipEventDestroy(c->ev_gate[b]);
-        if (c->ev_join[b]) (void)hipEventDestroy(c->ev_join[b]);
         if (c->ev_done[b]) (void)hipEventDestroy(c->ev_done[b]);
         if (c->ev_tail[b]) (void)hipEventDestroy(c->ev_tail[b]);
         if (c->ev_head[b]) (void)hipEventDestroy(c->ev_head[b]);
@@ -1364,68 +1337,42 @@ int pw_resident_launch(pw_context* c, pw_resident* r, uint32_t stages) {
     //   A (producer stream): stage_basic + pore-centre optimiser, ONE wave per unit -- the serial
     //     chain; every unit of a 1000-frame batch iterates at once.  Chains differ 10x in length;
     //     each finished unit is published to a queue.
-    //   B (aux stream): average diameter, 4 waves per unit, independent of A.
-    //   C (the set's consumer stream): window search, persistent teams consuming units as A publishes them.
-    //     A one-wave gate kernel ahead of C (and B) holds them back until every team of A is
-    //     resident, so they can never take the LDS A needs -- no launch-order assumption.
-    LaunchPlan pa, pb, pc;
+    //   C (the set's consumer stream): average diameter and window search, persistent teams consuming units as A
+    //     publishes them.  A one-wave gate kernel ahead of C holds it back until every team of A is
+    //     resident, so it can never take the LDS A needs -- no launch-order assumption.
+    LaunchPlan pa, pc;
     rc = plan_launch(c, r->n_units, r->nmax, 1, false, 1, &pa, 1, true);   // chains: no shifted frame
     if (rc != PW_OK) return rc;
     pa.grid = (int)r->n_units < pa.grid ? (int)r->n_units : pa.grid;
-    {
-        // PW_A_LDS_KB: pad the LDS request of the optimiser teams (tuning: keeps the bulk launches
-        // off a CU while its chains are young)
-        const char* al = getenv("PW_A_LDS_KB");
-        if (al && atoi(al) > 0) {
-            size_t want = (size_t)atoi(al) * 1024;
-            if (want > pa.lds && want <= 160 * 1024 - 256 - PW_KERNEL_STATIC_LDS) pa.lds = want;
-        }
-        if (getenv("PW_PLAN_DEBUG")) fprintf(stderr, "plan A: grid %d lds %zu\n", pa.grid, pa.lds);
-    }
-    bool do_avg = (stages & PW_STAGE_AVG) != 0;
+    if (getenv("PW_PLAN_DEBUG")) fprintf(stderr, "plan A: grid %d lds %zu\n", pa.grid, pa.lds);
     // Round 6: the average diameter is a stage of the WINDOW teams (before the window search of the unit they have just
     // taken), not a launch of its own.  Its teams -- four waves, one per SIMD of a CU, 96 of them persistent -- took the
     // four wave slots of their CU that the optimiser chains live on (two 256-register waves fill a SIMD, and a
     // 168-register wave beside one leaves no room for a second), i.e. 384 of the chip's 1024 chain slots, busy or not;
     // as a stage of the window teams the same work needs no slots of its own and a fifth more window teams fit
     // (1000 units 1.16 -> 1.13 ms per step, 4000 units 4.41 -> 4.13 ms, 500 units 0.91 -> 0.64:
-    // profiles/r06_avg_in_window_teams.txt).  PW_B_LAUNCH=1: the separate launch of rounds 1-5.
-    bool avg_in_c = false;
-    if (do_avg && !(getenv("PW_B_LAUNCH") && getenv("PW_B_LAUNCH")[0] == '1')) { avg_in_c = true; do_avg = false; }
-    pb.grid = 0;
-    if (do_avg) {
-        // one frame; the optimiser-state slots are this launch's scratch arena: 7 (51 KB) hold the ray vectors and
-        // the cone pairs of team_ray_tests, 2 (14 KB) make the stage fall back to the dense ray scan (PW_B_LB)
-        int b_lb = 7;
-        if (const char* e = getenv("PW_B_LB")) b_lb = atoi(e) > 0 ? atoi(e) : b_lb;
-        rc = plan_launch(c, r->n_units, r->nmax, 4, false, b_lb, &pb, 1, true);
-        if (rc != PW_OK) return rc;
-    }
+    // profiles/r06_avg_in_window_teams.txt).
+    const bool avg = (stages & PW_STAGE_AVG) != 0;
     // The window search: ONE launch of 4-wave teams, sampling and fits (the split into a sampling launch and one-wave
     // fit workers that round 4 built was 4-25x slower and is gone: profiles/r04_split_*)
-    rc = plan_launch(c, r->n_units, r->nmax, c->c_waves, true, -1, &pc, 1);      // one frame, shifted in place
+    rc = plan_launch(c, r->n_units, r->nmax, 4, true, -1, &pc, 1);      // one frame, shifted in place
     if (rc != PW_OK) return rc;
     // A batch of up to a few units per SIMD is latency-bound by its optimiser chains: one window team
     // per CU keeps LDS free for the chains of the next launch (measured on 1000 units: 2.56 -> 2.45 ms);
     // larger batches want every team the LDS admits (4000 units: 9.2 ms against 10.0).
     // (round 5, after the optimiser chains got a third faster: beyond that, five teams per four CUs -- 4000 units 4.80 ms
     // against 5.14 with two per CU, 8192: 9.41 / 10.1, 20 000: 22.8 / 24.3; profiles/r05_resweep.txt)
-    if (avg_in_c) {
-        // (with the average-diameter teams gone: five window teams per four CUs up to 1500 units -- 1000 units 1.126 ms with
-        // 320 teams, 1.163 with 304, 1.187 with 288, 1.127 with 352 -- eleven per eight CUs beyond: 4000 units 4.13 ms with
-        // 352 teams, 4.27 with 320, 4.31 with 384; small batches one team per two units)
+    if (avg) {
+        // (with the average diameter in the window teams: five window teams per four CUs up to 1500 units -- 1000 units
+        // 1.126 ms with 320 teams, 1.163 with 304, 1.187 with 288, 1.127 with 352 -- eleven per eight CUs beyond: 4000
+        // units 4.13 ms with 352 teams, 4.27 with 320, 4.31 with 384; small batches one team per two units)
         const long cap = r->n_units <= 6L * c->n_cu ? c->n_cu + c->n_cu / 4 : c->n_cu + (3 * c->n_cu) / 8;
         if (pc.grid > cap) pc.grid = (int)cap;
         if (r->n_units <= 300 && pc.grid > (r->n_units + 1) / 2) pc.grid = (int)((r->n_units + 1) / 2);
     } else if (r->n_units <= 6L * c->n_cu && pc.grid > c->n_cu) pc.grid = c->n_cu;
     else if (pc.grid > c->n_cu + c->n_cu / 4) pc.grid = c->n_cu + c->n_cu / 4;
-    // ... and the average-diameter launch, a fifth of the window search's work, gets by with one team
-    // per two CUs whatever the batch (1000 units: 1.84 -> 1.79 ms, 500: 1.28 -> 1.20; 4000: 6.59 -> 6.53)
-    const int pb_planned = pb.grid;
-    // (round 5: three teams per eight CUs -- 1000 units 1.25-1.27 ms against 1.29 with one per two CUs, 4000 the same)
-    if (do_avg && pb.grid > (3 * c->n_cu + 7) / 8) pb.grid = (3 * c->n_cu + 7) / 8;
     {
-        // PW_C_TEAMS / PW_B_TEAMS: cap the persistent teams of the window / average launches (tuning)
+        // PW_C_TEAMS: cap the persistent teams of the window launch (tuning; may also raise it)
         const char* ct = getenv("PW_C_TEAMS");
         if (ct && atoi(ct) > 0) {
             long g = (long)c->n_cu * 4;
@@ -1435,28 +1382,9 @@ int pw_resident_launch(pw_context* c, pw_resident* r, uint32_t stages) {
             if (g > (long)c->n_cu * per_cu) g = (long)c->n_cu * per_cu;
             pc.grid = atoi(ct) < g ? atoi(ct) : (int)g;
         }
-        const char* bt = getenv("PW_B_TEAMS");
-        if (bt && do_avg && atoi(bt) > 0) pb.grid = atoi(bt) < pb_planned ? atoi(bt) : pb_planned;   // (may also raise it)
     }
-    if (const char* cslots = getenv("PW_C_SLOTS")) {
-        // experiment: fewer window-fit slots than waves (less LDS per team, windows fitted in rounds);
-        // PW_C_TEAMS then sets the number of teams (up to what the smaller request admits per CU)
-        int k = atoi(cslots);
-        if (k >= 1 && k < 4 && pc.nw == 4) {
-            pc.nrot = pc.nlb = k;
-            pc.lds = UnitShared::bytes(r->nmax, k, k, 1, false, wanted_p_cap(c) > c->p_cap ? wanted_p_cap(c) : c->p_cap) + 64;
-            int per_cu = (int)(c->lds_per_cu / pc.lds);
-            if (per_cu > 4) per_cu = 4;
-            long g = (long)c->n_cu * per_cu;
-            const char* ct = getenv("PW_C_TEAMS");
-            if (ct && atoi(ct) > 0 && atoi(ct) < g) g = atoi(ct);
-            pc.grid = (int)(g < r->n_units ? g : r->n_units);
-            if (getenv("PW_PLAN_DEBUG")) fprintf(stderr, "plan C: slots %d lds %zu grid %d\n", k, pc.lds, pc.grid);
-        }
-    }
-    // teams: C[0..n) | A[0..n) | B (n = sets in flight: that many window and optimiser launches can be
-    // running at once; the average-diameter launches follow each other on one stream), every region
-    // as large as the largest grid seen so far -- see pw_context::max_a
+    // teams: C[0..n) | A[0..n) (n = sets in flight: that many window and optimiser launches can be
+    // running at once), every region as large as the largest grid seen so far -- see pw_context::max_a
     // How many analyses may be in flight.  A small batch leaves most of the chip idle while its few long
     // optimiser chains finish (the slowest of 1000 takes 3.4 ms, the mean 1 ms), so the period of
     // back-to-back analyses is their latency divided by the number in flight until the window teams
@@ -1470,10 +1398,9 @@ int pw_resident_launch(pw_context* c, pw_resident* r, uint32_t stages) {
     // 250 frames 0.86 against 1.07; 4000 frames 5.96 / 5.84 / 5.80 with four / three / two)
     if (ns == 0) ns = auto_sets(r->n_units);
     if (ns > r->nbuf) ns = r->nbuf;
-    if (pa.grid > c->max_a || pb.grid > c->max_b || pc.grid > c->max_c || ns != c->cur_sets) {
+    if (pa.grid > c->max_a || pc.grid > c->max_c || ns != c->cur_sets) {
         HIP_TRY(hipDeviceSynchronize());         // nothing is in flight while the layout changes
         if (pa.grid > c->max_a) c->max_a = pa.grid;
-        if (pb.grid > c->max_b) c->max_b = pb.grid;
         if (pc.grid > c->max_c) c->max_c = pc.grid;
         if (ns != c->cur_sets) {
             c->cur_sets = ns;
@@ -1481,8 +1408,7 @@ int pw_resident_launch(pw_context* c, pw_resident* r, uint32_t stages) {
             for (int k = 0; k < PW_SETS; ++k) c->done_valid[k] = c->tail_valid[k] = c->head_valid[k] = 0;
         }
     }
-    const int ws_b = ns * (c->max_c + c->max_a);
-    rc = ensure_workspace(c, ws_b + c->max_b, ns * c->max_c);
+    rc = ensure_workspace(c, ns * (c->max_c + c->max_a), ns * c->max_c);
     if (rc != PW_OK) return rc;
     if (c->slots_cap < r->n_units) {
         HIP_TRY(hipDeviceSynchronize());
@@ -1500,10 +1426,7 @@ int pw_resident_launch(pw_context* c, pw_resident* r, uint32_t stages) {
     const int nx = (b + 1) % ns;
     c->flip = b;
     const int ws_a = ns * c->max_c + b * c->max_a, ws_c = b * c->max_c;
-    {
-        const char* ps = getenv("PW_PROD_STREAMS");
-        c->prod = c->prods[((ps && ps[0] == '2') || c->tail_pct != 0) ? b : 0];
-    }
+    c->prod = c->prods[c->tail_pct != 0 ? b : 0];
     r->cur = (r->cur + 1) % r->nbuf;
     r->d_out = r->d_outs[r->cur];
     c->cur_queue = c->queue + b;
@@ -1515,7 +1438,6 @@ int pw_resident_launch(pw_context* c, pw_resident* r, uint32_t stages) {
             HIP_TRY(hipStreamWaitEvent(c->prods[k], c->ev_fork, 0));
             HIP_TRY(hipStreamWaitEvent(c->cons[k], c->ev_fork, 0));
         }
-        HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_fork, 0));
         c->need_fork = 0;
     }
     // the launch that used this set before has finished (it is `ns` launches back) ...
@@ -1585,22 +1507,11 @@ int pw_resident_launch(pw_context* c, pw_resident* r, uint32_t stages) {
             HIP_TRY(hipStreamWaitEvent(cs, c->ev_done[p], 0));
         }
     }
-    if (c->timing) { c->timed_avg = do_avg ? 1 : 0; HIP_TRY(hipEventRecord(c->ev_t[2][0], cs)); }
-    rc = launch_plan(c, r, avg_in_c ? MASK_WINDOWS_AVG : MASK_WINDOWS, pc, cs, ws_c, b * c->max_c, PW_SETS + b, PW_ROLE_CONSUMER, false);
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev_t[1][0], cs));
+    rc = launch_plan(c, r, avg ? MASK_WINDOWS_AVG : MASK_WINDOWS, pc, cs, ws_c, b * c->max_c, PW_SETS + b, PW_ROLE_CONSUMER, false);
     if (rc != PW_OK) return rc;
-    if (c->timing) HIP_TRY(hipEventRecord(c->ev_t[2][1], cs));
-    if (do_avg) {
-        HIP_TRY(hipStreamWaitEvent(c->aux, c->ev_gate[b], 0));
-        if (c->timing) HIP_TRY(hipEventRecord(c->ev_t[1][0], c->aux));
-        // (the launch's own counter: the previous average-diameter launch may still be running)
-        rc = launch_plan(c, r, PW_STAGE_AVG | PW_STAGE_MERGE | PW_STAGE_COM_ONLY, pb, c->aux, ws_b, -1, 2 * PW_SETS + b,
-                         PW_ROLE_PLAIN, false);
-        if (rc != PW_OK) return rc;
-        if (c->timing) HIP_TRY(hipEventRecord(c->ev_t[1][1], c->aux));
-        HIP_TRY(hipEventRecord(c->ev_join[b], c->aux));
-    }
+    if (c->timing) HIP_TRY(hipEventRecord(c->ev_t[1][1], cs));
     HIP_TRY(hipStreamWaitEvent(cs, c->ev_prod[b], 0));
-    if (do_avg) HIP_TRY(hipStreamWaitEvent(cs, c->ev_join[b], 0));
     HIP_TRY(hipEventRecord(c->ev_done[b], cs));
     c->done_valid[b] = 1;
     return PW_OK;
@@ -1749,7 +1660,7 @@ int pw_resident_upload(pw_context* c, const pw_batch_in* in, pw_resident** out) 
 
 // ---- a batch whose coordinates arrive while it is being analysed --------------------------------------------
 // One molecule type (template_atoms per unit), n_units known, coordinates appended in unit order.  The analysis
-// may be launched right after pw_resident_stream_begin: its chains and average-diameter teams take units in
+// may be launched right after pw_resident_stream_begin: its chains take units in
 // index order and wait for the `ready` counter, which every append raises behind its copy on the API stream.
 // What this hides is the reader: decoding a 1000-frame HISTORY file takes about as long as a third of the
 // analysis' own latency (reference: the frame loop of Trajectory._analysis_serial reads and analyses one frame
@@ -2149,16 +2060,17 @@ int pw_resident_time(pw_context* c, pw_resident* r, uint32_t stages, int iters, 
     return check_queue_error(c);     // a timed-out launch must not be reported as a time
 }
 
-// One analysis on its own (nothing else in flight), HIP events on the stream of each of its three
-// launches: ms[0] optimiser chains, ms[1] average diameter, ms[2] window search (a consumer: it runs
-// from the moment the chains are resident until the last published unit is fitted).
+// One analysis on its own (nothing else in flight), HIP events on the stream of each of its two
+// launches: ms[0] optimiser chains, ms[2] average diameter and window search (a consumer: it runs
+// from the moment the chains are resident until the last published unit is fitted).  ms[1] is 0: the
+// average diameter has no launch of its own.
 int pw_resident_stage_times(pw_context* c, pw_resident* r, float* ms) {
     if (!c || !r || !ms) return PW_E_BAD_ARG;
     PW_LOCK_CONTEXT(c);
     PW_HOST_UNSUPPORTED(c, "per-launch timing");
     if (c->fused) { snprintf(g_err, sizeof(g_err), "PW_FUSED=1: the analysis is one launch"); return PW_E_BAD_ARG; }
     PW_ON_DEVICE(c->device);
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < 2; ++k)
         for (int e = 0; e < 2; ++e)
             if (!c->ev_t[k][e]) HIP_TRY(hipEventCreate(&c->ev_t[k][e]));
     int rc = pw_resident_launch(c, r, PW_STAGE_ALL);     // warm-up, sizes the workspaces
@@ -2170,10 +2082,9 @@ int pw_resident_stage_times(pw_context* c, pw_resident* r, float* ms) {
     c->timing = 0;
     if (rc == PW_OK) rc = pw_resident_sync(c);
     if (rc != PW_OK) return rc;
-    for (int k = 0; k < 3; ++k) {
-        if (k == 1 && !c->timed_avg) { ms[k] = 0.f; continue; }      // (no launch of its own: a stage of the window teams)
-        HIP_TRY(hipEventElapsedTime(&ms[k], c->ev_t[k][0], c->ev_t[k][1]));
-    }
+    HIP_TRY(hipEventElapsedTime(&ms[0], c->ev_t[0][0], c->ev_t[0][1]));
+    ms[1] = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms[2], c->ev_t[1][0], c->ev_t[1][1]));
     return PW_OK;
 }
 

@@ -32,7 +32,7 @@
 #include "pw_blas.hpp"
 #include "pw_team.hpp"
 
-#if defined(PW_PROFILE) && defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_LB_TIMERS)
+#if defined(PW_PROFILE) && defined(__HIP_DEVICE_COMPILE__)
 #define LB_T0(var) long long var = wall_clock64()
 #define LB_T1(slot, var) do { if (prof && T::lane() == 0) atomicAdd(&prof[slot], (unsigned long long)(wall_clock64() - var)); } while (0)
 #else
@@ -387,9 +387,6 @@ __device__ inline __attribute__((always_inline)) int lb_bmv_body(LbMem<N>* m, in
             e = lb_expo(pa); emin = e < emin ? e : emin; emax = e > emax ? e : emax;
         }
         bool good = lb_plain_range(emin, emax) && rs != 0.0 && (!pact || r_b != 0.0) && (!act || m->rwt[li] != 0.0);
-#ifdef PW_LB_FORCE_FALLBACK
-        good = false;                     // (test builds: every call takes the guarded path after the speculative one)
-#endif
         if (T::ballot(!good)) return -1;
     }
     if (act) p[lane] = pi + sum2;
@@ -435,9 +432,6 @@ __device__ inline __attribute__((always_inline)) int lb_subsm_solves_body(LbMem<
     if (SPEC) {
         const unsigned e1 = lb_expo(t_ut), e2 = lb_expo(t_un);
         bool good = lb_plain_range(e1 < e2 ? e1 : e2, e1 > e2 ? e1 : e2) && (!act || m->rwn[li] != 0.0);
-#ifdef PW_LB_FORCE_FALLBACK
-        good = false;
-#endif
         if (T::ballot(!good)) return -1;
     }
     if (act) wv[lane] = xk;
@@ -927,7 +921,7 @@ struct Lbfgsb {
         PW_ASSUME_LDS(mem);
         double* a = which == 1 ? wt : (which == 2 ? wn : &WN(col, col));
         const int lda = which == 1 ? M : M2;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_LB_OLD_SOLVES) && !defined(PW_LB_OLD_POTRF)
+#if defined(__HIP_DEVICE_COMPILE__)
         if (T::WSIZE == 64) {
             double* rt = which == 1 ? mem->rwt : (which == 2 ? mem->rwn : mem->rwn + col);
             double* it = which == 2 ? mem->iwn : (double*)nullptr;
@@ -944,7 +938,7 @@ struct Lbfgsb {
     // 2 / 3 the first / second half of the diagonal of WN (after each of formk's factorisations)
     template <class T>
     PW_HD void tables(int which) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_LB_OLD_SOLVES)
+#if defined(__HIP_DEVICE_COMPILE__)
         PW_ASSUME_LDS(mem);
         if (T::WSIZE == 64) {
             const int i = T::lane();
@@ -1171,14 +1165,12 @@ struct Lbfgsb {
         PW_ASSUME_LDS(mem);
         if (col == 0) return 0;
         LB_F0(fb);
-#ifndef PW_LB_NO_SMALL
         if (col <= 2) {
             const int inf_s = bmv_small<T>(v, p);
             LB_F1(2, fb);
             return inf_s;
         }
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_LB_OLD_SOLVES)
+#if defined(__HIP_DEVICE_COMPILE__)
         if (T::WSIZE == 64) {
             const int inf_w = lb_bmv_wave<LbWave, N>(mem, col, v, p);
             LB_F1(2, fb);
@@ -1679,21 +1671,19 @@ struct Lbfgsb {
         }
         T::wave_sync();
         LB_F1(8, fk1);
-#ifndef PW_LB_NO_SMALL
         if (col <= 2) {
             LB_F0(fks);
             const int rs = formk_tail_small<T>();
             LB_F1(9, fks);
             return rs;
         }
-#endif
         LB_F0(fk2);
         int inf = factor<T>(2);
         LB_F1(9, fk2);
         if (inf != 0) return -1;
         int col2 = 2 * col;
         LB_F0(fk3);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_LB_OLD_SOLVES) && !defined(PW_LB_OLD_POTRF)
+#if defined(__HIP_DEVICE_COMPILE__)
         inf = p_dtrtrs_u<T>(true, col, col, wn, M2, &WN(0, col), M2, T::WSIZE == 64 ? mem->iwn : (const double*)nullptr);
 #else
         inf = p_dtrtrs_u<T>(true, col, col, wn, M2, &WN(0, col), M2);
@@ -1800,12 +1790,10 @@ struct Lbfgsb {
         int col2 = 2 * col;
         LB_F0(fs1);
         int inf;
-#ifndef PW_LB_NO_SMALL
         if (col <= 2) {
             inf = subsm_solves_small<T>(wv);
         } else
-#endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_LB_OLD_SOLVES)
+#if defined(__HIP_DEVICE_COMPILE__)
         if (T::WSIZE == 64) {
             inf = lb_subsm_solves_wave<LbWave, N>(mem, col, wv);
         } else
@@ -1820,11 +1808,7 @@ struct Lbfgsb {
         LB_F1(12, fs1);
         if (inf != 0) return inf;
         LB_F0(fst);
-#ifdef PW_NO_SPREAD_SUBSM
-        if (false) {
-#else
         if (T::WSIZE == 64 && col * nsub <= 32) {
-#endif
             // the col x nsub terms by one lane each (a division apiece) into team memory (LbMem::tri: the first kind at
             // [term], the second at [32 + term]), then every lane adds them to its copy of dd in the reference's order --
             // sixty reads of addresses that are the same in every lane, issued back to back (as v_readlane moves with a
@@ -2107,7 +2091,6 @@ struct Lbfgsb {
     template <class T>
     PW_HD int formt() {
         PW_ASSUME_LDS(mem);
-#ifndef PW_LB_NO_SMALL
         if (col <= 2) {
             // (one or two correction pairs: the statements below and potf2 in scalars, see bmv_small; the reciprocal
             // table of WT's diagonal is the lane-parallel product's, which does not run at this size)
@@ -2127,7 +2110,6 @@ struct Lbfgsb {
             T::wave_sync();
             return inf != 0 ? -3 : 0;
         }
-#endif
         for (int e = T::lane(); e < col * col; e += T::WSIZE) {
             int i = e / col, j = e % col;
             if (j < i) continue;

@@ -60,50 +60,6 @@ __shared__ unsigned long long pw_prof_lds[32];
 #define PW_T1(ws, slot, var) do {} while (0)
 #endif
 
-// unroll factors of the three bulk loops (measured: tests/tools/variant_sweep.sh)
-#define PW_PRAGMA_(x) _Pragma(#x)
-#define PW_PRAGMA(x) PW_PRAGMA_(x)
-#ifndef PW_UNROLL_LIST
-#define PW_UNROLL_LIST 4
-#endif
-#ifndef PW_UNROLL_GAP
-#define PW_UNROLL_GAP 2
-#endif
-#ifndef PW_UNROLL_RAY
-#define PW_UNROLL_RAY 2
-#endif
-#ifndef PW_UNROLL_KNN
-#define PW_UNROLL_KNN 2
-#endif
-// register tiles of the two bulk evaluations of the window search: path points / grid points per thread
-// that share one pass over the atoms (6 and 7 fill a 256-register budget; smaller tiles for smaller budgets)
-#ifndef PW_TILE_PATH
-#define PW_TILE_PATH 6
-#endif
-#ifndef PW_TILE_GRID
-#define PW_TILE_GRID 7
-#endif
-
-// PW_TEAM_STATE_IN_LDS (a translation unit's choice, before this header): the kernel keeps its UnitShared -- the
-// table of where everything of the team lives -- and its copy of the parameters in LDS instead of on its stack,
-// and the stage functions may assume so: their look-ups become ds_read instead of scratch loads, and the kernel
-// has no stack object whose address escapes into a call.
-#if defined(PW_TEAM_STATE_IN_LDS) && defined(__HIP_DEVICE_COMPILE__)
-#define PW_ASSUME_TEAM_STATE(sh, prm) do { PW_ASSUME_LDS(&(sh)); PW_ASSUME_LDS(&(prm)); } while (0)
-#define PW_ASSUME_TEAM_SH(sh) PW_ASSUME_LDS(&(sh))
-#else
-#define PW_ASSUME_TEAM_STATE(sh, prm) do {} while (0)
-#define PW_ASSUME_TEAM_SH(sh) do {} while (0)
-#endif
-
-// diagnostic builds (-DPW_DCHECKS, tests/tools/build_debug_variant.sh): an impossible value stops the wave where
-// rocgdb shows the line
-#if defined(PW_DCHECKS) && defined(__HIP_DEVICE_COMPILE__)
-#define PW_DCHECK(cond, code) do { if (!(cond)) asm volatile("s_mov_b32 m0, %0\n\ts_trap 2" :: "n"(code) : "memory"); } while (0)
-#else
-#define PW_DCHECK(cond, code) do {} while (0)
-#endif
-
 namespace pw {
 
 constexpr double GOLDEN_ANGLE = 2.399963229728653;   // np.pi * (3 - np.sqrt(5))
@@ -451,7 +407,7 @@ PW_HD inline void points_gap_values(const Frame& F, int n, const double* px, con
         for (int p = 0; p < NP; ++p) m2[p] = PW_INF;
         if (cand) {
             const int chi = coff[g + 1];
-PW_PRAGMA(unroll PW_UNROLL_LIST)
+#pragma unroll 4     // (measured: tests/tools/variant_sweep.sh)
             for (int c = coff[g]; c < chi; ++c) {
                 const int i = cand[c];
                 const double x = F.x[i], y = F.y[i], z = F.z[i], xx = F.xx[i];
@@ -463,7 +419,7 @@ PW_PRAGMA(unroll PW_UNROLL_LIST)
             }
         } else {
         const int hi = C.off[g + 1];
-PW_PRAGMA(unroll PW_UNROLL_GAP)
+#pragma unroll 2     // (measured: tests/tools/variant_sweep.sh)
         for (int i = C.off[g]; i < hi; ++i) {
             const double x = F.x[i], y = F.y[i], z = F.z[i], xx = F.xx[i];
 #pragma unroll
@@ -1276,7 +1232,7 @@ PW_HD inline __attribute__((always_inline)) void ray_scan_multi_impl(const Frame
             for (int r = 0; r < NR; ++r) mh[r] = 0u;
             const int base = blk + half;
             const int jend = n - base < 32 ? n - base : 32;
-PW_PRAGMA(unroll PW_UNROLL_RAY)
+#pragma unroll 2     // (measured: tests/tools/variant_sweep.sh)
             for (int j = 0; j < jend; ++j) {
                 int i = base + j;
                 double rx = F.x[i] - c0, ry = F.y[i] - c1, rz = F.z[i] - c2;
@@ -1336,6 +1292,10 @@ PW_PRAGMA(unroll PW_UNROLL_RAY)
 #pragma unroll
     for (int r = 0; r < NR; ++r) { hit[r] = any[r]; farthest[r] = far[r]; }
 }
+// (The out-of-line functions here whose body is an always-inline _impl of its own -- ray_scan_multi, team_max_dim,
+// stage_basic, stage_opt, stage_windows -- keep the split although the _impl has no other caller: merged into one
+// function, the body is optimised once instead of twice and compiles to other code, e.g. 148 VGPRs instead of 135 for
+// ray_scan_multi<4, false> and seven more scratch stores in stage_opt<DeviceTeam<1>>.)
 template <int NR, bool FAR = true>
 PW_NOINLINE PW_HD inline void ray_scan_multi(const Frame& F, int n, const double* cen, const double* dx,
                                              const double* dy, const double* dz, bool* hit, double* farthest) {
@@ -1433,8 +1393,6 @@ PW_HD inline __attribute__((always_inline)) bool team_ray_tests(const Frame& F, 
         const ConeBand b = bands[i];
         const bool two_sided = b.khi < 0;
         const int khi = two_sided ? -b.khi - 1 : b.khi;
-        PW_DCHECK(P >= 10 && P <= 4096, 102);
-        PW_DCHECK(b.klo >= 0 && khi < P, 103);
         const double rx = F.x[i] - c0, ry = F.y[i] - c1, rz = F.z[i] - c2;
         int off = getp.first(b.klo + T::lane());
         for (int kb = b.klo; kb <= khi; kb += T::WSIZE, off += GETP::STEP64) {
@@ -1553,9 +1511,10 @@ PW_NOINLINE PW_HD inline bool path_scan_thread(const Frame& F, int n, double vx,
         }
         k0 += NP;
     };
+    // (six points per pass fill a 256-register budget)
     while (k0 <= chunks && ok) {
-        if (PW_TILE_PATH > 5 && chunks - k0 + 1 <= 5) tile(std::integral_constant<int, 5>());
-        else tile(std::integral_constant<int, PW_TILE_PATH>());
+        if (chunks - k0 + 1 <= 5) tile(std::integral_constant<int, 5>());
+        else tile(std::integral_constant<int, 6>());
     }
     if (n_eval) *n_eval += chunks + 1;
     if (!ok) return false;
@@ -2043,7 +2002,7 @@ template <class T, bool VALUE_ONLY = false, bool EDGE = false>
 PW_HD inline __attribute__((always_inline)) void team_max_dim_body(UnitShared& sh, const Frame& F, int n,
                                                                    double* item_best = nullptr, const double* centre = nullptr) {
     const GramEdgeRule er(n);
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_MAXDIM_FEW)
+#if defined(__HIP_DEVICE_COMPILE__)
     // (the atoms of the outermost shell only, when they are few: team_max_dim_few)
     if (T::WSIZE == 64 && team_max_dim_few<T, VALUE_ONLY, EDGE>(sh, F, n, er, centre)) return;
 #else
@@ -2256,7 +2215,6 @@ PW_HD inline __attribute__((always_inline)) void team_max_dim_impl(UnitShared& s
 template <class T, bool VALUE_ONLY = false>
 PW_NOINLINE PW_HD inline void team_max_dim(UnitShared& sh, const Frame& F, int n, double* item_best = nullptr,
                                            const double* centre = nullptr) {
-    PW_ASSUME_TEAM_SH(sh);
     team_max_dim_impl<T, VALUE_ONLY>(sh, F, n, item_best, centre);
 }
 
@@ -2320,7 +2278,6 @@ PW_HD inline __attribute__((always_inline)) void stage_basic_impl(UnitShared& sh
 template <class T>
 PW_NOINLINE PW_HD inline void stage_basic(UnitShared& sh, TeamWorkspace* ws, int n, pw_unit_out* out,
                                            bool com_only) {
-    PW_ASSUME_TEAM_SH(sh);
     stage_basic_impl<T>(sh, ws, n, out, com_only);
 }
 
@@ -2354,14 +2311,14 @@ struct PoreObjective {
     double lx, ly, lz, lf, lg[3];
     int nfev;
     unsigned long long* prof;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_NEAR_GAP)
+#if defined(__HIP_DEVICE_COMPILE__)
     NearGap4<T> near_gap;
 #endif
     PW_HD PoreObjective(const Frame& A_, int n_, const double* lo_, const double* up_, PW_LDS int* cand_)
         : A(A_), n(n_), lo(lo_), up(up_), cand(cand_), have_last(false), lx(0.0), ly(0.0), lz(0.0), lf(0.0), nfev(0),
           prof(nullptr) {
         lg[0] = lg[1] = lg[2] = 0.0;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_NEAR_GAP)
+#if defined(__HIP_DEVICE_COMPILE__)
         near_gap.init();
 #endif
     }
@@ -2398,7 +2355,7 @@ struct PoreObjective {
 #if defined(PW_PROFILE) && defined(PW_LB_FINE) && defined(__HIP_DEVICE_COMPILE__)
             long long t_g4 = clock64();
 #endif
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_NEAR_GAP)
+#if defined(__HIP_DEVICE_COMPILE__)
             if (T::WSIZE == 64) near_gap.eval(A, n, cand, qx, qy, qz, gv);
             else
 #endif
@@ -2509,16 +2466,13 @@ PW_HD inline __attribute__((always_inline)) void stage_opt_impl(UnitShared& sh, 
 template <class T>
 PW_NOINLINE PW_HD inline void stage_opt(UnitShared& sh, TeamWorkspace* ws, int n, pw_unit_out* out,
                                         const pw_params& prm) {
-    PW_ASSUME_TEAM_STATE(sh, prm);
     stage_opt_impl<T>(sh, ws, n, out, prm);
 }
 
 // ---- stage: average diameter ---------------------------------------------------------------
-// INL: everything inlined into the caller (the average-diameter launch has a kernel of its own,
-// whose register budget then covers the whole stage: three waves per SIMD instead of two)
-template <class T, bool INL>
-PW_HD inline __attribute__((always_inline)) void stage_average_impl(UnitShared& sh, TeamWorkspace* ws, int n,
-                                                                    pw_unit_out* out, const pw_params& prm) {
+template <class T>
+PW_NOINLINE PW_HD inline void stage_average(UnitShared& sh, TeamWorkspace* ws, int n, pw_unit_out* out,
+                                             const pw_params& prm) {
     auto& v = *sh.v;
     PW_T0(t_a0);
     make_shifted<T>(sh, n, v.com[0], v.com[1], v.com[2]);
@@ -2528,7 +2482,7 @@ PW_HD inline __attribute__((always_inline)) void stage_average_impl(UnitShared& 
     T::sync();
     {
         double* ib = 2 * n + 2 <= ws->p_cap ? ws->vals : nullptr;     // per-item maxima (free until the rays)
-        if (INL) team_max_dim_impl<T, true>(sh, sh.S, n, ib); else team_max_dim<T, true>(sh, sh.S, n, ib);
+        team_max_dim<T, true>(sh, sh.S, n, ib);
     }
     double radius = v.maxd;
     T::sync();
@@ -2596,8 +2550,7 @@ PW_HD inline __attribute__((always_inline)) void stage_average_impl(UnitShared& 
                 int k = k0 + r * T::SIZE < P ? k0 + r * T::SIZE : k0;
                 sp.point(k, &dx[r], &dy[r], &dz[r]);
             }
-            if (INL) ray_scan_multi_impl<NR, true>(sh.S, n, cen, dx, dy, dz, hit, far);
-            else ray_scan_multi<NR>(sh.S, n, cen, dx, dy, dz, hit, far);
+            ray_scan_multi<NR>(sh.S, n, cen, dx, dy, dz, hit, far);
 #pragma unroll
             for (int r = 0; r < NR; ++r) {
                 int k = k0 + r * T::SIZE;
@@ -2641,13 +2594,6 @@ PW_HD inline __attribute__((always_inline)) void stage_average_impl(UnitShared& 
     T::sync();
 }
 
-template <class T>
-PW_NOINLINE PW_HD inline void stage_average(UnitShared& sh, TeamWorkspace* ws, int n, pw_unit_out* out,
-                                             const pw_params& prm) {
-    PW_ASSUME_TEAM_STATE(sh, prm);
-    stage_average_impl<T, false>(sh, ws, n, out, prm);
-}
-
 // ---- Nelder-Mead in the window plane (scipy.optimize.fmin defaults, N = 2) ------------------
 template <class T>
 PW_NOINLINE PW_HD inline void wave_fmin_xy(const Frame& F, int n, double z, double x0, double y0, double* xo,
@@ -2658,7 +2604,7 @@ PW_NOINLINE PW_HD inline void wave_fmin_xy(const Frame& F, int n, double z, doub
     // placed in scratch (global) memory on the GPU
     double x0s, y0s, f0s, x1s, y1s, f1s, x2s, y2s, f2s;
     int fcalls = 0;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_NEAR_GAP)
+#if defined(__HIP_DEVICE_COMPILE__)
     NearGap1<T> near_gap;
     near_gap.init();
     const Frame Fl = F;          // (by value: `F` is behind a generic pointer)
@@ -2760,12 +2706,12 @@ struct NeckObjective {
     bool have_last;
     double lz, lf, lg;
     int nfev;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_NEAR_GAP)
+#if defined(__HIP_DEVICE_COMPILE__)
     NearGap4<T> near_gap;
 #endif
     PW_HD NeckObjective(const Frame& R_, int n_, double xo_, double yo_, double lo_, double up_, PW_LDS int* cand_)
         : R(R_), n(n_), xo(xo_), yo(yo_), lo(lo_), up(up_), cand(cand_), have_last(false), lz(0.0), lf(0.0), lg(0.0), nfev(0) {
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_NEAR_GAP)
+#if defined(__HIP_DEVICE_COMPILE__)
         near_gap.init();
 #endif
     }
@@ -2776,7 +2722,7 @@ struct NeckObjective {
             double z1 = zc + h;
             double dz = z1 - zc;
             double zx[4] = {xo, xo, xo, xo}, zy[4] = {yo, yo, yo, yo}, zz[4] = {zc, z1, zc, z1}, gv[4];
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_NEAR_GAP)
+#if defined(__HIP_DEVICE_COMPILE__)
             if (T::WSIZE == 64) near_gap.eval(R, n, cand, zx, zy, zz, gv);
             else
 #endif
@@ -2815,10 +2761,7 @@ struct NeckObjective {
 template <class T>
 PW_NOINLINE __device__ inline bool wave_brute_bounded(Frame R, int n, PW_LDS double* scratch, int cap, double zopt,
                                                       double gstart, double gstep, int* gidx_out) {
-#ifndef PW_GRID_TAU
-#define PW_GRID_TAU 0.7     // (measured on CC3: 0.6 - 1.0 within 10 %, 0.4 and 1.6 slower, 0.2 leaves too many points)
-#endif
-    constexpr double TAU = PW_GRID_TAU;
+    constexpr double TAU = 0.7;     // (measured on CC3: 0.6 - 1.0 within 10 %, 0.4 and 1.6 slower, 0.2 leaves too many points)
     const PW_LDS ClassInfo* C = R.cls;
     const int kk = T::uniform_i(C->k);
     cap = T::uniform_i(cap);
@@ -3100,7 +3043,7 @@ PW_NOINLINE PW_HD inline void wave_window(const Frame& FS, const Frame& R, PW_LD
     int ppos = 0x7fffffff;
     bool ok = true;
     bool tubed = false;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_PATH_TUBE)
+#if defined(__HIP_DEVICE_COMPILE__)
     if (T::WSIZE == 64)
         tubed = wave_path_tube<T>(FS, n, (PW_LDS double*)lbmem, (int)(sizeof(LbMem<1>) / 8 / 4), cx, cy, cz, chunks, &pbest, &ppos, &ok);
 #endif
@@ -3262,7 +3205,7 @@ PW_NOINLINE PW_HD inline void wave_window(const Frame& FS, const Frame& R, PW_LD
         double gbest = PW_INF;
         int gidx = 0x7fffffff;
         bool listed = false;
-#if defined(__HIP_DEVICE_COMPILE__) && !defined(PW_NO_GRID_LISTS)
+#if defined(__HIP_DEVICE_COMPILE__)
         if (T::WSIZE == 64)
             listed = wave_brute_bounded<T>(R, n, (PW_LDS double*)lbmem, (int)(sizeof(LbMem<1>) / 8 / 4), zopt, gstart, gstep, &gidx);
 #endif
@@ -3270,8 +3213,8 @@ PW_NOINLINE PW_HD inline void wave_window(const Frame& FS, const Frame& R, PW_LD
             // (done, and gidx is the same in every lane: the grid bounded from above first, wave_brute_bounded)
             gbest = 0.0;
         } else if (T::WSIZE == 64) {
-            // a lane's (up to) seven grid points share one pass over the atoms (PW_TILE_GRID of them at a time)
-            constexpr int NP = PW_TILE_GRID;
+            // a lane's (up to) seven grid points share one pass over the atoms (seven fill a 256-register budget)
+            constexpr int NP = 7;
             for (int p0 = 0; p0 < 7; p0 += NP) {
                 double qx[NP], qy[NP], qz[NP], m[NP];
 #pragma unroll
@@ -3321,9 +3264,6 @@ PW_NOINLINE PW_HD inline void wave_window(const Frame& FS, const Frame& R, PW_LD
     double ux = row(cm1, -sm1, 0.0, tx, ty, tz);
     double uy = row(sm1, cm1, 0.0, tx, ty, tz);
     double uz = row(0.0, 0.0, 1.0, tx, ty, tz);
-#ifdef PW_HOST_DEBUG
-    printf("DBG cluster %d vec %.17g %.17g %.17g a1 %.17g a2 %.17g new_z %.17g d0 %.17g zopt %.17g xy %.17g %.17g dfin %.17g\n", cluster, vx, vy, vz, a1, a2, new_z, d0, zopt, xo, yo, dfin);
-#endif
     if (T::lane() == 0) {
         if (pw_unit_debug* dbg = (ws->dbg_base && cluster < PW_W_MAX) ? ws->dbg_base + ws->unit : nullptr) {
             double* wd = dbg->win[cluster];
@@ -3586,7 +3526,7 @@ PW_NOINLINE PW_HD inline void knn_window_group(PTS pts_, int Q4, int P, int grp,
         double thr[NK];
 #pragma unroll
         for (int p = 0; p < NK; ++p) thr[p] = tau;
-PW_PRAGMA(unroll PW_UNROLL_KNN)
+#pragma unroll 2     // (measured: tests/tools/variant_sweep.sh)
         for (int tt = t_lo; tt <= t_hi; ++tt) {
             const int j = k0 + tt;
             if (j < lo || j > hi) continue;
@@ -3636,8 +3576,6 @@ PW_PRAGMA(unroll PW_UNROLL_KNN)
 template <class T>
 PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh, TeamWorkspace* ws, int n, pw_unit_out* out,
                                                                   const pw_params& prm, WinArrays& wa) {
-    PW_ASSUME_TEAM_STATE(sh, prm);
-    PW_DCHECK(__builtin_amdgcn_read_exec() == ~0ull, 111);
     auto& v = *sh.v;
     // shift so that the optimised pore centre (pore_opt) or the centre of mass is the origin
     // (utilities.py:1380-1393)
@@ -3657,7 +3595,6 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
     if (T::wave() == 0) PW_T1(ws, 14, t_pre);
     PW_T0(t_md);
     team_max_dim<T, true>(sh, sh.S, n, 2 * n + 2 <= ws->p_cap ? ws->vals : nullptr);
-    PW_DCHECK(__builtin_amdgcn_read_exec() == ~0ull, 112);
     double radius = v.maxd / 2.0;
     T::sync();
     if (T::wave() == 0) PW_T1(ws, 15, t_md);
@@ -3690,7 +3627,6 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
         T::sync();
         return -1;
     }
-    PW_DCHECK(radius > 1.0 && radius < 1.0e3, 101);
     Sphere sp;
     sp.init(radius, P);
     // per-unit arrays of the sampling stages: LDS scratch first, global workspace otherwise
@@ -4004,7 +3940,6 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
         T::sync();
         int ncand = v.n_surv;
         int evals = 0;
-        PW_DCHECK(ncand >= 0 && ncand <= P, 104);
         if (T::wave() == 0) PW_T1(ws, 30, t_smp);     // rays + compaction
         PW_T0(t_path);
         // whole rounds: one path per thread.  The last, partial round would keep a handful of
@@ -4036,7 +3971,6 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
             const int j = j0 + T::tid();
             const bool have = j < whole;
             const int k = have ? labels[j] : 0;
-            PW_DCHECK(k >= 0 && k < P, 105);
             const double vx = pts[PT(k, 0)], vy = pts[PT(k, 1)], vz = pts[PT(k, 2)];
             const bool listed = cand_w != nullptr &&
                                 wave_path_candidates<T>(sh.S, n, have, vx, vy, vz, prm.increment, m_origin, cand_w, coff_w);
@@ -4256,8 +4190,8 @@ PW_HD inline __attribute__((always_inline)) void stage_windows_impl(UnitShared& 
     T::sync();
 }
 
-// out of line for the kernels that hold several stages; the window launch's own kernel (PW_KERNEL_WINDOWS) inlines the
-// stage -- a kernel saves no callee-saved registers, an out-of-line stage that fills the register file saves a hundred
+// out of line in every kernel, the window launch's own included: inlined there it saves the callee's frame, but the bulk
+// loops are allocated worse and the launch runs 8 % slower (profiles/r05_window_scratch_experiment.md)
 template <class T>
 PW_NOINLINE PW_HD inline void stage_windows(UnitShared& sh, TeamWorkspace* ws, int n, pw_unit_out* out,
                                              const pw_params& prm) {
@@ -4280,10 +4214,7 @@ PW_HD inline void record_or_status(pw_unit_out* out, int st, int evals) {
 #endif
 }
 
-constexpr unsigned PW_KERNEL_AVERAGE = PW_STAGE_AVG | PW_STAGE_MERGE | PW_STAGE_COM_ONLY;
-constexpr unsigned PW_KERNEL_WINDOWS = PW_STAGE_WINDOWS | PW_STAGE_REUSE_OPT | PW_STAGE_MERGE | PW_STAGE_COM_ONLY;
-
-template <class T, unsigned KMASK = 0xffffffffu>
+template <class T>
 PW_HD inline void analyse_unit(UnitShared& sh, TeamWorkspace* ws, int n, const double* xyz,
                                const double* vdw, const double* mass, unsigned stages,
                                pw_unit_out* out, const pw_params& prm, const unsigned char* tmpl = nullptr) {
@@ -4307,23 +4238,13 @@ PW_HD inline void analyse_unit(UnitShared& sh, TeamWorkspace* ws, int n, const d
     }
     PW_T0(t_load);
     load_unit<T>(sh, n, xyz, vdw, mass, tmpl);
-#ifndef PW_TIME_BASIC
     if (T::wave() == 0) PW_T1(ws, 5, t_load);      // (diagnostic builds: slot 5, every launch's load stage together)
-#endif
     if (reuse_opt) {
         // the optimiser launch already wrote the centre of mass
         if (T::tid() == 0) { sh.v->com[0] = out->com[0]; sh.v->com[1] = out->com[1]; sh.v->com[2] = out->com[2]; }
         T::sync();
-    } else if (KMASK == PW_KERNEL_AVERAGE) {
-        stage_basic_impl<T>(sh, ws, n, out, true);
     } else {
-#ifdef PW_TIME_BASIC
-        PW_T0(t_basic);
-#endif
         stage_basic<T>(sh, ws, n, out, (stages & PW_STAGE_COM_ONLY) != 0);
-#ifdef PW_TIME_BASIC
-        if (T::wave() == 0) PW_T1(ws, 5, t_basic);       // (diagnostic: slot 5 is then the basic stage, not the load)
-#endif
     }
     if (stages & PW_STAGE_OPT) stage_opt<T>(sh, ws, n, out, prm);
     if (reuse_opt) {
@@ -4337,8 +4258,7 @@ PW_HD inline void analyse_unit(UnitShared& sh, TeamWorkspace* ws, int n, const d
     }
     if (stages & PW_STAGE_AVG) {
         PW_T0(t_a);
-        if (KMASK == PW_KERNEL_AVERAGE) stage_average_impl<T, true>(sh, ws, n, out, prm);
-        else stage_average<T>(sh, ws, n, out, prm);
+        stage_average<T>(sh, ws, n, out, prm);
         if (T::wave() == 0) PW_T1(ws, 13, t_a);
         if ((stages & PW_STAGE_WINDOWS) && sh.S.x == sh.A.x) {
             // A team that keeps ONE frame has just shifted it in place (to the centre of mass) and the window search
@@ -4355,10 +4275,6 @@ PW_HD inline void analyse_unit(UnitShared& sh, TeamWorkspace* ws, int n, const d
     }
     if (stages & PW_STAGE_WINDOWS) {
         if (!(prm.pore_opt && (sh.v->status & PW_ST_NEGATIVE_PORE))) {
-#ifdef PW_INLINE_WINDOW_STAGE
-            if (KMASK == PW_KERNEL_WINDOWS) stage_windows_impl<T>(sh, ws, n, out, prm);
-            else
-#endif
             stage_windows<T>(sh, ws, n, out, prm);
         }
         else if (T::tid() == 0) out->n_windows = -1;     // no window search: None, whichever launch shape

@@ -475,7 +475,7 @@ def test_other_cages_with_fresh_noise_against_live_oracle(hip_ctx):
 
 def test_every_launch_shape_gives_the_same_records(monkeypatch):
     """One analysis, two launch shapes, the same bytes: the default pipeline (optimiser chains | average diameter
-    | window search, three launches) and PW_FUSED=1 (every stage in one team).  On the real MD frames and on the
+    and window search, two launches) and PW_FUSED=1 (every stage in one team).  On the real MD frames and on the
     static molecules (60 to 468 atoms, none to six windows).  (Round 4's split window search -- a third and fourth
     shape -- was measured 4-25x slower and removed in round 5.)"""
     from pywindow_amd import _lib

@@ -1,6 +1,6 @@
 """rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU counter CSV -> <tag>_instruction_counters.json
    python tests/tools/counter_summary.py counters.csv units out.json
-Wave-level instruction counts per launch, averaged over the dispatches of each of the three launches of
+Wave-level instruction counts per launch, averaged over the dispatches of each of the launches of
 the pipeline (told apart by grid and workgroup size)."""
 import csv
 import json

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Instruction-cache and wait counters of the three launches (one analysis at a time), separate --pmc passes
+# Instruction-cache and wait counters of the pipeline's launches (one analysis at a time), separate --pmc passes
 # (PW_PMC_SETS="A B;C D" replaces the default counter sets).
 #   tests/tools/icache_round.sh <tag>   -> gpurun_out/<tag>/pmc_icache*.csv
 tag=${1:-ic}

@@ -1,7 +1,7 @@
 """rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE counter CSVs -> profiles/<tag>_hbm_traffic.json.
    python tests/tools/traffic_summary.py fetch.csv write.csv units out.json
 Counter values are KB per dispatch; FETCH_SIZE is doubled as MI355X_MICROARCH.md prescribes for
-gfx950.  Dispatches are grouped by (grid, workgroup) = the three launches of the pipeline."""
+gfx950.  Dispatches are grouped by (grid, workgroup) = the launches of the pipeline."""
 import csv
 import json
 import sys
