@@ -395,6 +395,31 @@ int pw_shape_batch(pw_context *ctx, const pw_batch_in *in, pw_shape_out *out);
 int pw_circumcircle(pw_context *ctx, const double *xyz, int64_t n_atoms, const int32_t *atom_sets,
                     int64_t n_sets, double *diameter, double *centre);
 
+/* ---- distributions of analysis results: Gaussian kernel density sums -----------------------------
+ * What the reference's trajectory examples do with the analysis (examples/example_7.py:55-80): the
+ * window / pore / maximum diameters of a trajectory go through scipy.stats.gaussian_kde on a grid.
+ * One call takes n_jobs independent jobs (the per-molecule curves of a modular trajectory are many
+ * small ones); job k has samples x = samples[sample_first .. +n_samples), points
+ * g = points[point_first .. +n_points) and writes the RAW sums
+ *     sums[point_first + j] = sum_i exp(-0.5 * ((g[j] - x[i]) * inv_bandwidth)^2)
+ * The normalisation 1 / (n h sqrt(2 pi)) is the caller's, so that sums of parts of a sample set add.
+ * inv_bandwidth is 1 / h as a double the caller computed once; the product by it IS the definition
+ * (no division is repeated here).  The result is defined to the bit (pywindow_amd/csrc/pw_kde.hpp):
+ * the project's own exp (pw_math.hpp: pw_exp, within 1 ulp, results below the smallest normal are zero),
+ * partial sums over chunks of 512 samples added in order, the chunks' sums added in chunk order -- the
+ * same on every device, launch geometry, run, and on a device == -1 context (host threads).
+ * All pointers are host memory.  A job without samples gives zeros; jobs may share samples and points
+ * but not entries of `sums`.  inv_bandwidth <= 0, or a NaN or infinity in it, the samples or the points
+ * of any job: PW_E_BAD_ARG (pw_last_error names the job), and nothing is launched or written.
+ * Device work is queued on the context's stream; the call returns when the sums are in place. */
+typedef struct pw_kde_job {
+    int64_t sample_first, n_samples;   /* into `samples` */
+    int64_t point_first, n_points;     /* into `points` and `sums` */
+    double inv_bandwidth;              /* 1 / h, h the standard deviation of the kernel */
+} pw_kde_job;
+int pw_kde_sums(pw_context *ctx, const pw_kde_job *jobs, int64_t n_jobs, const double *samples,
+                const double *points, double *sums);
+
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */
 typedef struct pw_history pw_history;

@@ -179,6 +179,12 @@ UNIT_OUT_DTYPE = np.dtype(
     align=True,
 )
 
+#: numpy mirror of ``pw_kde_job``
+KDE_JOB_DTYPE = np.dtype(
+    [("sample_first", np.int64), ("n_samples", np.int64), ("point_first", np.int64), ("n_points", np.int64),
+     ("inv_bandwidth", np.float64)]
+)
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -258,6 +264,7 @@ EXPORTED_SYMBOLS = [
     "pw_resident_from_cells",
     "pw_shape_batch",
     "pw_circumcircle",
+    "pw_kde_sums",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -372,6 +379,7 @@ def load():
                                          ctypes.POINTER(vp), vp, vp]
     L.pw_shape_batch.argtypes = [vp, ctypes.POINTER(BatchIn), vp]
     L.pw_circumcircle.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
+    L.pw_kde_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -623,6 +631,23 @@ class Context:
         if batch.n_units:
             _check(load().pw_shape_batch(self._h, ctypes.byref(batch.c), out.ctypes.data), "pw_shape_batch")
         return out
+
+    def kde_sums(self, jobs, samples, points) -> np.ndarray:
+        """``pw_kde_sums``: the raw Gaussian kernel sums of a batch of jobs (``KDE_JOB_DTYPE`` records indexing the
+        float64 arrays ``samples`` and ``points``); returns the sums, laid out like ``points``.  A bandwidth that
+        is not positive, or a NaN / infinity anywhere, raises ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=KDE_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
+        g = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+        for first, count, size, what in (("sample_first", "n_samples", len(x), "samples"), ("point_first", "n_points", len(g), "points")):
+            if len(jobs) and ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > size)).any():
+                raise IndexError(f"a job reaches outside `{what}`")
+        sums = np.zeros(len(g))
+        rc = load().pw_kde_sums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, sums.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_kde_sums")
+        return sums
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

@@ -229,6 +229,52 @@ PW_NOINLINE PW_HD inline double pw_pow_np(double x, double y) {
     return pw_fma(tmpv, scale, scale);
 }
 
+// ---- exp(x) for x <= 0 ---------------------------------------------------------------------------
+// The Gaussian kernel of the trajectory distributions (pw_kde.hpp) is the one caller.  This is NOT a
+// restatement of any library's exp: it is the project's own definition, and what matters is that the
+// gfx950 build and the -ffp-contract=off host build return the SAME BITS (every operation below is
+// written out, fused multiply-adds only where pw_fma stands) and that the value is accurate.
+// Method: the table-driven scheme of pw_pow_np's second half, on the same 128-entry table of 2^(j/128)
+// as {tail, bits} pairs: x = (128 k + j) ln2/128 + r with |r| <= ln2/256 (Cody-Waite in two parts), a
+// degree-5 polynomial for exp(r) - 1, the result 2^k 2^(j/128) (1 + tail + p(r)) with one final fma.
+// Reduction boundaries: x = (i + 1/2) ln2/128 for integer i (tests/test_kde.py straddles every one
+// down to -745).
+// Accuracy: measured maximum 0.506 ulp against a 64-bit-mantissa exp over the 2.8e6 arguments
+// of tests/test_kde.py (bar: 1 ulp).
+// Range: -inf <= x <= 0.  A result below the smallest normal (x < -708.396..., or a product that
+// rounds below 2^-1022) is FLUSHED TO ZERO: gradual underflow would make the last bits depend on how a
+// target treats subnormals, and 1e-308 of a density is nothing.  Elsewhere: 0 < x < 709 follows the
+// same path and is as accurate, but nothing calls or tests it; x >= 709.78 and NaN give unspecified
+// finite-or-not values, never a trap.
+// `tab`: POW_EXP_TAB, or a copy of it (the device kernel keeps one in LDS -- a per-lane look-up in a
+// 2 KB table is what LDS is for).
+template <class Tab>
+PW_HD inline double pw_exp_tab(double x, Tab tab) {
+    const double InvLn2N = POW_EXP_HEAD[0], Shift = POW_EXP_HEAD[1], NegLn2hiN = POW_EXP_HEAD[2],
+                 NegLn2loN = POW_EXP_HEAD[3], C2 = POW_EXP_HEAD[4], C3 = POW_EXP_HEAD[5], C4 = POW_EXP_HEAD[6],
+                 C5 = POW_EXP_HEAD[7];
+    const double zz = pw_fma(x, InvLn2N, Shift);
+    const uint64_t ki = pw_d2bits(zz);
+    const double kd = zz - Shift;
+    const double r = pw_fma(kd, NegLn2loN, pw_fma(kd, NegLn2hiN, x));
+    const int idx = 2 * (int)(ki & 0x7f);
+    const uint64_t tbits = tab[idx];
+    const uint64_t sbits = tab[idx + 1] + (ki << 45);
+    const double q23 = pw_fma(r, C3, C2);
+    const double tail_r = r + pw_bits2d(tbits);
+    const double r2 = r * r;
+    const double q45 = pw_fma(r, C5, C4);
+    const double acc = pw_fma(q23, r2, tail_r);
+    const double r4 = r2 * r2;
+    const double tmp = pw_fma(q45, r4, acc);
+    const double scale = pw_bits2d(sbits);
+    const double res = pw_fma(tmp, scale, scale);
+    // x below ln(2^-1022): `scale` would be meaningless (its exponent field wrapped)
+    const bool gone = !(x >= -708.3964185322641) || res < 2.2250738585072014e-308;
+    return gone ? 0.0 : res;
+}
+PW_HD inline double pw_exp(double x) { return pw_exp_tab(x, POW_EXP_TAB); }
+
 // x ** 2 and x ** 3 for any finite x (pow's sign handling for integer exponents)
 PW_HD inline double pw_square_np(double x) {
     double a = pw_abs(x);

@@ -91,6 +91,70 @@ class RecordStore:
             out["0" if m < 0 else m] = engine.record_to_properties(rec, self.stages, self._more.get(u))
         return out
 
+    # ---- distributions ---------------------------------------------------------------------
+    #: quantity (the reference's property names) -> (record field, stages of which one must have run, status
+    #: bits that say the unit has no such value)
+    _QUANTITIES = {
+        "maximum_diameter": ("maxd", _lib.STAGE_ALL, 0),
+        "pore_diameter": ("pore_d", _lib.STAGE_ALL, 0),
+        "pore_volume": ("pore_vol", _lib.STAGE_ALL, 0),
+        "average_diameter": ("avg_d", _lib.STAGE_AVG, _lib.ST_POINTS_OVERFLOW),
+        "pore_diameter_opt": ("pore_opt_d", _lib.STAGE_OPT | _lib.STAGE_WINDOWS, _lib.ST_NEGATIVE_PORE),
+        "pore_volume_opt": ("pore_vol_opt", _lib.STAGE_OPT | _lib.STAGE_WINDOWS, _lib.ST_NEGATIVE_PORE),
+        "windows": (None, _lib.STAGE_WINDOWS, 0),
+    }
+
+    def _samples_by_unit(self, quantity: str):
+        """``(values, unit of every value)`` of :meth:`samples`."""
+        if quantity not in self._QUANTITIES:
+            raise KeyError(f"unknown quantity {quantity!r}: one of {sorted(self._QUANTITIES)}")
+        field, stages, missing = self._QUANTITIES[quantity]
+        if not self.stages & stages:
+            raise KeyError(f"{quantity!r} was not computed: the analysis ran without its stage (stages = {self.stages})")
+        recs = self.records
+        if field is not None:
+            units = np.flatnonzero((recs["status"] & missing) == 0) if missing else np.arange(len(recs))
+            return np.array(recs[field][units], dtype=np.float64), units
+        held = np.clip(recs["n_windows"], 0, _lib.W_MAX)
+        mask = np.arange(_lib.W_MAX)[None, :] < held[:, None]
+        unit, index = np.nonzero(mask)
+        values = np.array(recs["win_d"][mask], dtype=np.float64)
+        if len(self.extra):              # the windows a record has no room for, each after its unit's sixteen
+            unit = np.concatenate([unit, self.extra["unit"].astype(np.int64)])
+            index = np.concatenate([index, self.extra["index"].astype(np.int64)])
+            values = np.concatenate([values, self.extra["d"]])
+            order = np.lexsort((index, unit))
+            unit, values = unit[order], values[order]
+        return values, unit
+
+    def samples(self, quantity: str) -> np.ndarray:
+        """Every value of ``quantity`` in the store, in unit order: ``"maximum_diameter"``, ``"pore_diameter"``,
+        ``"pore_volume"``, ``"average_diameter"``, ``"pore_diameter_opt"``, ``"pore_volume_opt"``, or ``"windows"``
+        -- all window diameters, unit by unit in window order, those beyond what a record holds included.  What
+        the reference's examples collect from ``analysis_output`` (examples/example_7.py:53-66).  A unit that has
+        no such value contributes nothing (windows ``None``; a non-porous unit has no optimised pore; a unit
+        whose sampling overflowed has no average diameter); a quantity whose stage never ran is a ``KeyError``."""
+        return self._samples_by_unit(quantity)[0]
+
+    def distribution(self, quantity: str, points=1000, pad: float = 1.0, bw_method="scott", per_molecule: bool = False,
+                     device=None):
+        """Gaussian kernel density estimate of :meth:`samples` (pywindow_amd/distributions.py): a
+        ``Distribution``.  ``points``: an int for ``np.linspace(min - pad, max + pad, points)`` as the reference's
+        examples do, or the grid itself.  ``per_molecule`` (modular stores): ``{molecule: Distribution}``, every
+        molecule's curve on its own grid, all from one batched call."""
+        from . import distributions as D
+
+        values, unit = self._samples_by_unit(quantity)
+        if not per_molecule:
+            return D.gaussian_kde_1d(values, D.grid(values, points, pad), bw_method, device)
+        if not self.modular:
+            raise ValueError("per_molecule needs a modular analysis (the store has one unit per frame)")
+        mol = np.asarray(self.unit_molecule)[unit]
+        keys = [int(m) for m in np.unique(mol)]
+        sets = [values[mol == m] for m in keys]
+        curves = D.gaussian_kde_batch(sets, [D.grid(v, points, pad) for v in sets], bw_method, device)
+        return dict(zip(keys, curves))
+
     # ---- persistence -----------------------------------------------------------------------
     # One file: a 4096-byte header (magic, then JSON: format, stages, record layout, and for every array its
     # dtype, length and byte offset), then the arrays as they lie in memory, each at a 4096-byte boundary.
@@ -115,8 +179,9 @@ class RecordStore:
         head = MAGIC + json.dumps(meta).encode()
         if len(head) > HEADER_BYTES:
             raise ValueError("header too large")
-        # the file is sized first and filled through a memory map: one copy into the page cache, no write() calls
-        # (measured 2x faster than tofile() on the container's disk)
+        # the arrays go out with one sequential write() each, at their offsets (the gaps are holes that read as zeros,
+        # the end is sized afterwards): what a plain dump of the records costs, on any disk.  (Filling the file through
+        # a memory map and flushing it waits for the disk itself and took 2.8x a plain write on a slow one.)
         # ... into a temporary file beside the target, moved over it at the end: the arrays of a store that was LOADED
         # from `path` are read-only memory maps of that very file, and truncating it first would pull the pages from
         # under them (load, then save to the same name); a reader also never sees a half-written file
@@ -126,15 +191,12 @@ class RecordStore:
         fd, tmp = tempfile.mkstemp(prefix=path.name + ".", suffix=".tmp", dir=str(path.parent))
         try:
             with os.fdopen(fd, "wb") as fh:
+                fh.write(head)
+                for k, a in arrays.items():
+                    if a.nbytes:
+                        fh.seek(meta["arrays"][k]["offset"])
+                        fh.write(a.view(np.uint8).reshape(-1).data)
                 fh.truncate(at)
-            out = np.memmap(tmp, dtype=np.uint8, mode="r+", shape=(at,))
-            out[:len(head)] = np.frombuffer(head, dtype=np.uint8)
-            for k, a in arrays.items():
-                if a.nbytes:
-                    o = meta["arrays"][k]["offset"]
-                    out[o:o + a.nbytes] = a.view(np.uint8).reshape(-1)
-            out.flush()
-            del out
             # mkstemp creates the file 0600: give it what open(path, "wb") would have given -- the mode of the file it
             # replaces, else 0666 less the umask
             try:

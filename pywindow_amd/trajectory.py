@@ -270,6 +270,14 @@ class DLPOLY:
             view.attach(store)
         return view.record_store()
 
+    def distribution(self, quantity: str, points=1000, pad: float = 1.0, bw_method="scott", per_molecule: bool = False,
+                     device=None):
+        """Density curve of a quantity over everything analysed or loaded so far -- ``"windows"``,
+        ``"pore_diameter_opt"``, ``"maximum_diameter"``, ... -- what the reference's examples compute with
+        ``scipy.stats.gaussian_kde`` after ``analysis()`` (examples/example_7.py:53-80), summed on the GPU:
+        ``RecordStore.distribution`` of :attr:`analysis_store`."""
+        return self.analysis_store.distribution(quantity, points, pad, bw_method, per_molecule, device)
+
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
         selected frames, without building per-frame dicts."""
