@@ -419,6 +419,31 @@ typedef struct pw_kde_job {
 } pw_kde_job;
 int pw_kde_sums(pw_context *ctx, const pw_kde_job *jobs, int64_t n_jobs, const double *samples,
                 const double *points, double *sums);
+/* The joint distribution of TWO quantities (how the pore moves with the windows over a trajectory): what
+ * scipy.stats.gaussian_kde does with a 2 x n dataset and a mesh of points.  With a full covariance the
+ * kernel does not factor into two one-dimensional sums, hence an entry of its own.  samples and points
+ * are arrays of PAIRS ([.][2]: entry i is samples[2 i], samples[2 i + 1]); sample_first, n_samples,
+ * point_first, n_points count pairs; sums has one double per point.  Job k writes the RAW sums
+ *     sums[point_first + j] = sum_i exp(-0.5 * (z0^2 + z1^2)),
+ *     z0 = dx * w00,  z1 = dx * w10 + dy * w11,  (dx, dy) = point j - sample i
+ * where w00, w10, w11 are the lower-triangular inverse of the Cholesky factor L of the kernel's covariance
+ * (w00 = 1 / l00, w10 = -l10 / (l00 l11), w11 = 1 / l11), three doubles the caller computed once; the caller
+ * divides by n * 2 pi * l00 * l11.  Defined to the bit like pw_kde_sums (pw_kde.hpp: the difference is taken
+ * first and whitened second, z1 and z0^2 + z1^2 are single fused multiply-adds, the same pw_exp, the same
+ * chunks of 512 samples in the same order) -- the same on every device, launch geometry, run and on a
+ * device == -1 context; the partial sums of one call stay within a fixed workspace (64 MiB) whatever the
+ * size of the mesh, and the result does not depend on how the mesh was cut to achieve that.
+ * All pointers are host memory.  A job without samples gives zeros; jobs may share samples and points but
+ * not entries of `sums`.  w00 <= 0, w11 <= 0, or a NaN or infinity in the three factors, the samples or the
+ * points of any job: PW_E_BAD_ARG (pw_last_error names the job and the reason), and nothing is launched or
+ * written.  Device work is queued on the context's stream; the call returns when the sums are in place. */
+typedef struct pw_kde2_job {
+    int64_t sample_first, n_samples;   /* pairs, into `samples` */
+    int64_t point_first, n_points;     /* pairs, into `points`; entries of `sums` */
+    double w00, w10, w11;              /* inverse of the Cholesky factor of the kernel's covariance */
+} pw_kde2_job;
+int pw_kde2_sums(pw_context *ctx, const pw_kde2_job *jobs, int64_t n_jobs, const double *samples,
+                 const double *points, double *sums);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

@@ -14,7 +14,7 @@ import os as _os
 # told before it initialises (harmless if the host application already set it)
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
 
-from .distributions import Distribution, gaussian_kde_1d  # noqa: E402
+from .distributions import Distribution, Distribution2D, gaussian_kde_1d, gaussian_kde_2d  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -32,12 +32,14 @@ from .utilities import (  # noqa: E402
 __all__ = [
     "DLPOLY",
     "Distribution",
+    "Distribution2D",
     "MolecularSystem",
     "Molecule",
     "center_of_mass",
     "find_average_diameter",
     "find_windows",
     "gaussian_kde_1d",
+    "gaussian_kde_2d",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

@@ -185,6 +185,12 @@ KDE_JOB_DTYPE = np.dtype(
      ("inv_bandwidth", np.float64)]
 )
 
+#: numpy mirror of ``pw_kde2_job``
+KDE2_JOB_DTYPE = np.dtype(
+    [("sample_first", np.int64), ("n_samples", np.int64), ("point_first", np.int64), ("n_points", np.int64),
+     ("w00", np.float64), ("w10", np.float64), ("w11", np.float64)]
+)
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -265,6 +271,7 @@ EXPORTED_SYMBOLS = [
     "pw_shape_batch",
     "pw_circumcircle",
     "pw_kde_sums",
+    "pw_kde2_sums",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -380,6 +387,7 @@ def load():
     L.pw_shape_batch.argtypes = [vp, ctypes.POINTER(BatchIn), vp]
     L.pw_circumcircle.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
     L.pw_kde_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
+    L.pw_kde2_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -647,6 +655,24 @@ class Context:
         if rc == -2:
             raise ValueError(load().pw_last_error().decode(errors="replace"))
         _check(rc, "pw_kde_sums")
+        return sums
+
+    def kde2_sums(self, jobs, samples, points) -> np.ndarray:
+        """``pw_kde2_sums``: the raw sums of a batch of two-dimensional Gaussian kernel jobs (``KDE2_JOB_DTYPE``
+        records indexing the rows of the float64 arrays ``samples`` (N, 2) and ``points`` (M, 2) -- any list of
+        points, not only a mesh); returns the M sums.  Factors that are not finite with a positive diagonal, or a
+        NaN / infinity anywhere, raise ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=KDE2_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, 2)
+        g = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+        for first, count, size, what in (("sample_first", "n_samples", len(x), "samples"), ("point_first", "n_points", len(g), "points")):
+            if len(jobs) and ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > size)).any():
+                raise IndexError(f"a job reaches outside `{what}`")
+        sums = np.zeros(len(g))
+        rc = load().pw_kde2_sums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, sums.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_kde2_sums")
         return sums
 
     def circumcircle(self, coordinates, atom_sets):

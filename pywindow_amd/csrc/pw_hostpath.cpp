@@ -189,6 +189,47 @@ extern "C" int pw_hostpath_kde(const pw_kde_job* jobs, long n_jobs, const double
     return PW_OK;
 }
 
+// pw_kde2_sums on the host, the same way: threads over (job, block of points), a point's chunks in order
+extern "C" int pw_hostpath_kde2(const pw_kde2_job* jobs, long n_jobs, const double* samples, const double* points,
+                                double* sums, int threads) {
+    constexpr long BLOCK = 8;                      // points of one piece of work
+    std::vector<long> first((size_t)n_jobs + 1, 0);
+    for (long k = 0; k < n_jobs; ++k) first[k + 1] = first[k] + ((long)jobs[k].n_points + BLOCK - 1) / BLOCK;
+    const long total = first[n_jobs];
+    std::atomic<long> next{0};
+    auto worker = [&]() {
+        long k = 0;
+        for (;;) {
+            const long w = next.fetch_add(1);
+            if (w >= total) break;
+            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
+            const pw_kde2_job& J = jobs[k];
+            const long j0 = (w - first[k]) * BLOCK, j1 = std::min(j0 + BLOCK, (long)J.n_points);
+            const double* xy = samples + 2 * J.sample_first;
+            for (long j = j0; j < j1; ++j) {
+                const double g0 = points[2 * (J.point_first + j)], g1 = points[2 * (J.point_first + j) + 1];
+                double s = 0.0;
+                for (long i0 = 0; i0 < (long)J.n_samples; i0 += KDE_CHUNK) {
+                    const int len = (int)std::min((long)KDE_CHUNK, (long)J.n_samples - i0);
+                    const double p = kde2_chunk_sum(g0, g1, xy + 2 * i0, len, J.w00, J.w10, J.w11, POW_EXP_TAB);
+                    s = i0 == 0 ? p : s + p;
+                }
+                sums[J.point_first + j] = s;
+            }
+        }
+    };
+    if (threads < 1) threads = 1;
+    if ((long)threads > total) threads = (int)std::max(1l, total);
+    if (threads == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+    }
+    return PW_OK;
+}
+
 // pw_exp over an array (test instrumentation, pw_kde.hip: pw_internal_exp)
 extern "C" void pw_hostpath_exp(const double* x, long n, double* y) {
     for (long i = 0; i < n; ++i) y[i] = pw_exp(x[i]);

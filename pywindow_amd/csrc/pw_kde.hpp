@@ -1,5 +1,6 @@
 // pw_kde.hpp -- the raw sums of a one-dimensional Gaussian kernel density estimate
-// (include/pywindow_amd.h: pw_kde_sums), single source for the gfx950 kernels (pw_kde.hip) and the
+// (include/pywindow_amd.h: pw_kde_sums) and, further down, of a two-dimensional one (pw_kde2_sums),
+// single source for the gfx950 kernels (pw_kde.hip) and the
 // host path (pw_hostpath.cpp).  What the reference's trajectory examples do with the analysis: every
 // window / pore / maximum diameter of a trajectory goes through scipy.stats.gaussian_kde on a grid of
 // 1000 points (examples/example_7.py:55-80, example_8.py:50-75).
@@ -36,6 +37,45 @@ template <class Xs, class Tab>
 PW_HD inline double kde_chunk_sum(double g, Xs x, int len, double r, Tab tab) {
     double p = 0.0;
     for (int i = 0; i < len; ++i) p = p + kde_term(g, x[i], r, tab);
+    return p;
+}
+
+// ---- two dimensions: the raw sums of a joint (two-quantity) Gaussian KDE (pw_kde2_sums) ----------------
+// What the examples' scipy.stats.gaussian_kde does with a 2 x n dataset and a mesh of points.
+//
+// DEFINED RESULT.  For a job with samples (x0[i], x1[i]), points (g0[j], g1[j]) and the three doubles
+// w00, w10, w11 -- the lower-triangular inverse of the Cholesky factor of the kernel's covariance, computed
+// ONCE by the caller and part of the definition like r above:
+//
+//     dx = g0[j] - x0[i];  dy = g1[j] - x1[i]                                 (each operation rounded)
+//     z0 = dx * w00;  z1 = fma(dx, w10, dy * w11);  t = fma(z1, z1, z0 * z0)
+//     term(j, i) = pw_exp(-0.5 * t)
+//
+// (difference first, whitening second: whitening samples and points apart and subtracting afterwards loses
+// a digit where the offset is large against the kernel width).  The sum over i is the one above: chunks of
+// KDE_CHUNK samples added one after the other from zero, the chunks' sums added in chunk order.  How the
+// points of a job are cut into slabs to bound the workspace (KDE2_WORKSPACE_BYTES) has no part in it:
+// points are independent.
+constexpr int KDE2_LANE_POINTS = 2;    // mesh points a lane keeps in registers
+constexpr int KDE2_TILE = KDE_WAVE * KDE2_LANE_POINTS;
+constexpr int KDE2_STAGE = 256;        // sample pairs staged in LDS at a time (a chunk goes through in two halves)
+constexpr long KDE2_WORKSPACE_BYTES = 64l << 20;   // partial sums of one launch pair (see pw_kde.hip: kde2_plan)
+
+template <class Tab>
+PW_HD inline double kde2_term(double g0, double g1, double x0, double x1, double w00, double w10, double w11, Tab tab) {
+    const double dx = g0 - x0, dy = g1 - x1;
+    const double z0 = dx * w00;
+    const double z1 = pw_fma(dx, w10, dy * w11);
+    const double t = pw_fma(z1, z1, z0 * z0);
+    return pw_exp_tab(-0.5 * t, tab);
+}
+
+// one point's partial sum over sample pairs [0, len) of a chunk; xy = x0, x1, x0, x1, ...
+template <class Tab>
+PW_HD inline double kde2_chunk_sum(double g0, double g1, const double* xy, int len, double w00, double w10, double w11,
+                                   Tab tab) {
+    double p = 0.0;
+    for (int i = 0; i < len; ++i) p = p + kde2_term(g0, g1, xy[2 * i], xy[2 * i + 1], w00, w10, w11, tab);
     return p;
 }
 

@@ -155,6 +155,49 @@ class RecordStore:
         curves = D.gaussian_kde_batch(sets, [D.grid(v, points, pad) for v in sets], bw_method, device)
         return dict(zip(keys, curves))
 
+    def _pairs_by_unit(self, quantity_x: str, quantity_y: str):
+        """``(values of x, values of y, unit of every pair)`` of :meth:`sample_pairs`."""
+        vx, ux = self._samples_by_unit(quantity_x)
+        vy, uy = self._samples_by_unit(quantity_y)
+        if quantity_x == "windows" and quantity_y == "windows":
+            raise ValueError("'windows' against 'windows': the windows of a unit have no partner among themselves")
+        if quantity_y == "windows":
+            wy, wx, unit = self._pairs_by_unit(quantity_y, quantity_x)
+            return wx, wy, unit
+        # ux: the unit of every value of x (one per unit, or one per window); uy: one per unit, ascending
+        at = np.minimum(np.searchsorted(uy, ux), max(len(uy) - 1, 0))
+        has = uy[at] == ux if len(uy) else np.zeros(len(ux), dtype=bool)
+        return vx[has], vy[at[has]], ux[has]
+
+    def sample_pairs(self, quantity_x: str, quantity_y: str):
+        """``(values of quantity_x, values of quantity_y)``, pair by pair, for a joint distribution.  Two per-unit
+        quantities pair by unit over the units that have BOTH (a non-porous unit has no optimised pore, ...), in
+        unit order.  ``"windows"`` against a per-unit quantity pairs EVERY window diameter with its unit's value --
+        those beyond what a record holds included, in the order :meth:`samples` has.  ``"windows"`` against
+        ``"windows"`` is a ``ValueError``; unknown names and stages that never ran are :meth:`samples`' ``KeyError``."""
+        vx, vy, _ = self._pairs_by_unit(quantity_x, quantity_y)
+        return vx, vy
+
+    def joint_distribution(self, quantity_x: str, quantity_y: str, points=128, pad: float = 1.0, bw_method="scott",
+                           per_molecule: bool = False, device=None):
+        """Two-dimensional Gaussian kernel density estimate of :meth:`sample_pairs` (pywindow_amd/distributions.py):
+        a ``Distribution2D`` with ``density[iy, ix]`` at ``(x[ix], y[iy])``.  ``points``: an int or a pair of ints
+        for ``np.linspace(min - pad, max + pad, .)`` per axis, or the two axes themselves.  ``per_molecule``
+        (modular stores): ``{molecule: Distribution2D}``, every molecule's map on its own mesh, all from one
+        batched call."""
+        from . import distributions as D
+
+        vx, vy, unit = self._pairs_by_unit(quantity_x, quantity_y)
+        if not per_molecule:
+            return D.gaussian_kde_2d(vx, vy, points, bw_method, device, pad)
+        if not self.modular:
+            raise ValueError("per_molecule needs a modular analysis (the store has one unit per frame)")
+        mol = np.asarray(self.unit_molecule)[unit]
+        keys = [int(m) for m in np.unique(mol)]
+        sets = [(vx[mol == m], vy[mol == m]) for m in keys]
+        maps = D.gaussian_kde_2d_batch(sets, [D.grid_2d(sx, sy, points, pad) for sx, sy in sets], bw_method, device)
+        return dict(zip(keys, maps))
+
     # ---- persistence -----------------------------------------------------------------------
     # One file: a 4096-byte header (magic, then JSON: format, stages, record layout, and for every array its
     # dtype, length and byte offset), then the arrays as they lie in memory, each at a 4096-byte boundary.

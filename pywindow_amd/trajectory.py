@@ -278,6 +278,13 @@ class DLPOLY:
         ``RecordStore.distribution`` of :attr:`analysis_store`."""
         return self.analysis_store.distribution(quantity, points, pad, bw_method, per_molecule, device)
 
+    def joint_distribution(self, quantity_x: str, quantity_y: str, points=128, pad: float = 1.0, bw_method="scott",
+                           per_molecule: bool = False, device=None):
+        """Joint density of two quantities over everything analysed or loaded so far -- how the optimised pore moves
+        with the windows, the maximum diameter with the pore -- ``scipy.stats.gaussian_kde`` with a ``2 x n`` dataset
+        on a mesh, summed on the GPU: ``RecordStore.joint_distribution`` of :attr:`analysis_store`."""
+        return self.analysis_store.joint_distribution(quantity_x, quantity_y, points, pad, bw_method, per_molecule, device)
+
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
         selected frames, without building per-frame dicts."""
