@@ -444,6 +444,30 @@ typedef struct pw_kde2_job {
 } pw_kde2_job;
 int pw_kde2_sums(pw_context *ctx, const pw_kde2_job *jobs, int64_t n_jobs, const double *samples,
                  const double *points, double *sums);
+/* ---- dynamics of analysis results: lagged sums of a time correlation ------------------------------------
+ * How long a value of a trajectory lasts and whether one quantity follows another: the raw sums of an auto-
+ * or cross-correlation over the frame axis.  The reference has no counterpart (its examples stop at the
+ * distributions above).  Job k has two series a = series[a_first .. +n), b = series[b_first .. +n) -- the
+ * same range for an autocorrelation -- and writes, for lag j = 0 .. n_lags - 1,
+ *     sums[out_first + j] = sum over t in [0, n - j) of a[t] * b[t + j]
+ * Negative lags are the caller's (swap a and b).  The entry knows nothing of means, gaps or normalisation:
+ * the caller hands over centred series with zeros in the gaps, and gets the number of valid pairs of a lag
+ * from a second job over the two 0/1 masks (sums of ones are exact), so that sums of parts add.
+ * Defined to the bit (pywindow_amd/csrc/pw_corr.hpp): the t axis is cut into chunks of 512 from t = 0
+ * whatever the lag, a chunk's terms are accumulated by fused multiply-adds from zero in t order, the chunks'
+ * sums are added in chunk order -- the same on every device, launch geometry, run and on a device == -1
+ * context (host threads); the partial sums of one call stay within a fixed workspace (64 MiB) whatever the
+ * number of lags, and the result does not depend on how the lags were cut to achieve that.
+ * All pointers are host memory.  Any mix of job sizes in one call; a job with n == 0 writes nothing; jobs may
+ * share entries of `series` but not of `sums`.  n_lags > n, n_lags < 1 with n > 0, or a NaN or infinity in a
+ * series a job reads: PW_E_BAD_ARG (pw_last_error names the job and the reason), and nothing is launched or
+ * written.  Device work is queued on the context's stream, its memory allocated and freed in stream order;
+ * the call returns when the sums are in place. */
+typedef struct pw_corr_job {
+    int64_t a_first, b_first, n;       /* into `series`; a and b may be the same range */
+    int64_t out_first, n_lags;         /* into `sums`; 1 <= n_lags <= n */
+} pw_corr_job;
+int pw_corr_sums(pw_context *ctx, const pw_corr_job *jobs, int64_t n_jobs, const double *series, double *sums);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

@@ -15,6 +15,7 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
 
 from .distributions import Distribution, Distribution2D, gaussian_kde_1d, gaussian_kde_2d  # noqa: E402
+from .correlations import TimeCorrelation, time_correlation, time_correlation_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -40,6 +41,9 @@ __all__ = [
     "find_windows",
     "gaussian_kde_1d",
     "gaussian_kde_2d",
+    "TimeCorrelation",
+    "time_correlation",
+    "time_correlation_batch",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

@@ -191,6 +191,11 @@ KDE2_JOB_DTYPE = np.dtype(
      ("w00", np.float64), ("w10", np.float64), ("w11", np.float64)]
 )
 
+#: numpy mirror of ``pw_corr_job``
+CORR_JOB_DTYPE = np.dtype(
+    [("a_first", np.int64), ("b_first", np.int64), ("n", np.int64), ("out_first", np.int64), ("n_lags", np.int64)]
+)
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -272,6 +277,7 @@ EXPORTED_SYMBOLS = [
     "pw_circumcircle",
     "pw_kde_sums",
     "pw_kde2_sums",
+    "pw_corr_sums",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -388,6 +394,7 @@ def load():
     L.pw_circumcircle.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
     L.pw_kde_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.pw_kde2_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
+    L.pw_corr_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -673,6 +680,30 @@ class Context:
         if rc == -2:
             raise ValueError(load().pw_last_error().decode(errors="replace"))
         _check(rc, "pw_kde2_sums")
+        return sums
+
+    def corr_sums(self, jobs, series) -> np.ndarray:
+        """``pw_corr_sums``: the raw lagged sums ``S[k] = sum_t a[t] b[t + k]`` of a batch of jobs (``CORR_JOB_DTYPE``
+        records indexing the float64 array ``series`` and the result); returns the sums, as long as the furthest
+        ``out_first + n_lags`` of a job (entries no job writes are zero).  ``n_lags`` outside ``1 .. n``, or a NaN /
+        infinity in a series, raises ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=CORR_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
+        size = 0
+        if len(jobs):
+            for first in ("a_first", "b_first"):
+                if ((jobs[first] < 0) | (jobs["n"] < 0) | (jobs[first] + jobs["n"] > len(x))).any():
+                    raise IndexError("a job reaches outside `series`")
+            if (jobs["out_first"] < 0).any():
+                raise IndexError("a job writes before the start of the sums")
+            live = jobs[jobs["n"] > 0]
+            if len(live):
+                size = int(max(0, (live["out_first"] + live["n_lags"]).max()))
+        sums = np.zeros(size)
+        rc = load().pw_corr_sums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, sums.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_corr_sums")
         return sums
 
     def circumcircle(self, coordinates, atom_sets):

@@ -12,6 +12,7 @@
 #define pw pw_cpu          // a namespace of its own: nothing here merges with the HIP translation units' host code
 #include "pw_unit.hpp"
 #include "pw_kde.hpp"
+#include "pw_corr.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -216,6 +217,64 @@ extern "C" int pw_hostpath_kde2(const pw_kde2_job* jobs, long n_jobs, const doub
                 }
                 sums[J.point_first + j] = s;
             }
+        }
+    };
+    if (threads < 1) threads = 1;
+    if ((long)threads > total) threads = (int)std::max(1l, total);
+    if (threads == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+    }
+    return PW_OK;
+}
+
+// pw_corr_sums on the host (pw_corr.hip checks the arguments and sends device == -1 contexts here): the chunks
+// of pw_corr.hpp, a lag's chunks in order, so the sums have the device's bits.  Threads share out blocks of
+// BLOCK consecutive lags; a block's lags go through a chunk side by side (independent accumulators, each in
+// its own t order) as far as the shortest of them reaches, and finish one by one.
+extern "C" int pw_hostpath_corr(const pw_corr_job* jobs, long n_jobs, const double* series, double* sums, int threads) {
+    constexpr long BLOCK = 16;                     // lags of one piece of work
+    std::vector<long> first((size_t)n_jobs + 1, 0);
+    for (long k = 0; k < n_jobs; ++k)
+        first[k + 1] = first[k] + (jobs[k].n ? ((long)jobs[k].n_lags + BLOCK - 1) / BLOCK : 0);
+    const long total = first[n_jobs];
+    std::atomic<long> next{0};
+    auto worker = [&]() {
+        long k = 0;
+        for (;;) {
+            const long w = next.fetch_add(1);
+            if (w >= total) break;
+            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
+            const pw_corr_job& J = jobs[k];
+            const long n = (long)J.n, l0 = (w - first[k]) * BLOCK, l1 = std::min(l0 + BLOCK, (long)J.n_lags);
+            const double* a = series + J.a_first;
+            const double* b = series + J.b_first;
+            double s[BLOCK];
+            for (long c = 0; c * CORR_CHUNK < n - l0; ++c) {
+                const long t0 = c * CORR_CHUNK;
+                double p[BLOCK];
+                for (long j = 0; j < BLOCK; ++j) p[j] = 0.0;
+                long t = 0;
+                if (l1 - l0 == BLOCK) {
+                    const long all = std::max(0l, corr_chunk_len(n, l1 - 1, c));   // terms every lag of the block has
+                    const double* bb = b + t0 + l0;
+                    for (; t < all; ++t) {
+                        const double av = a[t0 + t];
+                        for (long j = 0; j < BLOCK; ++j) p[j] = pw_fma(av, bb[t + j], p[j]);
+                    }
+                }
+                for (long j = 0; j < l1 - l0; ++j) {
+                    const long len = corr_chunk_len(n, l0 + j, c);
+                    if (len <= 0) continue;        // the chunk does not exist for this lag
+                    double q = p[j];
+                    for (long u = t; u < len; ++u) q = pw_fma(a[t0 + u], b[t0 + u + l0 + j], q);
+                    s[j] = c == 0 ? q : s[j] + q;
+                }
+            }
+            for (long j = 0; j < l1 - l0; ++j) sums[J.out_first + l0 + j] = s[j];
         }
     };
     if (threads < 1) threads = 1;

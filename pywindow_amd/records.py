@@ -198,6 +198,80 @@ class RecordStore:
         maps = D.gaussian_kde_2d_batch(sets, [D.grid_2d(sx, sy, points, pad) for sx, sy in sets], bw_method, device)
         return dict(zip(keys, maps))
 
+    # ---- dynamics --------------------------------------------------------------------------
+    #: per-frame reductions of a unit's window diameters, for :meth:`series`
+    _WINDOW_SERIES = ("windows_min", "windows_max", "windows_mean", "n_windows")
+
+    def _value_by_unit(self, quantity: str):
+        """``(value of every unit (nan where it has none), which units have one)``."""
+        n = len(self.records)
+        values, has = np.full(n, np.nan), np.zeros(n, dtype=bool)
+        if quantity == "windows":
+            raise ValueError("'windows' is several values a frame: a series needs one of " + ", ".join(self._WINDOW_SERIES))
+        if quantity not in self._WINDOW_SERIES:
+            v, unit = self._samples_by_unit(quantity)
+            values[unit], has[unit] = v, True
+            return values, has
+        d, unit = self._samples_by_unit("windows")             # unit by unit, in window order
+        count = np.bincount(unit, minlength=n)
+        if quantity == "n_windows":
+            return count.astype(np.float64), np.ones(n, dtype=bool)
+        first = np.cumsum(count) - count
+        for u in np.flatnonzero(count).tolist():
+            w = d[first[u]:first[u] + count[u]]
+            values[u] = w.min() if quantity == "windows_min" else w.max() if quantity == "windows_max" else np.sum(w) / len(w)
+        return values, count > 0
+
+    def series(self, quantity: str, molecule=None):
+        """``(frames, values, valid)``: ``quantity`` along the frame axis.  Every per-unit name of :meth:`samples`, or a
+        per-frame reduction of the windows: ``"windows_min"``, ``"windows_max"``, ``"windows_mean"`` (``np.sum(d) /
+        len(d)`` of the unit's diameters, those beyond what a record holds included) or ``"n_windows"`` (how many there
+        are; 0 is a value).  ``frames = f0 + stride * arange(T)`` from the smallest frame of the store to the largest
+        in steps of the gcd of their differences; units are placed by their frame index, whatever their order in the
+        store.  A frame that is absent, or whose unit has no such value (non-porous, windows ``None``, ...), is a GAP:
+        ``valid[t]`` is ``False`` and ``values[t]`` nan.  Modular stores: ``molecule`` selects the molecule."""
+        values, has = self._value_by_unit(quantity)
+        if self.modular:
+            if molecule is None:
+                raise ValueError("a modular store holds several molecules a frame: say which with molecule=")
+            units = np.flatnonzero(np.asarray(self.unit_molecule) == int(molecule))
+        elif molecule is not None:
+            raise ValueError("molecule= needs a modular analysis (the store has one unit per frame)")
+        else:
+            units = np.arange(len(self.records))
+        f = np.asarray(self.unit_frame)[units]
+        if len(np.unique(f)) < 2:
+            raise ValueError("a series needs at least two frames")
+        if len(np.unique(f)) != len(f):
+            raise ValueError("a frame appears more than once")
+        f0 = int(f.min())
+        stride = int(np.gcd.reduce(f - f0))
+        at = (f - f0) // stride
+        frames = f0 + stride * np.arange(int(at.max()) + 1, dtype=np.int64)
+        out, valid = np.full(len(frames), np.nan), np.zeros(len(frames), dtype=bool)
+        out[at], valid[at] = values[units], has[units]
+        return frames, out, valid
+
+    def correlation(self, quantity: str, other=None, max_lag=None, per_molecule: bool = False, device=None):
+        """Lagged correlation of :meth:`series` over the frames (pywindow_amd/correlations.py): a ``TimeCorrelation``
+        of ``quantity`` with itself, or with ``other`` at later frames; gaps are left out pair by pair.  ``lag`` is in
+        frames.  ``per_molecule`` (modular stores): ``{molecule: TimeCorrelation}``, all from one batched call."""
+        from . import correlations as C
+
+        def pair(molecule):
+            frames, a, va = self.series(quantity, molecule)
+            b, vb = self.series(other, molecule)[1:] if other is not None else (None, None)
+            return int(frames[1] - frames[0]), (a, b, va, vb)
+
+        if not per_molecule:
+            stride, p = pair(None)
+            return C.time_correlation_batch([p], max_lag, device, stride)[0]
+        if not self.modular:
+            raise ValueError("per_molecule needs a modular analysis (the store has one unit per frame)")
+        keys = [int(m) for m in np.unique(self.unit_molecule)]
+        pairs = [pair(m) for m in keys]
+        return dict(zip(keys, C.time_correlation_batch([p for _, p in pairs], max_lag, device, [s for s, _ in pairs])))
+
     # ---- persistence -----------------------------------------------------------------------
     # One file: a 4096-byte header (magic, then JSON: format, stages, record layout, and for every array its
     # dtype, length and byte offset), then the arrays as they lie in memory, each at a 4096-byte boundary.

@@ -285,6 +285,13 @@ class DLPOLY:
         on a mesh, summed on the GPU: ``RecordStore.joint_distribution`` of :attr:`analysis_store`."""
         return self.analysis_store.joint_distribution(quantity_x, quantity_y, points, pad, bw_method, per_molecule, device)
 
+    def correlation(self, quantity: str, other=None, max_lag=None, per_molecule: bool = False, device=None):
+        """Lagged correlation over the frames analysed or loaded so far -- how long the pore keeps its size
+        (``correlation("pore_diameter_opt").time``, ``.n_effective``), whether it follows the windows
+        (``correlation("pore_diameter_opt", "windows_min")``) -- summed on the GPU: ``RecordStore.correlation`` of
+        :attr:`analysis_store`."""
+        return self.analysis_store.correlation(quantity, other, max_lag, per_molecule, device)
+
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
         selected frames, without building per-frame dicts."""
