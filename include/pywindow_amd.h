@@ -444,6 +444,33 @@ typedef struct pw_kde2_job {
 } pw_kde2_job;
 int pw_kde2_sums(pw_context *ctx, const pw_kde2_job *jobs, int64_t n_jobs, const double *samples,
                  const double *points, double *sums);
+/* The one-dimensional sums under MANY weight vectors at once: scipy.stats.gaussian_kde(samples, bw_method,
+ * weights=w) for a reweighted run, and the replicas of a block bootstrap (a replica is the sample set with integer
+ * multiplicities) for an error band.  All replicas share every exponential.  Job k has samples
+ * x = samples[sample_first .. +n_samples), points g = points[point_first .. +n_points), n_replicas weight
+ * vectors laid out sample-major, w[i][b] = weights[weight_first + i * n_replicas + b], and writes, replica-major,
+ *     sums[out_first + b * n_points + j] = sum_i w[i][b] * exp(-0.5 * ((g[j] - x[i]) * inv_bandwidth)^2)
+ * The caller divides by sum_i w[i][b] * h * sqrt(2 pi).  Defined to the bit (pw_kde.hpp): the terms are
+ * pw_kde_sums' own, a chunk of 512 samples is accumulated by fused multiply-adds p = fma(w, term, p) from +0 in
+ * sample order, the chunks' sums are added in chunk order -- the same on every device, launch geometry, run and
+ * on a device == -1 context; a replica's sums do not depend on which other replicas its job carries, and with
+ * all weights 1.0 they are pw_kde_sums' bits.  The partial sums of one call stay within a fixed workspace
+ * (64 MiB) and the result does not depend on how points and replicas were cut to achieve that.
+ * All pointers are host memory.  A job without samples writes zeros, a job without points nothing; jobs may
+ * share samples, points and weights but not entries of `sums`.  n_replicas < 1, inv_bandwidth <= 0, a negative
+ * weight, or a NaN or infinity in inv_bandwidth, the samples, the points or the weights of any job:
+ * PW_E_BAD_ARG (pw_last_error names the job and the reason), and nothing is launched or written.  Device work
+ * is queued on the context's stream, its memory allocated and freed in stream order; the call returns when
+ * the sums are in place. */
+typedef struct pw_kdew_job {
+    int64_t n_samples, n_points, n_replicas;
+    int64_t sample_first, point_first;   /* into `samples` / `points`, as pw_kde_job */
+    int64_t weight_first;                /* into `weights`: w[i * n_replicas + b], sample-major */
+    int64_t out_first;                   /* into `sums`:    S[b * n_points + j], replica-major */
+    double inv_bandwidth;                /* 1 / h */
+} pw_kdew_job;
+int pw_kde_wsums(pw_context *ctx, const pw_kdew_job *jobs, int64_t n_jobs, const double *samples,
+                 const double *points, const double *weights, double *sums);
 /* ---- dynamics of analysis results: lagged sums of a time correlation ------------------------------------
  * How long a value of a trajectory lasts and whether one quantity follows another: the raw sums of an auto-
  * or cross-correlation over the frame axis.  The reference has no counterpart (its examples stop at the

@@ -14,7 +14,15 @@ import os as _os
 # told before it initialises (harmless if the host application already set it)
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "12")
 
-from .distributions import Distribution, Distribution2D, gaussian_kde_1d, gaussian_kde_2d  # noqa: E402
+from .distributions import (  # noqa: E402
+    Distribution,
+    Distribution2D,
+    DistributionBand,
+    block_bootstrap_counts,
+    gaussian_kde_1d,
+    gaussian_kde_2d,
+    gaussian_kde_replicas,
+)
 from .correlations import TimeCorrelation, time_correlation, time_correlation_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
@@ -34,6 +42,9 @@ __all__ = [
     "DLPOLY",
     "Distribution",
     "Distribution2D",
+    "DistributionBand",
+    "block_bootstrap_counts",
+    "gaussian_kde_replicas",
     "MolecularSystem",
     "Molecule",
     "center_of_mass",

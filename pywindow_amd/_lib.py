@@ -191,6 +191,12 @@ KDE2_JOB_DTYPE = np.dtype(
      ("w00", np.float64), ("w10", np.float64), ("w11", np.float64)]
 )
 
+#: numpy mirror of ``pw_kdew_job``
+KDEW_JOB_DTYPE = np.dtype(
+    [("n_samples", np.int64), ("n_points", np.int64), ("n_replicas", np.int64), ("sample_first", np.int64),
+     ("point_first", np.int64), ("weight_first", np.int64), ("out_first", np.int64), ("inv_bandwidth", np.float64)]
+)
+
 #: numpy mirror of ``pw_corr_job``
 CORR_JOB_DTYPE = np.dtype(
     [("a_first", np.int64), ("b_first", np.int64), ("n", np.int64), ("out_first", np.int64), ("n_lags", np.int64)]
@@ -277,6 +283,7 @@ EXPORTED_SYMBOLS = [
     "pw_circumcircle",
     "pw_kde_sums",
     "pw_kde2_sums",
+    "pw_kde_wsums",
     "pw_corr_sums",
     "pw_history_open",
     "pw_history_frames",
@@ -394,6 +401,7 @@ def load():
     L.pw_circumcircle.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp]
     L.pw_kde_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.pw_kde2_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
+    L.pw_kde_wsums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp, vp]
     L.pw_corr_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
@@ -680,6 +688,35 @@ class Context:
         if rc == -2:
             raise ValueError(load().pw_last_error().decode(errors="replace"))
         _check(rc, "pw_kde2_sums")
+        return sums
+
+    def kde_wsums(self, jobs, samples, points, weights) -> np.ndarray:
+        """``pw_kde_wsums``: the raw Gaussian kernel sums of a batch of jobs under many weight vectors each
+        (``KDEW_JOB_DTYPE`` records indexing the float64 arrays ``samples``, ``points`` and ``weights`` -- sample-major,
+        ``w[i * n_replicas + b]`` -- and the result, replica-major ``S[b * n_points + j]``); returns the sums, as long
+        as the furthest ``out_first + n_replicas * n_points`` of a job (entries no job writes are zero).  No replica,
+        a bandwidth that is not positive, a negative weight, or a NaN / infinity anywhere, raises ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=KDEW_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
+        g = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        size = 0
+        if len(jobs):
+            for first, count, limit, what in (("sample_first", "n_samples", len(x), "samples"), ("point_first", "n_points", len(g), "points")):
+                if ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > limit)).any():
+                    raise IndexError(f"a job reaches outside `{what}`")
+            replicas = np.maximum(jobs["n_replicas"], 0)
+            if ((jobs["weight_first"] < 0) | (jobs["weight_first"] + jobs["n_samples"] * replicas > len(w))).any():
+                raise IndexError("a job reaches outside `weights`")
+            if (jobs["out_first"] < 0).any():
+                raise IndexError("a job writes before the start of the sums")
+            size = int((jobs["out_first"] + replicas * jobs["n_points"]).max())
+        sums = np.zeros(size)
+        rc = load().pw_kde_wsums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, w.ctypes.data,
+                                 sums.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_kde_wsums")
         return sums
 
     def corr_sums(self, jobs, series) -> np.ndarray:

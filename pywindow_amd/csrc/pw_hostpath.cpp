@@ -231,6 +231,53 @@ extern "C" int pw_hostpath_kde2(const pw_kde2_job* jobs, long n_jobs, const doub
     return PW_OK;
 }
 
+// pw_kde_wsums on the host (pw_kdew.hip checks the arguments and sends device == -1 contexts here): threads over
+// (job, block of points); a point's term is computed once and goes to every replica's sum, chunks in order
+extern "C" int pw_hostpath_kdew(const pw_kdew_job* jobs, long n_jobs, const double* samples, const double* points,
+                                const double* weights, double* sums, int threads) {
+    constexpr long BLOCK = 8;                      // grid points of one piece of work
+    std::vector<long> first((size_t)n_jobs + 1, 0);
+    for (long k = 0; k < n_jobs; ++k) first[k + 1] = first[k] + ((long)jobs[k].n_points + BLOCK - 1) / BLOCK;
+    const long total = first[n_jobs];
+    std::atomic<long> next{0};
+    auto worker = [&]() {
+        long k = 0;
+        std::vector<double> s, p;
+        for (;;) {
+            const long w = next.fetch_add(1);
+            if (w >= total) break;
+            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
+            const pw_kdew_job& J = jobs[k];
+            const long n = (long)J.n_samples, m = (long)J.n_points, nb = (long)J.n_replicas;
+            const long j0 = (w - first[k]) * BLOCK, j1 = std::min(j0 + BLOCK, m);
+            const double* x = samples + J.sample_first;
+            const double* wt = weights + J.weight_first;
+            s.assign((size_t)nb, 0.0);
+            p.assign((size_t)nb, 0.0);
+            for (long j = j0; j < j1; ++j) {
+                const double g = points[J.point_first + j];
+                for (long b = 0; b < nb; ++b) s[b] = 0.0;
+                for (long i0 = 0; i0 < n; i0 += KDE_CHUNK) {
+                    const int len = (int)std::min((long)KDE_CHUNK, n - i0);
+                    kdew_chunk_sums(g, x + i0, wt + i0 * nb, nb, len, nb, J.inv_bandwidth, POW_EXP_TAB, p.data());
+                    for (long b = 0; b < nb; ++b) s[b] = i0 == 0 ? p[b] : s[b] + p[b];
+                }
+                for (long b = 0; b < nb; ++b) sums[J.out_first + b * m + j] = s[b];
+            }
+        }
+    };
+    if (threads < 1) threads = 1;
+    if ((long)threads > total) threads = (int)std::max(1l, total);
+    if (threads == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+    }
+    return PW_OK;
+}
+
 // pw_corr_sums on the host (pw_corr.hip checks the arguments and sends device == -1 contexts here): the chunks
 // of pw_corr.hpp, a lag's chunks in order, so the sums have the device's bits.  Threads share out blocks of
 // BLOCK consecutive lags; a block's lags go through a chunk side by side (independent accumulators, each in

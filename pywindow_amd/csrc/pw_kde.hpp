@@ -1,6 +1,7 @@
 // pw_kde.hpp -- the raw sums of a one-dimensional Gaussian kernel density estimate
-// (include/pywindow_amd.h: pw_kde_sums) and, further down, of a two-dimensional one (pw_kde2_sums),
-// single source for the gfx950 kernels (pw_kde.hip) and the
+// (include/pywindow_amd.h: pw_kde_sums) and, further down, of a two-dimensional one (pw_kde2_sums) and of the
+// one-dimensional one under many weight vectors (pw_kde_wsums),
+// single source for the gfx950 kernels (pw_kde.hip, pw_kdew.hip) and the
 // host path (pw_hostpath.cpp).  What the reference's trajectory examples do with the analysis: every
 // window / pore / maximum diameter of a trajectory goes through scipy.stats.gaussian_kde on a grid of
 // 1000 points (examples/example_7.py:55-80, example_8.py:50-75).
@@ -77,6 +78,39 @@ PW_HD inline double kde2_chunk_sum(double g0, double g1, const double* xy, int l
     double p = 0.0;
     for (int i = 0; i < len; ++i) p = p + kde2_term(g0, g1, xy[2 * i], xy[2 * i + 1], w00, w10, w11, tab);
     return p;
+}
+
+// ---- weights: the raw sums of a one-dimensional KDE under many weight vectors at once (pw_kde_wsums) -----
+// scipy.stats.gaussian_kde(samples, bw_method, weights=w), and the replicas of a block bootstrap: a replica is
+// the sample set with integer multiplicities, i.e. a weight vector, and all replicas share every exponential.
+//
+// DEFINED RESULT.  For a job with samples x[0..n), points g[0..m), R weight vectors w[i][b] (sample-major:
+// weights[i * R + b]) and r = inv_bandwidth, with term(j, i) the kde_term above, unchanged:
+//
+//     part(c, b, j): p = +0;  p = pw_fma(w[i][b], term(j, i), p)  for i over chunk c in sample order
+//     S[b][j]      = (part(0, b, j) + part(1, b, j)) + part(2, b, j) + ...       in chunk order
+//
+// with the chunks the KDE_CHUNK samples counted from sample 0, as above.  A replica's sum is its own: it does
+// not depend on which other replicas the job carries, on how points and replicas are cut into tiles and slabs
+// (KDEW_WORKSPACE_BYTES), on the launch geometry or on the host's threads.  With all weights 1.0 the bits are
+// pw_kde_sums': fma(1, e, p) is p + e.  The caller divides by sum_i w[i][b] * h * sqrt(2 pi).
+constexpr int KDEW_LANE_POINTS = 2;    // grid points a lane keeps in registers
+constexpr int KDEW_TILE = KDE_WAVE * KDEW_LANE_POINTS;   // grid points of one work item
+constexpr int KDEW_REPLICAS = 32;      // replicas of one work item: a lane holds KDEW_LANE_POINTS x KDEW_REPLICAS sums
+constexpr int KDEW_GROUP = 8;          // replicas a cut-short replica tile goes through at a time
+constexpr long KDEW_WORKSPACE_BYTES = 64l << 20;   // partial sums of one launch pair (see pw_kdew.hip: kdew_plan)
+
+// one point's partial sums over samples [0, len) of a chunk under nb weight vectors: p[b], b < nb;
+// w: the first sample's weights, stride doubles from one sample to the next
+template <class Tab>
+PW_HD inline void kdew_chunk_sums(double g, const double* x, const double* w, long stride, int len, long nb, double r,
+                                  Tab tab, double* p) {
+    for (long b = 0; b < nb; ++b) p[b] = 0.0;
+    for (int i = 0; i < len; ++i) {
+        const double e = kde_term(g, x[i], r, tab);
+        const double* wi = w + (long)i * stride;
+        for (long b = 0; b < nb; ++b) p[b] = pw_fma(wi[b], e, p[b]);
+    }
 }
 
 PW_HD inline bool kde_finite(double v) { return (pw_d2bits(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }

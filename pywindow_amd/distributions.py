@@ -7,7 +7,12 @@ n x m sum of Gaussians is computed by ``pw_kde_sums`` (include/pywindow_amd.h; c
 curves in one launch -- and normalised here.  The bandwidth is SciPy's, to the bit (see
 :func:`bandwidth`); the curve agrees with SciPy's to rounding ("Trajectory distributions").
 
-* :func:`gaussian_kde_1d` -- one curve;  :func:`gaussian_kde_batch` -- many curves, one launch.
+* :func:`gaussian_kde_1d` -- one curve;  :func:`gaussian_kde_batch` -- many curves, one launch; both take
+  ``weights=`` (SciPy's), which go through ``pw_kde_wsums``.
+* :func:`gaussian_kde_replicas` -- one sample set under many weight vectors at a fixed bandwidth, every exponential
+  computed once (``pw_kde_wsums``);  :func:`block_bootstrap_counts` -- the weight vectors of a circular moving-block
+  bootstrap;  ``RecordStore.distribution_band`` / ``DLPOLY.distribution_band`` -> :class:`DistributionBand`, a curve
+  with a pointwise error band that knows how correlated the frames are.
 * :func:`gaussian_kde_2d` -- the joint density of two quantities on a mesh (``gaussian_kde`` with a ``2 x n``
   dataset; ``pw_kde2_sums``);  :func:`gaussian_kde_2d_batch` -- many maps, one call.
 * ``RecordStore.samples`` / ``.distribution`` / ``.sample_pairs`` / ``.joint_distribution`` (records.py) and
@@ -23,8 +28,9 @@ import numpy as np
 
 from . import _lib, engine
 
-__all__ = ["Distribution", "Distribution2D", "bandwidth", "bandwidth_2d", "gaussian_kde_1d", "gaussian_kde_batch",
-           "gaussian_kde_2d", "gaussian_kde_2d_batch", "grid", "grid_2d"]
+__all__ = ["Distribution", "Distribution2D", "DistributionBand", "bandwidth", "bandwidth_2d", "block_bootstrap_counts",
+           "gaussian_kde_1d", "gaussian_kde_batch", "gaussian_kde_2d", "gaussian_kde_2d_batch", "gaussian_kde_replicas",
+           "gaussian_kde_replicas_batch", "grid", "grid_2d"]
 
 
 @dataclasses.dataclass(frozen=True)
@@ -39,7 +45,39 @@ class Distribution:
     factor: float
 
 
-def bandwidth(samples, bw_method="scott") -> tuple[float, float]:
+@dataclasses.dataclass(frozen=True)
+class DistributionBand:
+    """A density curve with a pointwise bootstrap band: ``density`` is the :class:`Distribution`'s own, ``lower`` and
+    ``upper`` the ``(1 - level) / 2`` and ``1 - (1 - level) / 2`` quantiles over ``replicas`` block-bootstrap replicas
+    (blocks of ``block`` steps of the frame axis), each a KDE of the resampled set at the ORIGINAL ``bandwidth``."""
+
+    x: np.ndarray
+    density: np.ndarray
+    lower: np.ndarray
+    upper: np.ndarray
+    n: int
+    bandwidth: float
+    factor: float
+    replicas: int
+    block: int
+    level: float
+
+
+def _weights(weights, n: int) -> np.ndarray:
+    """The weights of ``n`` samples as SciPy keeps them: a float array divided by its sum."""
+    w = np.atleast_1d(weights).astype(float)
+    if w.ndim != 1 or len(w) != n:
+        raise ValueError(f"one weight per sample: {n} samples, weights of shape {w.shape}")
+    if not np.isfinite(w).all() or (w < 0.0).any():
+        raise ValueError("the weights must be finite and not negative")
+    total = np.sum(w)
+    if not total > 0.0:
+        raise ValueError("the weights sum to zero")
+    w /= total
+    return w
+
+
+def bandwidth(samples, bw_method="scott", weights=None) -> tuple[float, float]:
     """``(h, factor)`` with SciPy's meaning of ``bw_method``: ``"scott"`` (``n**-0.2``), ``"silverman"``
     (``(3n/4)**-0.2``) or a positive float, the factor itself; ``h**2`` is the factor squared times the sample
     variance (``ddof=1``).
@@ -47,14 +85,19 @@ def bandwidth(samples, bw_method="scott") -> tuple[float, float]:
     ``h`` equals ``sqrt(scipy.stats.gaussian_kde(samples, bw_method).covariance[0, 0])`` bit for bit, which
     fixes the route: SciPy takes the variance with uniform weights ``1/n`` (``np.cov(..., aweights=...)``),
     counts the samples as ``1 / sum(weights**2)`` -- not always exactly ``n`` -- and scales the variance, not
-    its root.  Fewer than two samples, or samples that are all equal, raise ``ValueError``."""
+    its root.  Fewer than two samples, or samples that are all equal, raise ``ValueError``.
+
+    ``weights`` (one per sample, not negative): ``h`` equals ``sqrt(gaussian_kde(samples, bw_method,
+    weights=weights).covariance[0, 0])`` bit for bit by the same route -- the weights divided by their sum, the samples
+    counted as ``neff = 1 / sum(w**2)``, ``np.cov(aweights=w)``.  Weights of the wrong length, negative, not finite or
+    summing to zero raise ``ValueError``."""
     x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
     n = len(x)
     if n < 2:
         raise ValueError(f"a density estimate needs at least two samples, got {n}")
     if not np.isfinite(x).all():
         raise ValueError("the samples contain NaN or infinity")
-    weights = np.ones(n) / n
+    weights = np.ones(n) / n if weights is None else _weights(weights, n)
     neff = 1.0 / np.sum(weights ** 2)
     if isinstance(bw_method, str):
         if bw_method == "scott":
@@ -76,37 +119,124 @@ def bandwidth(samples, bw_method="scott") -> tuple[float, float]:
     return h, float(factor)
 
 
-def gaussian_kde_batch(sample_sets, point_sets, bw_method="scott", device=None) -> list:
+def gaussian_kde_batch(sample_sets, point_sets, bw_method="scott", device=None, weights=None) -> list:
     """One :class:`Distribution` per (samples, points) pair, all from ONE ``pw_kde_sums`` call.  ``device``:
-    the HIP ordinal (``None``: the process's, ``engine.resolve_device``); ``-1`` the explicit host path."""
+    the HIP ordinal (``None``: the process's, ``engine.resolve_device``); ``-1`` the explicit host path.
+    ``weights``: a list with one array of weights (SciPy's ``weights=``) or ``None`` per set; the weighted sets go
+    through one ``pw_kde_wsums`` call, the others through ``pw_kde_sums`` as before."""
     xs = [np.ascontiguousarray(s, dtype=np.float64).reshape(-1) for s in sample_sets]
     gs = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1) for p in point_sets]
     if len(xs) != len(gs):
         raise ValueError("one set of points per set of samples")
-    hs = [bandwidth(x, bw_method) for x in xs]
+    ws = [None] * len(xs) if weights is None else list(weights)
+    if len(ws) != len(xs):
+        raise ValueError("one array of weights, or None, per set of samples")
+    hs = [bandwidth(x, bw_method, w) for x, w in zip(xs, ws)]
     for g in gs:
         if not np.isfinite(g).all():
             raise ValueError("the points contain NaN or infinity")
-    jobs = np.zeros(len(xs), dtype=_lib.KDE_JOB_DTYPE)
-    jobs["n_samples"] = [len(x) for x in xs]
-    jobs["n_points"] = [len(g) for g in gs]
-    jobs["sample_first"] = np.cumsum(jobs["n_samples"]) - jobs["n_samples"]
-    jobs["point_first"] = np.cumsum(jobs["n_points"]) - jobs["n_points"]
-    jobs["inv_bandwidth"] = [1.0 / h for h, _ in hs]
     if not len(xs):
         return []
-    sums = engine.context(device).kde_sums(jobs, np.concatenate(xs), np.concatenate(gs))
-    out = []
-    for job, g, (h, factor) in zip(jobs, gs, hs):
-        n = int(job["n_samples"])
-        s = sums[int(job["point_first"]):int(job["point_first"]) + len(g)]
-        out.append(Distribution(g, s / (n * h * math.sqrt(2.0 * math.pi)), n, h, factor))
+    out = [None] * len(xs)
+    plain = [k for k, w in enumerate(ws) if w is None]
+    if plain:
+        jobs = np.zeros(len(plain), dtype=_lib.KDE_JOB_DTYPE)
+        jobs["n_samples"] = [len(xs[k]) for k in plain]
+        jobs["n_points"] = [len(gs[k]) for k in plain]
+        jobs["sample_first"] = np.cumsum(jobs["n_samples"]) - jobs["n_samples"]
+        jobs["point_first"] = np.cumsum(jobs["n_points"]) - jobs["n_points"]
+        jobs["inv_bandwidth"] = [1.0 / hs[k][0] for k in plain]
+        sums = engine.context(device).kde_sums(jobs, np.concatenate([xs[k] for k in plain]), np.concatenate([gs[k] for k in plain]))
+        for job, k in zip(jobs, plain):
+            n, (h, factor) = int(job["n_samples"]), hs[k]
+            s = sums[int(job["point_first"]):int(job["point_first"]) + len(gs[k])]
+            out[k] = Distribution(gs[k], s / (n * h * math.sqrt(2.0 * math.pi)), n, h, factor)
+    heavy = [k for k, w in enumerate(ws) if w is not None]
+    if heavy:
+        rows = [_weights(ws[k], len(xs[k]))[None, :] for k in heavy]
+        curves = gaussian_kde_replicas_batch([xs[k] for k in heavy], [gs[k] for k in heavy], rows, [hs[k][0] for k in heavy], device)
+        for k, c in zip(heavy, curves):
+            out[k] = Distribution(gs[k], c[0], len(xs[k]), hs[k][0], hs[k][1])
     return out
 
 
-def gaussian_kde_1d(samples, points, bw_method="scott", device=None) -> Distribution:
-    """``scipy.stats.gaussian_kde(samples, bw_method)(points)`` for one-dimensional samples, summed on the GPU."""
-    return gaussian_kde_batch([samples], [points], bw_method, device)[0]
+def gaussian_kde_1d(samples, points, bw_method="scott", device=None, weights=None) -> Distribution:
+    """``scipy.stats.gaussian_kde(samples, bw_method, weights=weights)(points)`` for one-dimensional samples, summed
+    on the GPU."""
+    return gaussian_kde_batch([samples], [points], bw_method, device, None if weights is None else [weights])[0]
+
+
+def gaussian_kde_replicas_batch(sample_sets, point_sets, weight_sets, bandwidths, device=None) -> list:
+    """One ``(R_k, m_k)`` array of densities per (samples ``(n_k,)``, points ``(m_k,)``, weights ``(R_k, n_k)``,
+    bandwidth ``h_k``), all from ONE ``pw_kde_wsums`` call: row ``b`` is the KDE of the samples under the weights
+    ``weights[b]`` -- each row normalised by its own sum -- with a Gaussian kernel of standard deviation ``h_k``.  Every
+    exponential is computed once and shared by the set's rows."""
+    xs = [np.ascontiguousarray(s, dtype=np.float64).reshape(-1) for s in sample_sets]
+    gs = [np.ascontiguousarray(p, dtype=np.float64).reshape(-1) for p in point_sets]
+    ws = [np.ascontiguousarray(w, dtype=np.float64) for w in weight_sets]
+    hs = [float(h) for h in bandwidths]
+    if not (len(xs) == len(gs) == len(ws) == len(hs)):
+        raise ValueError("one set of points, one array of weights and one bandwidth per set of samples")
+    norms = []
+    for x, g, w, h in zip(xs, gs, ws, hs):
+        if w.ndim != 2 or w.shape[1] != len(x) or w.shape[0] < 1:
+            raise ValueError(f"the weights of {len(x)} samples are an (R, {len(x)}) array with R >= 1, got shape {w.shape}")
+        if not (np.isfinite(x).all() and np.isfinite(g).all()):
+            raise ValueError("the samples or the points contain NaN or infinity")
+        if not np.isfinite(w).all() or (w < 0.0).any():
+            raise ValueError("the weights must be finite and not negative")
+        if not (math.isfinite(h) and h > 0.0):
+            raise ValueError("the bandwidth is not a positive finite number")
+        total = np.sum(w, axis=1)
+        if not (total > 0.0).all():
+            raise ValueError("a row of weights sums to zero")
+        norms.append(total * (h * math.sqrt(2.0 * math.pi)))
+    if not xs:
+        return []
+    jobs = np.zeros(len(xs), dtype=_lib.KDEW_JOB_DTYPE)
+    jobs["n_samples"] = [len(x) for x in xs]
+    jobs["n_points"] = [len(g) for g in gs]
+    jobs["n_replicas"] = [w.shape[0] for w in ws]
+    jobs["sample_first"] = np.cumsum(jobs["n_samples"]) - jobs["n_samples"]
+    jobs["point_first"] = np.cumsum(jobs["n_points"]) - jobs["n_points"]
+    sizes = jobs["n_samples"] * jobs["n_replicas"]
+    jobs["weight_first"] = np.cumsum(sizes) - sizes
+    sizes = jobs["n_points"] * jobs["n_replicas"]
+    jobs["out_first"] = np.cumsum(sizes) - sizes
+    jobs["inv_bandwidth"] = [1.0 / h for h in hs]
+    # (sample-major for the kernel: a sample's weights under all replicas lie side by side)
+    sums = engine.context(device).kde_wsums(jobs, np.concatenate(xs), np.concatenate(gs),
+                                            np.concatenate([np.ascontiguousarray(w.T).reshape(-1) for w in ws]))
+    out = []
+    for job, g, w, norm in zip(jobs, gs, ws, norms):
+        first = int(job["out_first"])
+        out.append(sums[first:first + w.shape[0] * len(g)].reshape(w.shape[0], len(g)) / norm[:, None])
+    return out
+
+
+def gaussian_kde_replicas(samples, points, weights, bandwidth, device=None) -> np.ndarray:
+    """``(R, m)`` densities: the KDE of ``samples`` at ``points`` under each of the ``R`` rows of ``weights`` (``(R, n)``,
+    each row normalised by its own sum; a row that sums to zero is a ``ValueError``) with a Gaussian kernel of standard
+    deviation ``bandwidth``.  The replicas of a bootstrap are such rows: integer multiplicities."""
+    return gaussian_kde_replicas_batch([samples], [points], [weights], [bandwidth], device)[0]
+
+
+def block_bootstrap_counts(n_times: int, block: int, replicas: int, seed=0) -> np.ndarray:
+    """``(replicas, n_times)`` int64: how often every time of a series of ``n_times`` steps is drawn by each replica of
+    a CIRCULAR MOVING-BLOCK bootstrap.  A replica takes ``ceil(n_times / block)`` blocks of ``block`` consecutive
+    times, their starts drawn by ``np.random.default_rng(seed).integers(0, n_times, (replicas, blocks))``; blocks wrap
+    round the end of the series and the last one is cut so that every row sums to exactly ``n_times``.  ``block = 1``
+    is the ordinary bootstrap; ``block`` about twice the correlation time keeps the dependence of neighbouring frames
+    inside the blocks."""
+    n_times, block, replicas = int(n_times), int(block), int(replicas)
+    if n_times < 1 or block < 1 or replicas < 1:
+        raise ValueError("n_times, block and replicas must be at least 1")
+    blocks = -(-n_times // block)
+    starts = np.random.default_rng(seed).integers(0, n_times, (replicas, blocks))
+    step = np.arange(n_times)                                    # the draws of a replica, in order: block, offset in it
+    drawn = (starts[:, step // block] + step % block) % n_times
+    rows = np.repeat(np.arange(replicas), n_times)
+    return np.bincount(rows * n_times + drawn.reshape(-1), minlength=replicas * n_times).reshape(replicas, n_times).astype(np.int64)
 
 
 def grid(samples, points=1000, pad: float = 1.0) -> np.ndarray:

@@ -155,6 +155,65 @@ class RecordStore:
         curves = D.gaussian_kde_batch(sets, [D.grid(v, points, pad) for v in sets], bw_method, device)
         return dict(zip(keys, curves))
 
+    def distribution_band(self, quantity: str, points=1000, pad: float = 1.0, bw_method="scott", replicas: int = 200,
+                          block=None, level: float = 0.95, seed=0, per_molecule: bool = False, device=None):
+        """:meth:`distribution` with a pointwise error band (pywindow_amd/distributions.py): a ``DistributionBand``
+        whose ``density`` is :meth:`distribution`'s, bit for bit.  The band is a circular moving-block bootstrap over
+        the frame axis of :meth:`series`: ``replicas`` times, blocks of ``block`` consecutive frames are drawn until
+        the series is full again, a sample weighs as often as its frame was drawn (every window of a frame with its
+        frame; gap frames carry no samples), and the KDE is redone at the ORIGINAL bandwidth -- all replicas in one
+        ``pw_kde_wsums`` call that computes every exponential once.  ``lower`` / ``upper`` are ``np.quantile`` over the
+        replicas at ``(1 - level) / 2`` and ``1 - (1 - level) / 2``.  ``block=None``: ``max(1, ceil(2 * time))`` with
+        ``time`` the correlation time of ``correlation(quantity)`` (of ``"windows_mean"`` for ``"windows"``), so that
+        frames that are not independent stay together; ``block=1`` is the ordinary bootstrap, which takes every frame
+        for independent.  A replica that drew no sample is left out; ``.replicas`` is the number used.
+        ``per_molecule`` (modular stores): ``{molecule: DistributionBand}``, all molecules in one batched call."""
+        import math
+
+        from . import distributions as D
+
+        replicas = int(replicas)
+        if replicas < 1:
+            raise ValueError("replicas must be at least 1")
+        if not 0.0 < float(level) < 1.0:
+            raise ValueError("level must lie between 0 and 1")
+        if block is not None and int(block) < 1:
+            raise ValueError("block must be at least 1 frame")
+        values, unit = self._samples_by_unit(quantity)
+        if per_molecule and not self.modular:
+            raise ValueError("per_molecule needs a modular analysis (the store has one unit per frame)")
+        curves = self.distribution(quantity, points, pad, bw_method, per_molecule, device)
+        along = "windows_mean" if quantity == "windows" else quantity
+        if per_molecule:
+            mol = np.asarray(self.unit_molecule)[unit]
+            keys = sorted(curves)
+            picks = [np.flatnonzero(mol == m) for m in keys]
+            times = None if block is not None else self.correlation(along, per_molecule=True, device=device)
+        else:
+            keys, picks, curves = [None], [np.arange(len(values))], {None: curves}
+            times = None if block is not None else {None: self.correlation(along, device=device)}
+        weights, blocks = [], []
+        for m, pick in zip(keys, picks):
+            frames = self.series(along, m)[0]
+            length = int(block) if block is not None else max(1, math.ceil(2.0 * times[m].time))
+            counts = D.block_bootstrap_counts(len(frames), length, replicas, seed)
+            stride = int(frames[1] - frames[0])
+            w = counts[:, (np.asarray(self.unit_frame)[unit[pick]] - int(frames[0])) // stride].astype(np.float64)
+            w = w[w.sum(axis=1) > 0.0]
+            if not len(w):
+                raise ValueError("no replica drew a sample")
+            weights.append(w)
+            blocks.append(length)
+        dens = D.gaussian_kde_replicas_batch([values[p] for p in picks], [curves[m].x for m in keys], weights,
+                                             [curves[m].bandwidth for m in keys], device)
+        lo, hi = (1.0 - float(level)) / 2.0, 1.0 - (1.0 - float(level)) / 2.0
+        out = {}
+        for m, d, w, length in zip(keys, dens, weights, blocks):
+            c = curves[m]
+            out[m] = D.DistributionBand(c.x, c.density, np.quantile(d, lo, axis=0), np.quantile(d, hi, axis=0), c.n,
+                                        c.bandwidth, c.factor, len(w), length, float(level))
+        return out if per_molecule else out[None]
+
     def _pairs_by_unit(self, quantity_x: str, quantity_y: str):
         """``(values of x, values of y, unit of every pair)`` of :meth:`sample_pairs`."""
         vx, ux = self._samples_by_unit(quantity_x)

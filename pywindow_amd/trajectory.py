@@ -278,6 +278,14 @@ class DLPOLY:
         ``RecordStore.distribution`` of :attr:`analysis_store`."""
         return self.analysis_store.distribution(quantity, points, pad, bw_method, per_molecule, device)
 
+    def distribution_band(self, quantity: str, points=1000, pad: float = 1.0, bw_method="scott", replicas: int = 200,
+                          block=None, level: float = 0.95, seed=0, per_molecule: bool = False, device=None):
+        """:meth:`distribution` with a pointwise error band that knows how correlated the frames are: a circular
+        moving-block bootstrap over the frame axis (``block=None``: twice the correlation time of the quantity), all
+        replicas from one call on the GPU: ``RecordStore.distribution_band`` of :attr:`analysis_store`."""
+        return self.analysis_store.distribution_band(quantity, points, pad, bw_method, replicas, block, level, seed,
+                                                     per_molecule, device)
+
     def joint_distribution(self, quantity_x: str, quantity_y: str, points=128, pad: float = 1.0, bw_method="scott",
                            per_molecule: bool = False, device=None):
         """Joint density of two quantities over everything analysed or loaded so far -- how the optimised pore moves
