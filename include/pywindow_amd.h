@@ -495,6 +495,37 @@ typedef struct pw_corr_job {
     int64_t out_first, n_lags;         /* into `sums`; 1 <= n_lags <= n */
 } pw_corr_job;
 int pw_corr_sums(pw_context *ctx, const pw_corr_job *jobs, int64_t n_jobs, const double *series, double *sums);
+/* ---- spectra of analysis results: sums of a series against cosines and sines at rational frequencies ----
+ * At which frequency a cage breathes: the raw sums of a (Lomb-Scargle) periodogram over the frame axis.  The
+ * reference has no counterpart.  Job k has a series a = series[a_first .. +n), a period M and n_freq integer
+ * numerators j_q = j_first + q * j_step -- frequency j_q / M cycles per sample -- and writes, for q < n_freq,
+ *     re[out_first + q] = sum over t in [0, n) of a[t] cos(2 pi j_q t / M)
+ *     im[out_first + q] = sum over t in [0, n) of a[t] sin(2 pi j_q t / M)
+ * The entry knows nothing of means, gaps or normalisation: the caller hands over a centred series with zeros
+ * in the gaps and transforms the 0/1 mask with further jobs (at j and at 2 j: j_step = 2).
+ * Defined to the bit (pywindow_amd/csrc/pw_dft.hpp): the phase of an integer k is q = (j k) mod M in 64-bit
+ * integers, folded to q - M when 2 q >= M, u = (double)q / (double)M, ang = u * 6.283185307179586, and its
+ * (sine, cosine) pw_sincos(ang) -- the phases are exact integers, so the angle never exceeds pi.  The t axis is
+ * cut into chunks of 512 from t = 0; inside chunk ch, with r = t - 512 ch and (cA, sA) the phase of k = r,
+ * pc = fma(a[t], cA[r], pc) and ps = fma(a[t], sA[r], ps) from +0 in r order; with (cB, sB) the phase of
+ * k = 512 ch, re_ch = fma(cB, pc, -(sB * ps)) and im_ch = fma(sB, pc, cB * ps); the re_ch / im_ch are added in
+ * chunk order from +0 -- the same on every device, launch geometry, run and on a device == -1 context (host
+ * threads), whatever else shares the call; twiddles and partial sums of one call stay within a fixed workspace
+ * (64 MiB) whatever the number of frequencies, and the result does not depend on how they were cut for that.
+ * All pointers are host memory.  Any mix of job sizes in one call; a job with n == 0 or n_freq == 0 writes
+ * nothing; jobs may share entries of `series` but not of `re` / `im`.  n > 2^31, a period outside 2 .. 2^31,
+ * j_step < 1, a j_q outside 0 .. M - 1, a negative count or offset, or a NaN or infinity in a series a job
+ * reads: PW_E_BAD_ARG (pw_last_error names the job and the reason), and nothing is launched or written.
+ * Device work is queued on the context's stream, its memory allocated and freed in stream order; the call
+ * returns when the sums are in place. */
+typedef struct pw_dft_job {
+    int64_t a_first, n;                /* series a = series[a_first .. +n), n <= 2^31 */
+    int64_t period;                    /* M: frequencies are j / M cycles per sample, 2 <= M <= 2^31 */
+    int64_t j_first, j_step, n_freq;   /* j_q = j_first + q * j_step, every 0 <= j_q < M, j_step >= 1 */
+    int64_t out_first;                 /* into re[] and im[] */
+} pw_dft_job;
+int pw_dft_sums(pw_context *ctx, const pw_dft_job *jobs, int64_t n_jobs, const double *series, double *re,
+                double *im);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

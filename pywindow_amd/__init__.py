@@ -24,6 +24,7 @@ from .distributions import (  # noqa: E402
     gaussian_kde_replicas,
 )
 from .correlations import TimeCorrelation, time_correlation, time_correlation_batch  # noqa: E402
+from .spectra import Spectrum, dft_sums, dft_sums_batch, lomb_scargle, lomb_scargle_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -55,6 +56,11 @@ __all__ = [
     "TimeCorrelation",
     "time_correlation",
     "time_correlation_batch",
+    "Spectrum",
+    "dft_sums",
+    "dft_sums_batch",
+    "lomb_scargle",
+    "lomb_scargle_batch",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

@@ -202,6 +202,12 @@ CORR_JOB_DTYPE = np.dtype(
     [("a_first", np.int64), ("b_first", np.int64), ("n", np.int64), ("out_first", np.int64), ("n_lags", np.int64)]
 )
 
+#: numpy mirror of ``pw_dft_job``
+DFT_JOB_DTYPE = np.dtype(
+    [("a_first", np.int64), ("n", np.int64), ("period", np.int64), ("j_first", np.int64), ("j_step", np.int64),
+     ("n_freq", np.int64), ("out_first", np.int64)]
+)
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -285,6 +291,7 @@ EXPORTED_SYMBOLS = [
     "pw_kde2_sums",
     "pw_kde_wsums",
     "pw_corr_sums",
+    "pw_dft_sums",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -403,6 +410,7 @@ def load():
     L.pw_kde2_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.pw_kde_wsums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp, vp]
     L.pw_corr_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp]
+    L.pw_dft_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -742,6 +750,31 @@ class Context:
             raise ValueError(load().pw_last_error().decode(errors="replace"))
         _check(rc, "pw_corr_sums")
         return sums
+
+    def dft_sums(self, jobs, series) -> np.ndarray:
+        """``pw_dft_sums``: the raw sums ``sum_t a[t] exp(2 pi i j t / M)`` of a batch of jobs (``DFT_JOB_DTYPE`` records
+        indexing the float64 array ``series`` and the result) as one complex array ``re + 1j * im``, as long as the
+        furthest ``out_first + n_freq`` of a job (entries no job writes are zero).  A period outside ``2 .. 2^31``, a
+        frequency outside ``0 .. period - 1``, ``j_step < 1`` or a NaN / infinity in a series raises ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=DFT_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
+        size = 0
+        if len(jobs):
+            if ((jobs["a_first"] < 0) | (jobs["n"] < 0) | (jobs["a_first"] + jobs["n"] > len(x))).any():
+                raise IndexError("a job reaches outside `series`")
+            if (jobs["out_first"] < 0).any():
+                raise IndexError("a job writes before the start of the sums")
+            live = jobs[(jobs["n"] > 0) & (jobs["n_freq"] > 0)]
+            if len(live):
+                size = int(max(0, (live["out_first"] + live["n_freq"]).max()))
+        re, im = np.zeros(size), np.zeros(size)      # (the entry wants two arrays; the result carries their bits)
+        rc = load().pw_dft_sums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, re.ctypes.data, im.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_dft_sums")
+        out = np.empty(size, dtype=np.complex128)
+        out.real, out.imag = re, im
+        return out
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

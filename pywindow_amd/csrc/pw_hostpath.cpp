@@ -13,6 +13,7 @@
 #include "pw_unit.hpp"
 #include "pw_kde.hpp"
 #include "pw_corr.hpp"
+#include "pw_dft.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -334,6 +335,80 @@ extern "C" int pw_hostpath_corr(const pw_corr_job* jobs, long n_jobs, const doub
         for (auto& t : pool) t.join();
     }
     return PW_OK;
+}
+
+// pw_dft_sums on the host (pw_dft.hip checks the arguments and sends device == -1 contexts here): the definition
+// of pw_dft.hpp, a frequency's chunks in order, so the sums have the device's bits.  Threads share out blocks of
+// BLOCK consecutive frequencies of a job; a block's twiddles are computed once ([r][frequency], as the device's
+// table) and its frequencies go through a chunk side by side (independent accumulators, each in its own r order).
+extern "C" int pw_hostpath_dft(const pw_dft_job* jobs, long n_jobs, const double* series, double* re, double* im,
+                               int threads) {
+    constexpr long BLOCK = 8;                      // frequencies of one piece of work
+    std::vector<long> first((size_t)n_jobs + 1, 0);
+    for (long k = 0; k < n_jobs; ++k)
+        first[k + 1] = first[k] + (jobs[k].n && jobs[k].n_freq ? ((long)jobs[k].n_freq + BLOCK - 1) / BLOCK : 0);
+    const long total = first[n_jobs];
+    std::atomic<long> next{0};
+    auto worker = [&]() {
+        long k = 0;
+        std::vector<double> cA((size_t)DFT_CHUNK * BLOCK), sA((size_t)DFT_CHUNK * BLOCK);
+        for (;;) {
+            const long w = next.fetch_add(1);
+            if (w >= total) break;
+            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
+            const pw_dft_job& J = jobs[k];
+            const long n = (long)J.n, M = (long)J.period;
+            const long q0 = (w - first[k]) * BLOCK, count = std::min(BLOCK, (long)J.n_freq - q0);
+            const long steps = std::min(n, (long)DFT_CHUNK);
+            long j[BLOCK];
+            for (long f = 0; f < BLOCK; ++f) j[f] = (long)J.j_first + (q0 + std::min(f, count - 1)) * (long)J.j_step;
+            for (long r = 0; r < steps; ++r)
+                for (long f = 0; f < BLOCK; ++f) dft_phase(j[f], r, M, &cA[r * BLOCK + f], &sA[r * BLOCK + f]);
+            const double* a = series + J.a_first;
+            double sr[BLOCK], si[BLOCK];
+            for (long f = 0; f < BLOCK; ++f) sr[f] = si[f] = 0.0;
+            for (long t0 = 0; t0 < n; t0 += DFT_CHUNK) {
+                const long len = std::min((long)DFT_CHUNK, n - t0);
+                double pc[BLOCK], ps[BLOCK];
+                for (long f = 0; f < BLOCK; ++f) pc[f] = ps[f] = 0.0;
+                for (long r = 0; r < len; ++r) {
+                    const double av = a[t0 + r];
+                    const double* c = &cA[r * BLOCK];
+                    const double* s = &sA[r * BLOCK];
+                    for (long f = 0; f < BLOCK; ++f) {
+                        pc[f] = pw_fma(av, c[f], pc[f]);
+                        ps[f] = pw_fma(av, s[f], ps[f]);
+                    }
+                }
+                for (long f = 0; f < count; ++f) {
+                    double cB, sB, x, y;
+                    dft_phase(j[f], t0, M, &cB, &sB);
+                    dft_rotate(cB, sB, pc[f], ps[f], &x, &y);
+                    sr[f] = sr[f] + x;
+                    si[f] = si[f] + y;
+                }
+            }
+            for (long f = 0; f < count; ++f) {
+                re[J.out_first + q0 + f] = sr[f];
+                im[J.out_first + q0 + f] = si[f];
+            }
+        }
+    };
+    if (threads < 1) threads = 1;
+    if ((long)threads > total) threads = (int)std::max(1l, total);
+    if (threads == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+    }
+    return PW_OK;
+}
+
+// the phases of pw_dft.hpp for arbitrary k (test instrumentation, pw_dft.hip: pw_internal_dft_twiddles)
+extern "C" void pw_hostpath_dft_twiddles(long j, long M, const long* k, long n, double* c, double* s) {
+    for (long i = 0; i < n; ++i) dft_phase(j, k[i], M, &c[i], &s[i]);
 }
 
 // pw_exp over an array (test instrumentation, pw_kde.hip: pw_internal_exp)

@@ -331,6 +331,29 @@ class RecordStore:
         pairs = [pair(m) for m in keys]
         return dict(zip(keys, C.time_correlation_batch([p for _, p in pairs], max_lag, device, [s for s, _ in pairs])))
 
+    def spectrum(self, quantity: str, molecule=None, per_molecule: bool = False, oversample: int = 4,
+                 max_frequency: float = 0.5, dt: float = 1.0, device=None):
+        """Generalised Lomb-Scargle periodogram of :meth:`series` over the frames (pywindow_amd/spectra.py): a
+        ``Spectrum`` whose ``peak_frequency`` says at which frequency ``quantity`` oscillates; gaps are left out
+        exactly.  ``frequency`` is in cycles per ``dt`` (the time of one frame; the stride of the frame axis is taken
+        from the series), ``max_frequency`` in cycles per sample.  ``per_molecule`` (modular stores): ``{molecule:
+        Spectrum}``, all from one batched call."""
+        from . import spectra as S
+
+        def one(mol):
+            frames, a, valid = self.series(quantity, mol)
+            return int(frames[1] - frames[0]), (a, valid)
+
+        if not per_molecule:
+            stride, p = one(molecule)
+            return S.lomb_scargle_batch([p], oversample, max_frequency, stride, dt, device)[0]
+        if not self.modular:
+            raise ValueError("per_molecule needs a modular analysis (the store has one unit per frame)")
+        keys = [int(m) for m in np.unique(self.unit_molecule)]
+        each = [one(m) for m in keys]
+        return dict(zip(keys, S.lomb_scargle_batch([p for _, p in each], oversample, max_frequency, [s for s, _ in each],
+                                                   dt, device)))
+
     # ---- persistence -----------------------------------------------------------------------
     # One file: a 4096-byte header (magic, then JSON: format, stages, record layout, and for every array its
     # dtype, length and byte offset), then the arrays as they lie in memory, each at a 4096-byte boundary.

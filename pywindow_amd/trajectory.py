@@ -300,6 +300,13 @@ class DLPOLY:
         :attr:`analysis_store`."""
         return self.analysis_store.correlation(quantity, other, max_lag, per_molecule, device)
 
+    def spectrum(self, quantity: str, molecule=None, per_molecule: bool = False, oversample: int = 4,
+                 max_frequency: float = 0.5, dt: float = 1.0, device=None):
+        """At which frequency the cage breathes (``spectrum("pore_diameter_opt").peak_frequency``, ``.peak_period``):
+        the generalised Lomb-Scargle periodogram over the frames analysed or loaded so far, gaps left out exactly,
+        summed on the GPU: ``RecordStore.spectrum`` of :attr:`analysis_store`."""
+        return self.analysis_store.spectrum(quantity, molecule, per_molecule, oversample, max_frequency, dt, device)
+
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
         selected frames, without building per-frame dicts."""
