@@ -526,6 +526,43 @@ typedef struct pw_dft_job {
 } pw_dft_job;
 int pw_dft_sums(pw_context *ctx, const pw_dft_job *jobs, int64_t n_jobs, const double *series, double *re,
                 double *im);
+/* ---- gating statistics: how often and for how long a series stays above or below a threshold -------------
+ * What fraction of the time a cage admits a guest of diameter d, how often it opens and how long an opening or
+ * a closure lasts, for many d at once.  The reference has no counterpart.  Job k has a series
+ * a = series[a_first .. +n) and n_thr thresholds d_q = thresholds[d_first + q]; for each of them every entry
+ * has a state -- OPEN a[t] >= d, CLOSED a[t] < d, GAP a[t] a NaN (recognised on the bits) -- and the series is
+ * cut into maximal runs of equal state; a run's neighbour is a run of the opposite state, a gap run or an end
+ * of the series.  Row r = out_first + q of counts holds, at counts[r * PW_GATE_FIELDS + f]:
+ *     f = 0, 1    n_open, n_closed                entries in each state
+ *     f = 2, 3    open_runs, closed_runs          maximal runs of each state, whatever bounds them
+ *     f = 4, 5    longest_open, longest_closed    length of the longest such run (0 if none)
+ *     f = 6       openings                        open runs whose LEFT neighbour is a closed run
+ *     f = 7       closings                        closed runs whose left neighbour is an open run
+ *     f = 8, 9    complete_open_runs, complete_closed_runs      runs bounded by the opposite state on BOTH
+ *                 sides, so their true length is known; a run touching a gap or an end is censored
+ *     f = 10, 11  complete_open_frames, complete_closed_frames  summed lengths of the complete runs
+ * With n_bins = B > 0, hist[(r * 2 + s) * B + min(len, B) - 1] counts the COMPLETE runs of length len, s = 0
+ * open, s = 1 closed; the last bin takes every length >= B.  With B == 0 hist may be NULL and is not touched.
+ * Every output is an integer, so the result is this definition itself on every device, launch geometry and
+ * run and on a device == -1 context (host threads), whatever else shares the call; the workspace of one call
+ * stays within 64 MiB whatever the number of thresholds -- they go through 256 at a time at the least, at
+ * 4 bytes per threshold and 512 entries, so a series of more than 3.3e7 entries takes n / 512 KiB instead, 4 GiB
+ * at n = 2^31 -- and the result does not depend on how they were cut for that (pywindow_amd/csrc/pw_gate.hpp).
+ * All pointers are host memory.  Any mix of job sizes in one call; a job with n == 0 or n_thr == 0 writes
+ * nothing; jobs may share entries of `series` and `thresholds` but not rows of `counts` / `hist`; thresholds
+ * in any order, repeats allowed.  An infinity in a series a job reads, a NaN or an infinity among the
+ * thresholds it reads, n > 2^31, a negative count, offset or n_bins, or hist == NULL with n_bins > 0:
+ * PW_E_BAD_ARG (pw_last_error names the job and the reason), and nothing is launched or written.  Device work
+ * is queued on the context's stream, its memory allocated and freed in stream order; the call returns when the
+ * counts are in place. */
+#define PW_GATE_FIELDS 12
+typedef struct pw_gate_job {
+    int64_t a_first, n;                /* series a = series[a_first .. +n), n <= 2^31; a NaN entry is a GAP */
+    int64_t d_first, n_thr;            /* thresholds d_q = thresholds[d_first + q], q < n_thr */
+    int64_t out_first;                 /* row out_first + q of counts[] (and of hist[]) belongs to threshold q */
+} pw_gate_job;
+int pw_gate_counts(pw_context *ctx, const pw_gate_job *jobs, int64_t n_jobs, const double *series,
+                   const double *thresholds, int64_t n_bins, int64_t *counts, int64_t *hist);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

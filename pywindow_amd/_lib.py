@@ -208,6 +208,14 @@ DFT_JOB_DTYPE = np.dtype(
      ("n_freq", np.int64), ("out_first", np.int64)]
 )
 
+#: numpy mirror of ``pw_gate_job``
+GATE_JOB_DTYPE = np.dtype(
+    [("a_first", np.int64), ("n", np.int64), ("d_first", np.int64), ("n_thr", np.int64), ("out_first", np.int64)]
+)
+#: the columns of a row of ``pw_gate_counts`` (``PW_GATE_FIELDS``)
+GATE_FIELDS = ("n_open", "n_closed", "open_runs", "closed_runs", "longest_open", "longest_closed", "openings", "closings",
+               "complete_open_runs", "complete_closed_runs", "complete_open_frames", "complete_closed_frames")
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -292,6 +300,7 @@ EXPORTED_SYMBOLS = [
     "pw_kde_wsums",
     "pw_corr_sums",
     "pw_dft_sums",
+    "pw_gate_counts",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -411,6 +420,7 @@ def load():
     L.pw_kde_wsums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp, vp]
     L.pw_corr_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp]
     L.pw_dft_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
+    L.pw_gate_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -775,6 +785,36 @@ class Context:
         out = np.empty(size, dtype=np.complex128)
         out.real, out.imag = re, im
         return out
+
+    def gate_counts(self, jobs, series, thresholds, n_bins: int = 0):
+        """``pw_gate_counts``: the gating statistics of a batch of jobs (``GATE_JOB_DTYPE`` records indexing the float64
+        arrays ``series`` -- a NaN is a gap -- and ``thresholds``, and the rows of the result): ``(counts (R, 12) int64,
+        hist (R, 2, n_bins) int64)``, the columns of ``counts`` as ``GATE_FIELDS`` names them, ``hist[r, 0]`` / ``[r, 1]``
+        the lengths of the complete open / closed runs (the last bin takes every length ``>= n_bins``), ``R`` the
+        furthest ``out_first + n_thr`` of a job (rows no job writes are zero).  An infinity in a series, a NaN or an
+        infinity among the thresholds, or a negative ``n_bins`` raises ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=GATE_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
+        d = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        n_bins = int(n_bins)
+        rows = 0
+        if len(jobs):
+            for first, count, limit, what in (("a_first", "n", len(x), "series"), ("d_first", "n_thr", len(d), "thresholds")):
+                if ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > limit)).any():
+                    raise IndexError(f"a job reaches outside `{what}`")
+            if (jobs["out_first"] < 0).any():
+                raise IndexError("a job writes before the start of the counts")
+            live = jobs[(jobs["n"] > 0) & (jobs["n_thr"] > 0)]
+            if len(live):
+                rows = int((live["out_first"] + live["n_thr"]).max())
+        counts = np.zeros((rows, len(GATE_FIELDS)), dtype=np.int64)
+        hist = np.zeros((rows, 2, max(n_bins, 0)), dtype=np.int64)
+        rc = load().pw_gate_counts(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, d.ctypes.data, n_bins,
+                                   counts.ctypes.data, hist.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_gate_counts")
+        return counts, hist
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

@@ -14,6 +14,7 @@
 #include "pw_kde.hpp"
 #include "pw_corr.hpp"
 #include "pw_dft.hpp"
+#include "pw_gate.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -391,6 +392,59 @@ extern "C" int pw_hostpath_dft(const pw_dft_job* jobs, long n_jobs, const double
             for (long f = 0; f < count; ++f) {
                 re[J.out_first + q0 + f] = sr[f];
                 im[J.out_first + q0 + f] = si[f];
+            }
+        }
+    };
+    if (threads < 1) threads = 1;
+    if ((long)threads > total) threads = (int)std::max(1l, total);
+    if (threads == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+    }
+    return PW_OK;
+}
+
+// pw_gate_counts on the host (pw_gate.hip checks the arguments and sends device == -1 contexts here): the chunks,
+// summaries and merge of pw_gate.hpp, the very functions the kernels run.  Threads share out (job, block of BLOCK
+// consecutive thresholds) pairs; a threshold goes through the series chunk by chunk, and its row is its own.
+extern "C" int pw_hostpath_gate(const pw_gate_job* jobs, long n_jobs, const double* series, const double* thresholds,
+                                long n_bins, long* counts, long* hist, int threads) {
+    constexpr long BLOCK = 16;                     // thresholds of one piece of work
+    std::vector<long> first((size_t)n_jobs + 1, 0);
+    for (long k = 0; k < n_jobs; ++k)
+        first[k + 1] = first[k] + (jobs[k].n && jobs[k].n_thr ? ((long)jobs[k].n_thr + BLOCK - 1) / BLOCK : 0);
+    const long total = first[n_jobs];
+    std::atomic<long> next{0};
+    auto worker = [&]() {
+        long k = 0;
+        for (;;) {
+            const long w = next.fetch_add(1);
+            if (w >= total) break;
+            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
+            const pw_gate_job& J = jobs[k];
+            const long n = (long)J.n, q0 = (w - first[k]) * BLOCK, q1 = std::min(q0 + BLOCK, (long)J.n_thr);
+            const double* a = series + J.a_first;
+            for (long q = q0; q < q1; ++q) {
+                const double d = thresholds[J.d_first + q];
+                const long row = (long)J.out_first + q;
+                long* h = n_bins > 0 ? hist + row * 2 * n_bins : nullptr;
+                for (long i = 0; i < 2 * n_bins; ++i) h[i] = 0;
+                auto bin = [&](int s, long len) {
+                    if (n_bins > 0) h[s * n_bins + std::min(len, n_bins) - 1] += 1;
+                };
+                GateWalk W;
+                GateTally<long> T;
+                for (long t0 = 0; t0 < n; t0 += GATE_CHUNK)
+                    gate_merge(W, gate_chunk(a + t0, (int)std::min((long)GATE_CHUNK, n - t0), d, T, bin), T, bin);
+                gate_finish(W, T, bin);
+                long* c = counts + row * GATE_FIELDS;
+                c[0] = T.n_open; c[1] = T.n_closed; c[2] = T.open_runs; c[3] = T.closed_runs;
+                c[4] = T.longest_open; c[5] = T.longest_closed; c[6] = T.openings; c[7] = T.closings;
+                c[8] = T.complete_open_runs; c[9] = T.complete_closed_runs;
+                c[10] = T.complete_open_frames; c[11] = T.complete_closed_frames;
             }
         }
     };

@@ -354,6 +354,38 @@ class RecordStore:
         return dict(zip(keys, S.lomb_scargle_batch([p for _, p in each], oversample, max_frequency, [s for s, _ in each],
                                                    dt, device)))
 
+    def gating(self, quantity: str = "windows_max", thresholds=200, molecule=None, per_molecule: bool = False,
+               n_bins: int = 64, device=None):
+        """Gating statistics of :meth:`series` over the frames (pywindow_amd/gating.py): a ``Gating`` that says, for a
+        guest of every diameter of ``thresholds``, what fraction of the time ``quantity`` admits it (``windows_max``: the
+        largest window does; ``windows_min``: every window does), how often it opens and closes and how long the
+        openings and closures last; gaps end a run and censor it.  ``thresholds``: an int for ``np.linspace(min, max,
+        thresholds)`` over the valid values of the series, or the thresholds themselves.  Lengths are in frames (the
+        stride of the frame axis is taken from the series).  ``per_molecule`` (modular stores): ``{molecule: Gating}``,
+        all from one batched call."""
+        from . import gating as G
+
+        def one(mol):
+            frames, a, valid = self.series(quantity, mol)
+            if isinstance(thresholds, (bool, np.bool_)):
+                raise ValueError("thresholds: a number of thresholds or the thresholds themselves, not a bool")
+            if isinstance(thresholds, (int, np.integer)):
+                if thresholds < 1 or not valid.any():
+                    raise ValueError("thresholds: at least one, over a series with a valid entry")
+                d = np.linspace(a[valid].min(), a[valid].max(), int(thresholds))
+            else:
+                d = np.asarray(thresholds, dtype=np.float64)
+            return int(frames[1] - frames[0]), (a, d, valid)
+
+        if not per_molecule:
+            stride, item = one(molecule)
+            return G.gate_statistics_batch([item], n_bins, stride, device)[0]
+        if not self.modular:
+            raise ValueError("per_molecule needs a modular analysis (the store has one unit per frame)")
+        keys = [int(m) for m in np.unique(self.unit_molecule)]
+        each = [one(m) for m in keys]
+        return dict(zip(keys, G.gate_statistics_batch([i for _, i in each], n_bins, [s for s, _ in each], device)))
+
     # ---- persistence -----------------------------------------------------------------------
     # One file: a 4096-byte header (magic, then JSON: format, stages, record layout, and for every array its
     # dtype, length and byte offset), then the arrays as they lie in memory, each at a 4096-byte boundary.

@@ -307,6 +307,14 @@ class DLPOLY:
         summed on the GPU: ``RecordStore.spectrum`` of :attr:`analysis_store`."""
         return self.analysis_store.spectrum(quantity, molecule, per_molecule, oversample, max_frequency, dt, device)
 
+    def gating(self, quantity: str = "windows_max", thresholds=200, molecule=None, per_molecule: bool = False,
+               n_bins: int = 64, device=None):
+        """For guests of the diameters ``thresholds``: what fraction of the time the cage is open
+        (``gating("windows_max", thresholds=[3.3, 3.64]).open_fraction``), how often it opens (``.openings``) and how
+        long an opening or a closure lasts (``.mean_open``, ``.open_lengths``), over the frames analysed or loaded so
+        far, counted on the GPU: ``RecordStore.gating`` of :attr:`analysis_store`."""
+        return self.analysis_store.gating(quantity, thresholds, molecule, per_molecule, n_bins, device)
+
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
         selected frames, without building per-frame dicts."""
