@@ -303,6 +303,9 @@ int corr_sums(pw_context* ctx, const pw_corr_job* jobs, int64_t n_jobs, const do
         CORR_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
         CORR_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
         CORR_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
+        CORR_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
+        CORR_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
         CORR_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(CorrSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
         CORR_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
         if (kernel_ms) CORR_TRY(hipEventRecord(ev.a, st));

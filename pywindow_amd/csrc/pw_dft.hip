@@ -366,6 +366,9 @@ int dft_sums(pw_context* ctx, const pw_dft_job* jobs, int64_t n_jobs, const doub
         DFT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
         DFT_TRY(buf.alloc(&d_ws, sizeof(double2) * (size_t)pairs));
         DFT_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs * 2));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
+        DFT_TRY(poison_scratch(poison, d_ws, sizeof(double2) * (size_t)pairs, st));
+        DFT_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs * 2, st));
         DFT_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(DftSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
         DFT_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
         if (kernel_ms) DFT_TRY(hipEventRecord(ev.a, st));

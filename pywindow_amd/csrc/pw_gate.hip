@@ -305,6 +305,10 @@ int gate_counts(pw_context* ctx, const pw_gate_job* jobs, int64_t n_jobs, const 
         GATE_TRY(buf.alloc(&d_ws, sizeof(unsigned) * (size_t)words));
         GATE_TRY(buf.alloc(&d_counts, count_bytes));
         GATE_TRY(buf.alloc(&d_hist, hist_bytes));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp; the result is zeroed below)
+        GATE_TRY(poison_scratch(poison, d_ws, sizeof(unsigned) * (size_t)words, st));
+        GATE_TRY(poison_scratch(poison, d_counts, count_bytes, st));
+        GATE_TRY(poison_scratch(poison, d_hist, hist_bytes, st));
         GATE_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(GateSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
         GATE_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
         GATE_TRY(hipMemcpyAsync(d_thr, thresholds + d_lo, sizeof(double) * (size_t)(d_hi - d_lo), hipMemcpyHostToDevice, st));

@@ -291,6 +291,9 @@ int kde_sums(pw_context* ctx, const pw_kde_job* jobs, int64_t n_jobs, const doub
         KDE_TRY(buf.alloc(&d_g, sizeof(double) * (size_t)(p_hi - p_lo)));
         KDE_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
         KDE_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
+        KDE_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
+        KDE_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
         KDE_TRY(hipMemcpyAsync(d_jobs, dev.data(), sizeof(KdeJobDev) * dev.size(), hipMemcpyHostToDevice, st));
         if (s_hi > s_lo)
             KDE_TRY(hipMemcpyAsync(d_x, samples + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
@@ -428,6 +431,9 @@ int kde2_sums(pw_context* ctx, const pw_kde2_job* jobs, int64_t n_jobs, const do
         KDE_TRY(buf.alloc(&d_g, sizeof(double2) * (size_t)(p_hi - p_lo)));
         KDE_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
         KDE_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
+        KDE_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
+        KDE_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
         KDE_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(Kde2SlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
         if (s_hi > s_lo)
             KDE_TRY(hipMemcpyAsync(d_x, samples + 2 * s_lo, sizeof(double2) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
@@ -483,6 +489,12 @@ extern "C" int pw_internal_kde2_sums(pw_context* ctx, const pw_kde2_job* jobs, i
                                      const double* points, double* sums, int64_t workspace_bytes, float* kernel_ms) {
     return kde2_sums(ctx, jobs, n_jobs, samples, points, sums, workspace_bytes, kernel_ms);
 }
+
+// test hook (not part of the header): on != 0 makes every statistical entry of the library -- the two here and those
+// of pw_kdew.hip, pw_corr.hip, pw_dft.hip and pw_gate.hip -- fill its device workspace and its compact device result
+// with bytes 0xFF before its first kernel (pw_host.hpp: poison_scratch).  Process-wide, off at start; no kernel and
+// no result changes, unless a kernel reads what the call never wrote.
+extern "C" void pw_internal_poison_scratch(int on) { g_poison_scratch.store(on != 0, std::memory_order_relaxed); }
 
 // test instrumentation (not part of the header): y[i] = pw_exp(x[i]) on the context's device, or on the host
 // for a device == -1 context -- the two must agree to the bit (tests/test_gpu_kde.py)

@@ -328,6 +328,9 @@ int kdew_sums(pw_context* ctx, const pw_kdew_job* jobs, int64_t n_jobs, const do
         KDEW_TRY(buf.alloc(&d_w, sizeof(double) * (size_t)(w_hi - w_lo)));
         KDEW_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
         KDEW_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
+        KDEW_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
+        KDEW_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
         KDEW_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(KdewSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
         if (s_hi > s_lo) {
             KDEW_TRY(hipMemcpyAsync(d_x, samples + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
