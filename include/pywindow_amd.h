@@ -563,6 +563,41 @@ typedef struct pw_gate_job {
 } pw_gate_job;
 int pw_gate_counts(pw_context *ctx, const pw_gate_job *jobs, int64_t n_jobs, const double *series,
                    const double *thresholds, int64_t n_bins, int64_t *counts, int64_t *hist);
+/* ---- trajectory kinetics: lagged state-transition counts of a series ---------------------------------------
+ * What the rates between the states of a cage are and whether the process is Markovian at the frame spacing:
+ * C_k[i][j] = #{t : s[t] = i, s[t + k] = j} for many lags k, from which the transition matrices, populations,
+ * implied timescales and the Chapman-Kolmogorov test follow.  The reference has no counterpart.  Job k has a
+ * series a = series[a_first .. +n), n_edges strictly increasing edges e = edges[e_first .. +n_edges) and n_lags
+ * lags k_q = lag_first + q * lag_step.  The state of a non-NaN entry is the number of the job's edges with
+ * e <= a[t] (np.searchsorted(edges, a, side="right"): an entry equal to an edge is in the upper state, and so
+ * is -0.0 at an edge 0.0); a NaN entry -- recognised on the bits -- is a GAP.  Row r = out_first + q holds
+ *     counts[r * n_states * n_states + i * n_states + j] = the number of t with 0 <= t, t + k_q < n, neither
+ *     entry a gap, s[t] = i and s[t + k_q] = j;
+ * a pair with a gap at either end is counted nowhere.  Lag 0 gives the populations on the diagonal; a lag >= n
+ * gives a row of zeros, which is written; states that a job's edges cannot reach (i, j > n_edges) are zeros of
+ * the row, also written.  1 <= n_states <= PW_TRANS_MAX_STATES holds for the whole call.
+ * Every output is an integer, so the result is this definition itself on every device, launch geometry and
+ * run and on a device == -1 context (host threads), whatever else shares the call.  The device classifies every
+ * entry once into one bit mask a state, n_states rounded up to 2, 4, 8 or 16 times n / 8 bytes a job; jobs share
+ * a launch while their masks stay within 64 MiB, and a job whose masks alone are more goes alone -- at 16 states
+ * a series of more than 3.3e7 entries, 2 n bytes, 4 GiB at n = 2^31 -- and the result does not depend on how the
+ * jobs were cut for that (pywindow_amd/csrc/pw_trans.hpp).
+ * All pointers are host memory.  Any mix of jobs in one call; a job with n == 0 or n_lags == 0 writes nothing;
+ * jobs may share entries of `series` and `edges` but not rows of `counts`, and rows no job owns are never
+ * touched.  An infinity in a series a job reads, a NaN, an infinity or a pair that does not increase among the
+ * edges it reads, n_edges >= n_states, n > 2^31, a negative field, lag_step < 1, a largest lag of 2^62 or more,
+ * or n_states outside 1 .. 16: PW_E_BAD_ARG (pw_last_error names the job and the reason), and nothing is
+ * launched or written.  Device work is queued on the context's stream, its memory allocated and freed in stream
+ * order; the call returns when the counts are in place. */
+#define PW_TRANS_MAX_STATES 16
+typedef struct pw_trans_job {
+    int64_t a_first, n;                /* series a = series[a_first .. +n), n <= 2^31; a NaN entry is a GAP */
+    int64_t e_first, n_edges;          /* edges e = edges[e_first .. +n_edges), strictly increasing, n_edges < n_states */
+    int64_t lag_first, lag_step, n_lags;   /* lags k_q = lag_first + q * lag_step, lag_first >= 0, lag_step >= 1 */
+    int64_t out_first;                 /* row out_first + q of counts[] belongs to lag k_q */
+} pw_trans_job;
+int pw_trans_counts(pw_context *ctx, const pw_trans_job *jobs, int64_t n_jobs, const double *series,
+                    const double *edges, int64_t n_states, int64_t *counts);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

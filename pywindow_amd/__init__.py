@@ -26,6 +26,7 @@ from .distributions import (  # noqa: E402
 from .correlations import TimeCorrelation, time_correlation, time_correlation_batch  # noqa: E402
 from .spectra import Spectrum, dft_sums, dft_sums_batch, lomb_scargle, lomb_scargle_batch  # noqa: E402
 from .gating import Gating, gate_statistics, gate_statistics_batch  # noqa: E402
+from .kinetics import Kinetics, transition_counts, transition_counts_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -65,6 +66,9 @@ __all__ = [
     "Gating",
     "gate_statistics",
     "gate_statistics_batch",
+    "Kinetics",
+    "transition_counts",
+    "transition_counts_batch",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

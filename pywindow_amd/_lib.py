@@ -216,6 +216,14 @@ GATE_JOB_DTYPE = np.dtype(
 GATE_FIELDS = ("n_open", "n_closed", "open_runs", "closed_runs", "longest_open", "longest_closed", "openings", "closings",
                "complete_open_runs", "complete_closed_runs", "complete_open_frames", "complete_closed_frames")
 
+#: numpy mirror of ``pw_trans_job``
+TRANS_JOB_DTYPE = np.dtype(
+    [("a_first", np.int64), ("n", np.int64), ("e_first", np.int64), ("n_edges", np.int64), ("lag_first", np.int64),
+     ("lag_step", np.int64), ("n_lags", np.int64), ("out_first", np.int64)]
+)
+#: ``PW_TRANS_MAX_STATES``
+TRANS_MAX_STATES = 16
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -301,6 +309,7 @@ EXPORTED_SYMBOLS = [
     "pw_corr_sums",
     "pw_dft_sums",
     "pw_gate_counts",
+    "pw_trans_counts",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -421,6 +430,7 @@ def load():
     L.pw_corr_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp]
     L.pw_dft_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.pw_gate_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp]
+    L.pw_trans_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -815,6 +825,36 @@ class Context:
             raise ValueError(load().pw_last_error().decode(errors="replace"))
         _check(rc, "pw_gate_counts")
         return counts, hist
+
+    def trans_counts(self, jobs, series, edges, n_states: int) -> np.ndarray:
+        """``pw_trans_counts``: the lagged state-transition counts of a batch of jobs (``TRANS_JOB_DTYPE`` records indexing
+        the float64 arrays ``series`` -- a NaN is a gap -- and ``edges``, and the rows of the result): ``counts (R,
+        n_states, n_states) int64`` with ``counts[out_first + q, i, j]`` the number of pairs ``s[t] = i, s[t + k_q] = j``,
+        ``R`` the furthest ``out_first + n_lags`` of a job (rows no job writes are zero).  An infinity in a series, edges
+        that are not finite and strictly increasing, ``n_edges >= n_states``, ``lag_step < 1`` or ``n_states`` outside
+        ``1 .. 16`` raises ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=TRANS_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        n_states = int(n_states)
+        rows = 0
+        if len(jobs):
+            for first, count, limit, what in (("a_first", "n", len(x), "series"), ("e_first", "n_edges", len(e), "edges")):
+                if ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > limit)).any():
+                    raise IndexError(f"a job reaches outside `{what}`")
+            if (jobs["out_first"] < 0).any():
+                raise IndexError("a job writes before the start of the counts")
+            live = jobs[(jobs["n"] > 0) & (jobs["n_lags"] > 0)]
+            if len(live):
+                rows = int((live["out_first"] + live["n_lags"]).max())
+        side = min(max(n_states, 0), TRANS_MAX_STATES)
+        counts = np.zeros((rows, side, side), dtype=np.int64)
+        rc = load().pw_trans_counts(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, e.ctypes.data, n_states,
+                                    counts.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_trans_counts")
+        return counts
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

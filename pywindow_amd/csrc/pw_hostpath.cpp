@@ -15,6 +15,7 @@
 #include "pw_corr.hpp"
 #include "pw_dft.hpp"
 #include "pw_gate.hpp"
+#include "pw_trans.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -456,6 +457,84 @@ extern "C" int pw_hostpath_gate(const pw_gate_job* jobs, long n_jobs, const doub
         std::vector<std::thread> pool;
         for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
         for (auto& t : pool) t.join();
+    }
+    return PW_OK;
+}
+
+// pw_trans_counts on the host (pw_trans.hip checks the arguments and sends device == -1 contexts here): the masks,
+// funnel shift and popcount of pw_trans.hpp with 64-bit words.  First the threads share out the jobs and classify every
+// entry once (trans_state) into one mask a reachable state, [state][word] with a word of zeros after the last; then
+// they share out (job, block of BLOCK consecutive lags) pairs, and a lag's row is its own.
+extern "C" int pw_hostpath_trans(const pw_trans_job* jobs, long n_jobs, const double* series, const double* edges,
+                                 long n_states, long* counts, int threads) {
+    typedef unsigned long long u64;
+    constexpr long BLOCK = 16;                     // lags of one piece of work
+    const long S = n_states;
+    std::vector<long> first((size_t)n_jobs + 1, 0), m_first((size_t)n_jobs + 1, 0);
+    for (long k = 0; k < n_jobs; ++k) {
+        const bool live = jobs[k].n && jobs[k].n_lags;
+        first[k + 1] = first[k] + (live ? ((long)jobs[k].n_lags + BLOCK - 1) / BLOCK : 0);
+        m_first[k + 1] = m_first[k] + (live ? ((long)jobs[k].n_edges + 1) * (((long)jobs[k].n + 63) / 64 + 1) : 0);
+    }
+    const long total = first[n_jobs];
+    std::vector<u64> masks((size_t)m_first[n_jobs], 0);
+    std::atomic<long> next_job{0}, next{0};
+    auto packer = [&]() {
+        for (;;) {
+            const long k = next_job.fetch_add(1);
+            if (k >= n_jobs) break;
+            const pw_trans_job& J = jobs[k];
+            if (!J.n || !J.n_lags) continue;
+            const long n = (long)J.n, stride = (n + 63) / 64 + 1;
+            const double* a = series + J.a_first;
+            u64* M = masks.data() + m_first[k];
+            for (long t = 0; t < n; ++t) {
+                const int s = trans_state(a[t], J.n_edges ? edges + J.e_first : nullptr, (int)J.n_edges);
+                if (s != TRANS_GAP) M[s * stride + t / 64] |= 1ull << (t % 64);
+            }
+        }
+    };
+    auto worker = [&]() {
+        long k = 0;
+        for (;;) {
+            const long w = next.fetch_add(1);
+            if (w >= total) break;
+            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
+            const pw_trans_job& J = jobs[k];
+            const long n = (long)J.n, nw = (n + 63) / 64, stride = nw + 1, ns = (long)J.n_edges + 1;
+            const long q0 = (w - first[k]) * BLOCK, q1 = std::min(q0 + BLOCK, (long)J.n_lags);
+            const u64* M = masks.data() + m_first[k];
+            for (long q = q0; q < q1; ++q) {
+                const long lag = (long)J.lag_first + q * (long)J.lag_step;
+                long c[TRANS_MAX_STATES][TRANS_MAX_STATES] = {};
+                if (lag < n) {
+                    const long ko = lag / 64;
+                    const unsigned r = (unsigned)(lag % 64);
+                    for (long x = 0; x + ko < nw; ++x)
+                        for (long j = 0; j < ns; ++j) {
+                            const u64 partner = trans_funnel(M[j * stride + x + ko + 1], M[j * stride + x + ko], r);
+                            for (long i = 0; i < ns; ++i) trans_count(c[i][j], M[i * stride + x] & partner);
+                        }
+                }
+                long* row = counts + ((long)J.out_first + q) * S * S;
+                for (long i = 0; i < S; ++i)
+                    for (long j = 0; j < S; ++j) row[i * S + j] = c[i][j];
+            }
+        }
+    };
+    if (threads < 1) threads = 1;
+    for (int phase = 0; phase < 2; ++phase) {
+        const long pieces = phase == 0 ? n_jobs : total;
+        const int count = (long)threads > pieces ? (int)std::max(1l, pieces) : threads;
+        if (count == 1) {
+            if (phase == 0) packer(); else worker();
+        } else {
+            std::vector<std::thread> pool;
+            for (int t = 0; t < count; ++t) {
+                if (phase == 0) pool.emplace_back(packer); else pool.emplace_back(worker);
+            }
+            for (auto& t : pool) t.join();
+        }
     }
     return PW_OK;
 }

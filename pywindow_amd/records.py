@@ -261,10 +261,17 @@ class RecordStore:
     #: per-frame reductions of a unit's window diameters, for :meth:`series`
     _WINDOW_SERIES = ("windows_min", "windows_max", "windows_mean", "n_windows")
 
-    def _value_by_unit(self, quantity: str):
+    def _value_by_unit(self, quantity: str, guest=None):
         """``(value of every unit (nan where it has none), which units have one)``."""
         n = len(self.records)
         values, has = np.full(n, np.nan), np.zeros(n, dtype=bool)
+        if quantity == "windows_open":
+            if guest is None or not np.isfinite(float(guest)):
+                raise ValueError("'windows_open' counts the windows a guest passes: say its diameter with guest=")
+            d, unit = self._samples_by_unit("windows")
+            return np.bincount(unit[d >= float(guest)], minlength=n).astype(np.float64), np.ones(n, dtype=bool)
+        if guest is not None:
+            raise ValueError("guest= belongs to 'windows_open'")
         if quantity == "windows":
             raise ValueError("'windows' is several values a frame: a series needs one of " + ", ".join(self._WINDOW_SERIES))
         if quantity not in self._WINDOW_SERIES:
@@ -281,15 +288,16 @@ class RecordStore:
             values[u] = w.min() if quantity == "windows_min" else w.max() if quantity == "windows_max" else np.sum(w) / len(w)
         return values, count > 0
 
-    def series(self, quantity: str, molecule=None):
+    def series(self, quantity: str, molecule=None, guest=None):
         """``(frames, values, valid)``: ``quantity`` along the frame axis.  Every per-unit name of :meth:`samples`, or a
         per-frame reduction of the windows: ``"windows_min"``, ``"windows_max"``, ``"windows_mean"`` (``np.sum(d) /
         len(d)`` of the unit's diameters, those beyond what a record holds included) or ``"n_windows"`` (how many there
-        are; 0 is a value).  ``frames = f0 + stride * arange(T)`` from the smallest frame of the store to the largest
+        are; 0 is a value), or ``"windows_open"`` with ``guest=d``: how many of the unit's windows have a diameter ``>= d``,
+        the cooperative-gating state (0 is a value, also for a unit without windows).  ``frames = f0 + stride * arange(T)`` from the smallest frame of the store to the largest
         in steps of the gcd of their differences; units are placed by their frame index, whatever their order in the
         store.  A frame that is absent, or whose unit has no such value (non-porous, windows ``None``, ...), is a GAP:
         ``valid[t]`` is ``False`` and ``values[t]`` nan.  Modular stores: ``molecule`` selects the molecule."""
-        values, has = self._value_by_unit(quantity)
+        values, has = self._value_by_unit(quantity, guest)
         if self.modular:
             if molecule is None:
                 raise ValueError("a modular store holds several molecules a frame: say which with molecule=")
@@ -385,6 +393,45 @@ class RecordStore:
         keys = [int(m) for m in np.unique(self.unit_molecule)]
         each = [one(m) for m in keys]
         return dict(zip(keys, G.gate_statistics_batch([i for _, i in each], n_bins, [s for s, _ in each], device)))
+
+    def kinetics(self, quantity: str = "windows_max", edges=None, max_lag=None, lag_step: int = 1, molecule=None,
+                 per_molecule: bool = False, guest=None, device=None):
+        """Lagged state-transition counts of :meth:`series` over the frames (pywindow_amd/kinetics.py): a ``Kinetics``
+        with the count matrices ``C_k[i][j] = #{t : s[t] = i, s[t + k] = j}``, the transition matrices, the populations
+        and the implied timescales; a pair with a gap at either end is counted nowhere.  ``edges`` cut the value axis
+        into states (a value equal to an edge is in the upper one).  ``quantity="windows_open"`` with ``guest=d`` is the
+        number of windows open to a guest of diameter ``d``; its ``edges`` default to ``0.5, 1.5, ...`` up to the largest
+        count seen, one state per count.  The lags are ``0, lag_step, 2 * lag_step, ...`` up to ``max_lag`` (default
+        ``T // 2``), both in samples of the series; ``Kinetics.lag`` is in frames (the stride of the frame axis is taken
+        from the series).  ``per_molecule`` (modular stores): ``{molecule: Kinetics}``, all from one batched call."""
+        from . import kinetics as K
+
+        lag_step = int(lag_step)
+        if lag_step < 1:
+            raise ValueError("lag_step: at least 1")
+
+        def one(mol):
+            frames, a, valid = self.series(quantity, mol, guest)
+            if edges is not None:
+                e = np.asarray(edges, dtype=np.float64)
+            elif quantity == "windows_open":
+                e = 0.5 + np.arange(int(a[valid].max()) if valid.any() else 0)
+            else:
+                raise ValueError("edges: the values that separate the states (only 'windows_open' has a default)")
+            top = len(a) // 2 if max_lag is None else int(max_lag)
+            if top < 0:
+                raise ValueError("max_lag is negative")
+            return int(frames[1] - frames[0]), (a, e, valid), (0, lag_step, top // lag_step + 1)
+
+        if not per_molecule:
+            stride, item, grid = one(molecule)
+            return K.transition_counts_batch([item], grid, stride, device)[0]
+        if not self.modular:
+            raise ValueError("per_molecule needs a modular analysis (the store has one unit per frame)")
+        keys = [int(m) for m in np.unique(self.unit_molecule)]
+        each = [one(m) for m in keys]
+        return dict(zip(keys, K.transition_counts_batch([i for _, i, _ in each], [g for _, _, g in each],
+                                                        [s for s, _, _ in each], device)))
 
     # ---- persistence -----------------------------------------------------------------------
     # One file: a 4096-byte header (magic, then JSON: format, stages, record layout, and for every array its

@@ -315,6 +315,14 @@ class DLPOLY:
         far, counted on the GPU: ``RecordStore.gating`` of :attr:`analysis_store`."""
         return self.analysis_store.gating(quantity, thresholds, molecule, per_molecule, n_bins, device)
 
+    def kinetics(self, quantity: str = "windows_max", edges=None, max_lag=None, lag_step: int = 1, molecule=None,
+                 per_molecule: bool = False, guest=None, device=None):
+        """Rates and the Markov test of a gating process: the lagged transition counts between the states that ``edges``
+        cut ``quantity`` into (``kinetics("windows_open", guest=3.3).timescales``: the implied timescales of the number
+        of windows open to a guest of 3.3 A), over the frames analysed or loaded so far, counted on the GPU:
+        ``RecordStore.kinetics`` of :attr:`analysis_store`."""
+        return self.analysis_store.kinetics(quantity, edges, max_lag, lag_step, molecule, per_molecule, guest, device)
+
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
         selected frames, without building per-frame dicts."""
