@@ -598,6 +598,42 @@ typedef struct pw_trans_job {
 } pw_trans_job;
 int pw_trans_counts(pw_context *ctx, const pw_trans_job *jobs, int64_t n_jobs, const double *series,
                     const double *edges, int64_t n_states, int64_t *counts);
+/* ---- superposition: the rotation that brings one set of points onto another, and their RMSD ------------------
+ * The least-squares fit of a frame onto a reference (Horn's quaternion method), the first step of every question
+ * about one particular window of a tumbling cage, and the pairwise RMSD behind conformational clustering.  The
+ * reference has no counterpart.  Job k has n mobile points x = xyz[mobile_first .. +n) and n target points
+ * y = xyz[target_first .. +n) (rows of three doubles; the same rows, or rows other jobs use, are fine) and the
+ * weights w = weights[weight_first .. +n), or 1.0 for every point when weight_first == -1.  Row `out` of the
+ * result holds the proper rotation R (det +1, also for a mirror-image target and for n = 1, 2, collinear or
+ * planar sets, where it is *a* minimiser), the weighted centroids, so that R (x - centre_mobile) + centre_target
+ * lies on y, rmsd = sqrt(sum w |R (x - cx) - (y - cy)|^2 / sum w) taken as a direct sum of residuals, the two
+ * largest eigenvalues of Horn's 4 x 4 matrix (their gap says how well R is determined) and the Jacobi sweeps.
+ * The result is DEFINED: 64 strided accumulators a sum folded pairwise, a cyclic Jacobi with a written sweep rule
+ * (pywindow_amd/csrc/pw_superpose.hpp), the same bits on every device, launch geometry and run and on a
+ * device == -1 context (host threads), whatever else shares the call and however the jobs are cut into launches
+ * to keep the workspace within 16 MiB (28 doubles a job).
+ * All pointers are host memory; n_points is the number of rows of xyz and of entries of weights (weights may be
+ * null when no job has any).  Jobs may not share rows of `out`; rows no job owns are never touched.  n < 1, a
+ * range outside the arrays, a coordinate a job reads that is not finite, a weight it reads that is negative or not
+ * finite, or weights that sum to 0: PW_E_BAD_ARG (pw_last_error names the job and the reason), and nothing is
+ * launched or written.  Device work is queued on the context's stream, its memory allocated and freed in stream
+ * order; the call returns when the rows are in place. */
+typedef struct pw_superpose_job {
+    int64_t mobile_first, target_first; /* first rows of the two point sets in xyz */
+    int64_t weight_first;               /* first weight, or -1: every weight is 1.0 */
+    int64_t n;                          /* points, >= 1 */
+    int64_t out;                        /* the job's row of the result */
+} pw_superpose_job;
+typedef struct pw_superpose_out {
+    double rotation[3][3];
+    double centre_mobile[3], centre_target[3];
+    double rmsd;
+    double lambda[2];                   /* the two largest eigenvalues of Horn's matrix, descending */
+    int32_t sweeps;
+    int32_t reserved;                   /* padding to a multiple of 8 bytes; written as 0 */
+} pw_superpose_out;
+int pw_superpose(pw_context *ctx, const pw_superpose_job *jobs, int64_t n_jobs, const double *xyz,
+                 const double *weights, int64_t n_points, pw_superpose_out *out);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

@@ -27,6 +27,8 @@ from .correlations import TimeCorrelation, time_correlation, time_correlation_ba
 from .spectra import Spectrum, dft_sums, dft_sums_batch, lomb_scargle, lomb_scargle_batch  # noqa: E402
 from .gating import Gating, gate_statistics, gate_statistics_batch  # noqa: E402
 from .kinetics import Kinetics, transition_counts, transition_counts_batch  # noqa: E402
+from .superposition import Superposition, rmsd_matrix, superpose, superpose_batch  # noqa: E402
+from .tracks import WindowTracks, track_windows  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -69,6 +71,12 @@ __all__ = [
     "Kinetics",
     "transition_counts",
     "transition_counts_batch",
+    "Superposition",
+    "superpose",
+    "superpose_batch",
+    "rmsd_matrix",
+    "WindowTracks",
+    "track_windows",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

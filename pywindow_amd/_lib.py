@@ -224,6 +224,17 @@ TRANS_JOB_DTYPE = np.dtype(
 #: ``PW_TRANS_MAX_STATES``
 TRANS_MAX_STATES = 16
 
+#: numpy mirror of ``pw_superpose_job``
+SUPERPOSE_JOB_DTYPE = np.dtype(
+    [("mobile_first", np.int64), ("target_first", np.int64), ("weight_first", np.int64), ("n", np.int64), ("out", np.int64)]
+)
+#: numpy mirror of ``pw_superpose_out``
+SUPERPOSE_OUT_DTYPE = np.dtype(
+    [("rotation", np.float64, (3, 3)), ("centre_mobile", np.float64, (3,)), ("centre_target", np.float64, (3,)),
+     ("rmsd", np.float64), ("lambda", np.float64, (2,)), ("sweeps", np.int32), ("reserved", np.int32)],
+)
+assert SUPERPOSE_OUT_DTYPE.itemsize == 152
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -310,6 +321,7 @@ EXPORTED_SYMBOLS = [
     "pw_dft_sums",
     "pw_gate_counts",
     "pw_trans_counts",
+    "pw_superpose",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -431,6 +443,7 @@ def load():
     L.pw_dft_sums.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
     L.pw_gate_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp]
     L.pw_trans_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
+    L.pw_superpose.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -855,6 +868,32 @@ class Context:
             raise ValueError(load().pw_last_error().decode(errors="replace"))
         _check(rc, "pw_trans_counts")
         return counts
+
+    def superpose(self, jobs, xyz, weights=None, out=None) -> np.ndarray:
+        """``pw_superpose``: the least-squares superposition of a batch of jobs (``SUPERPOSE_JOB_DTYPE`` records indexing
+        the rows of ``xyz`` (M, 3) float64 and the entries of ``weights`` (M) float64, ``weight_first = -1`` for weights
+        of one): a ``SUPERPOSE_OUT_DTYPE`` array with row ``out`` of every job filled in -- ``out`` given, or zeros up to
+        the furthest row of a job; rows no job writes stay as they are.  ``n < 1``, a coordinate that is not finite, a
+        weight that is negative or not finite, weights that sum to 0 or a range outside the arrays raise
+        ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=SUPERPOSE_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w is not None and len(w) != len(x):
+            raise ValueError("one weight per row of xyz")
+        if len(jobs) and (jobs["out"] < 0).any():
+            raise ValueError("a job writes before the start of the result")
+        rows = int(jobs["out"].max()) + 1 if len(jobs) else 0
+        if out is None:
+            out = np.zeros(rows, dtype=SUPERPOSE_OUT_DTYPE)
+        elif out.dtype != SUPERPOSE_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1 or len(out) < rows:
+            raise ValueError("out: a contiguous SUPERPOSE_OUT_DTYPE array with a row for every job")
+        rc = load().pw_superpose(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, None if w is None else w.ctypes.data,
+                                 len(x), out.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_superpose")
+        return out
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

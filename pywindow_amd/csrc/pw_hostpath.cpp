@@ -16,6 +16,7 @@
 #include "pw_dft.hpp"
 #include "pw_gate.hpp"
 #include "pw_trans.hpp"
+#include "pw_superpose.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -535,6 +536,74 @@ extern "C" int pw_hostpath_trans(const pw_trans_job* jobs, long n_jobs, const do
             }
             for (auto& t : pool) t.join();
         }
+    }
+    return PW_OK;
+}
+
+// pw_superpose on the host (pw_superpose.hip checks the arguments and sends device == -1 contexts here): the 64
+// accumulators of pw_superpose.hpp as arrays, atom i going to accumulator i % 64, folded by sup_fold.  The threads
+// share out blocks of BLOCK jobs; a job's row is its own.
+extern "C" int pw_hostpath_superpose(const pw_superpose_job* jobs, long n_jobs, const double* xyz, const double* weights,
+                                     pw_superpose_out* out, int threads) {
+    constexpr long BLOCK = 16;
+    const long pieces = (n_jobs + BLOCK - 1) / BLOCK;
+    std::atomic<long> next{0};
+    auto one = [&](const pw_superpose_job& J) {
+        const long n = (long)J.n;
+        const double* x = xyz + 3 * (long)J.mobile_first;
+        const double* y = xyz + 3 * (long)J.target_first;
+        const double* w = J.weight_first < 0 ? nullptr : weights + (long)J.weight_first;
+        SupSums acc[SUP_ACC];
+        double lanes[SUP_ACC];
+        for (int l = 0; l < SUP_ACC; ++l) sup_sums_zero(acc[l]);
+        for (long i = 0; i < n; ++i) sup_sums_atom(acc[i % SUP_ACC], x, y, w, i);
+        SupSums s;
+        auto fold = [&](auto field) {
+            for (int l = 0; l < SUP_ACC; ++l) lanes[l] = field(l);
+            return sup_fold(lanes);
+        };
+        s.w = fold([&](int l) { return acc[l].w; });
+        for (int a = 0; a < 3; ++a) {
+            s.x[a] = fold([&](int l) { return acc[l].x[a]; });
+            s.y[a] = fold([&](int l) { return acc[l].y[a]; });
+        }
+        SupCentres c;
+        sup_centres(s, c);
+        double macc[SUP_ACC][9] = {};
+        for (long i = 0; i < n; ++i) sup_moment_atom(macc[i % SUP_ACC], c, x, y, w, i);
+        double m[9], r[9], lambda[2];
+        for (int k = 0; k < 9; ++k) m[k] = fold([&](int l) { return macc[l][k]; });
+        const int sweeps = sup_solve(m, r, lambda);
+        for (int l = 0; l < SUP_ACC; ++l) lanes[l] = 0.0;
+        for (long i = 0; i < n; ++i) lanes[i % SUP_ACC] = sup_residual_atom(lanes[i % SUP_ACC], r, c, x, y, w, i);
+        const double e = sup_fold(lanes);
+        pw_superpose_out* o = out + (long)J.out;
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) o->rotation[a][b] = r[3 * a + b];
+            o->centre_mobile[a] = c.cx[a];
+            o->centre_target[a] = c.cy[a];
+        }
+        o->rmsd = pw_sqrt(e / c.W);
+        o->lambda[0] = lambda[0];
+        o->lambda[1] = lambda[1];
+        o->sweeps = sweeps;
+        o->reserved = 0;
+    };
+    auto worker = [&]() {
+        for (;;) {
+            const long p = next.fetch_add(1);
+            if (p >= pieces) break;
+            for (long k = p * BLOCK; k < std::min((p + 1) * BLOCK, n_jobs); ++k) one(jobs[k]);
+        }
+    };
+    if (threads < 1) threads = 1;
+    const int count = (long)threads > pieces ? (int)std::max(1l, pieces) : threads;
+    if (count == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < count; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
     }
     return PW_OK;
 }

@@ -54,6 +54,7 @@ class RecordStore:
             raise ValueError("one frame / molecule index per record")
         self._more = None
         self._spans = None
+        self._tracks = None
 
     # ---- index -----------------------------------------------------------------------------
     @property
@@ -261,6 +262,28 @@ class RecordStore:
     #: per-frame reductions of a unit's window diameters, for :meth:`series`
     _WINDOW_SERIES = ("windows_min", "windows_max", "windows_mean", "n_windows")
 
+    def attach_tracks(self, tracks) -> None:
+        """Keep the ``WindowTracks`` of this store (pywindow_amd/tracks.py) so that :meth:`series` knows
+        ``"window_site"``.  In memory only: tracks are not written by :meth:`save`, and the record file is unchanged."""
+        if len(tracks.site_of) != len(self._samples_by_unit("windows")[0]):
+            raise ValueError("the tracks are not of this store: one site per window")
+        self._tracks = tracks
+
+    def _site_series(self, quantity: str, site, molecule, guest):
+        if quantity != "window_site":
+            raise ValueError("site= belongs to 'window_site'")
+        if self._tracks is None:
+            raise ValueError("'window_site' needs window tracks: attach_tracks(track_windows(...)) first")
+        if site is None:
+            raise ValueError("'window_site' is one series a site: say which with site=")
+        if molecule is not None or guest is not None:
+            raise ValueError("'window_site' takes neither molecule= nor guest=")
+        t = self._tracks
+        j = int(site)
+        if not 0 <= j < t.diameter.shape[1]:
+            raise ValueError(f"site: 0 .. {t.diameter.shape[1] - 1}")
+        return t.frames.copy(), t.diameter[:, j].copy(), t.valid[:, j].copy()
+
     def _value_by_unit(self, quantity: str, guest=None):
         """``(value of every unit (nan where it has none), which units have one)``."""
         n = len(self.records)
@@ -288,7 +311,7 @@ class RecordStore:
             values[u] = w.min() if quantity == "windows_min" else w.max() if quantity == "windows_max" else np.sum(w) / len(w)
         return values, count > 0
 
-    def series(self, quantity: str, molecule=None, guest=None):
+    def series(self, quantity: str, molecule=None, guest=None, site=None):
         """``(frames, values, valid)``: ``quantity`` along the frame axis.  Every per-unit name of :meth:`samples`, or a
         per-frame reduction of the windows: ``"windows_min"``, ``"windows_max"``, ``"windows_mean"`` (``np.sum(d) /
         len(d)`` of the unit's diameters, those beyond what a record holds included) or ``"n_windows"`` (how many there
@@ -296,7 +319,12 @@ class RecordStore:
         the cooperative-gating state (0 is a value, also for a unit without windows).  ``frames = f0 + stride * arange(T)`` from the smallest frame of the store to the largest
         in steps of the gcd of their differences; units are placed by their frame index, whatever their order in the
         store.  A frame that is absent, or whose unit has no such value (non-porous, windows ``None``, ...), is a GAP:
-        ``valid[t]`` is ``False`` and ``values[t]`` nan.  Modular stores: ``molecule`` selects the molecule."""
+        ``valid[t]`` is ``False`` and ``values[t]`` nan.  Modular stores: ``molecule`` selects the molecule.
+        ``"window_site"`` with ``site=j``, once tracks are attached (:meth:`attach_tracks`): the diameter of the window
+        at site ``j`` of the cage, a gap where the frame has no window there; ``site=`` with any other quantity, or
+        ``"window_site"`` without tracks, is a ``ValueError``."""
+        if site is not None or quantity == "window_site":
+            return self._site_series(quantity, site, molecule, guest)
         values, has = self._value_by_unit(quantity, guest)
         if self.modular:
             if molecule is None:
@@ -319,15 +347,20 @@ class RecordStore:
         out[at], valid[at] = values[units], has[units]
         return frames, out, valid
 
-    def correlation(self, quantity: str, other=None, max_lag=None, per_molecule: bool = False, device=None):
+    def correlation(self, quantity: str, other=None, max_lag=None, per_molecule: bool = False, device=None, site=None):
         """Lagged correlation of :meth:`series` over the frames (pywindow_amd/correlations.py): a ``TimeCorrelation``
         of ``quantity`` with itself, or with ``other`` at later frames; gaps are left out pair by pair.  ``lag`` is in
-        frames.  ``per_molecule`` (modular stores): ``{molecule: TimeCorrelation}``, all from one batched call."""
+        frames.  ``per_molecule`` (modular stores): ``{molecule: TimeCorrelation}``, all from one batched call.
+        ``site``: passed to :meth:`series` for ``quantity`` (``"window_site"``); ``other`` may be ``("window_site", j)``,
+        so that ``correlation("window_site", ("window_site", 2), site=0)`` says whether two windows open together."""
         from . import correlations as C
 
         def pair(molecule):
-            frames, a, va = self.series(quantity, molecule)
-            b, vb = self.series(other, molecule)[1:] if other is not None else (None, None)
+            frames, a, va = self.series(quantity, molecule, site=site)
+            if isinstance(other, tuple):
+                b, vb = self.series(other[0], molecule, site=other[1])[1:]
+            else:
+                b, vb = self.series(other, molecule)[1:] if other is not None else (None, None)
             return int(frames[1] - frames[0]), (a, b, va, vb)
 
         if not per_molecule:
@@ -340,16 +373,16 @@ class RecordStore:
         return dict(zip(keys, C.time_correlation_batch([p for _, p in pairs], max_lag, device, [s for s, _ in pairs])))
 
     def spectrum(self, quantity: str, molecule=None, per_molecule: bool = False, oversample: int = 4,
-                 max_frequency: float = 0.5, dt: float = 1.0, device=None):
+                 max_frequency: float = 0.5, dt: float = 1.0, device=None, site=None):
         """Generalised Lomb-Scargle periodogram of :meth:`series` over the frames (pywindow_amd/spectra.py): a
         ``Spectrum`` whose ``peak_frequency`` says at which frequency ``quantity`` oscillates; gaps are left out
         exactly.  ``frequency`` is in cycles per ``dt`` (the time of one frame; the stride of the frame axis is taken
         from the series), ``max_frequency`` in cycles per sample.  ``per_molecule`` (modular stores): ``{molecule:
-        Spectrum}``, all from one batched call."""
+        Spectrum}``, all from one batched call.  ``site``: passed to :meth:`series` (``"window_site"``)."""
         from . import spectra as S
 
         def one(mol):
-            frames, a, valid = self.series(quantity, mol)
+            frames, a, valid = self.series(quantity, mol, site=site)
             return int(frames[1] - frames[0]), (a, valid)
 
         if not per_molecule:
@@ -363,18 +396,18 @@ class RecordStore:
                                                    dt, device)))
 
     def gating(self, quantity: str = "windows_max", thresholds=200, molecule=None, per_molecule: bool = False,
-               n_bins: int = 64, device=None):
+               n_bins: int = 64, device=None, site=None):
         """Gating statistics of :meth:`series` over the frames (pywindow_amd/gating.py): a ``Gating`` that says, for a
         guest of every diameter of ``thresholds``, what fraction of the time ``quantity`` admits it (``windows_max``: the
         largest window does; ``windows_min``: every window does), how often it opens and closes and how long the
         openings and closures last; gaps end a run and censor it.  ``thresholds``: an int for ``np.linspace(min, max,
         thresholds)`` over the valid values of the series, or the thresholds themselves.  Lengths are in frames (the
         stride of the frame axis is taken from the series).  ``per_molecule`` (modular stores): ``{molecule: Gating}``,
-        all from one batched call."""
+        all from one batched call.  ``site``: passed to :meth:`series` (``"window_site"``: the gating of ONE window)."""
         from . import gating as G
 
         def one(mol):
-            frames, a, valid = self.series(quantity, mol)
+            frames, a, valid = self.series(quantity, mol, site=site)
             if isinstance(thresholds, (bool, np.bool_)):
                 raise ValueError("thresholds: a number of thresholds or the thresholds themselves, not a bool")
             if isinstance(thresholds, (int, np.integer)):
@@ -395,7 +428,7 @@ class RecordStore:
         return dict(zip(keys, G.gate_statistics_batch([i for _, i in each], n_bins, [s for s, _ in each], device)))
 
     def kinetics(self, quantity: str = "windows_max", edges=None, max_lag=None, lag_step: int = 1, molecule=None,
-                 per_molecule: bool = False, guest=None, device=None):
+                 per_molecule: bool = False, guest=None, device=None, site=None):
         """Lagged state-transition counts of :meth:`series` over the frames (pywindow_amd/kinetics.py): a ``Kinetics``
         with the count matrices ``C_k[i][j] = #{t : s[t] = i, s[t + k] = j}``, the transition matrices, the populations
         and the implied timescales; a pair with a gap at either end is counted nowhere.  ``edges`` cut the value axis
@@ -403,7 +436,8 @@ class RecordStore:
         number of windows open to a guest of diameter ``d``; its ``edges`` default to ``0.5, 1.5, ...`` up to the largest
         count seen, one state per count.  The lags are ``0, lag_step, 2 * lag_step, ...`` up to ``max_lag`` (default
         ``T // 2``), both in samples of the series; ``Kinetics.lag`` is in frames (the stride of the frame axis is taken
-        from the series).  ``per_molecule`` (modular stores): ``{molecule: Kinetics}``, all from one batched call."""
+        from the series).  ``per_molecule`` (modular stores): ``{molecule: Kinetics}``, all from one batched call.
+        ``site``: passed to :meth:`series` (``"window_site"``)."""
         from . import kinetics as K
 
         lag_step = int(lag_step)
@@ -411,7 +445,7 @@ class RecordStore:
             raise ValueError("lag_step: at least 1")
 
         def one(mol):
-            frames, a, valid = self.series(quantity, mol, guest)
+            frames, a, valid = self.series(quantity, mol, guest, site)
             if edges is not None:
                 e = np.asarray(edges, dtype=np.float64)
             elif quantity == "windows_open":

@@ -77,6 +77,7 @@ class DLPOLY:
         self.frames: dict = {}
         self.analysis_output: dict = {}
         self._stores: list = []                 # the records behind analysis_output, one RecordStore per analysis
+        self._tracks = None                     # the latest track_windows result and the frames it covers
         #: host-side legs of the latest analysis_records / analysis call, milliseconds (the analysis itself runs
         #: asynchronously: what the host sees of it is the wait in the download)
         self.last_timings: dict = {}
@@ -268,7 +269,10 @@ class DLPOLY:
         view = LazyAnalysis()
         for store in self._stores:
             view.attach(store)
-        return view.record_store()
+        store = view.record_store()
+        if self._tracks is not None and np.array_equal(self._tracks[1], store.unit_frame) and not store.modular:
+            store.attach_tracks(self._tracks[0])            # (tracks of other frames than the store now has are stale)
+        return store
 
     def distribution(self, quantity: str, points=1000, pad: float = 1.0, bw_method="scott", per_molecule: bool = False,
                      device=None):
@@ -293,35 +297,116 @@ class DLPOLY:
         on a mesh, summed on the GPU: ``RecordStore.joint_distribution`` of :attr:`analysis_store`."""
         return self.analysis_store.joint_distribution(quantity_x, quantity_y, points, pad, bw_method, per_molecule, device)
 
-    def correlation(self, quantity: str, other=None, max_lag=None, per_molecule: bool = False, device=None):
+    def correlation(self, quantity: str, other=None, max_lag=None, per_molecule: bool = False, device=None, site=None):
         """Lagged correlation over the frames analysed or loaded so far -- how long the pore keeps its size
         (``correlation("pore_diameter_opt").time``, ``.n_effective``), whether it follows the windows
         (``correlation("pore_diameter_opt", "windows_min")``) -- summed on the GPU: ``RecordStore.correlation`` of
         :attr:`analysis_store`."""
-        return self.analysis_store.correlation(quantity, other, max_lag, per_molecule, device)
+        return self.analysis_store.correlation(quantity, other, max_lag, per_molecule, device, site)
 
     def spectrum(self, quantity: str, molecule=None, per_molecule: bool = False, oversample: int = 4,
-                 max_frequency: float = 0.5, dt: float = 1.0, device=None):
+                 max_frequency: float = 0.5, dt: float = 1.0, device=None, site=None):
         """At which frequency the cage breathes (``spectrum("pore_diameter_opt").peak_frequency``, ``.peak_period``):
         the generalised Lomb-Scargle periodogram over the frames analysed or loaded so far, gaps left out exactly,
         summed on the GPU: ``RecordStore.spectrum`` of :attr:`analysis_store`."""
-        return self.analysis_store.spectrum(quantity, molecule, per_molecule, oversample, max_frequency, dt, device)
+        return self.analysis_store.spectrum(quantity, molecule, per_molecule, oversample, max_frequency, dt, device, site)
 
     def gating(self, quantity: str = "windows_max", thresholds=200, molecule=None, per_molecule: bool = False,
-               n_bins: int = 64, device=None):
+               n_bins: int = 64, device=None, site=None):
         """For guests of the diameters ``thresholds``: what fraction of the time the cage is open
         (``gating("windows_max", thresholds=[3.3, 3.64]).open_fraction``), how often it opens (``.openings``) and how
         long an opening or a closure lasts (``.mean_open``, ``.open_lengths``), over the frames analysed or loaded so
         far, counted on the GPU: ``RecordStore.gating`` of :attr:`analysis_store`."""
-        return self.analysis_store.gating(quantity, thresholds, molecule, per_molecule, n_bins, device)
+        return self.analysis_store.gating(quantity, thresholds, molecule, per_molecule, n_bins, device, site)
 
     def kinetics(self, quantity: str = "windows_max", edges=None, max_lag=None, lag_step: int = 1, molecule=None,
-                 per_molecule: bool = False, guest=None, device=None):
+                 per_molecule: bool = False, guest=None, device=None, site=None):
         """Rates and the Markov test of a gating process: the lagged transition counts between the states that ``edges``
         cut ``quantity`` into (``kinetics("windows_open", guest=3.3).timescales``: the implied timescales of the number
         of windows open to a guest of 3.3 A), over the frames analysed or loaded so far, counted on the GPU:
         ``RecordStore.kinetics`` of :attr:`analysis_store`."""
-        return self.analysis_store.kinetics(quantity, edges, max_lag, lag_step, molecule, per_molecule, guest, device)
+        return self.analysis_store.kinetics(quantity, edges, max_lag, lag_step, molecule, per_molecule, guest, device, site)
+
+    # ---- superposition and window identity (pywindow_amd/superposition.py, pywindow_amd/tracks.py) -------------
+    def _rigid_frames(self, frames, what: str):
+        """The coordinates of the selected frames as they are in the file.  A periodic trajectory is refused: its
+        molecules are rebuilt through the boundary frame by frame, and the atom order of a rebuilt molecule is not
+        fixed across frames, so row ``i`` of two frames need not be the same atom."""
+        if self.periodic:
+            raise ValueError(f"{what}: a periodic or modular trajectory is not supported yet (the atom order of a "
+                             "rebuilt molecule is not fixed across frames)")
+        sel = self._select(frames)
+        if not sel:
+            raise ValueError(f"{what}: no frames selected")
+        return sel, self._read_selected(sel, False)[0]
+
+    def _weights(self, weights, swap_atoms, forcefield):
+        if weights is None:
+            return None
+        if isinstance(weights, str):
+            if weights != "mass":
+                raise ValueError('weights: "mass", None or one weight per atom')
+            return MASS[element_ids(self.elements(swap_atoms, forcefield))]
+        return np.asarray(weights, dtype=np.float64)
+
+    def superposition(self, reference: int = 0, frames="all", weights="mass", swap_atoms=None, forcefield=None,
+                      device=None) -> dict:
+        """Every selected frame onto frame ``reference`` of the trajectory by least squares (``pw_superpose``, one call
+        on the GPU): ``{"frames" (T), "rotation" (T, 3, 3), "rmsd" (T), "centre" (T, 3), "eigenvalues" (T, 2),
+        "reference_centre" (3)}`` with ``rotation[t] @ (x - centre[t]) + reference_centre`` frame ``t`` in the
+        orientation of the reference.  ``weights``: ``"mass"`` (the centre is the centre of mass), ``None`` or one
+        weight per atom.  Whole, non-periodic molecules only: a periodic (or modular) trajectory raises ``ValueError``
+        -- the atom order of a rebuilt molecule is not fixed across frames."""
+        from . import superposition as SP
+
+        sel, coords = self._rigid_frames(frames, "superposition")
+        ref = int(reference)
+        if ref in sel:
+            at, xyz = sel.index(ref), coords
+        else:
+            if not 0 <= ref < self.no_of_frames:
+                raise ValueError("reference: not a frame of the trajectory")
+            at, xyz = len(sel), np.concatenate([coords, self.read_coordinates(ref, 1)])
+        rows = SP.superpose_onto(xyz, at, self._weights(weights, swap_atoms, forcefield), device)
+        return {"frames": np.asarray(sel, dtype=np.int64), "rotation": rows["rotation"][:len(sel)].copy(),
+                "rmsd": rows["rmsd"][:len(sel)].copy(), "centre": rows["centre_mobile"][:len(sel)].copy(),
+                "eigenvalues": rows["lambda"][:len(sel)].copy(), "reference_centre": rows["centre_target"][0].copy()}
+
+    def rmsd_matrix(self, frames="all", weights="mass", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
+        """The (T, T) least-squares RMSD between every two selected frames (``pywindow_amd.rmsd_matrix``): the input
+        of a conformational clustering.  Same restrictions as :meth:`superposition`."""
+        from . import superposition as SP
+
+        _, coords = self._rigid_frames(frames, "rmsd_matrix")
+        return SP.rmsd_matrix(coords, self._weights(weights, swap_atoms, forcefield), device)
+
+    def track_windows(self, reference: int = 0, sites=None, min_cosine=None, weights="mass", swap_atoms=None,
+                      forcefield=None, device=None):
+        """Follow every window through the frames analysed so far: :meth:`superposition` of those frames onto frame
+        ``reference``, ``pywindow_amd.track_windows`` with the rotations about each record's centre of mass, and the
+        ``WindowTracks`` attached to :attr:`analysis_store`, so that ``gating("window_site", site=j)``,
+        ``kinetics``, ``spectrum`` and ``correlation`` speak of ONE window.  ``sites``: by default the windows of the
+        reference frame (which must then be among the analysed ones).  Non-modular, non-periodic analyses only."""
+        from . import tracks as TR
+
+        self._tracks = None
+        store = self.analysis_store
+        if store.modular:
+            raise ValueError("track_windows: a periodic or modular trajectory is not supported yet (the atom order of a "
+                             "rebuilt molecule is not fixed across frames)")
+        unit_frames = [int(f) for f in store.unit_frame]
+        if not unit_frames:
+            raise ValueError("track_windows: no frame has been analysed yet")
+        sup = self.superposition(reference, unit_frames, weights, swap_atoms, forcefield, device)
+        ref = int(reference)
+        if sites is None and ref not in unit_frames:
+            raise ValueError("track_windows: the reference frame has not been analysed: give the sites")
+        # the centre a record's windows are measured from is the record's own (the analysis shifts nothing)
+        tracks = TR.track_windows(store, sup["rotation"], np.asarray(store.records["com"], dtype=np.float64), sites,
+                                  min_cosine, unit_frames.index(ref) if ref in unit_frames else 0)
+        self._tracks = (tracks, np.array(store.unit_frame))
+        store.attach_tracks(tracks)
+        return tracks
 
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
