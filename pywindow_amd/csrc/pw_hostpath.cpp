@@ -617,3 +617,10 @@ extern "C" void pw_hostpath_dft_twiddles(long j, long M, const long* k, long n, 
 extern "C" void pw_hostpath_exp(const double* x, long n, double* y) {
     for (long i = 0; i < n; ++i) y[i] = pw_exp(x[i]);
 }
+
+// one function of pw_math.hpp over an array, with the reciprocal-square-root table the analysis above uses
+// (test instrumentation, pw_kernels.hip: pw_internal_math); y is null for the functions of one argument
+extern "C" void pw_hostpath_math(int which, const double* x, const double* y, long n, double* out) {
+    std::call_once(g_rsq_once, [] { rsqrt14_decode(g_rsq); });
+    for (long i = 0; i < n; ++i) out[i] = pw_math_probe(which, x[i], y ? y[i] : 0.0, g_rsq);
+}

@@ -37,6 +37,7 @@ using namespace pw;
 extern "C" int pw_hostpath_run(const pw_batch_in* in, unsigned stages, pw_unit_out* out, const pw_params* prm, int p_cap,
                                int threads, pw_unit_debug* dbg, pw_extra_window* xw, unsigned xw_cap, unsigned* xw_count);
 extern "C" int pw_hostpath_default_threads(void);
+extern "C" void pw_hostpath_math(int which, const double* x, const double* y, long n, double* out);
 // pw_kernels_big.hip: the same source with the team's shared block in global memory (molecules beyond LDS)
 extern "C" size_t pw_internal_big_block_bytes(int nmax, int p_cap);
 extern "C" int pw_internal_big_launch(void* stream, int grid, long n_units, const long* atom_offset, const double* xyz,
@@ -439,6 +440,16 @@ __global__ void pw_div_check_kernel(unsigned long long n, int mode, unsigned lon
             if (atomicAdd(&out[0], 1ull) == 0ull) { out[1] = as_u(a); out[2] = as_u(b); out[3] = as_u(got); }
         }
     }
+}
+
+// One function of pw_math.hpp element by element (test instrumentation, pw_internal_math): neighbouring lanes take
+// different arguments, so the branches of the functions diverge as they do inside an analysis.  rsq_tab: the context's
+// table, the one the analysis kernels read.  y: null for the functions of one argument.
+__global__ void __launch_bounds__(256)
+pw_math_probe_kernel(int which, long n, const double* __restrict__ x, const double* __restrict__ y,
+                     const unsigned* __restrict__ rsq_tab, double* __restrict__ out) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+        out[i] = pw_math_probe(which, x[i], y ? y[i] : 0.0, rsq_tab);
 }
 
 // Start of a pipeline launch: the record buffer, the hand-off queue with its slots and the three work
@@ -1193,6 +1204,42 @@ void* pw_internal_rebuild_stream(pw_context* c) {
 }
 
 void* pw_context_stream(pw_context* c) { return c ? (void*)c->stream : nullptr; }
+
+// test instrumentation (not part of the header): out[i] = f_which(x[i] [, y[i]]) for one function of pw_math.hpp
+// (which: PW_MATH_*; y is read by PW_MATH_POW and PW_MATH_DIV only) on the context's device -- with the context's own
+// reciprocal-square-root table -- or on the host path for a device == -1 context.  The two must agree to the bit
+// (tests/test_gpu_math.py).
+int pw_internal_math(pw_context* c, int which, const double* x, const double* y, int64_t n, double* out) {
+    if (!c || which < 0 || which >= PW_MATH_COUNT || n < 0) return PW_E_BAD_ARG;
+    if (n && (!x || !out || (pw_math_probe_binary(which) && !y))) return PW_E_BAD_ARG;
+    if (n == 0) return PW_OK;
+    PW_LOCK_CONTEXT(c);
+    if (!pw_math_probe_binary(which)) y = nullptr;
+    if (c->device < 0) {
+        pw_hostpath_math(which, x, y, (long)n, out);
+        return PW_OK;
+    }
+    PW_ON_DEVICE(c->device);
+    hipStream_t st = c->stream;
+    const size_t bytes = sizeof(double) * (size_t)n;
+    // device memory of the call, allocated and released in stream order
+    struct Buffers {
+        hipStream_t st;
+        double* p[3] = {nullptr, nullptr, nullptr};
+        ~Buffers() { for (double* q : p) if (q) (void)hipFreeAsync(q, st); }
+    } buf{st};
+    for (int k = 0; k < 3; ++k)
+        if (k != 1 || y) HIP_TRY(hipMallocAsync((void**)&buf.p[k], bytes, st));
+    HIP_TRY(hipMemcpyAsync(buf.p[0], x, bytes, hipMemcpyHostToDevice, st));
+    if (y) HIP_TRY(hipMemcpyAsync(buf.p[1], y, bytes, hipMemcpyHostToDevice, st));
+    const long blocks = ((long)n + 255) / 256;
+    hipLaunchKernelGGL(pw_math_probe_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, which, (long)n,
+                       buf.p[0], buf.p[1], c->rsq_tab, buf.p[2]);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, buf.p[2], bytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return PW_OK;
+}
 
 // Page-locked host staging buffer of the context (grown on demand, one per context): the reader decodes
 // frames straight into it and pw_resident_upload's copies from it are real asynchronous DMA instead of

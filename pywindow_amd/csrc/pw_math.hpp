@@ -170,8 +170,9 @@ PW_HD inline double pw_cos(double x) { return pw_cos_np(x); }
 // The reference writes x ** 2, r ** 3 and m ** 0.5 on numpy float64 SCALARS (utilities.py:93, 431,
 // 1095, 1434); those go to glibc's pow() (e_pow.c: table-driven log to ~68 bits, then exp), which
 // is within 0.52 ulp but not correctly rounded: pow(x, 2.0) != x*x for 0.08 % of the arguments.
-// Main path of the FMA build, operation by operation; x positive and normal, |y log x| moderate
-// (everything on this path), otherwise the caller's plain expression is used.
+// Main path of the FMA build, operation by operation; x positive and normal, the result normal with room to
+// spare: 2^-1020 <= x^y < 2^1020 (everything on this path), otherwise the caller's plain expression is used --
+// glibc's handling of a result that under- or overflows is not restated, and below 2^-1022 `scale` is meaningless.
 PW_NOINLINE PW_HD inline double pw_pow_np(double x, double y) {
     const uint64_t ix = pw_d2bits(x);
     const uint64_t tmp = ix - 0x3fe6955500000000ull;
@@ -275,15 +276,16 @@ PW_HD inline double pw_exp_tab(double x, Tab tab) {
 }
 PW_HD inline double pw_exp(double x) { return pw_exp_tab(x, POW_EXP_TAB); }
 
-// x ** 2 and x ** 3 for any finite x (pow's sign handling for integer exponents)
+// x ** 2 and x ** 3 for any finite x (pow's sign handling for integer exponents).  Outside pw_pow_np's domain -- a
+// power below 2^-1020 or beyond 1e300, zero, infinities, NaN -- the plain product, which is within one ulp of pow.
 PW_HD inline double pw_square_np(double x) {
     double a = pw_abs(x);
-    if (!(a >= 2.2250738585072014e-308 && a < 1e150)) return x * x;
+    if (!(a >= 0x1p-510 && a < 1e150)) return x * x;
     return pw_pow_np(a, 2.0);
 }
 PW_HD inline double pw_cube_np(double x) {
     double a = pw_abs(x);
-    if (!(a >= 2.2250738585072014e-308 && a < 1e100)) return x * x * x;
+    if (!(a >= 0x1p-340 && a < 1e100)) return x * x * x;
     double r = pw_pow_np(a, 3.0);
     return x < 0.0 ? -r : r;
 }
@@ -324,7 +326,7 @@ PW_HD inline double pw_rsqrt14(double y, const unsigned* tab) {
     uint64_t rb = ((uint64_t)((int)(v >> 16) - k) << 52) | ((uint64_t)(v & 0xffffu) << 36);
     return pw_bits2d(rb);
 }
-// numpy.arccos(x) for |x| <= 1
+// numpy.arccos(x) for |x| <= 1; NaN beyond, as numpy (|vx| / sqrt(vx ** 2) can round to 1 + 2^-52)
 PW_NOINLINE PW_HD inline double pw_acos_np(double x, const unsigned* tab) {
     const double c4 = pw_bits2d(0xbf918000993b24c3ull), c3 = pw_bits2d(0x3fa400006f70d42dull),
                  c2 = pw_bits2d(0xbfb7fffffffffe97ull), c1 = pw_bits2d(0x3fcfffffffffff9dull);
@@ -378,39 +380,65 @@ PW_NOINLINE PW_HD inline double pw_acos_np(double x, const unsigned* tab) {
     const double z3 = H - C;
     double z = pw_fma(z3, Q, z6);
     z = z + H;
-    return pw_bits2d(pw_d2bits(z) ^ sign) + hi;
+    const double res = pw_bits2d(pw_d2bits(z) ^ sign) + hi;
+    return nax < -1.0 ? pw_bits2d(0x7ff8000000000000ull) : res;
 }
 
-// natural log, fdlibm-style kernel (< 1 ulp); x > 0, normal.
-PW_HD inline double pw_log(double x) {
-    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10,
-                 Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01,
-                 Lg3 = 2.857142874366239149e-01, Lg4 = 2.222219843214978396e-01,
-                 Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
-                 Lg7 = 1.479819860511658591e-01;
-    union { double d; uint64_t u; } cv;
-    cv.d = x;
-    int e = (int)((cv.u >> 52) & 0x7ff) - 1023;
-    cv.u = (cv.u & 0x000fffffffffffffull) | 0x3ff0000000000000ull;  // m in [1,2)
-    double m = cv.d;
-    if (m > 1.4142135623730951) { m *= 0.5; e += 1; }
-    double f = m - 1.0;
-    double s = f / (2.0 + f);
-    double z = s * s;
-    double w = z * z;
-    double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
-    double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
-    double R = t2 + t1;
-    double hfsq = 0.5 * f * f;
-    double dk = (double)e;
-    return dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
-}
-
+// ---- numpy.log10, through its floor ---------------------------------------------------------------------------
+// The reference sizes the sampling sphere with int(numpy.log10(area) * 250 * adjust), and numpy.log10 (SVML) is
+// correctly rounded on every argument it has been compared on -- among them the doubles next to 10^(m/250), where the
+// product is within an ulp of the integer m and a logarithm that is one ulp off floors to the wrong count
+// (tests/test_math_edges.py; the fdlibm-style kernel that stood here did on 689 of 47870).  So: log(x) as hi + lo to
+// ~2^-66 by the table-driven first half of pw_pow_np (same table, same operations), times 1 / ln 10 as hi + lo,
+// rounded once at the end.  x positive and normal.
 PW_HD inline double pw_log10(double x) {
     const double ivln10_hi = 0.4342944819032518, ivln10_lo = 1.098319650216765e-17;
-    double lg = pw_log(x);
-    DD p = two_prod(lg, ivln10_hi);
-    return p.hi + (p.lo + lg * ivln10_lo);
+    const uint64_t ix = pw_d2bits(x);
+    const uint64_t tmp = ix - 0x3fe6955500000000ull;
+    const int i = (int)((tmp >> 45) & 0x7f);
+    const double kd = (double)(int)((int64_t)tmp >> 52);
+    const double z = pw_bits2d(ix - (tmp & 0xfff0000000000000ull));
+    const double invc = POW_LOG_TAB[4 * i], logc = POW_LOG_TAB[4 * i + 2], logctail = POW_LOG_TAB[4 * i + 3];
+    const double A0 = POW_LOG_HEAD[2], A1 = POW_LOG_HEAD[3], A2 = POW_LOG_HEAD[4], A3 = POW_LOG_HEAD[5],
+                 A4 = POW_LOG_HEAD[6], A5 = POW_LOG_HEAD[7], A6 = POW_LOG_HEAD[8];
+    const double r = pw_fma(z, invc, -1.0);
+    const double t1 = pw_fma(kd, POW_LOG_HEAD[0], logc);
+    const double t2 = r + t1;
+    const double ar = r * A0, ar2 = r * ar, ar3 = r * ar2;
+    const double hi = t2 + ar2;
+    double lo = pw_fma(kd, POW_LOG_HEAD[1], logctail) + ((t1 - t2) + r);
+    lo = lo + pw_fma(ar, r, -ar2);
+    lo = lo + ((t2 - hi) + ar2);
+    lo = pw_fma(ar3, pw_fma(ar2, pw_fma(pw_fma(r, A6, A5), ar2, pw_fma(r, A4, A3)), pw_fma(r, A2, A1)), lo);
+    const double lhi = hi + lo;
+    const double llo = (hi - lhi) + lo;
+    DD p = two_prod(lhi, ivln10_hi);
+    return p.hi + (p.lo + pw_fma(lhi, ivln10_lo, llo * ivln10_hi));
+}
+
+// ---- test instrumentation: one function of this header, chosen by number --------------------------
+// pw_internal_math (pw_kernels.hip; pw_hostpath.cpp for a device == -1 context) applies this to arrays so that the
+// gfx950 build and the host build can be compared bit for bit, argument by argument (tests/test_gpu_math.py,
+// tests/_math_cases.py holds the numbers).  `y` is read by PW_MATH_POW and PW_MATH_DIV only.
+enum {
+    PW_MATH_SIN = 0, PW_MATH_COS = 1, PW_MATH_POW = 2, PW_MATH_SQUARE = 3, PW_MATH_CUBE = 4, PW_MATH_ACOS = 5,
+    PW_MATH_LOG10 = 6, PW_MATH_SQRT = 7, PW_MATH_DIV = 8, PW_MATH_COUNT = 9
+};
+PW_HD inline bool pw_math_probe_binary(int which) { return which == PW_MATH_POW || which == PW_MATH_DIV; }
+PW_HD inline double pw_math_probe(int which, double x, double y, const unsigned* rsq_tab) {
+    // sin / cos beyond 1.05e8 (unspecified above, and the reduced argument would index past SC_TAB): not evaluated
+    if (which <= PW_MATH_COS && !(pw_abs(x) <= 1.05e8)) return pw_bits2d(0x7ff8000000000000ull);
+    switch (which) {
+        case PW_MATH_SIN: return pw_sin_np(x);
+        case PW_MATH_COS: return pw_cos_np(x);
+        case PW_MATH_POW: return pw_pow_np(x, y);
+        case PW_MATH_SQUARE: return pw_square_np(x);
+        case PW_MATH_CUBE: return pw_cube_np(x);
+        case PW_MATH_ACOS: return pw_acos_np(x, rsq_tab);
+        case PW_MATH_LOG10: return pw_log10(x);
+        case PW_MATH_SQRT: return pw_sqrt(x);
+        default: return x / y;
+    }
 }
 
 }  // namespace pw
