@@ -634,6 +634,43 @@ typedef struct pw_superpose_out {
 } pw_superpose_out;
 int pw_superpose(pw_context *ctx, const pw_superpose_job *jobs, int64_t n_jobs, const double *xyz,
                  const double *weights, int64_t n_points, pw_superpose_out *out);
+/* ---- conformational clustering of frames: the gromos method over a distance matrix ----------------------------
+ * Which conformations a cage visits, which frame stands for each and which conformation every frame is in: the
+ * clustering of Daura et al. (1999), GROMACS's `gromos`, over a matrix of pairwise distances such as the RMSD
+ * matrix of pw_superpose.  The reference has no counterpart.  Job k has the n x n row-major matrix
+ * d = dist[d_first .. + n * n) and a cutoff.  ONLY THE STRICT UPPER TRIANGLE IS READ: the diagonal and the lower
+ * triangle may hold anything, a NaN included.  Frames i != j are neighbours iff d[min(i,j)][max(i,j)] <= cutoff;
+ * every frame is a neighbour of itself; all frames start active.  While any frame is active:
+ *     1. for every active i, count the active neighbours of i, itself included;
+ *     2. the centre c is the active frame with the largest count, the SMALLEST INDEX among equal counts;
+ *     3. cluster k (0, 1, ... in the order found) is c and its active neighbours: labels[out_first + j] = k for
+ *        each of them, centres[out_first + k] = c, sizes[out_first + k] = the count;
+ *     4. the members of cluster k become inactive.
+ * So sizes do not increase with k, every frame has exactly one label, and n_clusters[k'] of job k' is the number
+ * of clusters.  All n entries of centres and sizes are written: past the number of clusters they are -1 and 0.
+ * Every output is an integer, so the result is this definition itself on every device, launch geometry and run
+ * and on a device == -1 context (host threads), whatever else shares the call.  The device thresholds the matrix
+ * once into a bit matrix of n^2 / 8 bytes a job (pywindow_amd/csrc/pw_cluster.hpp); the matrix goes to the device
+ * in slabs of whole rows of at most 64 MiB, so it is never there as a whole; jobs share the launches of their
+ * rounds while their bit matrices stay within 256 MiB; a round (two launches) finds one cluster of every such
+ * job, so a job costs as many rounds as it has clusters and one more; and the result depends on none of that.
+ * All pointers are host memory; n_dist is the number of entries of dist.  Any mix of jobs in one call; jobs may
+ * share a matrix -- many cutoffs over one matrix, which is then thresholded for each from one upload -- but not
+ * entries of labels, centres and sizes; entries no job owns are never touched.  A job with n == 0 writes only
+ * its n_clusters = 0.  A NaN in the strict upper triangle of a job's matrix, a NaN cutoff, a negative field,
+ * n > PW_CLUSTER_MAX_N or a matrix that reaches outside dist: PW_E_BAD_ARG (pw_last_error names the job and the
+ * reason), and nothing is launched or written.  Infinities are legal, in the matrix (never neighbours unless the
+ * cutoff is +inf) and as the cutoff (-inf: every frame a cluster of its own).  Device work is queued on the
+ * context's stream, its memory allocated and freed in stream order; the call returns when the results are in
+ * place. */
+#define PW_CLUSTER_MAX_N 32768
+typedef struct pw_cluster_job {
+    int64_t d_first, n;     /* matrix = dist[d_first .. + n*n), row-major; 0 <= n <= PW_CLUSTER_MAX_N */
+    double  cutoff;         /* neighbours: d <= cutoff; any non-NaN value, -inf .. +inf */
+    int64_t out_first;      /* labels / centres / sizes [out_first .. +n), n_clusters[its job index] */
+} pw_cluster_job;
+int pw_cluster_gromos(pw_context *ctx, const pw_cluster_job *jobs, int64_t n_jobs, const double *dist,
+                      int64_t n_dist, int32_t *labels, int32_t *centres, int32_t *sizes, int64_t *n_clusters);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

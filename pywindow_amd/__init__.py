@@ -29,6 +29,7 @@ from .gating import Gating, gate_statistics, gate_statistics_batch  # noqa: E402
 from .kinetics import Kinetics, transition_counts, transition_counts_batch  # noqa: E402
 from .superposition import Superposition, rmsd_matrix, superpose, superpose_batch  # noqa: E402
 from .tracks import WindowTracks, track_windows  # noqa: E402
+from .clustering import Clusters, cluster_frames, cluster_frames_scan  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -77,6 +78,9 @@ __all__ = [
     "rmsd_matrix",
     "WindowTracks",
     "track_windows",
+    "Clusters",
+    "cluster_frames",
+    "cluster_frames_scan",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

@@ -235,6 +235,13 @@ SUPERPOSE_OUT_DTYPE = np.dtype(
 )
 assert SUPERPOSE_OUT_DTYPE.itemsize == 152
 
+#: numpy mirror of ``pw_cluster_job``
+CLUSTER_JOB_DTYPE = np.dtype(
+    [("d_first", np.int64), ("n", np.int64), ("cutoff", np.float64), ("out_first", np.int64)]
+)
+#: ``PW_CLUSTER_MAX_N``
+CLUSTER_MAX_N = 32768
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -322,6 +329,7 @@ EXPORTED_SYMBOLS = [
     "pw_gate_counts",
     "pw_trans_counts",
     "pw_superpose",
+    "pw_cluster_gromos",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -444,6 +452,7 @@ def load():
     L.pw_gate_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, vp]
     L.pw_trans_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     L.pw_superpose.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
+    L.pw_cluster_gromos.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -894,6 +903,38 @@ class Context:
             raise ValueError(load().pw_last_error().decode(errors="replace"))
         _check(rc, "pw_superpose")
         return out
+
+    def cluster_gromos(self, jobs, dist, labels=None, centres=None, sizes=None):
+        """``pw_cluster_gromos``: the gromos clustering of a batch of jobs (``CLUSTER_JOB_DTYPE`` records indexing the
+        float64 array ``dist`` -- ``n * n`` row-major entries from ``d_first``, of which only the strict upper triangle is
+        read -- and the entries of the results): ``(labels, centres, sizes, n_clusters)``, the first three int32 with the
+        ``n`` entries from ``out_first`` of every job filled in -- given, or ``-1``, ``-1`` and ``0`` up to the furthest
+        entry of a job; entries no job owns stay as they are -- and ``n_clusters`` int64, one per job.  A NaN in the strict
+        upper triangle, a NaN cutoff or ``n`` above ``CLUSTER_MAX_N`` raises ``ValueError``; a matrix that reaches outside
+        ``dist`` or results too short for a job ``IndexError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=CLUSTER_JOB_DTYPE).reshape(-1)
+        d = np.ascontiguousarray(dist, dtype=np.float64).reshape(-1)
+        size = 0
+        if len(jobs):
+            if ((jobs["d_first"] < 0) | (jobs["n"] < 0) | (jobs["d_first"] + jobs["n"] * jobs["n"] > len(d))).any():
+                raise IndexError("a job reaches outside `dist`")
+            if (jobs["out_first"] < 0).any():
+                raise IndexError("a job writes before the start of the results")
+            size = int((jobs["out_first"] + jobs["n"]).max())
+        out = []
+        for given, fill, what in ((labels, -1, "labels"), (centres, -1, "centres"), (sizes, 0, "sizes")):
+            if given is None:
+                given = np.full(size, fill, dtype=np.int32)
+            elif given.dtype != np.int32 or not given.flags.c_contiguous or given.ndim != 1 or len(given) < size:
+                raise IndexError(f"{what}: a contiguous int32 array with an entry for every frame of every job")
+            out.append(given)
+        n_clusters = np.zeros(len(jobs), dtype=np.int64)
+        rc = load().pw_cluster_gromos(self._h, jobs.ctypes.data, len(jobs), d.ctypes.data, len(d), out[0].ctypes.data,
+                                      out[1].ctypes.data, out[2].ctypes.data, n_clusters.ctypes.data)
+        if rc == -2:
+            raise ValueError(load().pw_last_error().decode(errors="replace"))
+        _check(rc, "pw_cluster_gromos")
+        return out[0], out[1], out[2], n_clusters
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

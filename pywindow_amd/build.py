@@ -14,7 +14,7 @@ import sys
 PKG = pathlib.Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 OUT = PKG / "libpywindow_hip.so"
-SOURCES = ["pw_kernels.hip", "pw_kernels_big.hip", "pw_rebuild.hip", "pw_shape.hip", "pw_kde.hip", "pw_kdew.hip", "pw_corr.hip", "pw_dft.hip", "pw_gate.hip", "pw_trans.hip", "pw_superpose.hip", "pw_history.cpp", "pw_hostpath.cpp"]
+SOURCES = ["pw_kernels.hip", "pw_kernels_big.hip", "pw_rebuild.hip", "pw_shape.hip", "pw_kde.hip", "pw_kdew.hip", "pw_corr.hip", "pw_dft.hip", "pw_gate.hip", "pw_trans.hip", "pw_superpose.hip", "pw_cluster.hip", "pw_history.cpp", "pw_hostpath.cpp"]
 # -ffp-contract=off: the numerical core relies on explicit fma() only (pw_common.hpp)
 
 
@@ -49,6 +49,7 @@ def build(force: bool = False, verbose: bool = True) -> pathlib.Path:
     obj_g = CSRC / "pw_gate.o"
     obj_n = CSRC / "pw_trans.o"
     obj_p = CSRC / "pw_superpose.o"
+    obj_u = CSRC / "pw_cluster.o"
     obj_h = CSRC / "pw_history.o"
     obj_c = CSRC / "pw_hostpath.o"
     hip_flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c"]
@@ -64,11 +65,12 @@ def build(force: bool = False, verbose: bool = True) -> pathlib.Path:
         [hipcc(), *hip_flags, str(CSRC / "pw_gate.hip"), "-o", str(obj_g)],
         [hipcc(), *hip_flags, str(CSRC / "pw_trans.hip"), "-o", str(obj_n)],
         [hipcc(), *hip_flags, str(CSRC / "pw_superpose.hip"), "-o", str(obj_p)],
+        [hipcc(), *hip_flags, str(CSRC / "pw_cluster.hip"), "-o", str(obj_u)],
         ["g++", "-O2", "-std=c++17", "-fPIC", "-c", str(CSRC / "pw_history.cpp"), "-o", str(obj_h)],
         # the explicit host path (pw_context_create(-1)): the unit pipeline for a one-lane team, g++
         ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-pthread", "-c", str(CSRC / "pw_hostpath.cpp"),
          "-o", str(obj_c)],
-        [hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-pthread", str(obj_k), str(obj_b), str(obj_r), str(obj_s), str(obj_d), str(obj_w), str(obj_t), str(obj_f), str(obj_g), str(obj_n), str(obj_p), str(obj_h),
+        [hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-pthread", str(obj_k), str(obj_b), str(obj_r), str(obj_s), str(obj_d), str(obj_w), str(obj_t), str(obj_f), str(obj_g), str(obj_n), str(obj_p), str(obj_u), str(obj_h),
          str(obj_c), "-o", str(OUT)],
     ]
     # the translation units are independent: compile them side by side (PW_BUILD_JOBS, default 4), then link

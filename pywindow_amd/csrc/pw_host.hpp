@@ -25,7 +25,7 @@ struct DeviceScope {
 };
 
 // Test hook (pw_kde.hip: pw_internal_poison_scratch): while the flag is set, the statistical entries (pw_kde_sums,
-// pw_kde2_sums, pw_kde_wsums, pw_corr_sums, pw_dft_sums, pw_gate_counts, pw_trans_counts, pw_superpose) fill their workspace and their
+// pw_kde2_sums, pw_kde_wsums, pw_corr_sums, pw_dft_sums, pw_gate_counts, pw_trans_counts, pw_superpose, pw_cluster_gromos) fill their workspace and their
 // compact device result with bytes 0xFF -- a NaN as a double, garbage as a gate summary or a bit mask -- before their first kernel,
 // so that a read of device memory the call never wrote shows in the result.  Off at start; an entry reads the flag
 // once a call, and the host path (device -1) never does.

@@ -17,12 +17,15 @@
 #include "pw_gate.hpp"
 #include "pw_trans.hpp"
 #include "pw_superpose.hpp"
+#include "pw_cluster.hpp"
 
 #include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
 #include <atomic>
+#include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -604,6 +607,154 @@ extern "C" int pw_hostpath_superpose(const pw_superpose_job* jobs, long n_jobs, 
         std::vector<std::thread> pool;
         for (int t = 0; t < count; ++t) pool.emplace_back(worker);
         for (auto& t : pool) t.join();
+    }
+    return PW_OK;
+}
+
+// pw_cluster_gromos on the host (pw_cluster.hip checks the arguments and sends device == -1 contexts here): the bit
+// matrix, the keys and the tail mask of pw_cluster.hpp.  The threads of a call are started once and woken a piece of
+// work (a round of counts is too short to start threads for): they share out the rows of the pack, the tile rows of the
+// mirror and the rows of every round's counts, each keeping the largest key of its rows; the largest of those is the
+// centre, whatever the number of threads.  A round with little to count is taken by the calling thread alone.
+namespace {
+struct ClusterCrew {
+    int threads;
+    std::vector<std::thread> pool;
+    std::mutex m;
+    std::condition_variable go, back;
+    std::function<void(int)> work;
+    long generation = 0;
+    int pending = 0;
+    bool stop = false;
+    explicit ClusterCrew(int t) : threads(t < 1 ? 1 : t) {
+        for (int i = 1; i < threads; ++i) pool.emplace_back([this, i] { serve(i); });
+    }
+    ~ClusterCrew() {
+        {
+            std::lock_guard<std::mutex> g(m);
+            stop = true;
+        }
+        go.notify_all();
+        for (auto& t : pool) t.join();
+    }
+    void serve(int me) {
+        long seen = 0;
+        for (;;) {
+            std::unique_lock<std::mutex> g(m);
+            go.wait(g, [&] { return stop || generation != seen; });
+            if (stop) return;
+            seen = generation;
+            g.unlock();
+            work(me);
+            g.lock();
+            if (--pending == 0) back.notify_one();
+        }
+    }
+    // f(t) for t = 0 .. threads - 1, t = 0 on the calling thread; returns when all have
+    void run(const std::function<void(int)>& f) {
+        if (threads == 1) return f(0);
+        {
+            std::lock_guard<std::mutex> g(m);
+            work = f;
+            pending = threads - 1;
+            ++generation;
+        }
+        go.notify_all();
+        f(0);
+        std::unique_lock<std::mutex> g(m);
+        back.wait(g, [&] { return pending == 0; });
+    }
+};
+}  // namespace
+
+extern "C" int pw_hostpath_cluster(const pw_cluster_job* jobs, long n_jobs, const double* dist, int* labels, int* centres,
+                                   int* sizes, long* n_clusters, int threads) {
+    typedef cluster_word u64;
+    constexpr long SMALL = 4096;                   // words of a round below which the calling thread counts alone
+    long n_max = 0;
+    for (long k = 0; k < n_jobs; ++k) n_max = std::max(n_max, (long)jobs[k].n);
+    if (threads < 1) threads = 1;
+    if ((long)threads > (n_max + 63) / 64) threads = (int)std::max(1l, (n_max + 63) / 64);
+    ClusterCrew crew(threads);
+    const int T = crew.threads;
+    std::vector<u64> bits, active;
+    std::vector<u64> best((size_t)T);
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_cluster_job& J = jobs[k];
+        const long n = (long)J.n, W = cluster_words(n), S = cluster_stride(n);
+        n_clusters[k] = 0;
+        if (n == 0) continue;
+        const double* d = dist + J.d_first;
+        const double cutoff = J.cutoff;
+        int* lab = labels + J.out_first;
+        int* cen = centres + J.out_first;
+        int* siz = sizes + J.out_first;
+        bits.assign((size_t)(n * S), 0);
+        active.resize((size_t)S);
+        u64* B = bits.data();
+        // pack: the diagonal and the strict upper triangle, rows shared out in blocks of 64
+        crew.run([&](int t) {
+            for (long I = t; I < W; I += T)
+                for (long i = 64 * I; i < std::min(64 * I + 64, n); ++i) {
+                    B[i * S + i / 64] |= 1ull << (i % 64);
+                    for (long j = i + 1; j < n; ++j)
+                        if (cluster_pack_bit(i, j, n, d[i * n + j], cutoff)) B[i * S + j / 64] |= 1ull << (j % 64);
+                }
+        });
+        // mirror: tile (I, Jt), I <= Jt, transposed into tile (Jt, I); a thread owns the tile rows Jt it writes
+        crew.run([&](int t) {
+            for (long Jt = t; Jt < W; Jt += T)
+                for (long I = 0; I <= Jt; ++I) {
+                    u64 a[64], tr[64];
+                    for (long l = 0; l < 64; ++l) a[l] = 64 * I + l < n ? B[(64 * I + l) * S + Jt] : 0;
+                    for (int c = 0; c < 64; ++c) {
+                        u64 v = 0;
+                        for (int l = 0; l < 64; ++l) v |= ((a[l] >> c) & 1ull) << l;
+                        tr[c] = v;
+                    }
+                    for (long c = 0; c < 64 && 64 * Jt + c < n; ++c) {
+                        u64& out = B[(64 * Jt + c) * S + I];
+                        out = I == Jt ? (out | tr[c]) : tr[c];
+                    }
+                }
+        });
+        for (long w = 0; w < S; ++w) active[w] = cluster_tail_mask(n, w);
+        for (long j = 0; j < n; ++j) {
+            cen[j] = -1;
+            siz[j] = 0;
+        }
+        const u64* A = active.data();
+        long left = n, found = 0;
+        while (left > 0) {
+            auto count_rows = [&](long lo, long hi) {
+                u64 mine = 0;
+                for (long i = lo; i < hi; ++i) {
+                    if (!((A[i >> 6] >> (i & 63)) & 1)) continue;
+                    unsigned count = 0;
+                    for (long w = 0; w < W; ++w) count += (unsigned)cluster_popcount(B[i * S + w] & A[w]);
+                    mine = std::max(mine, cluster_key(count, (unsigned)i));
+                }
+                return mine;
+            };
+            u64 key = 0;
+            if (T == 1 || left * W < SMALL) {
+                key = count_rows(0, n);
+            } else {
+                crew.run([&](int t) { best[t] = count_rows(n * t / T, n * (t + 1) / T); });
+                for (int t = 0; t < T; ++t) key = std::max(key, best[t]);
+            }
+            const long c = (long)cluster_key_row(key);
+            cen[found] = (int)c;
+            siz[found] = (int)cluster_key_count(key);
+            for (long w = 0; w < W; ++w) {
+                u64 m = B[c * S + w] & active[w];
+                active[w] &= ~m;
+                for (; m; m &= m - 1) lab[64 * w + __builtin_ctzll(m)] = (int)found;
+            }
+            left -= (long)cluster_key_count(key);
+            ++found;
+        }
+        n_clusters[k] = found;
     }
     return PW_OK;
 }

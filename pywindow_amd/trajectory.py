@@ -374,11 +374,25 @@ class DLPOLY:
 
     def rmsd_matrix(self, frames="all", weights="mass", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """The (T, T) least-squares RMSD between every two selected frames (``pywindow_amd.rmsd_matrix``): the input
-        of a conformational clustering.  Same restrictions as :meth:`superposition`."""
+        of a conformational clustering (:meth:`conformations`).  Same restrictions as :meth:`superposition`."""
         from . import superposition as SP
 
         _, coords = self._rigid_frames(frames, "rmsd_matrix")
         return SP.rmsd_matrix(coords, self._weights(weights, swap_atoms, forcefield), device)
+
+    def conformations(self, cutoff, frames="all", weights="mass", swap_atoms=None, forcefield=None, device=None):
+        """The conformations the selected frames fall into: :meth:`rmsd_matrix` of those frames, then the gromos
+        clustering of ``pywindow_amd.cluster_frames`` at ``cutoff`` (an RMSD, in the units of the coordinates) on the
+        GPU -- a :class:`pywindow_amd.Clusters` whose ``frames`` are the trajectory's frame numbers.  A list of cutoffs
+        gives a list of results from one matrix.  Same restrictions as :meth:`superposition`."""
+        from . import clustering as CL
+        from . import superposition as SP
+
+        sel, coords = self._rigid_frames(frames, "conformations")
+        dist = SP.rmsd_matrix(coords, self._weights(weights, swap_atoms, forcefield), device)
+        if isinstance(cutoff, (list, tuple, np.ndarray)):
+            return CL.cluster_frames_scan(dist, cutoff, device, frames=sel)
+        return CL.cluster_frames(dist, cutoff, device, frames=sel)
 
     def track_windows(self, reference: int = 0, sites=None, min_cosine=None, weights="mass", swap_atoms=None,
                       forcefield=None, device=None):
