@@ -501,6 +501,28 @@ def _dptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
+# ---- what the wrappers of the statistical entries (Context.kde_sums ... Context.cluster_gromos) share ----------
+
+def _span_inside(jobs, first: str, count: str, limit: int, what: str) -> None:
+    """Every job's entries ``[first, first + count)`` lie inside the array ``what`` of ``limit`` entries."""
+    if ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > limit)).any():
+        raise IndexError(f"a job reaches outside `{what}`")
+
+
+def _writes_from_start(jobs, first: str, what: str, error=IndexError) -> None:
+    if (jobs[first] < 0).any():
+        raise error(f"a job writes before the start of the {what}")
+
+
+def _stat_call(name: str, *args) -> None:
+    """The entry ``name`` of the library: a refused argument (``PW_E_BAD_ARG``) is a ``ValueError`` with the
+    library's message, any other failure a ``PwHipError``."""
+    rc = getattr(load(), name)(*args)
+    if rc == -2:
+        raise ValueError(load().pw_last_error().decode(errors="replace"))
+    _check(rc, name)
+
+
 class Batch:
     """Host-side description of a ragged batch of molecules (keeps arrays alive)."""
 
@@ -712,14 +734,10 @@ class Context:
         jobs = np.ascontiguousarray(jobs, dtype=KDE_JOB_DTYPE).reshape(-1)
         x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
         g = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
-        for first, count, size, what in (("sample_first", "n_samples", len(x), "samples"), ("point_first", "n_points", len(g), "points")):
-            if len(jobs) and ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > size)).any():
-                raise IndexError(f"a job reaches outside `{what}`")
+        _span_inside(jobs, "sample_first", "n_samples", len(x), "samples")
+        _span_inside(jobs, "point_first", "n_points", len(g), "points")
         sums = np.zeros(len(g))
-        rc = load().pw_kde_sums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, sums.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_kde_sums")
+        _stat_call("pw_kde_sums", self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, sums.ctypes.data)
         return sums
 
     def kde2_sums(self, jobs, samples, points) -> np.ndarray:
@@ -730,14 +748,10 @@ class Context:
         jobs = np.ascontiguousarray(jobs, dtype=KDE2_JOB_DTYPE).reshape(-1)
         x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1, 2)
         g = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
-        for first, count, size, what in (("sample_first", "n_samples", len(x), "samples"), ("point_first", "n_points", len(g), "points")):
-            if len(jobs) and ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > size)).any():
-                raise IndexError(f"a job reaches outside `{what}`")
+        _span_inside(jobs, "sample_first", "n_samples", len(x), "samples")
+        _span_inside(jobs, "point_first", "n_points", len(g), "points")
         sums = np.zeros(len(g))
-        rc = load().pw_kde2_sums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, sums.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_kde2_sums")
+        _stat_call("pw_kde2_sums", self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, sums.ctypes.data)
         return sums
 
     def kde_wsums(self, jobs, samples, points, weights) -> np.ndarray:
@@ -750,23 +764,15 @@ class Context:
         x = np.ascontiguousarray(samples, dtype=np.float64).reshape(-1)
         g = np.ascontiguousarray(points, dtype=np.float64).reshape(-1)
         w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-        size = 0
-        if len(jobs):
-            for first, count, limit, what in (("sample_first", "n_samples", len(x), "samples"), ("point_first", "n_points", len(g), "points")):
-                if ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > limit)).any():
-                    raise IndexError(f"a job reaches outside `{what}`")
-            replicas = np.maximum(jobs["n_replicas"], 0)
-            if ((jobs["weight_first"] < 0) | (jobs["weight_first"] + jobs["n_samples"] * replicas > len(w))).any():
-                raise IndexError("a job reaches outside `weights`")
-            if (jobs["out_first"] < 0).any():
-                raise IndexError("a job writes before the start of the sums")
-            size = int((jobs["out_first"] + replicas * jobs["n_points"]).max())
-        sums = np.zeros(size)
-        rc = load().pw_kde_wsums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, w.ctypes.data,
-                                 sums.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_kde_wsums")
+        _span_inside(jobs, "sample_first", "n_samples", len(x), "samples")
+        _span_inside(jobs, "point_first", "n_points", len(g), "points")
+        replicas = np.maximum(jobs["n_replicas"], 0)
+        if ((jobs["weight_first"] < 0) | (jobs["weight_first"] + jobs["n_samples"] * replicas > len(w))).any():
+            raise IndexError("a job reaches outside `weights`")
+        _writes_from_start(jobs, "out_first", "sums")
+        sums = np.zeros(int((jobs["out_first"] + replicas * jobs["n_points"]).max()) if len(jobs) else 0)
+        _stat_call("pw_kde_wsums", self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, g.ctypes.data, w.ctypes.data,
+                   sums.ctypes.data)
         return sums
 
     def corr_sums(self, jobs, series) -> np.ndarray:
@@ -776,21 +782,12 @@ class Context:
         infinity in a series, raises ``ValueError``."""
         jobs = np.ascontiguousarray(jobs, dtype=CORR_JOB_DTYPE).reshape(-1)
         x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
-        size = 0
-        if len(jobs):
-            for first in ("a_first", "b_first"):
-                if ((jobs[first] < 0) | (jobs["n"] < 0) | (jobs[first] + jobs["n"] > len(x))).any():
-                    raise IndexError("a job reaches outside `series`")
-            if (jobs["out_first"] < 0).any():
-                raise IndexError("a job writes before the start of the sums")
-            live = jobs[jobs["n"] > 0]
-            if len(live):
-                size = int(max(0, (live["out_first"] + live["n_lags"]).max()))
-        sums = np.zeros(size)
-        rc = load().pw_corr_sums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, sums.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_corr_sums")
+        _span_inside(jobs, "a_first", "n", len(x), "series")
+        _span_inside(jobs, "b_first", "n", len(x), "series")
+        _writes_from_start(jobs, "out_first", "sums")
+        live = jobs[jobs["n"] > 0]
+        sums = np.zeros(int(max(0, (live["out_first"] + live["n_lags"]).max())) if len(live) else 0)
+        _stat_call("pw_corr_sums", self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, sums.ctypes.data)
         return sums
 
     def dft_sums(self, jobs, series) -> np.ndarray:
@@ -800,20 +797,12 @@ class Context:
         frequency outside ``0 .. period - 1``, ``j_step < 1`` or a NaN / infinity in a series raises ``ValueError``."""
         jobs = np.ascontiguousarray(jobs, dtype=DFT_JOB_DTYPE).reshape(-1)
         x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
-        size = 0
-        if len(jobs):
-            if ((jobs["a_first"] < 0) | (jobs["n"] < 0) | (jobs["a_first"] + jobs["n"] > len(x))).any():
-                raise IndexError("a job reaches outside `series`")
-            if (jobs["out_first"] < 0).any():
-                raise IndexError("a job writes before the start of the sums")
-            live = jobs[(jobs["n"] > 0) & (jobs["n_freq"] > 0)]
-            if len(live):
-                size = int(max(0, (live["out_first"] + live["n_freq"]).max()))
+        _span_inside(jobs, "a_first", "n", len(x), "series")
+        _writes_from_start(jobs, "out_first", "sums")
+        live = jobs[(jobs["n"] > 0) & (jobs["n_freq"] > 0)]
+        size = int(max(0, (live["out_first"] + live["n_freq"]).max())) if len(live) else 0
         re, im = np.zeros(size), np.zeros(size)      # (the entry wants two arrays; the result carries their bits)
-        rc = load().pw_dft_sums(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, re.ctypes.data, im.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_dft_sums")
+        _stat_call("pw_dft_sums", self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, re.ctypes.data, im.ctypes.data)
         out = np.empty(size, dtype=np.complex128)
         out.real, out.imag = re, im
         return out
@@ -829,23 +818,15 @@ class Context:
         x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
         d = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
         n_bins = int(n_bins)
-        rows = 0
-        if len(jobs):
-            for first, count, limit, what in (("a_first", "n", len(x), "series"), ("d_first", "n_thr", len(d), "thresholds")):
-                if ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > limit)).any():
-                    raise IndexError(f"a job reaches outside `{what}`")
-            if (jobs["out_first"] < 0).any():
-                raise IndexError("a job writes before the start of the counts")
-            live = jobs[(jobs["n"] > 0) & (jobs["n_thr"] > 0)]
-            if len(live):
-                rows = int((live["out_first"] + live["n_thr"]).max())
+        _span_inside(jobs, "a_first", "n", len(x), "series")
+        _span_inside(jobs, "d_first", "n_thr", len(d), "thresholds")
+        _writes_from_start(jobs, "out_first", "counts")
+        live = jobs[(jobs["n"] > 0) & (jobs["n_thr"] > 0)]
+        rows = int((live["out_first"] + live["n_thr"]).max()) if len(live) else 0
         counts = np.zeros((rows, len(GATE_FIELDS)), dtype=np.int64)
         hist = np.zeros((rows, 2, max(n_bins, 0)), dtype=np.int64)
-        rc = load().pw_gate_counts(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, d.ctypes.data, n_bins,
-                                   counts.ctypes.data, hist.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_gate_counts")
+        _stat_call("pw_gate_counts", self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, d.ctypes.data, n_bins,
+                   counts.ctypes.data, hist.ctypes.data)
         return counts, hist
 
     def trans_counts(self, jobs, series, edges, n_states: int) -> np.ndarray:
@@ -859,23 +840,15 @@ class Context:
         x = np.ascontiguousarray(series, dtype=np.float64).reshape(-1)
         e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
         n_states = int(n_states)
-        rows = 0
-        if len(jobs):
-            for first, count, limit, what in (("a_first", "n", len(x), "series"), ("e_first", "n_edges", len(e), "edges")):
-                if ((jobs[first] < 0) | (jobs[count] < 0) | (jobs[first] + jobs[count] > limit)).any():
-                    raise IndexError(f"a job reaches outside `{what}`")
-            if (jobs["out_first"] < 0).any():
-                raise IndexError("a job writes before the start of the counts")
-            live = jobs[(jobs["n"] > 0) & (jobs["n_lags"] > 0)]
-            if len(live):
-                rows = int((live["out_first"] + live["n_lags"]).max())
+        _span_inside(jobs, "a_first", "n", len(x), "series")
+        _span_inside(jobs, "e_first", "n_edges", len(e), "edges")
+        _writes_from_start(jobs, "out_first", "counts")
+        live = jobs[(jobs["n"] > 0) & (jobs["n_lags"] > 0)]
+        rows = int((live["out_first"] + live["n_lags"]).max()) if len(live) else 0
         side = min(max(n_states, 0), TRANS_MAX_STATES)
         counts = np.zeros((rows, side, side), dtype=np.int64)
-        rc = load().pw_trans_counts(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, e.ctypes.data, n_states,
-                                    counts.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_trans_counts")
+        _stat_call("pw_trans_counts", self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, e.ctypes.data, n_states,
+                   counts.ctypes.data)
         return counts
 
     def superpose(self, jobs, xyz, weights=None, out=None) -> np.ndarray:
@@ -890,18 +863,14 @@ class Context:
         w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
         if w is not None and len(w) != len(x):
             raise ValueError("one weight per row of xyz")
-        if len(jobs) and (jobs["out"] < 0).any():
-            raise ValueError("a job writes before the start of the result")
+        _writes_from_start(jobs, "out", "result", error=ValueError)
         rows = int(jobs["out"].max()) + 1 if len(jobs) else 0
         if out is None:
             out = np.zeros(rows, dtype=SUPERPOSE_OUT_DTYPE)
         elif out.dtype != SUPERPOSE_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1 or len(out) < rows:
             raise ValueError("out: a contiguous SUPERPOSE_OUT_DTYPE array with a row for every job")
-        rc = load().pw_superpose(self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, None if w is None else w.ctypes.data,
-                                 len(x), out.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_superpose")
+        _stat_call("pw_superpose", self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, None if w is None else w.ctypes.data,
+                   len(x), out.ctypes.data)
         return out
 
     def cluster_gromos(self, jobs, dist, labels=None, centres=None, sizes=None):
@@ -914,13 +883,10 @@ class Context:
         ``dist`` or results too short for a job ``IndexError``."""
         jobs = np.ascontiguousarray(jobs, dtype=CLUSTER_JOB_DTYPE).reshape(-1)
         d = np.ascontiguousarray(dist, dtype=np.float64).reshape(-1)
-        size = 0
-        if len(jobs):
-            if ((jobs["d_first"] < 0) | (jobs["n"] < 0) | (jobs["d_first"] + jobs["n"] * jobs["n"] > len(d))).any():
-                raise IndexError("a job reaches outside `dist`")
-            if (jobs["out_first"] < 0).any():
-                raise IndexError("a job writes before the start of the results")
-            size = int((jobs["out_first"] + jobs["n"]).max())
+        if ((jobs["d_first"] < 0) | (jobs["n"] < 0) | (jobs["d_first"] + jobs["n"] * jobs["n"] > len(d))).any():
+            raise IndexError("a job reaches outside `dist`")
+        _writes_from_start(jobs, "out_first", "results")
+        size = int((jobs["out_first"] + jobs["n"]).max()) if len(jobs) else 0
         out = []
         for given, fill, what in ((labels, -1, "labels"), (centres, -1, "centres"), (sizes, 0, "sizes")):
             if given is None:
@@ -929,11 +895,8 @@ class Context:
                 raise IndexError(f"{what}: a contiguous int32 array with an entry for every frame of every job")
             out.append(given)
         n_clusters = np.zeros(len(jobs), dtype=np.int64)
-        rc = load().pw_cluster_gromos(self._h, jobs.ctypes.data, len(jobs), d.ctypes.data, len(d), out[0].ctypes.data,
-                                      out[1].ctypes.data, out[2].ctypes.data, n_clusters.ctypes.data)
-        if rc == -2:
-            raise ValueError(load().pw_last_error().decode(errors="replace"))
-        _check(rc, "pw_cluster_gromos")
+        _stat_call("pw_cluster_gromos", self._h, jobs.ctypes.data, len(jobs), d.ctypes.data, len(d), out[0].ctypes.data,
+                   out[1].ctypes.data, out[2].ctypes.data, n_clusters.ctypes.data)
         return out[0], out[1], out[2], n_clusters
 
     def circumcircle(self, coordinates, atom_sets):

@@ -38,41 +38,16 @@ def build(force: bool = False, verbose: bool = True) -> pathlib.Path:
         return OUT
     # one translation unit per source, compiled separately (mixing "-x hip" and "-x c++" in one
     # hipcc command silently drops --offload-arch) and linked by hipcc
-    obj_k = CSRC / "pw_kernels.o"
-    obj_b = CSRC / "pw_kernels_big.o"
-    obj_r = CSRC / "pw_rebuild.o"
-    obj_s = CSRC / "pw_shape.o"
-    obj_d = CSRC / "pw_kde.o"
-    obj_w = CSRC / "pw_kdew.o"
-    obj_t = CSRC / "pw_corr.o"
-    obj_f = CSRC / "pw_dft.o"
-    obj_g = CSRC / "pw_gate.o"
-    obj_n = CSRC / "pw_trans.o"
-    obj_p = CSRC / "pw_superpose.o"
-    obj_u = CSRC / "pw_cluster.o"
-    obj_h = CSRC / "pw_history.o"
-    obj_c = CSRC / "pw_hostpath.o"
-    hip_flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c"]
-    cmds = [
-        [hipcc(), *hip_flags, str(CSRC / "pw_kernels.hip"), "-o", str(obj_k)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_kernels_big.hip"), "-o", str(obj_b)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_rebuild.hip"), "-o", str(obj_r)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_shape.hip"), "-o", str(obj_s)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_kde.hip"), "-o", str(obj_d)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_kdew.hip"), "-o", str(obj_w)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_corr.hip"), "-o", str(obj_t)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_dft.hip"), "-o", str(obj_f)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_gate.hip"), "-o", str(obj_g)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_trans.hip"), "-o", str(obj_n)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_superpose.hip"), "-o", str(obj_p)],
-        [hipcc(), *hip_flags, str(CSRC / "pw_cluster.hip"), "-o", str(obj_u)],
-        ["g++", "-O2", "-std=c++17", "-fPIC", "-c", str(CSRC / "pw_history.cpp"), "-o", str(obj_h)],
+    compiler = {   # by the file's name where it has a line of its own, by its suffix otherwise
+        ".hip": [hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-c"],
+        "pw_history.cpp": ["g++", "-O2", "-std=c++17", "-fPIC", "-c"],
         # the explicit host path (pw_context_create(-1)): the unit pipeline for a one-lane team, g++
-        ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-pthread", "-c", str(CSRC / "pw_hostpath.cpp"),
-         "-o", str(obj_c)],
-        [hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-pthread", str(obj_k), str(obj_b), str(obj_r), str(obj_s), str(obj_d), str(obj_w), str(obj_t), str(obj_f), str(obj_g), str(obj_n), str(obj_p), str(obj_u), str(obj_h),
-         str(obj_c), "-o", str(OUT)],
-    ]
+        "pw_hostpath.cpp": ["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-mfma", "-fPIC", "-pthread", "-c"],
+    }
+    objs = [str((CSRC / src).with_suffix(".o")) for src in SOURCES]
+    cmds = [[*compiler[src if src in compiler else pathlib.Path(src).suffix], str(CSRC / src), "-o", obj]
+            for src, obj in zip(SOURCES, objs)]
+    cmds.append([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-pthread", *objs, "-o", str(OUT)])
     # the translation units are independent: compile them side by side (PW_BUILD_JOBS, default 4), then link
     from concurrent.futures import ThreadPoolExecutor
 

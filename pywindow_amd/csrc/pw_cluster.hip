@@ -24,12 +24,10 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_cluster.hpp"
-#include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 
 using namespace pw;
 
-extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip
-extern "C" int pw_context_device(pw_context* ctx);
 extern "C" int pw_hostpath_cluster(const pw_cluster_job* jobs, long n_jobs, const double* dist, int* labels, int* centres,
                                    int* sizes, long* n_clusters, int threads);   // pw_hostpath.cpp
 
@@ -177,41 +175,6 @@ pw_cluster_pick_kernel(const ClusterJobDev* __restrict__ jobs, const u64* __rest
     }
 }
 
-// device memory of one call, allocated and released in stream order
-struct StreamBuffers {
-    static constexpr int CAP = 8;
-    hipStream_t st;
-    void* p[CAP];
-    int n = 0;
-    explicit StreamBuffers(hipStream_t s) : st(s) {}
-    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
-    template <class X> hipError_t alloc(X** out, size_t bytes) {
-        if (n >= CAP) return hipErrorOutOfMemory;
-        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-#define CLUSTER_TRY(call)                                                                  \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
-            return PW_E_HIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-int cluster_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_cluster_gromos: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
-}
-
 struct ClusterMatrix {
     long d_first, n;
 };
@@ -247,21 +210,22 @@ int cluster_gromos(pw_context* ctx, const pw_cluster_job* jobs, int64_t n_jobs, 
     std::vector<long> mat_of((size_t)n_jobs, -1);
     for (long k = 0; k < (long)n_jobs; ++k) {
         const pw_cluster_job& J = jobs[k];
-        if (J.d_first < 0 || J.n < 0 || J.out_first < 0) return cluster_bad("negative field", k);
-        if (J.n > CLUSTER_MAX_N) return cluster_bad("n above PW_CLUSTER_MAX_N (32768)", k);
-        if (gate_nan(J.cutoff)) return cluster_bad("the cutoff is a NaN", k);
+        if (J.d_first < 0 || J.n < 0 || J.out_first < 0) return stat_bad("pw_cluster_gromos", k, "negative field");
+        if (J.n > CLUSTER_MAX_N) return stat_bad("pw_cluster_gromos", k, "n above PW_CLUSTER_MAX_N (32768)");
+        if (pw_isnan_bits(J.cutoff)) return stat_bad("pw_cluster_gromos", k, "the cutoff is a NaN");
         const long n = (long)J.n;
         if ((long)J.d_first > (long)n_dist || n * n > (long)n_dist - (long)J.d_first)
-            return cluster_bad("the matrix reaches outside dist", k);
+            return stat_bad("pw_cluster_gromos", k, "the matrix reaches outside dist");
         if (n == 0) continue;
-        if (!dist || !labels || !centres || !sizes) return cluster_bad("null array", k);
+        if (!dist || !labels || !centres || !sizes) return stat_bad("pw_cluster_gromos", k, "null array");
         for (size_t m = 0; m < mats.size(); ++m)
             if (mats[m].d_first == (long)J.d_first && mats[m].n == n) mat_of[k] = (long)m;
         if (mat_of[k] >= 0) continue;
         const double* d = dist + J.d_first;
         for (long i = 0; i + 1 < n; ++i)
             for (long j = i + 1; j < n; ++j)
-                if (gate_nan(d[i * n + j])) return cluster_bad("a NaN in the strict upper triangle of the matrix", k);
+                if (pw_isnan_bits(d[i * n + j]))
+                    return stat_bad("pw_cluster_gromos", k, "a NaN in the strict upper triangle of the matrix");
         mat_of[k] = (long)mats.size();
         mats.push_back(ClusterMatrix{(long)J.d_first, n});
     }
@@ -310,13 +274,10 @@ int cluster_gromos(pw_context* ctx, const pw_cluster_job* jobs, int64_t n_jobs, 
     const long live = (long)devs.size();
 
     DeviceScope dev_scope_;
-    CLUSTER_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        CLUSTER_TRY(hipEventCreate(&ev.a));
-        CLUSTER_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     std::vector<long> ncl_host((size_t)live, 0);
     std::vector<int> done_host((size_t)live, 0);
     {
@@ -325,27 +286,27 @@ int cluster_gromos(pw_context* ctx, const pw_cluster_job* jobs, int64_t n_jobs, 
         double* d_slab;
         u64 *d_bits, *d_active, *d_state;                            // d_state: keys [live], then cluster counts [live]
         int *d_done, *d_out;                                         // d_out: labels, centres, sizes [total] each
-        CLUSTER_TRY(buf.alloc(&d_jobs, sizeof(ClusterJobDev) * (size_t)live));
-        CLUSTER_TRY(buf.alloc(&d_slab, sizeof(double) * (size_t)slab_doubles));
-        CLUSTER_TRY(buf.alloc(&d_bits, sizeof(u64) * (size_t)max_words));
-        CLUSTER_TRY(buf.alloc(&d_active, sizeof(u64) * (size_t)active_words));
-        CLUSTER_TRY(buf.alloc(&d_state, sizeof(u64) * 2 * (size_t)live));
-        CLUSTER_TRY(buf.alloc(&d_done, sizeof(int) * (size_t)live));
-        CLUSTER_TRY(buf.alloc(&d_out, sizeof(int) * 3 * (size_t)total));
+        STAT_TRY(buf.alloc(&d_jobs, sizeof(ClusterJobDev) * (size_t)live));
+        STAT_TRY(buf.alloc(&d_slab, sizeof(double) * (size_t)slab_doubles));
+        STAT_TRY(buf.alloc(&d_bits, sizeof(u64) * (size_t)max_words));
+        STAT_TRY(buf.alloc(&d_active, sizeof(u64) * (size_t)active_words));
+        STAT_TRY(buf.alloc(&d_state, sizeof(u64) * 2 * (size_t)live));
+        STAT_TRY(buf.alloc(&d_done, sizeof(int) * (size_t)live));
+        STAT_TRY(buf.alloc(&d_out, sizeof(int) * 3 * (size_t)total));
         u64* d_keys = d_state;
         long* d_ncl = (long*)(d_state + live);
         int *d_labels = d_out, *d_centres = d_out + total, *d_sizes = d_out + 2 * total;
-        const bool poison = scratch_poisoned();                      // (test hook, pw_host.hpp)
-        CLUSTER_TRY(poison_scratch(poison, d_bits, sizeof(u64) * (size_t)max_words, st));
-        CLUSTER_TRY(poison_scratch(poison, d_active, sizeof(u64) * (size_t)active_words, st));
-        CLUSTER_TRY(poison_scratch(poison, d_state, sizeof(u64) * 2 * (size_t)live, st));
-        CLUSTER_TRY(poison_scratch(poison, d_done, sizeof(int) * (size_t)live, st));
-        CLUSTER_TRY(poison_scratch(poison, d_out, sizeof(int) * 3 * (size_t)total, st));
-        CLUSTER_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(ClusterJobDev) * (size_t)live, hipMemcpyHostToDevice, st));
-        if (kernel_ms) CLUSTER_TRY(hipEventRecord(ev.a, st));
+        const bool poison = scratch_poisoned();                      // (test hook, pw_stat_host.hpp)
+        STAT_TRY(poison_scratch(poison, d_bits, sizeof(u64) * (size_t)max_words, st));
+        STAT_TRY(poison_scratch(poison, d_active, sizeof(u64) * (size_t)active_words, st));
+        STAT_TRY(poison_scratch(poison, d_state, sizeof(u64) * 2 * (size_t)live, st));
+        STAT_TRY(poison_scratch(poison, d_done, sizeof(int) * (size_t)live, st));
+        STAT_TRY(poison_scratch(poison, d_out, sizeof(int) * 3 * (size_t)total, st));
+        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(ClusterJobDev) * (size_t)live, hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
         hipLaunchKernelGGL(pw_cluster_init_kernel, dim3((unsigned)live), dim3(256), 0, st, d_jobs, d_active, d_keys, d_ncl,
                            d_done, d_centres, d_sizes);
-        CLUSTER_TRY(hipGetLastError());
+        STAT_TRY(hipGetLastError());
         // (groups follow one another on the stream, so the next one may take the workspace and the slab over; every
         // kernel strides over its work, so the launch geometry is free)
         for (const ClusterGroup& G : groups) {
@@ -362,31 +323,31 @@ int cluster_gromos(pw_context* ctx, const pw_cluster_job* jobs, int64_t n_jobs, 
                 const long slab_rows = slab_bytes / (8 * n) < 1 ? 1 : slab_bytes / (8 * n) < n ? slab_bytes / (8 * n) : n;
                 for (long r0 = 0; r0 < n; r0 += slab_rows) {
                     const long rows = n - r0 < slab_rows ? n - r0 : slab_rows;
-                    CLUSTER_TRY(hipMemcpyAsync(d_slab, dist + mats[m].d_first + r0 * n, sizeof(double) * (size_t)(rows * n),
+                    STAT_TRY(hipMemcpyAsync(d_slab, dist + mats[m].d_first + r0 * n, sizeof(double) * (size_t)(rows * n),
                                                hipMemcpyHostToDevice, st));
                     hipLaunchKernelGGL(pw_cluster_pack_kernel, dim3(cluster_grid((rows * S + 3) / 4, 1l << 16), count), dim3(256),
                                        0, st, gj, m, d_slab, r0, rows, d_bits);
-                    CLUSTER_TRY(hipGetLastError());
+                    STAT_TRY(hipGetLastError());
                 }
             }
             const long T = cluster_words(G.n_max);
             hipLaunchKernelGGL(pw_cluster_mirror_kernel, dim3(cluster_grid((T * T + 3) / 4, 1l << 16), count), dim3(256), 0, st,
                                gj, d_bits);
-            CLUSTER_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
             // a job takes one round a cluster and one more to find no frame active
             for (long queued = 0;;) {
                 for (int r = 0; r < rounds; ++r) {
                     hipLaunchKernelGGL(pw_cluster_count_kernel, dim3(cluster_grid((G.n_max + 3) / 4, 2048), count), dim3(256), 0,
                                        st, gj, d_bits, d_active, d_keys, d_done);
-                    CLUSTER_TRY(hipGetLastError());
+                    STAT_TRY(hipGetLastError());
                     hipLaunchKernelGGL(pw_cluster_pick_kernel, dim3(count), dim3(256), 0, st, gj, d_bits, d_active, d_keys, d_ncl,
                                        d_done, d_labels, d_centres, d_sizes);
-                    CLUSTER_TRY(hipGetLastError());
+                    STAT_TRY(hipGetLastError());
                 }
                 queued += rounds;
-                CLUSTER_TRY(hipMemcpyAsync(done_host.data() + G.first, d_done + G.first, sizeof(int) * count,
+                STAT_TRY(hipMemcpyAsync(done_host.data() + G.first, d_done + G.first, sizeof(int) * count,
                                            hipMemcpyDeviceToHost, st));
-                CLUSTER_TRY(hipStreamSynchronize(st));
+                STAT_TRY(hipStreamSynchronize(st));
                 bool all = true;
                 for (long q = G.first; q < G.last; ++q) all = all && done_host[q] != 0;
                 if (all) break;
@@ -396,18 +357,18 @@ int cluster_gromos(pw_context* ctx, const pw_cluster_job* jobs, int64_t n_jobs, 
                 }
             }
         }
-        if (kernel_ms) CLUSTER_TRY(hipEventRecord(ev.b, st));
+        STAT_TRY(ev.stop(st));
         // (the compact result is in job order: neighbours in the caller's arrays come back in one copy an array)
         for (const ClusterCopy& c : copies) {
             const size_t bytes = sizeof(int) * (size_t)c.count;
-            CLUSTER_TRY(hipMemcpyAsync(labels + c.host, d_labels + c.dev, bytes, hipMemcpyDeviceToHost, st));
-            CLUSTER_TRY(hipMemcpyAsync(centres + c.host, d_centres + c.dev, bytes, hipMemcpyDeviceToHost, st));
-            CLUSTER_TRY(hipMemcpyAsync(sizes + c.host, d_sizes + c.dev, bytes, hipMemcpyDeviceToHost, st));
+            STAT_TRY(hipMemcpyAsync(labels + c.host, d_labels + c.dev, bytes, hipMemcpyDeviceToHost, st));
+            STAT_TRY(hipMemcpyAsync(centres + c.host, d_centres + c.dev, bytes, hipMemcpyDeviceToHost, st));
+            STAT_TRY(hipMemcpyAsync(sizes + c.host, d_sizes + c.dev, bytes, hipMemcpyDeviceToHost, st));
         }
-        CLUSTER_TRY(hipMemcpyAsync(ncl_host.data(), d_ncl, sizeof(long) * (size_t)live, hipMemcpyDeviceToHost, st));
+        STAT_TRY(hipMemcpyAsync(ncl_host.data(), d_ncl, sizeof(long) * (size_t)live, hipMemcpyDeviceToHost, st));
     }
-    CLUSTER_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) CLUSTER_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     for (long k = 0; k < (long)n_jobs; ++k)
         if (jobs[k].n == 0) n_clusters[k] = 0;
     for (long q = 0; q < live; ++q) n_clusters[job_of[q]] = ncl_host[q];

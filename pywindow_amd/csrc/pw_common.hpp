@@ -60,6 +60,19 @@ PW_HD inline double pw_min(double a, double b) { return a < b ? a : b; }
 
 constexpr double PW_INF = __builtin_huge_val();
 
+// on the bits, so that no compiler flag has a say: neither a NaN nor an infinity / a NaN (host-side validation of
+// the statistical entries)
+PW_HD inline bool pw_finite(double v) {
+    union { double d; unsigned long long u; } c;
+    c.d = v;
+    return (c.u & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+PW_HD inline bool pw_isnan_bits(double v) {
+    union { double d; unsigned long long u; } c;
+    c.d = v;
+    return (c.u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull && (c.u & 0x000fffffffffffffull) != 0;
+}
+
 // ---- a division whose divisor is known in advance -------------------------------------------------------------
 // On gfx950 a / b is eleven dependent instructions: v_div_scale x2, v_rcp_f64, two Newton steps on the reciprocal,
 // q = a * r, rem = fma(-b, q, a), v_div_fmas (= fma(rem, r, q)), v_div_fixup.  Everything up to the refined

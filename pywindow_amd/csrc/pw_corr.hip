@@ -17,12 +17,10 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_corr.hpp"
-#include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 
 using namespace pw;
 
-extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip
-extern "C" int pw_context_device(pw_context* ctx);
 extern "C" int pw_hostpath_corr(const pw_corr_job* jobs, long n_jobs, const double* series, double* sums,
                                 int threads);      // pw_hostpath.cpp
 
@@ -43,17 +41,6 @@ struct CorrSlabDev {
     long out_first;            // the slab's m sums in the compact result of the call
     int tiles, chunks;         // chunks: those that have a term for the slab's first lag
 };
-
-// the last entry k with key(k) <= v; keys ascending, key(0) == 0 <= v < key(n)
-template <class Key>
-__device__ inline int corr_find(int n, long v, Key key) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (key(mid) <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // R doubles at a 16-byte aligned LDS address, as R / 2 16-byte reads
 __device__ inline void corr_read(const double* p, double (&v)[R]) {
@@ -118,7 +105,7 @@ pw_corr_partial_kernel(const CorrSlabDev* __restrict__ slabs, int n_slabs, long 
     __shared__ __attribute__((aligned(16))) double s_b[CORR_B_GROUPS * CORR_B_PITCH];
     const int lane = threadIdx.x;
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int q = corr_find(n_slabs, item, [&](int j) { return slabs[j].item_first; });
+        const int q = stat_find(n_slabs, item, [&](int j) { return slabs[j].item_first; });
         const CorrSlabDev job = slabs[q];
         const long local = item - job.item_first;
         const long chunk = local / job.tiles;
@@ -158,7 +145,7 @@ __global__ void __launch_bounds__(256)
 pw_corr_reduce_kernel(const CorrSlabDev* __restrict__ slabs, int n_slabs, long out_lo, long count,
                       const double* __restrict__ part, double* __restrict__ out) {
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x * blockDim.x) {
-        const int q = corr_find(n_slabs, t, [&](int j) { return slabs[j].out_first - out_lo; });
+        const int q = stat_find(n_slabs, t, [&](int j) { return slabs[j].out_first - out_lo; });
         const long m = slabs[q].m, j = out_lo + t - slabs[q].out_first;
         const long terms = slabs[q].n - (slabs[q].lag_first + j);            // >= 1: n_lags <= n
         const long chunks = (terms + CORR_CHUNK - 1) / CORR_CHUNK;
@@ -167,41 +154,6 @@ pw_corr_reduce_kernel(const CorrSlabDev* __restrict__ slabs, int n_slabs, long o
         for (long c = 1; c < chunks; ++c) s = s + p[c * m];
         out[out_lo + t] = s;
     }
-}
-
-// device memory of one call, allocated and released in stream order
-struct StreamBuffers {
-    static constexpr int CAP = 8;
-    hipStream_t st;
-    void* p[CAP];
-    int n = 0;
-    explicit StreamBuffers(hipStream_t s) : st(s) {}
-    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
-    template <class X> hipError_t alloc(X** out, size_t bytes) {
-        if (n >= CAP) return hipErrorOutOfMemory;
-        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-#define CORR_TRY(call)                                                                     \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
-            return PW_E_HIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-int corr_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_corr_sums: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
 }
 
 // slabs [first, last) share one launch pair and one workspace of `parts` doubles
@@ -260,15 +212,15 @@ int corr_sums(pw_context* ctx, const pw_corr_job* jobs, int64_t n_jobs, const do
     long s_lo = -1, s_hi = 0;
     for (long k = 0; k < (long)n_jobs; ++k) {
         const pw_corr_job& J = jobs[k];
-        if (J.n < 0 || J.a_first < 0 || J.b_first < 0 || J.out_first < 0) return corr_bad("negative range", k);
-        if (J.n_lags > J.n) return corr_bad("more lags than entries (n_lags > n)", k);
+        if (J.n < 0 || J.a_first < 0 || J.b_first < 0 || J.out_first < 0) return stat_bad("pw_corr_sums", k, "negative range");
+        if (J.n_lags > J.n) return stat_bad("pw_corr_sums", k, "more lags than entries (n_lags > n)");
         if (J.n == 0) continue;
-        if (J.n_lags < 1) return corr_bad("no lag (n_lags < 1)", k);
-        if (!series || !sums) return corr_bad("null array", k);
-        if ((J.n + CORR_CHUNK - 1) / CORR_CHUNK > 0x7fffffff) return corr_bad("too large", k);
+        if (J.n_lags < 1) return stat_bad("pw_corr_sums", k, "no lag (n_lags < 1)");
+        if (!series || !sums) return stat_bad("pw_corr_sums", k, "null array");
+        if ((J.n + CORR_CHUNK - 1) / CORR_CHUNK > 0x7fffffff) return stat_bad("pw_corr_sums", k, "too large");
         for (long i = 0; i < (long)J.n; ++i)
-            if (!corr_finite(series[J.a_first + i]) || !corr_finite(series[J.b_first + i]))
-                return corr_bad("a series holds a NaN or an infinity", k);
+            if (!pw_finite(series[J.a_first + i]) || !pw_finite(series[J.b_first + i]))
+                return stat_bad("pw_corr_sums", k, "a series holds a NaN or an infinity");
         const long lo = (long)(J.a_first < J.b_first ? J.a_first : J.b_first);
         const long hi = (long)(J.a_first > J.b_first ? J.a_first : J.b_first) + (long)J.n;
         if (s_lo < 0 || lo < s_lo) s_lo = lo;
@@ -281,34 +233,31 @@ int corr_sums(pw_context* ctx, const pw_corr_job* jobs, int64_t n_jobs, const do
     std::vector<CorrSlabDev> slabs;
     std::vector<CorrLaunch> launches;
     corr_plan(jobs, (long)n_jobs, s_lo, (long)(workspace_bytes ? workspace_bytes : CORR_WORKSPACE_BYTES) / 8, slabs, launches);
-    if (slabs.size() > 0x7ffffff0) return corr_bad("too large", (long)n_jobs - 1);
+    if (slabs.size() > 0x7ffffff0) return stat_bad("pw_corr_sums", (long)n_jobs - 1, "too large");
     long parts = 0;
     for (const CorrLaunch& L : launches) parts = L.parts > parts ? L.parts : parts;
     const long outs = launches.back().out_hi;
 
     DeviceScope dev_scope_;
-    CORR_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        CORR_TRY(hipEventCreate(&ev.a));
-        CORR_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     std::vector<double> host_out((size_t)outs);
     {
         StreamBuffers buf(st);
         CorrSlabDev* d_slabs;
         double *d_x, *d_part, *d_out;
-        CORR_TRY(buf.alloc(&d_slabs, sizeof(CorrSlabDev) * slabs.size()));
-        CORR_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
-        CORR_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
-        CORR_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
-        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
-        CORR_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
-        CORR_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
-        CORR_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(CorrSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
-        CORR_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
-        if (kernel_ms) CORR_TRY(hipEventRecord(ev.a, st));
+        STAT_TRY(buf.alloc(&d_slabs, sizeof(CorrSlabDev) * slabs.size()));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
+        STAT_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
+        STAT_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_stat_host.hpp)
+        STAT_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
+        STAT_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
+        STAT_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(CorrSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one may take the workspace over; both kernels
         // stride over their work, so the launch geometry is free)
         for (const CorrLaunch& L : launches) {
@@ -316,17 +265,17 @@ int corr_sums(pw_context* ctx, const pw_corr_job* jobs, int64_t n_jobs, const do
             const long grid1 = L.items < (1l << 20) ? L.items : (1l << 20);
             hipLaunchKernelGGL(pw_corr_partial_kernel, dim3((unsigned)grid1), dim3(CORR_WAVE), 0, st, d_slabs + L.first, count,
                                L.items, d_x, d_part);
-            CORR_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
             const long blocks2 = (L.out_hi - L.out_lo + 255) / 256;
             hipLaunchKernelGGL(pw_corr_reduce_kernel, dim3((unsigned)(blocks2 < 65536 ? blocks2 : 65536)), dim3(256), 0, st,
                                d_slabs + L.first, count, L.out_lo, L.out_hi - L.out_lo, d_part, d_out);
-            CORR_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
         }
-        if (kernel_ms) CORR_TRY(hipEventRecord(ev.b, st));
-        CORR_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs, hipMemcpyDeviceToHost, st));
+        STAT_TRY(ev.stop(st));
+        STAT_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs, hipMemcpyDeviceToHost, st));
     }
-    CORR_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) CORR_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     long at = 0;                                                 // (the compact result is in job order)
     for (long k = 0; k < (long)n_jobs; ++k)
         if (jobs[k].n)

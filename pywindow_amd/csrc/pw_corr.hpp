@@ -40,10 +40,4 @@ PW_HD inline long corr_chunk_len(long n, long k, long c) {
     return left < CORR_CHUNK ? left : CORR_CHUNK;
 }
 
-PW_HD inline bool corr_finite(double v) {
-    union { double d; unsigned long long u; } c;
-    c.d = v;
-    return (c.u & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
 }  // namespace pw

@@ -19,12 +19,10 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_dft.hpp"
-#include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 
 using namespace pw;
 
-extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip
-extern "C" int pw_context_device(pw_context* ctx);
 extern "C" int pw_hostpath_dft(const pw_dft_job* jobs, long n_jobs, const double* series, double* re, double* im,
                                int threads);       // pw_hostpath.cpp
 extern "C" void pw_hostpath_dft_twiddles(long j, long M, const long* k, long n, double* c, double* s);
@@ -56,22 +54,11 @@ struct DftSlabDev {
     int tiles, groups, chunks;
 };
 
-// the last entry k with key(k) <= v; keys ascending, key(0) == 0 <= v < key(n)
-template <class Key>
-__device__ inline int dft_find(int n, long v, Key key) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (key(mid) <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // (cA, sA) of every (frequency, r < 512) of the slabs of one launch: pw_sincos once per pair
 __global__ void __launch_bounds__(256)
 pw_dft_twiddle_kernel(const DftSlabDev* __restrict__ slabs, int n_slabs, long total, double2* __restrict__ ws) {
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        const int q = dft_find(n_slabs, t, [&](int i) { return slabs[i].tw_item_first; });
+        const int q = stat_find(n_slabs, t, [&](int i) { return slabs[i].tw_item_first; });
         const long local = t - slabs[q].tw_item_first;     // r * m + f
         const long r = local / slabs[q].m, f = local - r * slabs[q].m;
         double c, s;
@@ -112,7 +99,7 @@ pw_dft_partial_kernel(const DftSlabDev* __restrict__ slabs, int n_slabs, long to
     const int tid = threadIdx.x, lane = tid & (DFT_WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid / DFT_WAVE);
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int q = dft_find(n_slabs, item, [&](int i) { return slabs[i].item_first; });
+        const int q = stat_find(n_slabs, item, [&](int i) { return slabs[i].item_first; });
         const DftSlabDev job = slabs[q];
         const long local = item - job.item_first;
         const long group = local / job.tiles;
@@ -179,7 +166,7 @@ pw_dft_reduce_kernel(const DftSlabDev* __restrict__ slabs, int n_slabs, long tot
     __shared__ double2 s_rot[DFT_RED_CHUNKS][DFT_RED_FREQS];
     const int fl = threadIdx.x % DFT_RED_FREQS, cl = threadIdx.x / DFT_RED_FREQS;
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int q = dft_find(n_slabs, item, [&](int i) { return slabs[i].red_first; });
+        const int q = stat_find(n_slabs, item, [&](int i) { return slabs[i].red_first; });
         const long f = (item - slabs[q].red_first) * DFT_RED_FREQS + fl;
         const long m = slabs[q].m, M = slabs[q].M;
         const int chunks = slabs[q].chunks;
@@ -218,41 +205,6 @@ __global__ void __launch_bounds__(256)
 pw_dft_phase_kernel(long j, long M, const long* __restrict__ k, long n, double* __restrict__ c, double* __restrict__ s) {
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (long)gridDim.x * blockDim.x)
         dft_phase(j, k[t], M, &c[t], &s[t]);
-}
-
-// device memory of one call, allocated and released in stream order
-struct StreamBuffers {
-    static constexpr int CAP = 8;
-    hipStream_t st;
-    void* p[CAP];
-    int n = 0;
-    explicit StreamBuffers(hipStream_t s) : st(s) {}
-    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
-    template <class X> hipError_t alloc(X** out, size_t bytes) {
-        if (n >= CAP) return hipErrorOutOfMemory;
-        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-#define DFT_TRY(call)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
-            return PW_E_HIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-int dft_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_dft_sums: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
 }
 
 // slabs [first, last) share one launch (three kernels) and one workspace of `ws` pairs of doubles
@@ -321,17 +273,18 @@ int dft_sums(pw_context* ctx, const pw_dft_job* jobs, int64_t n_jobs, const doub
     long s_lo = -1, s_hi = 0;
     for (long k = 0; k < (long)n_jobs; ++k) {
         const pw_dft_job& J = jobs[k];
-        if (J.n < 0 || J.n_freq < 0 || J.a_first < 0 || J.out_first < 0) return dft_bad("negative range", k);
-        if (J.n > DFT_MAX) return dft_bad("too long (n > 2^31)", k);
-        if (J.period < 2 || J.period > DFT_MAX) return dft_bad("period outside 2 .. 2^31", k);
-        if (J.j_step < 1) return dft_bad("j_step < 1", k);
-        if (J.j_first < 0 || J.j_first >= J.period) return dft_bad("a frequency outside 0 .. period - 1 (j_first)", k);
+        if (J.n < 0 || J.n_freq < 0 || J.a_first < 0 || J.out_first < 0) return stat_bad("pw_dft_sums", k, "negative range");
+        if (J.n > DFT_MAX) return stat_bad("pw_dft_sums", k, "too long (n > 2^31)");
+        if (J.period < 2 || J.period > DFT_MAX) return stat_bad("pw_dft_sums", k, "period outside 2 .. 2^31");
+        if (J.j_step < 1) return stat_bad("pw_dft_sums", k, "j_step < 1");
+        if (J.j_first < 0 || J.j_first >= J.period)
+            return stat_bad("pw_dft_sums", k, "a frequency outside 0 .. period - 1 (j_first)");
         if (J.n_freq > 0 && (J.n_freq - 1 > (J.period - 1 - J.j_first) / J.j_step))
-            return dft_bad("a frequency outside 0 .. period - 1 (j_first + (n_freq - 1) j_step >= period)", k);
+            return stat_bad("pw_dft_sums", k, "a frequency outside 0 .. period - 1 (j_first + (n_freq - 1) j_step >= period)");
         if (J.n == 0 || J.n_freq == 0) continue;
-        if (!series || !re || !im) return dft_bad("null array", k);
+        if (!series || !re || !im) return stat_bad("pw_dft_sums", k, "null array");
         for (long i = 0; i < (long)J.n; ++i)
-            if (!dft_finite(series[J.a_first + i])) return dft_bad("the series holds a NaN or an infinity", k);
+            if (!pw_finite(series[J.a_first + i])) return stat_bad("pw_dft_sums", k, "the series holds a NaN or an infinity");
         const long lo = (long)J.a_first, hi = lo + (long)J.n;
         if (s_lo < 0 || lo < s_lo) s_lo = lo;
         if (hi > s_hi) s_hi = hi;
@@ -343,54 +296,51 @@ int dft_sums(pw_context* ctx, const pw_dft_job* jobs, int64_t n_jobs, const doub
     std::vector<DftSlabDev> slabs;
     std::vector<DftLaunch> launches;
     dft_plan(jobs, (long)n_jobs, s_lo, (long)(workspace_bytes ? workspace_bytes : DFT_WORKSPACE_BYTES) / 16, slabs, launches);
-    if (slabs.size() > 0x7ffffff0) return dft_bad("too large", (long)n_jobs - 1);
+    if (slabs.size() > 0x7ffffff0) return stat_bad("pw_dft_sums", (long)n_jobs - 1, "too large");
     long pairs = 0;
     for (const DftLaunch& L : launches) pairs = L.ws > pairs ? L.ws : pairs;
     const long outs = slabs.back().out_first + slabs.back().m;
 
     DeviceScope dev_scope_;
-    DFT_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        DFT_TRY(hipEventCreate(&ev.a));
-        DFT_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     std::vector<double> host_out((size_t)outs * 2);
     {
         StreamBuffers buf(st);
         DftSlabDev* d_slabs;
         double *d_x, *d_out;
         double2* d_ws;
-        DFT_TRY(buf.alloc(&d_slabs, sizeof(DftSlabDev) * slabs.size()));
-        DFT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
-        DFT_TRY(buf.alloc(&d_ws, sizeof(double2) * (size_t)pairs));
-        DFT_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs * 2));
-        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
-        DFT_TRY(poison_scratch(poison, d_ws, sizeof(double2) * (size_t)pairs, st));
-        DFT_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs * 2, st));
-        DFT_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(DftSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
-        DFT_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
-        if (kernel_ms) DFT_TRY(hipEventRecord(ev.a, st));
+        STAT_TRY(buf.alloc(&d_slabs, sizeof(DftSlabDev) * slabs.size()));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
+        STAT_TRY(buf.alloc(&d_ws, sizeof(double2) * (size_t)pairs));
+        STAT_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs * 2));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_stat_host.hpp)
+        STAT_TRY(poison_scratch(poison, d_ws, sizeof(double2) * (size_t)pairs, st));
+        STAT_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs * 2, st));
+        STAT_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(DftSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one may take the workspace over; all three kernels
         // stride over their work, so the launch geometry is free)
         for (const DftLaunch& L : launches) {
             const int count = (int)(L.last - L.first);
             hipLaunchKernelGGL(pw_dft_twiddle_kernel, dim3(dft_grid((L.tw_items + 255) / 256)), dim3(256), 0, st,
                                d_slabs + L.first, count, L.tw_items, d_ws);
-            DFT_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
             hipLaunchKernelGGL(pw_dft_partial_kernel, dim3(dft_grid(L.items)), dim3(DFT_THREADS), 0, st, d_slabs + L.first,
                                count, L.items, d_x, d_ws);
-            DFT_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
             hipLaunchKernelGGL(pw_dft_reduce_kernel, dim3(dft_grid(L.red_items)), dim3(256), 0, st, d_slabs + L.first, count,
                                L.red_items, outs, d_ws, d_out);
-            DFT_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
         }
-        if (kernel_ms) DFT_TRY(hipEventRecord(ev.b, st));
-        DFT_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs * 2, hipMemcpyDeviceToHost, st));
+        STAT_TRY(ev.stop(st));
+        STAT_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs * 2, hipMemcpyDeviceToHost, st));
     }
-    DFT_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) DFT_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     long at = 0;                                                 // (the compact result is in job order)
     for (long k = 0; k < (long)n_jobs; ++k)
         if (jobs[k].n && jobs[k].n_freq)
@@ -429,21 +379,21 @@ extern "C" int pw_internal_dft_twiddles(pw_context* ctx, int64_t j, int64_t M, c
         return PW_OK;
     }
     DeviceScope dev_scope_;
-    DFT_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
     {
         StreamBuffers buf(st);
         long* d_k;
         double* d_cs;
-        DFT_TRY(buf.alloc(&d_k, sizeof(long) * (size_t)n));
-        DFT_TRY(buf.alloc(&d_cs, sizeof(double) * (size_t)n * 2));
-        DFT_TRY(hipMemcpyAsync(d_k, k, sizeof(long) * (size_t)n, hipMemcpyHostToDevice, st));
+        STAT_TRY(buf.alloc(&d_k, sizeof(long) * (size_t)n));
+        STAT_TRY(buf.alloc(&d_cs, sizeof(double) * (size_t)n * 2));
+        STAT_TRY(hipMemcpyAsync(d_k, k, sizeof(long) * (size_t)n, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(pw_dft_phase_kernel, dim3(dft_grid((n + 255) / 256)), dim3(256), 0, st, (long)j, (long)M, d_k,
                            (long)n, d_cs, d_cs + n);
-        DFT_TRY(hipGetLastError());
-        DFT_TRY(hipMemcpyAsync(c, d_cs, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
-        DFT_TRY(hipMemcpyAsync(s, d_cs + n, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+        STAT_TRY(hipGetLastError());
+        STAT_TRY(hipMemcpyAsync(c, d_cs, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+        STAT_TRY(hipMemcpyAsync(s, d_cs + n, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     }
-    DFT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(hipStreamSynchronize(st));
     return PW_OK;
 }

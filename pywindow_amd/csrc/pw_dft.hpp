@@ -53,10 +53,4 @@ PW_HD inline void dft_rotate(double cB, double sB, double pc, double ps, double*
     *im = pw_fma(sB, pc, cB * ps);
 }
 
-PW_HD inline bool dft_finite(double v) {
-    union { double d; unsigned long long u; } c;
-    c.d = v;
-    return (c.u & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
 }  // namespace pw

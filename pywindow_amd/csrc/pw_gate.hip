@@ -17,12 +17,10 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_gate.hpp"
-#include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 
 using namespace pw;
 
-extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip
-extern "C" int pw_context_device(pw_context* ctx);
 extern "C" int pw_hostpath_gate(const pw_gate_job* jobs, long n_jobs, const double* series, const double* thresholds,
                                 long n_bins, long* counts, long* hist, int threads);   // pw_hostpath.cpp
 
@@ -43,17 +41,6 @@ struct GateSlabDev {
     long lane_first;           // first of the slab's m thresholds among those of its launch
     int tiles, chunks;
 };
-
-// the last entry k with key(k) <= v; keys ascending, key(0) == 0 <= v < key(n)
-template <class Key>
-__device__ inline int gate_find(int n, long v, Key key) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (key(mid) <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // one more complete run of `len` entries in row `row`, s = 0 open, 1 closed; the last bin takes every length >= B
 struct GateHistAtomic {
@@ -80,7 +67,7 @@ pw_gate_chunk_kernel(const GateSlabDev* __restrict__ slabs, int n_slabs, long to
     __shared__ double s_a[GATE_CHUNK];
     const int tid = threadIdx.x;
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int q = gate_find(n_slabs, item, [&](int i) { return slabs[i].item_first; });
+        const int q = stat_find(n_slabs, item, [&](int i) { return slabs[i].item_first; });
         const GateSlabDev S = slabs[q];
         const long local = item - S.item_first;
         const long ch = local / S.tiles;                             // (tiles fastest: neighbours share the chunk)
@@ -119,7 +106,7 @@ __global__ void __launch_bounds__(256)
 pw_gate_merge_kernel(const GateSlabDev* __restrict__ slabs, int n_slabs, long total, const unsigned* __restrict__ ws,
                      long* counts, long* hist, long n_bins) {
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        const int q = gate_find(n_slabs, t, [&](int i) { return slabs[i].lane_first; });
+        const int q = stat_find(n_slabs, t, [&](int i) { return slabs[i].lane_first; });
         const long f = t - slabs[q].lane_first, m = slabs[q].m;
         const int chunks = slabs[q].chunks;
         const long row = slabs[q].row_first + f;
@@ -143,41 +130,6 @@ pw_gate_merge_kernel(const GateSlabDev* __restrict__ slabs, int n_slabs, long to
         c[10] += T.complete_open_frames;
         c[11] += T.complete_closed_frames;
     }
-}
-
-// device memory of one call, allocated and released in stream order
-struct StreamBuffers {
-    static constexpr int CAP = 8;
-    hipStream_t st;
-    void* p[CAP];
-    int n = 0;
-    explicit StreamBuffers(hipStream_t s) : st(s) {}
-    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
-    template <class X> hipError_t alloc(X** out, size_t bytes) {
-        if (n >= CAP) return hipErrorOutOfMemory;
-        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-#define GATE_TRY(call)                                                                     \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
-            return PW_E_HIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-int gate_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_gate_counts: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
 }
 
 // slabs [first, last) share one launch (two kernels) and one workspace of `ws` summaries
@@ -250,18 +202,20 @@ int gate_counts(pw_context* ctx, const pw_gate_job* jobs, int64_t n_jobs, const 
     long s_lo = -1, s_hi = 0, d_lo = -1, d_hi = 0;
     for (long k = 0; k < (long)n_jobs; ++k) {
         const pw_gate_job& J = jobs[k];
-        if (J.n < 0 || J.n_thr < 0 || J.a_first < 0 || J.d_first < 0 || J.out_first < 0) return gate_bad("negative range", k);
-        if (J.n > GATE_MAX) return gate_bad("too long (n > 2^31)", k);
-        if (n_bins < 0) return gate_bad("n_bins is negative", k);
+        if (J.n < 0 || J.n_thr < 0 || J.a_first < 0 || J.d_first < 0 || J.out_first < 0)
+            return stat_bad("pw_gate_counts", k, "negative range");
+        if (J.n > GATE_MAX) return stat_bad("pw_gate_counts", k, "too long (n > 2^31)");
+        if (n_bins < 0) return stat_bad("pw_gate_counts", k, "n_bins is negative");
         if (J.n == 0 || J.n_thr == 0) continue;
-        if (!series || !thresholds || !counts) return gate_bad("null array", k);
-        if (n_bins > 0 && !hist) return gate_bad("hist is null with n_bins > 0", k);
+        if (!series || !thresholds || !counts) return stat_bad("pw_gate_counts", k, "null array");
+        if (n_bins > 0 && !hist) return stat_bad("pw_gate_counts", k, "hist is null with n_bins > 0");
         for (long i = 0; i < (long)J.n; ++i) {
             const double v = series[J.a_first + i];
-            if (!gate_finite(v) && !gate_nan(v)) return gate_bad("the series holds an infinity", k);
+            if (!pw_finite(v) && !pw_isnan_bits(v)) return stat_bad("pw_gate_counts", k, "the series holds an infinity");
         }
         for (long i = 0; i < (long)J.n_thr; ++i)
-            if (!gate_finite(thresholds[J.d_first + i])) return gate_bad("a threshold is a NaN or an infinity", k);
+            if (!pw_finite(thresholds[J.d_first + i]))
+                return stat_bad("pw_gate_counts", k, "a threshold is a NaN or an infinity");
         const long lo = (long)J.a_first, hi = lo + (long)J.n, dl = (long)J.d_first, dh = dl + (long)J.n_thr;
         if (s_lo < 0 || lo < s_lo) s_lo = lo;
         if (hi > s_hi) s_hi = hi;
@@ -278,7 +232,7 @@ int gate_counts(pw_context* ctx, const pw_gate_job* jobs, int64_t n_jobs, const 
     std::vector<GateCopy> copies;
     gate_plan(jobs, (long)n_jobs, s_lo, d_lo, (long)(workspace_bytes ? workspace_bytes : GATE_WORKSPACE_BYTES) / 4, slabs,
               launches, copies);
-    if (slabs.size() > 0x7ffffff0) return gate_bad("too large", (long)n_jobs - 1);
+    if (slabs.size() > 0x7ffffff0) return stat_bad("pw_gate_counts", (long)n_jobs - 1, "too large");
     long words = 0;
     for (const GateLaunch& L : launches) words = L.ws > words ? L.ws : words;
     const long rows = slabs.back().row_first + slabs.back().m;
@@ -286,58 +240,55 @@ int gate_counts(pw_context* ctx, const pw_gate_job* jobs, int64_t n_jobs, const 
     const size_t hist_bytes = sizeof(long) * (size_t)rows * 2 * (size_t)n_bins;
 
     DeviceScope dev_scope_;
-    GATE_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        GATE_TRY(hipEventCreate(&ev.a));
-        GATE_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     {
         StreamBuffers buf(st);
         GateSlabDev* d_slabs;
         double *d_x, *d_thr;
         unsigned* d_ws;
         long *d_counts, *d_hist;
-        GATE_TRY(buf.alloc(&d_slabs, sizeof(GateSlabDev) * slabs.size()));
-        GATE_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
-        GATE_TRY(buf.alloc(&d_thr, sizeof(double) * (size_t)(d_hi - d_lo)));
-        GATE_TRY(buf.alloc(&d_ws, sizeof(unsigned) * (size_t)words));
-        GATE_TRY(buf.alloc(&d_counts, count_bytes));
-        GATE_TRY(buf.alloc(&d_hist, hist_bytes));
-        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp; the result is zeroed below)
-        GATE_TRY(poison_scratch(poison, d_ws, sizeof(unsigned) * (size_t)words, st));
-        GATE_TRY(poison_scratch(poison, d_counts, count_bytes, st));
-        GATE_TRY(poison_scratch(poison, d_hist, hist_bytes, st));
-        GATE_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(GateSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
-        GATE_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
-        GATE_TRY(hipMemcpyAsync(d_thr, thresholds + d_lo, sizeof(double) * (size_t)(d_hi - d_lo), hipMemcpyHostToDevice, st));
-        if (kernel_ms) GATE_TRY(hipEventRecord(ev.a, st));
-        GATE_TRY(hipMemsetAsync(d_counts, 0, count_bytes, st));
-        if (hist_bytes) GATE_TRY(hipMemsetAsync(d_hist, 0, hist_bytes, st));
+        STAT_TRY(buf.alloc(&d_slabs, sizeof(GateSlabDev) * slabs.size()));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
+        STAT_TRY(buf.alloc(&d_thr, sizeof(double) * (size_t)(d_hi - d_lo)));
+        STAT_TRY(buf.alloc(&d_ws, sizeof(unsigned) * (size_t)words));
+        STAT_TRY(buf.alloc(&d_counts, count_bytes));
+        STAT_TRY(buf.alloc(&d_hist, hist_bytes));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_stat_host.hpp; the result is zeroed below)
+        STAT_TRY(poison_scratch(poison, d_ws, sizeof(unsigned) * (size_t)words, st));
+        STAT_TRY(poison_scratch(poison, d_counts, count_bytes, st));
+        STAT_TRY(poison_scratch(poison, d_hist, hist_bytes, st));
+        STAT_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(GateSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_thr, thresholds + d_lo, sizeof(double) * (size_t)(d_hi - d_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
+        STAT_TRY(hipMemsetAsync(d_counts, 0, count_bytes, st));
+        if (hist_bytes) STAT_TRY(hipMemsetAsync(d_hist, 0, hist_bytes, st));
         // (launches follow one another on the stream, so the next one may take the workspace over; both kernels
         // stride over their work, so the launch geometry is free)
         for (const GateLaunch& L : launches) {
             const int count = (int)(L.last - L.first);
             hipLaunchKernelGGL(pw_gate_chunk_kernel, dim3(gate_grid(L.items)), dim3(GATE_TILE), 0, st, d_slabs + L.first, count,
                                L.items, d_x, d_thr, d_ws, d_counts, d_hist, (long)n_bins);
-            GATE_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
             hipLaunchKernelGGL(pw_gate_merge_kernel, dim3(gate_grid((L.lanes + 255) / 256)), dim3(256), 0, st, d_slabs + L.first,
                                count, L.lanes, d_ws, d_counts, d_hist, (long)n_bins);
-            GATE_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
         }
-        if (kernel_ms) GATE_TRY(hipEventRecord(ev.b, st));
+        STAT_TRY(ev.stop(st));
         // (the compact result is in job order: neighbours in the caller's arrays come back in one copy)
         for (const GateCopy& c : copies) {
-            GATE_TRY(hipMemcpyAsync(counts + c.host * GATE_FIELDS, d_counts + c.dev * GATE_FIELDS,
+            STAT_TRY(hipMemcpyAsync(counts + c.host * GATE_FIELDS, d_counts + c.dev * GATE_FIELDS,
                                     sizeof(long) * (size_t)c.rows * GATE_FIELDS, hipMemcpyDeviceToHost, st));
             if (hist_bytes)
-                GATE_TRY(hipMemcpyAsync(hist + c.host * 2 * n_bins, d_hist + c.dev * 2 * n_bins,
+                STAT_TRY(hipMemcpyAsync(hist + c.host * 2 * n_bins, d_hist + c.dev * 2 * n_bins,
                                         sizeof(long) * (size_t)c.rows * 2 * (size_t)n_bins, hipMemcpyDeviceToHost, st));
         }
     }
-    GATE_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) GATE_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     return PW_OK;
 }
 

@@ -29,16 +29,6 @@ constexpr long GATE_MAX = 1l << 31;      // largest n
 // states: two bits each in a summary; x ^ y == 1 says "opposite" whenever one of the two is OPEN or CLOSED
 constexpr unsigned GATE_CLOSED = 0, GATE_OPEN = 1, GATE_GAP = 2, GATE_NONE = 3;
 
-PW_HD inline bool gate_nan(double v) {
-    union { double d; unsigned long long u; } c;
-    c.d = v;
-    return (c.u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull && (c.u & 0x000fffffffffffffull) != 0;
-}
-PW_HD inline bool gate_finite(double v) {
-    union { double d; unsigned long long u; } c;
-    c.d = v;
-    return (c.u & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
 // (an infinity never reaches this: the entry refuses it, so all ones in the exponent is a NaN)
 PW_HD inline unsigned gate_state(double a, double d) {
     union { double d; unsigned long long u; } c;

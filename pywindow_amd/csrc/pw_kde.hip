@@ -14,13 +14,11 @@
 #include <vector>
 
 #include "../../include/pywindow_amd.h"
-#include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 #include "pw_kde.hpp"
 
 using namespace pw;
 
-extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip
-extern "C" int pw_context_device(pw_context* ctx);
 extern "C" int pw_hostpath_kde(const pw_kde_job* jobs, long n_jobs, const double* samples, const double* points,
                                double* sums, int threads);   // pw_hostpath.cpp
 extern "C" void pw_hostpath_exp(const double* x, long n, double* y);
@@ -39,17 +37,6 @@ struct KdeJobDev {
     int tiles, chunks;
 };
 
-// the last entry k with key(k) <= v; keys ascending, key(0) == 0 <= v < key(n)
-template <class Key>
-__device__ inline int kde_find(int n, long v, Key key) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (key(mid) <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __global__ void __launch_bounds__(KDE_WAVE)
 pw_kde_partial_kernel(const KdeJobDev* __restrict__ jobs, int n_jobs, const double* __restrict__ samples,
                       const double* __restrict__ points, double* __restrict__ part) {
@@ -59,7 +46,7 @@ pw_kde_partial_kernel(const KdeJobDev* __restrict__ jobs, int n_jobs, const doub
     for (int t = lane; t < 256; t += KDE_WAVE) s_tab[t] = POW_EXP_TAB[t];
     const long total = jobs[n_jobs].item_first;
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int k = kde_find(n_jobs, item, [&](int q) { return jobs[q].item_first; });
+        const int k = stat_find(n_jobs, item, [&](int q) { return jobs[q].item_first; });
         const KdeJobDev job = jobs[k];
         const long local = item - job.item_first;
         const long chunk = local / job.tiles;
@@ -94,7 +81,7 @@ pw_kde_reduce_kernel(const KdeJobDev* __restrict__ jobs, int n_jobs, const doubl
                      double* __restrict__ out) {
     const long total = jobs[n_jobs].out_first;
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        const int k = kde_find(n_jobs, t, [&](int q) { return jobs[q].out_first; });
+        const int k = stat_find(n_jobs, t, [&](int q) { return jobs[q].out_first; });
         const long m = jobs[k].m, j = t - jobs[k].out_first;
         const double* p = part + jobs[k].part_first + j;
         double s = 0.0;
@@ -127,7 +114,7 @@ pw_kde2_partial_kernel(const Kde2SlabDev* __restrict__ slabs, int n_slabs, long 
     const int lane = threadIdx.x;
     for (int t = lane; t < 256; t += KDE_WAVE) s_tab[t] = POW_EXP_TAB[t];
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int k = kde_find(n_slabs, item, [&](int q) { return slabs[q].item_first; });
+        const int k = stat_find(n_slabs, item, [&](int q) { return slabs[q].item_first; });
         const Kde2SlabDev job = slabs[k];
         const long local = item - job.item_first;
         const long chunk = local / job.tiles;
@@ -168,7 +155,7 @@ __global__ void __launch_bounds__(256)
 pw_kde2_reduce_kernel(const Kde2SlabDev* __restrict__ slabs, int n_slabs, long out_lo, long count,
                       const double* __restrict__ part, double* __restrict__ out) {
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x * blockDim.x) {
-        const int k = kde_find(n_slabs, t, [&](int q) { return slabs[q].out_first - out_lo; });
+        const int k = stat_find(n_slabs, t, [&](int q) { return slabs[q].out_first - out_lo; });
         const long m = slabs[k].m, j = out_lo + t - slabs[k].out_first;
         const double* p = part + slabs[k].part_first + j;
         double s = 0.0;
@@ -187,41 +174,6 @@ pw_exp_kernel(long n, const double* __restrict__ x, double* __restrict__ y) {
         y[i] = pw_exp_tab(x[i], s_tab);
 }
 
-// device memory of one call, allocated and released in stream order
-struct StreamBuffers {
-    static constexpr int CAP = 8;
-    hipStream_t st;
-    void* p[CAP];
-    int n = 0;
-    explicit StreamBuffers(hipStream_t s) : st(s) {}
-    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
-    template <class X> hipError_t alloc(X** out, size_t bytes) {
-        if (n >= CAP) return hipErrorOutOfMemory;
-        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-#define KDE_TRY(call)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
-            return PW_E_HIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-int kde_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_kde_sums: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
-}
-
 // kernel_ms: when not null, the time of the two kernels by HIP events on the context's stream
 int kde_sums(pw_context* ctx, const pw_kde_job* jobs, int64_t n_jobs, const double* samples, const double* points,
              double* sums, float* kernel_ms) {
@@ -233,13 +185,15 @@ int kde_sums(pw_context* ctx, const pw_kde_job* jobs, int64_t n_jobs, const doub
     long s_lo = -1, s_hi = 0, p_lo = -1, p_hi = 0;
     for (long k = 0; k < (long)n_jobs; ++k) {
         const pw_kde_job& J = jobs[k];
-        if (J.n_samples < 0 || J.n_points < 0 || J.sample_first < 0 || J.point_first < 0) return kde_bad("negative range", k);
-        if ((J.n_samples && !samples) || (J.n_points && (!points || !sums))) return kde_bad("null array", k);
-        if (!kde_finite(J.inv_bandwidth) || !(J.inv_bandwidth > 0.0)) return kde_bad("bandwidth not positive and finite", k);
+        if (J.n_samples < 0 || J.n_points < 0 || J.sample_first < 0 || J.point_first < 0)
+            return stat_bad("pw_kde_sums", k, "negative range");
+        if ((J.n_samples && !samples) || (J.n_points && (!points || !sums))) return stat_bad("pw_kde_sums", k, "null array");
+        if (!pw_finite(J.inv_bandwidth) || !(J.inv_bandwidth > 0.0))
+            return stat_bad("pw_kde_sums", k, "bandwidth not positive and finite");
         for (long i = 0; i < (long)J.n_samples; ++i)
-            if (!kde_finite(samples[J.sample_first + i])) return kde_bad("a sample is NaN or infinite", k);
+            if (!pw_finite(samples[J.sample_first + i])) return stat_bad("pw_kde_sums", k, "a sample is NaN or infinite");
         for (long i = 0; i < (long)J.n_points; ++i)
-            if (!kde_finite(points[J.point_first + i])) return kde_bad("a point is NaN or infinite", k);
+            if (!pw_finite(points[J.point_first + i])) return stat_bad("pw_kde_sums", k, "a point is NaN or infinite");
         if (J.n_samples) {
             if (s_lo < 0 || J.sample_first < s_lo) s_lo = (long)J.sample_first;
             if (J.sample_first + J.n_samples > s_hi) s_hi = (long)(J.sample_first + J.n_samples);
@@ -264,7 +218,7 @@ int kde_sums(pw_context* ctx, const pw_kde_job* jobs, int64_t n_jobs, const doub
         D.point_first = D.m ? (long)J.point_first - p_lo : 0;
         D.r = J.inv_bandwidth;
         const long tiles = (D.m + KDE_TILE - 1) / KDE_TILE, chunks = D.m ? (D.n + KDE_CHUNK - 1) / KDE_CHUNK : 0;
-        if (tiles > 0x7fffffff || chunks > 0x7fffffff) return kde_bad("too large", k);
+        if (tiles > 0x7fffffff || chunks > 0x7fffffff) return stat_bad("pw_kde_sums", k, "too large");
         D.tiles = (int)tiles; D.chunks = (int)chunks;
         D.item_first = items; D.part_first = parts; D.out_first = outs;
         items += tiles * chunks; parts += chunks * D.m; outs += D.m;
@@ -274,54 +228,46 @@ int kde_sums(pw_context* ctx, const pw_kde_job* jobs, int64_t n_jobs, const doub
     E.item_first = items; E.part_first = parts; E.out_first = outs;
 
     DeviceScope dev_scope_;
-    KDE_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        KDE_TRY(hipEventCreate(&ev.a));
-        KDE_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     std::vector<double> host_out((size_t)outs);
     {
         StreamBuffers buf(st);
         KdeJobDev* d_jobs;
         double *d_x, *d_g, *d_part, *d_out;
-        KDE_TRY(buf.alloc(&d_jobs, sizeof(KdeJobDev) * dev.size()));
-        KDE_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
-        KDE_TRY(buf.alloc(&d_g, sizeof(double) * (size_t)(p_hi - p_lo)));
-        KDE_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
-        KDE_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
-        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
-        KDE_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
-        KDE_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
-        KDE_TRY(hipMemcpyAsync(d_jobs, dev.data(), sizeof(KdeJobDev) * dev.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(buf.alloc(&d_jobs, sizeof(KdeJobDev) * dev.size()));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
+        STAT_TRY(buf.alloc(&d_g, sizeof(double) * (size_t)(p_hi - p_lo)));
+        STAT_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
+        STAT_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_stat_host.hpp)
+        STAT_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
+        STAT_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
+        STAT_TRY(hipMemcpyAsync(d_jobs, dev.data(), sizeof(KdeJobDev) * dev.size(), hipMemcpyHostToDevice, st));
         if (s_hi > s_lo)
-            KDE_TRY(hipMemcpyAsync(d_x, samples + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
-        KDE_TRY(hipMemcpyAsync(d_g, points + p_lo, sizeof(double) * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
-        if (kernel_ms) KDE_TRY(hipEventRecord(ev.a, st));
+            STAT_TRY(hipMemcpyAsync(d_x, samples + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_g, points + p_lo, sizeof(double) * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
         // (a job without samples has no pair and its sums are the reduce kernel's zeros; the launch geometry is
         // free: both kernels stride over their work)
         const long grid1 = items < 1 ? 1 : (items < (1l << 20) ? items : (1l << 20));
         hipLaunchKernelGGL(pw_kde_partial_kernel, dim3((unsigned)grid1), dim3(KDE_WAVE), 0, st, d_jobs, (int)n_jobs, d_x, d_g,
                            d_part);
-        KDE_TRY(hipGetLastError());
+        STAT_TRY(hipGetLastError());
         const long blocks2 = (outs + 255) / 256;
         hipLaunchKernelGGL(pw_kde_reduce_kernel, dim3((unsigned)(blocks2 < 65536 ? blocks2 : 65536)), dim3(256), 0, st, d_jobs,
                            (int)n_jobs, d_part, d_out);
-        KDE_TRY(hipGetLastError());
-        if (kernel_ms) KDE_TRY(hipEventRecord(ev.b, st));
-        KDE_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs, hipMemcpyDeviceToHost, st));
+        STAT_TRY(hipGetLastError());
+        STAT_TRY(ev.stop(st));
+        STAT_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs, hipMemcpyDeviceToHost, st));
     }
-    KDE_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) KDE_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     for (long k = 0; k < (long)n_jobs; ++k)
         for (long j = 0; j < dev[k].m; ++j) sums[jobs[k].point_first + j] = host_out[(size_t)(dev[k].out_first + j)];
     return PW_OK;
-}
-
-int kde2_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_kde2_sums: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
 }
 
 // slabs [first, last) share one launch pair and one workspace of `parts` doubles
@@ -381,15 +327,16 @@ int kde2_sums(pw_context* ctx, const pw_kde2_job* jobs, int64_t n_jobs, const do
     long s_lo = -1, s_hi = 0, p_lo = -1, p_hi = 0;
     for (long k = 0; k < (long)n_jobs; ++k) {
         const pw_kde2_job& J = jobs[k];
-        if (J.n_samples < 0 || J.n_points < 0 || J.sample_first < 0 || J.point_first < 0) return kde2_bad("negative range", k);
-        if ((J.n_samples && !samples) || (J.n_points && (!points || !sums))) return kde2_bad("null array", k);
-        if (!kde_finite(J.w00) || !kde_finite(J.w10) || !kde_finite(J.w11) || !(J.w00 > 0.0) || !(J.w11 > 0.0))
-            return kde2_bad("factors not finite with a positive diagonal", k);
-        if ((J.n_samples + KDE_CHUNK - 1) / KDE_CHUNK > 0x7fffffff) return kde2_bad("too large", k);
+        if (J.n_samples < 0 || J.n_points < 0 || J.sample_first < 0 || J.point_first < 0)
+            return stat_bad("pw_kde2_sums", k, "negative range");
+        if ((J.n_samples && !samples) || (J.n_points && (!points || !sums))) return stat_bad("pw_kde2_sums", k, "null array");
+        if (!pw_finite(J.w00) || !pw_finite(J.w10) || !pw_finite(J.w11) || !(J.w00 > 0.0) || !(J.w11 > 0.0))
+            return stat_bad("pw_kde2_sums", k, "factors not finite with a positive diagonal");
+        if ((J.n_samples + KDE_CHUNK - 1) / KDE_CHUNK > 0x7fffffff) return stat_bad("pw_kde2_sums", k, "too large");
         for (long i = 0; i < 2 * (long)J.n_samples; ++i)
-            if (!kde_finite(samples[2 * J.sample_first + i])) return kde2_bad("a sample is NaN or infinite", k);
+            if (!pw_finite(samples[2 * J.sample_first + i])) return stat_bad("pw_kde2_sums", k, "a sample is NaN or infinite");
         for (long i = 0; i < 2 * (long)J.n_points; ++i)
-            if (!kde_finite(points[2 * J.point_first + i])) return kde2_bad("a point is NaN or infinite", k);
+            if (!pw_finite(points[2 * J.point_first + i])) return stat_bad("pw_kde2_sums", k, "a point is NaN or infinite");
         if (J.n_samples) {
             if (s_lo < 0 || J.sample_first < s_lo) s_lo = (long)J.sample_first;
             if (J.sample_first + J.n_samples > s_hi) s_hi = (long)(J.sample_first + J.n_samples);
@@ -407,38 +354,35 @@ int kde2_sums(pw_context* ctx, const pw_kde2_job* jobs, int64_t n_jobs, const do
     std::vector<Kde2SlabDev> slabs;
     std::vector<Kde2Launch> launches;
     kde2_plan(jobs, (long)n_jobs, s_lo, p_lo, (long)(workspace_bytes ? workspace_bytes : KDE2_WORKSPACE_BYTES) / 8, slabs, launches);
-    if (slabs.size() > 0x7ffffff0) return kde2_bad("too large", (long)n_jobs - 1);
+    if (slabs.size() > 0x7ffffff0) return stat_bad("pw_kde2_sums", (long)n_jobs - 1, "too large");
     long parts = 0;
     for (const Kde2Launch& L : launches) parts = L.parts > parts ? L.parts : parts;
     const long outs = launches.back().out_hi;
 
     DeviceScope dev_scope_;
-    KDE_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        KDE_TRY(hipEventCreate(&ev.a));
-        KDE_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     std::vector<double> host_out((size_t)outs);
     {
         StreamBuffers buf(st);
         Kde2SlabDev* d_slabs;
         double2 *d_x, *d_g;
         double *d_part, *d_out;
-        KDE_TRY(buf.alloc(&d_slabs, sizeof(Kde2SlabDev) * slabs.size()));
-        KDE_TRY(buf.alloc(&d_x, sizeof(double2) * (size_t)(s_hi - s_lo)));
-        KDE_TRY(buf.alloc(&d_g, sizeof(double2) * (size_t)(p_hi - p_lo)));
-        KDE_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
-        KDE_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
-        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
-        KDE_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
-        KDE_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
-        KDE_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(Kde2SlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(buf.alloc(&d_slabs, sizeof(Kde2SlabDev) * slabs.size()));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double2) * (size_t)(s_hi - s_lo)));
+        STAT_TRY(buf.alloc(&d_g, sizeof(double2) * (size_t)(p_hi - p_lo)));
+        STAT_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
+        STAT_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_stat_host.hpp)
+        STAT_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
+        STAT_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
+        STAT_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(Kde2SlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
         if (s_hi > s_lo)
-            KDE_TRY(hipMemcpyAsync(d_x, samples + 2 * s_lo, sizeof(double2) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
-        KDE_TRY(hipMemcpyAsync(d_g, points + 2 * p_lo, sizeof(double2) * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
-        if (kernel_ms) KDE_TRY(hipEventRecord(ev.a, st));
+            STAT_TRY(hipMemcpyAsync(d_x, samples + 2 * s_lo, sizeof(double2) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_g, points + 2 * p_lo, sizeof(double2) * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one may take the workspace over; a slab without
         // samples has no item and its sums are the reduce kernel's zeros; both kernels stride over their work)
         for (const Kde2Launch& L : launches) {
@@ -447,18 +391,18 @@ int kde2_sums(pw_context* ctx, const pw_kde2_job* jobs, int64_t n_jobs, const do
                 const long grid1 = L.items < (1l << 20) ? L.items : (1l << 20);
                 hipLaunchKernelGGL(pw_kde2_partial_kernel, dim3((unsigned)grid1), dim3(KDE_WAVE), 0, st, d_slabs + L.first, count,
                                    L.items, d_x, d_g, d_part);
-                KDE_TRY(hipGetLastError());
+                STAT_TRY(hipGetLastError());
             }
             const long blocks2 = (L.out_hi - L.out_lo + 255) / 256;
             hipLaunchKernelGGL(pw_kde2_reduce_kernel, dim3((unsigned)(blocks2 < 65536 ? blocks2 : 65536)), dim3(256), 0, st,
                                d_slabs + L.first, count, L.out_lo, L.out_hi - L.out_lo, d_part, d_out);
-            KDE_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
         }
-        if (kernel_ms) KDE_TRY(hipEventRecord(ev.b, st));
-        KDE_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs, hipMemcpyDeviceToHost, st));
+        STAT_TRY(ev.stop(st));
+        STAT_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs, hipMemcpyDeviceToHost, st));
     }
-    KDE_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) KDE_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     long at = 0;                                                 // (the compact result is in job order)
     for (long k = 0; k < (long)n_jobs; ++k)
         for (long j = 0; j < (long)jobs[k].n_points; ++j) sums[jobs[k].point_first + j] = host_out[(size_t)at++];
@@ -492,7 +436,7 @@ extern "C" int pw_internal_kde2_sums(pw_context* ctx, const pw_kde2_job* jobs, i
 
 // test hook (not part of the header): on != 0 makes every statistical entry of the library -- the two here and those
 // of pw_kdew.hip, pw_corr.hip, pw_dft.hip and pw_gate.hip -- fill its device workspace and its compact device result
-// with bytes 0xFF before its first kernel (pw_host.hpp: poison_scratch).  Process-wide, off at start; no kernel and
+// with bytes 0xFF before its first kernel (pw_stat_host.hpp: poison_scratch).  Process-wide, off at start; no kernel and
 // no result changes, unless a kernel reads what the call never wrote.
 extern "C" void pw_internal_poison_scratch(int on) { g_poison_scratch.store(on != 0, std::memory_order_relaxed); }
 
@@ -507,19 +451,19 @@ extern "C" int pw_internal_exp(pw_context* ctx, const double* x, int64_t n, doub
         return PW_OK;
     }
     DeviceScope dev_scope_;
-    KDE_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
     {
         StreamBuffers buf(st);
         double *d_x, *d_y;
-        KDE_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)n));
-        KDE_TRY(buf.alloc(&d_y, sizeof(double) * (size_t)n));
-        KDE_TRY(hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)n));
+        STAT_TRY(buf.alloc(&d_y, sizeof(double) * (size_t)n));
+        STAT_TRY(hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
         const long blocks = ((long)n + 255) / 256;
         hipLaunchKernelGGL(pw_exp_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, (long)n, d_x, d_y);
-        KDE_TRY(hipGetLastError());
-        KDE_TRY(hipMemcpyAsync(y, d_y, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+        STAT_TRY(hipGetLastError());
+        STAT_TRY(hipMemcpyAsync(y, d_y, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     }
-    KDE_TRY(hipStreamSynchronize(st));
+    STAT_TRY(hipStreamSynchronize(st));
     return PW_OK;
 }

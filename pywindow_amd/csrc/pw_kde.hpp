@@ -113,6 +113,4 @@ PW_HD inline void kdew_chunk_sums(double g, const double* x, const double* w, lo
     }
 }
 
-PW_HD inline bool kde_finite(double v) { return (pw_d2bits(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
-
 }  // namespace pw

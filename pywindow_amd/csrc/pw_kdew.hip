@@ -17,13 +17,11 @@
 #include <vector>
 
 #include "../../include/pywindow_amd.h"
-#include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 #include "pw_kde.hpp"
 
 using namespace pw;
 
-extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip
-extern "C" int pw_context_device(pw_context* ctx);
 extern "C" int pw_hostpath_kdew(const pw_kdew_job* jobs, long n_jobs, const double* samples, const double* points,
                                 const double* weights, double* sums, int threads);   // pw_hostpath.cpp
 
@@ -45,17 +43,6 @@ struct KdewSlabDev {
     long out_first;            // the slab's [nb][m] sums in the compact result of the call
     int ptiles, rtiles, chunks;
 };
-
-// the last entry k with key(k) <= v; keys ascending, key(0) == 0 <= v < key(n)
-template <class Key>
-__device__ inline int kdew_find(int n, long v, Key key) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (key(mid) <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 // kdew_chunk_sums for P points x the replicas of a tile side by side: the same operations in the same order for
 // every (point, replica).  w: the chunk's first sample's weights from the tile's first replica on (wave-uniform).
@@ -100,7 +87,7 @@ pw_kdew_partial_kernel(const KdewSlabDev* __restrict__ slabs, int n_slabs, long 
     const int lane = threadIdx.x;
     for (int t = lane; t < 256; t += KDE_WAVE) s_tab[t] = POW_EXP_TAB[t];
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int k = kdew_find(n_slabs, item, [&](int q) { return slabs[q].item_first; });
+        const int k = stat_find(n_slabs, item, [&](int q) { return slabs[q].item_first; });
         const KdewSlabDev job = slabs[k];
         const long local = item - job.item_first;
         const long per_chunk = (long)job.ptiles * job.rtiles;
@@ -146,7 +133,7 @@ __global__ void __launch_bounds__(256)
 pw_kdew_reduce_kernel(const KdewSlabDev* __restrict__ slabs, int n_slabs, long out_lo, long count,
                       const double* __restrict__ part, double* __restrict__ out) {
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < count; t += (long)gridDim.x * blockDim.x) {
-        const int k = kdew_find(n_slabs, t, [&](int q) { return slabs[q].out_first - out_lo; });
+        const int k = stat_find(n_slabs, t, [&](int q) { return slabs[q].out_first - out_lo; });
         const long at = out_lo + t - slabs[k].out_first;         // b * m + j within the slab
         const long pitch = slabs[k].nb * slabs[k].m;             // from one chunk's partials to the next
         const double* p = part + slabs[k].part_first + at;
@@ -154,41 +141,6 @@ pw_kdew_reduce_kernel(const KdewSlabDev* __restrict__ slabs, int n_slabs, long o
         for (int c = 0; c < slabs[k].chunks; ++c) s = c == 0 ? p[0] : s + p[(long)c * pitch];
         out[out_lo + t] = s;
     }
-}
-
-// device memory of one call, allocated and released in stream order
-struct StreamBuffers {
-    static constexpr int CAP = 8;
-    hipStream_t st;
-    void* p[CAP];
-    int n = 0;
-    explicit StreamBuffers(hipStream_t s) : st(s) {}
-    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
-    template <class X> hipError_t alloc(X** out, size_t bytes) {
-        if (n >= CAP) return hipErrorOutOfMemory;
-        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-#define KDEW_TRY(call)                                                                     \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
-            return PW_E_HIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-int kdew_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_kde_wsums: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
 }
 
 // slabs [first, last) share one launch pair and one workspace of `parts` doubles
@@ -268,20 +220,22 @@ int kdew_sums(pw_context* ctx, const pw_kdew_job* jobs, int64_t n_jobs, const do
     for (long k = 0; k < (long)n_jobs; ++k) {
         const pw_kdew_job& J = jobs[k];
         if (J.n_samples < 0 || J.n_points < 0 || J.sample_first < 0 || J.point_first < 0 || J.weight_first < 0 || J.out_first < 0)
-            return kdew_bad("negative range", k);
-        if (J.n_replicas < 1) return kdew_bad("no replica (n_replicas < 1)", k);
+            return stat_bad("pw_kde_wsums", k, "negative range");
+        if (J.n_replicas < 1) return stat_bad("pw_kde_wsums", k, "no replica (n_replicas < 1)");
         if (J.n_samples > KDEW_LIMIT || J.n_points > KDEW_LIMIT || J.n_replicas > KDEW_LIMIT ||
             (J.n_points && J.n_replicas > KDEW_LIMIT / J.n_points) || (J.n_samples && J.n_replicas > KDEW_LIMIT / J.n_samples))
-            return kdew_bad("too large", k);
-        if ((J.n_samples && (!samples || !weights)) || (J.n_points && (!points || !sums))) return kdew_bad("null array", k);
-        if (!kde_finite(J.inv_bandwidth) || !(J.inv_bandwidth > 0.0)) return kdew_bad("bandwidth not positive and finite", k);
+            return stat_bad("pw_kde_wsums", k, "too large");
+        if ((J.n_samples && (!samples || !weights)) || (J.n_points && (!points || !sums)))
+            return stat_bad("pw_kde_wsums", k, "null array");
+        if (!pw_finite(J.inv_bandwidth) || !(J.inv_bandwidth > 0.0))
+            return stat_bad("pw_kde_wsums", k, "bandwidth not positive and finite");
         for (long i = 0; i < (long)J.n_samples; ++i)
-            if (!kde_finite(samples[J.sample_first + i])) return kdew_bad("a sample is NaN or infinite", k);
+            if (!pw_finite(samples[J.sample_first + i])) return stat_bad("pw_kde_wsums", k, "a sample is NaN or infinite");
         for (long i = 0; i < (long)J.n_points; ++i)
-            if (!kde_finite(points[J.point_first + i])) return kdew_bad("a point is NaN or infinite", k);
+            if (!pw_finite(points[J.point_first + i])) return stat_bad("pw_kde_wsums", k, "a point is NaN or infinite");
         for (long i = 0; i < (long)(J.n_samples * J.n_replicas); ++i) {
             const double w = weights[J.weight_first + i];
-            if (!kde_finite(w) || !(w >= 0.0)) return kdew_bad("a weight is negative, NaN or infinite", k);
+            if (!pw_finite(w) || !(w >= 0.0)) return stat_bad("pw_kde_wsums", k, "a weight is negative, NaN or infinite");
         }
         if (J.n_points == 0) continue;
         if (J.n_samples) {
@@ -304,40 +258,37 @@ int kdew_sums(pw_context* ctx, const pw_kdew_job* jobs, int64_t n_jobs, const do
     std::vector<KdewLaunch> launches;
     kdew_plan(jobs, (long)n_jobs, s_lo, p_lo, w_lo, (long)(workspace_bytes ? workspace_bytes : KDEW_WORKSPACE_BYTES) / 8, slabs,
               places, launches);
-    if (slabs.size() > 0x7ffffff0) return kdew_bad("too large", (long)n_jobs - 1);
+    if (slabs.size() > 0x7ffffff0) return stat_bad("pw_kde_wsums", (long)n_jobs - 1, "too large");
     long parts = 0;
     for (const KdewLaunch& L : launches) parts = L.parts > parts ? L.parts : parts;
     const long outs = launches.back().out_hi;
 
     DeviceScope dev_scope_;
-    KDEW_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        KDEW_TRY(hipEventCreate(&ev.a));
-        KDEW_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     std::vector<double> host_out((size_t)outs);
     {
         StreamBuffers buf(st);
         KdewSlabDev* d_slabs;
         double *d_x, *d_g, *d_w, *d_part, *d_out;
-        KDEW_TRY(buf.alloc(&d_slabs, sizeof(KdewSlabDev) * slabs.size()));
-        KDEW_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
-        KDEW_TRY(buf.alloc(&d_g, sizeof(double) * (size_t)(p_hi - p_lo)));
-        KDEW_TRY(buf.alloc(&d_w, sizeof(double) * (size_t)(w_hi - w_lo)));
-        KDEW_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
-        KDEW_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
-        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
-        KDEW_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
-        KDEW_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
-        KDEW_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(KdewSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(buf.alloc(&d_slabs, sizeof(KdewSlabDev) * slabs.size()));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
+        STAT_TRY(buf.alloc(&d_g, sizeof(double) * (size_t)(p_hi - p_lo)));
+        STAT_TRY(buf.alloc(&d_w, sizeof(double) * (size_t)(w_hi - w_lo)));
+        STAT_TRY(buf.alloc(&d_part, sizeof(double) * (size_t)parts));
+        STAT_TRY(buf.alloc(&d_out, sizeof(double) * (size_t)outs));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_stat_host.hpp)
+        STAT_TRY(poison_scratch(poison, d_part, sizeof(double) * (size_t)parts, st));
+        STAT_TRY(poison_scratch(poison, d_out, sizeof(double) * (size_t)outs, st));
+        STAT_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(KdewSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
         if (s_hi > s_lo) {
-            KDEW_TRY(hipMemcpyAsync(d_x, samples + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
-            KDEW_TRY(hipMemcpyAsync(d_w, weights + w_lo, sizeof(double) * (size_t)(w_hi - w_lo), hipMemcpyHostToDevice, st));
+            STAT_TRY(hipMemcpyAsync(d_x, samples + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
+            STAT_TRY(hipMemcpyAsync(d_w, weights + w_lo, sizeof(double) * (size_t)(w_hi - w_lo), hipMemcpyHostToDevice, st));
         }
-        KDEW_TRY(hipMemcpyAsync(d_g, points + p_lo, sizeof(double) * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
-        if (kernel_ms) KDEW_TRY(hipEventRecord(ev.a, st));
+        STAT_TRY(hipMemcpyAsync(d_g, points + p_lo, sizeof(double) * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one may take the workspace over; a slab without
         // samples has no item and its sums are the reduce kernel's zeros; both kernels stride over their work)
         for (const KdewLaunch& L : launches) {
@@ -346,18 +297,18 @@ int kdew_sums(pw_context* ctx, const pw_kdew_job* jobs, int64_t n_jobs, const do
                 const long grid1 = L.items < (1l << 20) ? L.items : (1l << 20);
                 hipLaunchKernelGGL(pw_kdew_partial_kernel, dim3((unsigned)grid1), dim3(KDE_WAVE), 0, st, d_slabs + L.first, count,
                                    L.items, d_x, d_g, d_w, d_part);
-                KDEW_TRY(hipGetLastError());
+                STAT_TRY(hipGetLastError());
             }
             const long blocks2 = (L.out_hi - L.out_lo + 255) / 256;
             hipLaunchKernelGGL(pw_kdew_reduce_kernel, dim3((unsigned)(blocks2 < 65536 ? blocks2 : 65536)), dim3(256), 0, st,
                                d_slabs + L.first, count, L.out_lo, L.out_hi - L.out_lo, d_part, d_out);
-            KDEW_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
         }
-        if (kernel_ms) KDEW_TRY(hipEventRecord(ev.b, st));
-        KDEW_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs, hipMemcpyDeviceToHost, st));
+        STAT_TRY(ev.stop(st));
+        STAT_TRY(hipMemcpyAsync(host_out.data(), d_out, sizeof(double) * (size_t)outs, hipMemcpyDeviceToHost, st));
     }
-    KDEW_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) KDEW_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     for (size_t q = 0; q < slabs.size(); ++q) {                   // a slab's [nb][m] block into the job's [R][n_points]
         const KdewSlabDev& D = slabs[q];
         const pw_kdew_job& J = jobs[places[q].job];

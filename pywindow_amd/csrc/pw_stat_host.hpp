@@ -1,0 +1,95 @@
+// pw_stat_host.hpp -- what the translation units of the statistical entries (pw_kde.hip, pw_kdew.hip, pw_corr.hip,
+// pw_dft.hip, pw_gate.hip, pw_trans.hip, pw_superpose.hip, pw_cluster.hip) share on the host side of a call: device
+// memory and events of one call, the two ways an entry reports a failure, the search of a work item's slab and the
+// poison switch.  Not for pw_hostpath.cpp: this is HIP.
+#pragma once
+#include <stdio.h>
+
+#include <atomic>
+
+#include "../../include/pywindow_amd.h"
+#include "pw_host.hpp"
+
+extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip (512 bytes, thread local)
+extern "C" int pw_context_device(pw_context* ctx);
+
+namespace pw {
+
+// Test hook (pw_kde.hip: pw_internal_poison_scratch): while the flag is set, the statistical entries (pw_kde_sums,
+// pw_kde2_sums, pw_kde_wsums, pw_corr_sums, pw_dft_sums, pw_gate_counts, pw_trans_counts, pw_superpose, pw_cluster_gromos) fill their workspace and their
+// compact device result with bytes 0xFF -- a NaN as a double, garbage as a gate summary or a bit mask -- before their first kernel,
+// so that a read of device memory the call never wrote shows in the result.  Off at start; an entry reads the flag
+// once a call, and the host path (device -1) never does.
+inline std::atomic<int> g_poison_scratch{0};
+inline bool scratch_poisoned() { return g_poison_scratch.load(std::memory_order_relaxed) != 0; }
+inline hipError_t poison_scratch(bool on, void* p, size_t bytes, hipStream_t st) {
+    return on && bytes ? hipMemsetAsync(p, 0xFF, bytes, st) : hipSuccess;
+}
+
+// (what follows has internal linkage, as when every file had a copy of its own: it adds nothing to the library's symbols)
+namespace {
+
+// device memory of one call, allocated and released in stream order
+struct StreamBuffers {
+    static constexpr int CAP = 8;
+    hipStream_t st;
+    void* p[CAP];
+    int n = 0;
+    explicit StreamBuffers(hipStream_t s) : st(s) {}
+    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
+    template <class X> hipError_t alloc(X** out, size_t bytes) {
+        if (n >= CAP) return hipErrorOutOfMemory;
+        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
+        if (e == hipSuccess) p[n++] = *out;
+        return e;
+    }
+};
+
+// the time of a call's kernels by HIP events on its stream, for the measurement hooks; ms null (every entry of the
+// header): no event is made and every step is hipSuccess
+struct Events {
+    float* ms;
+    hipEvent_t a = nullptr, b = nullptr;
+    explicit Events(float* kernel_ms) : ms(kernel_ms) {}
+    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    hipError_t create() {
+        if (!ms) return hipSuccess;
+        const hipError_t e = hipEventCreate(&a);
+        return e != hipSuccess ? e : hipEventCreate(&b);
+    }
+    hipError_t start(hipStream_t st) { return ms ? hipEventRecord(a, st) : hipSuccess; }
+    hipError_t stop(hipStream_t st) { return ms ? hipEventRecord(b, st) : hipSuccess; }
+    hipError_t read() { return ms ? hipEventElapsedTime(ms, a, b) : hipSuccess; }   // (after the stream is synchronised)
+};
+
+// a job the entry `entry` (its name in the header) refuses
+inline int stat_bad(const char* entry, long k, const char* what) {
+    snprintf(pw_internal_error_buffer(), 512, "%s: job %ld: %s", entry, k, what);
+    return PW_E_BAD_ARG;
+}
+
+#if defined(__HIPCC__)
+// the last entry k with key(k) <= v; keys ascending, key(0) == 0 <= v < key(n)
+template <class Key>
+__device__ inline int stat_find(int n, long v, Key key) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (key(mid) <= v) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+#endif
+
+}  // namespace
+
+}  // namespace pw
+
+#define STAT_TRY(call)                                                                     \
+    do {                                                                                   \
+        hipError_t e_ = (call);                                                            \
+        if (e_ != hipSuccess) {                                                            \
+            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
+            return PW_E_HIP;                                                               \
+        }                                                                                  \
+    } while (0)

@@ -22,12 +22,10 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_superpose.hpp"
-#include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 
 using namespace pw;
 
-extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip
-extern "C" int pw_context_device(pw_context* ctx);
 extern "C" int pw_hostpath_superpose(const pw_superpose_job* jobs, long n_jobs, const double* xyz, const double* weights,
                                      pw_superpose_out* out, int threads);   // pw_hostpath.cpp
 
@@ -166,41 +164,6 @@ pw_superpose_residual_kernel(const SupJobDev* __restrict__ jobs, long count, con
     }
 }
 
-// device memory of one call, allocated and released in stream order
-struct StreamBuffers {
-    static constexpr int CAP = 8;
-    hipStream_t st;
-    void* p[CAP];
-    int n = 0;
-    explicit StreamBuffers(hipStream_t s) : st(s) {}
-    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
-    template <class X> hipError_t alloc(X** out, size_t bytes) {
-        if (n >= CAP) return hipErrorOutOfMemory;
-        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-#define SUP_TRY(call)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
-            return PW_E_HIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-int sup_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_superpose: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
-}
-
 inline unsigned sup_grid(long blocks) { return (unsigned)(blocks < (1l << 16) ? (blocks < 1 ? 1 : blocks) : (1l << 16)); }
 
 // Everything is checked before anything is launched or written.  The entries a call reads are found once, by a
@@ -212,14 +175,14 @@ int sup_check(const pw_superpose_job* jobs, long n_jobs, const double* xyz, cons
     r_hi = w_hi = 0;
     for (long k = 0; k < n_jobs; ++k) {
         const pw_superpose_job& J = jobs[k];
-        if (J.n < 1) return sup_bad("n < 1", k);
-        if (J.out < 0) return sup_bad("a negative row of the result", k);
+        if (J.n < 1) return stat_bad("pw_superpose", k, "n < 1");
+        if (J.out < 0) return stat_bad("pw_superpose", k, "a negative row of the result");
         if (J.mobile_first < 0 || J.target_first < 0 || J.n > n_points || J.mobile_first > n_points - J.n ||
             J.target_first > n_points - J.n)
-            return sup_bad("points outside xyz", k);
+            return stat_bad("pw_superpose", k, "points outside xyz");
         if (J.weight_first < -1 || (J.weight_first >= 0 && J.weight_first > n_points - J.n))
-            return sup_bad("weights outside the array", k);
-        if (!xyz || (J.weight_first >= 0 && !weights)) return sup_bad("null array", k);
+            return stat_bad("pw_superpose", k, "weights outside the array");
+        if (!xyz || (J.weight_first >= 0 && !weights)) return stat_bad("pw_superpose", k, "null array");
         const long lo = (long)(J.mobile_first < J.target_first ? J.mobile_first : J.target_first);
         const long hi = (long)(J.mobile_first < J.target_first ? J.target_first : J.mobile_first) + (long)J.n;
         if (r_lo < 0 || lo < r_lo) r_lo = lo;
@@ -243,7 +206,7 @@ int sup_check(const pw_superpose_job* jobs, long n_jobs, const double* xyz, cons
         depth += used[i];
         if (depth > 0) {
             const double* p = xyz + 3 * (r_lo + i);
-            if (!sup_finite(p[0]) || !sup_finite(p[1]) || !sup_finite(p[2])) bad_row = r_lo + i;
+            if (!pw_finite(p[0]) || !pw_finite(p[1]) || !pw_finite(p[2])) bad_row = r_lo + i;
         }
     }
     // positive[i]: the weights > 0 before entry i of the span
@@ -251,7 +214,7 @@ int sup_check(const pw_superpose_job* jobs, long n_jobs, const double* xyz, cons
     for (long i = 0, depth = 0; i < w_hi - w_lo; ++i) {
         depth += usedw[i];
         const double v = weights[w_lo + i];
-        if (depth > 0 && bad_w < 0 && (!sup_finite(v) || v < 0.0)) bad_w = w_lo + i;
+        if (depth > 0 && bad_w < 0 && (!pw_finite(v) || v < 0.0)) bad_w = w_lo + i;
         positive[i + 1] = positive[i] + (v > 0.0 ? 1 : 0);
     }
     if (bad_row < 0 && bad_w < 0 && w_hi == w_lo) return PW_OK;
@@ -259,11 +222,12 @@ int sup_check(const pw_superpose_job* jobs, long n_jobs, const double* xyz, cons
         const pw_superpose_job& J = jobs[k];
         if (bad_row >= 0 && ((bad_row >= J.mobile_first && bad_row < J.mobile_first + J.n) ||
                              (bad_row >= J.target_first && bad_row < J.target_first + J.n)))
-            return sup_bad("a coordinate is not finite", k);
+            return stat_bad("pw_superpose", k, "a coordinate is not finite");
         if (J.weight_first < 0) continue;
-        if (bad_w >= J.weight_first && bad_w < J.weight_first + J.n) return sup_bad("a weight is negative or not finite", k);
+        if (bad_w >= J.weight_first && bad_w < J.weight_first + J.n)
+            return stat_bad("pw_superpose", k, "a weight is negative or not finite");
         if (bad_row < 0 && bad_w < 0 && positive[J.weight_first + J.n - w_lo] == positive[J.weight_first - w_lo])
-            return sup_bad("the weights sum to 0", k);
+            return stat_bad("pw_superpose", k, "the weights sum to 0");
     }
     return PW_OK;
 }
@@ -296,31 +260,28 @@ int superpose(pw_context* ctx, const pw_superpose_job* jobs, int64_t n_jobs, con
     const size_t ws_bytes = (size_t)per * SUP_JOB_WORKSPACE, out_bytes = sizeof(pw_superpose_out) * (size_t)N;
 
     DeviceScope dev_scope_;
-    SUP_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        SUP_TRY(hipEventCreate(&ev.a));
-        SUP_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     {
         StreamBuffers buf(st);
         SupJobDev* d_jobs;
         double *d_x, *d_w, *d_ws;
         pw_superpose_out* d_out;
-        SUP_TRY(buf.alloc(&d_jobs, sizeof(SupJobDev) * (size_t)N));
-        SUP_TRY(buf.alloc(&d_x, sizeof(double) * 3 * (size_t)(r_hi - r_lo)));
-        SUP_TRY(buf.alloc(&d_w, sizeof(double) * (size_t)(w_hi - w_lo)));
-        SUP_TRY(buf.alloc(&d_ws, ws_bytes));
-        SUP_TRY(buf.alloc(&d_out, out_bytes));
-        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp)
-        SUP_TRY(poison_scratch(poison, d_ws, ws_bytes, st));
-        SUP_TRY(poison_scratch(poison, d_out, out_bytes, st));
-        SUP_TRY(hipMemcpyAsync(d_jobs, dev.data(), sizeof(SupJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
-        SUP_TRY(hipMemcpyAsync(d_x, xyz + 3 * r_lo, sizeof(double) * 3 * (size_t)(r_hi - r_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(buf.alloc(&d_jobs, sizeof(SupJobDev) * (size_t)N));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double) * 3 * (size_t)(r_hi - r_lo)));
+        STAT_TRY(buf.alloc(&d_w, sizeof(double) * (size_t)(w_hi - w_lo)));
+        STAT_TRY(buf.alloc(&d_ws, ws_bytes));
+        STAT_TRY(buf.alloc(&d_out, out_bytes));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_stat_host.hpp)
+        STAT_TRY(poison_scratch(poison, d_ws, ws_bytes, st));
+        STAT_TRY(poison_scratch(poison, d_out, out_bytes, st));
+        STAT_TRY(hipMemcpyAsync(d_jobs, dev.data(), sizeof(SupJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_x, xyz + 3 * r_lo, sizeof(double) * 3 * (size_t)(r_hi - r_lo), hipMemcpyHostToDevice, st));
         if (w_hi > w_lo)
-            SUP_TRY(hipMemcpyAsync(d_w, weights + w_lo, sizeof(double) * (size_t)(w_hi - w_lo), hipMemcpyHostToDevice, st));
-        if (kernel_ms) SUP_TRY(hipEventRecord(ev.a, st));
+            STAT_TRY(hipMemcpyAsync(d_w, weights + w_lo, sizeof(double) * (size_t)(w_hi - w_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one may take the workspace over; all three kernels
         // stride over their jobs, so the launch geometry is free)
         for (long first = 0; first < N; first += per) {
@@ -328,25 +289,25 @@ int superpose(pw_context* ctx, const pw_superpose_job* jobs, int64_t n_jobs, con
             const unsigned waves = sup_grid((count + SUP_WAVES - 1) / SUP_WAVES);
             hipLaunchKernelGGL(pw_superpose_moments_kernel, dim3(waves), dim3(64 * SUP_WAVES), 0, st, d_jobs + first, count,
                                d_x, d_w, d_ws);
-            SUP_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
             hipLaunchKernelGGL(pw_superpose_solve_kernel, dim3(sup_grid((count + 63) / 64)), dim3(64), 0, st, count, d_ws);
-            SUP_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
             hipLaunchKernelGGL(pw_superpose_residual_kernel, dim3(waves), dim3(64 * SUP_WAVES), 0, st, d_jobs + first, count,
                                d_x, d_w, d_ws, d_out + first);
-            SUP_TRY(hipGetLastError());
+            STAT_TRY(hipGetLastError());
         }
-        if (kernel_ms) SUP_TRY(hipEventRecord(ev.b, st));
+        STAT_TRY(ev.stop(st));
         // (the compact result is in job order: neighbours in the caller's array come back in one copy)
         for (long k = 0; k < N;) {
             long e = k + 1;
             while (e < N && jobs[e].out == jobs[e - 1].out + 1) ++e;
-            SUP_TRY(hipMemcpyAsync(out + jobs[k].out, d_out + k, sizeof(pw_superpose_out) * (size_t)(e - k),
+            STAT_TRY(hipMemcpyAsync(out + jobs[k].out, d_out + k, sizeof(pw_superpose_out) * (size_t)(e - k),
                                    hipMemcpyDeviceToHost, st));
             k = e;
         }
     }
-    SUP_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) SUP_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     return PW_OK;
 }
 

@@ -47,12 +47,6 @@ constexpr int SUP_MOMENT_FIELDS = 16;               // M[9], centre_mobile[3], c
 constexpr int SUP_SOLVE_FIELDS = 12;                // rotation[9], lambda[2], sweeps
 constexpr long SUP_JOB_WORKSPACE = 8l * (SUP_MOMENT_FIELDS + SUP_SOLVE_FIELDS);
 
-PW_HD inline bool sup_finite(double v) {
-    union { double d; unsigned long long u; } c;
-    c.d = v;
-    return (c.u & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
 // ---- the per-atom updates of accumulator l: `w` null means weights of 1.0 -------------------------------------
 struct SupSums {                 // pass (a)
     double w, x[3], y[3];

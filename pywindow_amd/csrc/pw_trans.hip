@@ -23,12 +23,10 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_trans.hpp"
-#include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 
 using namespace pw;
 
-extern "C" char* pw_internal_error_buffer(void);   // pw_kernels.hip
-extern "C" int pw_context_device(pw_context* ctx);
 extern "C" int pw_hostpath_trans(const pw_trans_job* jobs, long n_jobs, const double* series, const double* edges,
                                  long n_states, long* counts, int threads);   // pw_hostpath.cpp
 
@@ -56,24 +54,13 @@ struct TransSlabDev {
     int n_edges;
 };
 
-// the last entry k with key(k) <= v; keys ascending, key(0) == 0 <= v < key(n)
-template <class Key>
-__device__ inline int trans_find(int n, long v, Key key) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (key(mid) <= v) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 template <int P>
 __global__ void __launch_bounds__(256)
 pw_trans_pack_kernel(const TransSlabDev* __restrict__ slabs, int n_slabs, long total, const double* __restrict__ series,
                      const double* __restrict__ edges, unsigned* __restrict__ ws) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (long it = (long)blockIdx.x * 4 + wave; it < total; it += (long)gridDim.x * 4) {
-        const int q = trans_find(n_slabs, it, [&](int i) { return slabs[i].wave_first; });
+        const int q = stat_find(n_slabs, it, [&](int i) { return slabs[i].wave_first; });
         const long lw = it - slabs[q].wave_first, t = lw * 64 + lane;
         int s = TRANS_GAP;
         if (t < slabs[q].n) s = trans_state(series[slabs[q].a_first + t], edges + slabs[q].e_first, slabs[q].n_edges);
@@ -124,7 +111,7 @@ pw_trans_count_kernel(const TransSlabDev* __restrict__ slabs, int n_slabs, long 
     const int tid = threadIdx.x;
     const int nob = (S + BI - 1) / BI;
     for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int q = trans_find(n_slabs, item, [&](int i) { return slabs[i].item_first; });
+        const int q = stat_find(n_slabs, item, [&](int i) { return slabs[i].item_first; });
         const TransSlabDev D = slabs[q];
         const long local = item - D.item_first;
         const int i0 = (int)(local % nob) * BI;                      // (origin blocks fastest, then tiles: neighbours
@@ -212,41 +199,6 @@ pw_trans_count_kernel(const TransSlabDev* __restrict__ slabs, int n_slabs, long 
     }
 }
 
-// device memory of one call, allocated and released in stream order
-struct StreamBuffers {
-    static constexpr int CAP = 8;
-    hipStream_t st;
-    void* p[CAP];
-    int n = 0;
-    explicit StreamBuffers(hipStream_t s) : st(s) {}
-    ~StreamBuffers() { for (int i = 0; i < n; ++i) if (p[i]) (void)hipFreeAsync(p[i], st); }
-    template <class X> hipError_t alloc(X** out, size_t bytes) {
-        if (n >= CAP) return hipErrorOutOfMemory;
-        hipError_t e = hipMallocAsync((void**)out, bytes ? bytes : 8, st);
-        if (e == hipSuccess) p[n++] = *out;
-        return e;
-    }
-};
-
-struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
-#define TRANS_TRY(call)                                                                    \
-    do {                                                                                   \
-        hipError_t e_ = (call);                                                            \
-        if (e_ != hipSuccess) {                                                            \
-            snprintf(pw_internal_error_buffer(), 512, "%s: %s", #call, hipGetErrorString(e_)); \
-            return PW_E_HIP;                                                               \
-        }                                                                                  \
-    } while (0)
-
-int trans_bad(const char* what, long k) {
-    snprintf(pw_internal_error_buffer(), 512, "pw_trans_counts: job %ld: %s", k, what);
-    return PW_E_BAD_ARG;
-}
-
 // slabs [first, last) share one launch (two kernels) and one workspace of `words` mask words
 struct TransLaunch {
     long first, last, waves, items, words;
@@ -326,24 +278,25 @@ int trans_counts(pw_context* ctx, const pw_trans_job* jobs, int64_t n_jobs, cons
     for (long k = 0; k < (long)n_jobs; ++k) {
         const pw_trans_job& J = jobs[k];
         if (J.n < 0 || J.n_edges < 0 || J.n_lags < 0 || J.a_first < 0 || J.e_first < 0 || J.lag_first < 0 || J.out_first < 0)
-            return trans_bad("negative range", k);
-        if (J.lag_step < 1) return trans_bad("lag_step < 1", k);
-        if (n_states < 1 || n_states > TRANS_MAX_STATES) return trans_bad("n_states outside 1 .. 16", k);
-        if (J.n_edges >= n_states) return trans_bad("n_edges >= n_states", k);
-        if (J.n > TRANS_MAX) return trans_bad("too long (n > 2^31)", k);
+            return stat_bad("pw_trans_counts", k, "negative range");
+        if (J.lag_step < 1) return stat_bad("pw_trans_counts", k, "lag_step < 1");
+        if (n_states < 1 || n_states > TRANS_MAX_STATES) return stat_bad("pw_trans_counts", k, "n_states outside 1 .. 16");
+        if (J.n_edges >= n_states) return stat_bad("pw_trans_counts", k, "n_edges >= n_states");
+        if (J.n > TRANS_MAX) return stat_bad("pw_trans_counts", k, "too long (n > 2^31)");
         if (J.n == 0 || J.n_lags == 0) continue;
         long reach;
         if (__builtin_mul_overflow((long)J.n_lags - 1, (long)J.lag_step, &reach) ||
             __builtin_add_overflow(reach, (long)J.lag_first, &reach) || reach >= TRANS_MAX_LAG)
-            return trans_bad("the largest lag exceeds 2^62", k);
-        if (!series || !counts || (J.n_edges && !edges)) return trans_bad("null array", k);
+            return stat_bad("pw_trans_counts", k, "the largest lag exceeds 2^62");
+        if (!series || !counts || (J.n_edges && !edges)) return stat_bad("pw_trans_counts", k, "null array");
         for (long i = 0; i < (long)J.n; ++i) {
             const double v = series[J.a_first + i];
-            if (!gate_finite(v) && !gate_nan(v)) return trans_bad("the series holds an infinity", k);
+            if (!pw_finite(v) && !pw_isnan_bits(v)) return stat_bad("pw_trans_counts", k, "the series holds an infinity");
         }
         for (long i = 0; i < (long)J.n_edges; ++i) {
-            if (!gate_finite(edges[J.e_first + i])) return trans_bad("an edge is a NaN or an infinity", k);
-            if (i && !(edges[J.e_first + i - 1] < edges[J.e_first + i])) return trans_bad("the edges do not increase strictly", k);
+            if (!pw_finite(edges[J.e_first + i])) return stat_bad("pw_trans_counts", k, "an edge is a NaN or an infinity");
+            if (i && !(edges[J.e_first + i - 1] < edges[J.e_first + i]))
+                return stat_bad("pw_trans_counts", k, "the edges do not increase strictly");
         }
         const long lo = (long)J.a_first, hi = lo + (long)J.n;
         if (s_lo < 0 || lo < s_lo) s_lo = lo;
@@ -366,7 +319,7 @@ int trans_counts(pw_context* ctx, const pw_trans_job* jobs, int64_t n_jobs, cons
     std::vector<TransCopy> copies;
     trans_plan(jobs, (long)n_jobs, s_lo, e_lo, (long)(workspace_bytes ? workspace_bytes : TRANS_WORKSPACE_BYTES) / 4, P, nob,
                slabs, launches, copies);
-    if (slabs.size() > 0x7ffffff0) return trans_bad("too large", (long)n_jobs - 1);
+    if (slabs.size() > 0x7ffffff0) return stat_bad("pw_trans_counts", (long)n_jobs - 1, "too large");
     long words = 0;
     for (const TransLaunch& L : launches) words = L.words > words ? L.words : words;
     const long rows = slabs.back().row_first + slabs.back().n_lags;
@@ -374,33 +327,30 @@ int trans_counts(pw_context* ctx, const pw_trans_job* jobs, int64_t n_jobs, cons
     const size_t count_bytes = row_bytes * (size_t)rows;
 
     DeviceScope dev_scope_;
-    TRANS_TRY(dev_scope_.enter(pw_context_device(ctx)));
+    STAT_TRY(dev_scope_.enter(pw_context_device(ctx)));
     hipStream_t st = (hipStream_t)pw_context_stream(ctx);
-    Events ev;
-    if (kernel_ms) {
-        TRANS_TRY(hipEventCreate(&ev.a));
-        TRANS_TRY(hipEventCreate(&ev.b));
-    }
+    Events ev(kernel_ms);
+    STAT_TRY(ev.create());
     {
         StreamBuffers buf(st);
         TransSlabDev* d_slabs;
         double *d_x, *d_e;
         unsigned* d_ws;
         long* d_counts;
-        TRANS_TRY(buf.alloc(&d_slabs, sizeof(TransSlabDev) * slabs.size()));
-        TRANS_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
-        TRANS_TRY(buf.alloc(&d_e, sizeof(double) * (size_t)(e_hi - e_lo)));
-        TRANS_TRY(buf.alloc(&d_ws, sizeof(unsigned) * (size_t)words));
-        TRANS_TRY(buf.alloc(&d_counts, count_bytes));
-        const bool poison = scratch_poisoned();                  // (test hook, pw_host.hpp; the result is zeroed below)
-        TRANS_TRY(poison_scratch(poison, d_ws, sizeof(unsigned) * (size_t)words, st));
-        TRANS_TRY(poison_scratch(poison, d_counts, count_bytes, st));
-        TRANS_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(TransSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
-        TRANS_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(buf.alloc(&d_slabs, sizeof(TransSlabDev) * slabs.size()));
+        STAT_TRY(buf.alloc(&d_x, sizeof(double) * (size_t)(s_hi - s_lo)));
+        STAT_TRY(buf.alloc(&d_e, sizeof(double) * (size_t)(e_hi - e_lo)));
+        STAT_TRY(buf.alloc(&d_ws, sizeof(unsigned) * (size_t)words));
+        STAT_TRY(buf.alloc(&d_counts, count_bytes));
+        const bool poison = scratch_poisoned();                  // (test hook, pw_stat_host.hpp; the result is zeroed below)
+        STAT_TRY(poison_scratch(poison, d_ws, sizeof(unsigned) * (size_t)words, st));
+        STAT_TRY(poison_scratch(poison, d_counts, count_bytes, st));
+        STAT_TRY(hipMemcpyAsync(d_slabs, slabs.data(), sizeof(TransSlabDev) * slabs.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
         if (e_hi > e_lo)
-            TRANS_TRY(hipMemcpyAsync(d_e, edges + e_lo, sizeof(double) * (size_t)(e_hi - e_lo), hipMemcpyHostToDevice, st));
-        if (kernel_ms) TRANS_TRY(hipEventRecord(ev.a, st));
-        TRANS_TRY(hipMemsetAsync(d_counts, 0, count_bytes, st));
+            STAT_TRY(hipMemcpyAsync(d_e, edges + e_lo, sizeof(double) * (size_t)(e_hi - e_lo), hipMemcpyHostToDevice, st));
+        STAT_TRY(ev.start(st));
+        STAT_TRY(hipMemsetAsync(d_counts, 0, count_bytes, st));
         // (launches follow one another on the stream, so the next one may take the workspace over; both kernels
         // stride over their work, so the launch geometry is free)
         for (const TransLaunch& L : launches) {
@@ -408,16 +358,16 @@ int trans_counts(pw_context* ctx, const pw_trans_job* jobs, int64_t n_jobs, cons
                            : P == 4 ? trans_launch<4, trans_block(4)>(L, d_slabs, d_x, d_e, d_ws, d_counts, S, st)
                            : P == 8 ? trans_launch<8, trans_block(8)>(L, d_slabs, d_x, d_e, d_ws, d_counts, S, st)
                                     : trans_launch<16, trans_block(16)>(L, d_slabs, d_x, d_e, d_ws, d_counts, S, st);
-            TRANS_TRY(e);
+            STAT_TRY(e);
         }
-        if (kernel_ms) TRANS_TRY(hipEventRecord(ev.b, st));
+        STAT_TRY(ev.stop(st));
         // (the compact result is in job order: neighbours in the caller's array come back in one copy)
         for (const TransCopy& c : copies)
-            TRANS_TRY(hipMemcpyAsync((char*)counts + (size_t)c.host * row_bytes, (char*)d_counts + (size_t)c.dev * row_bytes,
+            STAT_TRY(hipMemcpyAsync((char*)counts + (size_t)c.host * row_bytes, (char*)d_counts + (size_t)c.dev * row_bytes,
                                      (size_t)c.rows * row_bytes, hipMemcpyDeviceToHost, st));
     }
-    TRANS_TRY(hipStreamSynchronize(st));
-    if (kernel_ms) TRANS_TRY(hipEventElapsedTime(kernel_ms, ev.a, ev.b));
+    STAT_TRY(hipStreamSynchronize(st));
+    STAT_TRY(ev.read());
     return PW_OK;
 }
 
