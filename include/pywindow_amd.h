@@ -671,6 +671,58 @@ typedef struct pw_cluster_job {
 } pw_cluster_job;
 int pw_cluster_gromos(pw_context *ctx, const pw_cluster_job *jobs, int64_t n_jobs, const double *dist,
                       int64_t n_dist, int32_t *labels, int32_t *centres, int32_t *sizes, int64_t *n_clusters);
+/* ---- essential dynamics: column mean and scatter matrix of superposed frames, and projections on modes ---------
+ * Which collective motion of the atoms lies behind a trajectory: principal component analysis of the superposed
+ * coordinates (Amadei et al. 1993; GROMACS's covar and anaeig).  The reference has no counterpart.  Job k has the
+ * row-major matrix X = data[x_first .. + T * D) of T rows and D columns and, when transform_first >= 0, the T rows
+ * transforms[transform_first .. + T) of pw_superpose, of which only rotation, centre_mobile and centre_target are
+ * read: then D is a multiple of 3, row t is D / 3 points, and each point is taken as
+ * y = R_t (x - centre_mobile_t) + centre_target_t, applied as the rows are loaded -- the aligned coordinates never
+ * exist anywhere.  Without transforms y = x.
+ * pw_covariance writes mean[mean_first .. + D), mean_a = (sum_t y_ta) / T, and, unless s_first == -1 (the mean
+ * only), the scatter matrix S = scatter[s_first .. + D * D), row-major, BOTH triangles,
+ * S[a][b] = sum_t (y_ta - mean_a)(y_tb - mean_b).  Nothing is divided by T - 1: that is the caller's one IEEE
+ * division.  pw_project reads mean[mean_first .. + D) and the k vectors V = vectors[v_first .. + k * D), row-major,
+ * and writes P = proj[p_first .. + T * k), P[t][j] = sum_a (y_ta - mean_a) V[j][a].
+ * The result is DEFINED (pywindow_amd/csrc/pw_cov.hpp): the transform is three subtractions, one product and two
+ * fma a row of R, and one addition; the rows are cut into chunks of PW_COV_CHUNK; a column's chunk sums are
+ * sequential in t and are added in chunk order; an entry of S is the sequential fma(z_a, z_b, acc) over a chunk's
+ * rows, z = y - mean, the chunk partials added in chunk order, so S is symmetric to the bit and T = 1 gives +0
+ * everywhere; an entry of P is taken by 64 accumulators striding over the columns, folded pairwise as in
+ * pw_superpose.  No floating-point atomics and no MFMA.  The same bits on every device, launch geometry and run
+ * and on a device == -1 context (host threads), whatever else shares the call and however a job's tiles and
+ * chunks are cut into launches to keep the workspace within 256 MiB.  There is no capacity in T, nor in D up to
+ * PW_COV_MAX_D.
+ * All pointers are host memory; n_data, n_transforms, n_mean, n_scatter, n_vectors and n_proj are the entries
+ * (rows, for transforms) of the arrays; transforms may be null when no job has any, scatter when every job has
+ * s_first == -1.  Jobs may share inputs but not entries of the outputs; entries no job owns are never touched.
+ * T < 1, D < 1, D > PW_COV_MAX_D, D % 3 != 0 with transforms, k < 1, a range outside data, the transforms or the
+ * outputs, a value a job reads that is not finite, or jobs that share output entries: PW_E_BAD_ARG (pw_last_error
+ * names the job and the reason), and nothing is launched or written.  Device work is queued on the context's
+ * stream, its memory allocated and freed in stream order; the call returns when the results are in place. */
+#define PW_COV_CHUNK 256
+#define PW_COV_MAX_D 3072
+typedef struct pw_cov_job {
+    int64_t x_first;          /* X = data[x_first .. + T * D), row-major */
+    int64_t T, D;             /* rows >= 1, columns 1 .. PW_COV_MAX_D */
+    int64_t transform_first;  /* first of the T rows of transforms, or -1: none */
+    int64_t mean_first;       /* mean[mean_first .. + D) is written */
+    int64_t s_first;          /* scatter[s_first .. + D * D) is written, or -1: the mean only */
+} pw_cov_job;
+int pw_covariance(pw_context *ctx, const pw_cov_job *jobs, int64_t n_jobs, const double *data, int64_t n_data,
+                  const pw_superpose_out *transforms, int64_t n_transforms, double *mean, int64_t n_mean,
+                  double *scatter, int64_t n_scatter);
+typedef struct pw_project_job {
+    int64_t x_first;          /* X = data[x_first .. + T * D), row-major */
+    int64_t T, D;
+    int64_t transform_first;  /* first of the T rows of transforms, or -1: none */
+    int64_t mean_first;       /* mean[mean_first .. + D) is READ */
+    int64_t v_first, k;       /* V = vectors[v_first .. + k * D), k >= 1 */
+    int64_t p_first;          /* proj[p_first .. + T * k) is written */
+} pw_project_job;
+int pw_project(pw_context *ctx, const pw_project_job *jobs, int64_t n_jobs, const double *data, int64_t n_data,
+               const pw_superpose_out *transforms, int64_t n_transforms, const double *mean, int64_t n_mean,
+               const double *vectors, int64_t n_vectors, double *proj, int64_t n_proj);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

@@ -30,6 +30,7 @@ from .kinetics import Kinetics, transition_counts, transition_counts_batch  # no
 from .superposition import Superposition, rmsd_matrix, superpose, superpose_batch  # noqa: E402
 from .tracks import WindowTracks, track_windows  # noqa: E402
 from .clustering import Clusters, cluster_frames, cluster_frames_scan  # noqa: E402
+from .modes import Modes, covariance, principal_modes, project  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -81,6 +82,10 @@ __all__ = [
     "Clusters",
     "cluster_frames",
     "cluster_frames_scan",
+    "Modes",
+    "covariance",
+    "project",
+    "principal_modes",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

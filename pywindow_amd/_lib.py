@@ -242,6 +242,20 @@ CLUSTER_JOB_DTYPE = np.dtype(
 #: ``PW_CLUSTER_MAX_N``
 CLUSTER_MAX_N = 32768
 
+#: numpy mirror of ``pw_cov_job``
+COV_JOB_DTYPE = np.dtype(
+    [("x_first", np.int64), ("T", np.int64), ("D", np.int64), ("transform_first", np.int64), ("mean_first", np.int64),
+     ("s_first", np.int64)]
+)
+#: numpy mirror of ``pw_project_job``
+PROJECT_JOB_DTYPE = np.dtype(
+    [("x_first", np.int64), ("T", np.int64), ("D", np.int64), ("transform_first", np.int64), ("mean_first", np.int64),
+     ("v_first", np.int64), ("k", np.int64), ("p_first", np.int64)]
+)
+#: ``PW_COV_CHUNK``, ``PW_COV_MAX_D``
+COV_CHUNK = 256
+COV_MAX_D = 3072
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -330,6 +344,8 @@ EXPORTED_SYMBOLS = [
     "pw_trans_counts",
     "pw_superpose",
     "pw_cluster_gromos",
+    "pw_covariance",
+    "pw_project",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -453,6 +469,11 @@ def load():
     L.pw_trans_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     L.pw_superpose.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     L.pw_cluster_gromos.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp, vp]
+    i64 = ctypes.c_int64
+    L.pw_covariance.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
+    L.pw_project.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
+    L.pw_internal_covariance.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_internal_project.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -501,7 +522,7 @@ def _dptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
-# ---- what the wrappers of the statistical entries (Context.kde_sums ... Context.cluster_gromos) share ----------
+# ---- what the wrappers of the statistical entries (Context.kde_sums ... Context.project) share ----------
 
 def _span_inside(jobs, first: str, count: str, limit: int, what: str) -> None:
     """Every job's entries ``[first, first + count)`` lie inside the array ``what`` of ``limit`` entries."""
@@ -898,6 +919,64 @@ class Context:
         _stat_call("pw_cluster_gromos", self._h, jobs.ctypes.data, len(jobs), d.ctypes.data, len(d), out[0].ctypes.data,
                    out[1].ctypes.data, out[2].ctypes.data, n_clusters.ctypes.data)
         return out[0], out[1], out[2], n_clusters
+
+    def covariance(self, jobs, data, transforms=None, mean=None, scatter=None, workspace_bytes=None, kernel_ms=None):
+        """``pw_covariance``: the column mean and the scatter matrix of a batch of jobs (``COV_JOB_DTYPE`` records indexing
+        the float64 array ``data``, the ``SUPERPOSE_OUT_DTYPE`` rows ``transforms`` and the entries of the results):
+        ``(mean, scatter)``, float64, with the ``D`` entries from ``mean_first`` and the ``D * D`` from ``s_first`` of every
+        job filled in -- given, or zeros up to the furthest entry of a job; entries no job owns stay as they are.
+        ``s_first = -1``: the mean only.  ``workspace_bytes`` (the budget of the partial sums; the result may not depend
+        on it) and ``kernel_ms`` (a list that receives the kernels' time by HIP events) go through the hook
+        ``pw_internal_covariance``.  Whatever the library refuses (include/pywindow_amd.h) raises ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=COV_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+        tr = None if transforms is None else np.ascontiguousarray(transforms, dtype=SUPERPOSE_OUT_DTYPE).reshape(-1)
+
+        def result(given, size, what):
+            if given is None:
+                return np.zeros(max(size, 0))
+            if given.dtype != np.float64 or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError(f"{what}: a contiguous one-dimensional float64 array")
+            return given
+
+        wanted = jobs["s_first"] >= 0
+        mean = result(mean, int((jobs["mean_first"] + jobs["D"]).max()) if len(jobs) else 0, "mean")
+        scatter = result(scatter, int((jobs["s_first"] + jobs["D"] * jobs["D"])[wanted].max()) if wanted.any() else 0, "scatter")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), None if tr is None else tr.ctypes.data,
+                0 if tr is None else len(tr), mean.ctypes.data, len(mean), scatter.ctypes.data, len(scatter)]
+        if workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_covariance", *args)
+        else:
+            ms = ctypes.c_float(0.0)
+            _stat_call("pw_internal_covariance", *args, int(workspace_bytes or 0), ctypes.byref(ms))
+            if kernel_ms is not None:
+                kernel_ms.append(float(ms.value))
+        return mean, scatter
+
+    def project(self, jobs, data, mean, vectors, transforms=None, proj=None, kernel_ms=None):
+        """``pw_project``: the projections of the centred rows of a batch of jobs (``PROJECT_JOB_DTYPE`` records indexing
+        ``data``, ``transforms``, ``mean`` and ``vectors`` as :meth:`covariance` does) on their ``k`` vectors: ``proj``,
+        float64, with the ``T * k`` entries from ``p_first`` of every job filled in -- given, or zeros up to the furthest
+        entry of a job.  Whatever the library refuses raises ``ValueError``."""
+        jobs = np.ascontiguousarray(jobs, dtype=PROJECT_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
+        m = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
+        v = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1)
+        tr = None if transforms is None else np.ascontiguousarray(transforms, dtype=SUPERPOSE_OUT_DTYPE).reshape(-1)
+        if proj is None:
+            ok = (jobs["T"] > 0) & (jobs["k"] > 0) & (jobs["p_first"] >= 0)
+            proj = np.zeros(int((jobs["p_first"] + jobs["T"] * jobs["k"])[ok].max()) if ok.any() else 0)
+        elif proj.dtype != np.float64 or not proj.flags.c_contiguous or proj.ndim != 1:
+            raise ValueError("proj: a contiguous one-dimensional float64 array")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), None if tr is None else tr.ctypes.data,
+                0 if tr is None else len(tr), m.ctypes.data, len(m), v.ctypes.data, len(v), proj.ctypes.data, len(proj)]
+        if kernel_ms is None:
+            _stat_call("pw_project", *args)
+        else:
+            ms = ctypes.c_float(0.0)
+            _stat_call("pw_internal_project", *args, ctypes.byref(ms))
+            kernel_ms.append(float(ms.value))
+        return proj
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

@@ -18,6 +18,7 @@
 #include "pw_trans.hpp"
 #include "pw_superpose.hpp"
 #include "pw_cluster.hpp"
+#include "pw_cov.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -755,6 +756,140 @@ extern "C" int pw_hostpath_cluster(const pw_cluster_job* jobs, long n_jobs, cons
             ++found;
         }
         n_clusters[k] = found;
+    }
+    return PW_OK;
+}
+
+// pw_covariance and pw_project on the host (pw_cov.hip checks the arguments and sends device == -1 contexts here): the
+// values, chunks and orders of pw_cov.hpp.  A job's values y are computed once into a buffer of the job, rows shared
+// out among the threads; then blocks of columns take their chunk sums in order, the rows are centred in place, and
+// the blocks of COV_HOST_BLOCK x COV_HOST_BLOCK entries on or above the diagonal take their chunk partials in order
+// and are written to both triangles.  An entry's sums are its own, whatever the number of threads.
+namespace {
+constexpr long COV_HOST_BLOCK = 32;
+
+// f(piece) for piece = 0 .. pieces - 1, shared out among at most `threads` threads
+template <class F>
+void cov_share(long pieces, int threads, F f) {
+    std::atomic<long> next{0};
+    auto worker = [&]() {
+        for (;;) {
+            const long p = next.fetch_add(1);
+            if (p >= pieces) break;
+            f(p);
+        }
+    };
+    const int count = (long)threads > pieces ? (int)std::max(1l, pieces) : std::max(1, threads);
+    if (count == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < count; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+    }
+}
+
+// y[t][a] of the job's rows, or z = y - mean when mean is not null
+void cov_host_values(const double* x, const double* tr, long T, long D, const double* mean, int threads, double* y) {
+    constexpr long ROWS = 64;
+    cov_share((T + ROWS - 1) / ROWS, threads, [&](long p) {
+        for (long t = p * ROWS; t < std::min((p + 1) * ROWS, T); ++t) {
+            const double* trow = tr ? tr + t * COV_TRANSFORM_DOUBLES : nullptr;
+            for (long a = 0; a < D; ++a) {
+                const double v = cov_y(x + t * D, trow, a);
+                y[t * D + a] = mean ? v - mean[a] : v;
+            }
+        }
+    });
+}
+}  // namespace
+
+extern "C" int pw_hostpath_covariance(const pw_cov_job* jobs, long n_jobs, const double* data, const double* transforms,
+                                      double* mean, double* scatter, int threads) {
+    std::vector<double> y;
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_cov_job& J = jobs[k];
+        const long T = (long)J.T, D = (long)J.D, chunks = (T + COV_CHUNK - 1) / COV_CHUNK;
+        const double* x = data + (long)J.x_first;
+        const double* tr = J.transform_first < 0 ? nullptr : transforms + (long)J.transform_first * COV_TRANSFORM_DOUBLES;
+        double* m = mean + (long)J.mean_first;
+        y.resize((size_t)(T * D));
+        cov_host_values(x, tr, T, D, nullptr, threads, y.data());
+        const long col_blocks = (D + COV_HOST_BLOCK - 1) / COV_HOST_BLOCK;
+        cov_share(col_blocks, threads, [&](long p) {
+            const long a0 = p * COV_HOST_BLOCK, w = std::min(COV_HOST_BLOCK, D - a0);
+            double total[COV_HOST_BLOCK];
+            for (long c = 0; c < chunks; ++c) {
+                double s[COV_HOST_BLOCK];
+                for (long i = 0; i < w; ++i) s[i] = 0.0;
+                for (long t = c * COV_CHUNK; t < std::min((c + 1) * COV_CHUNK, T); ++t)
+                    for (long i = 0; i < w; ++i) s[i] = s[i] + y[t * D + a0 + i];
+                for (long i = 0; i < w; ++i) total[i] = c == 0 ? s[i] : total[i] + s[i];
+            }
+            for (long i = 0; i < w; ++i) m[a0 + i] = total[i] / (double)T;
+        });
+        if (J.s_first < 0) continue;
+        cov_share((T + 63) / 64, threads, [&](long p) {
+            for (long t = p * 64; t < std::min((p + 1) * 64, T); ++t)
+                for (long a = 0; a < D; ++a) y[t * D + a] = y[t * D + a] - m[a];
+        });
+        double* S = scatter + (long)J.s_first;
+        cov_share(col_blocks * (col_blocks + 1) / 2, threads, [&](long p) {
+            int ba, bb;
+            cov_tile_of(p, (int)col_blocks, ba, bb);
+            const long a0 = ba * COV_HOST_BLOCK, b0 = bb * COV_HOST_BLOCK;
+            const long wa = std::min(COV_HOST_BLOCK, D - a0), wb = std::min(COV_HOST_BLOCK, D - b0);
+            double s[COV_HOST_BLOCK][COV_HOST_BLOCK], part[COV_HOST_BLOCK][COV_HOST_BLOCK];
+            for (long c = 0; c < chunks; ++c) {
+                for (long i = 0; i < wa; ++i)
+                    for (long j = 0; j < wb; ++j) part[i][j] = 0.0;
+                for (long t = c * COV_CHUNK; t < std::min((c + 1) * COV_CHUNK, T); ++t) {
+                    const double* za = y.data() + t * D + a0;
+                    const double* zb = y.data() + t * D + b0;
+                    for (long i = 0; i < wa; ++i) {
+                        const double zi = za[i];
+                        for (long j = 0; j < wb; ++j) part[i][j] = pw_fma(zi, zb[j], part[i][j]);
+                    }
+                }
+                for (long i = 0; i < wa; ++i)
+                    for (long j = 0; j < wb; ++j) s[i][j] = c == 0 ? part[i][j] : s[i][j] + part[i][j];
+            }
+            for (long i = 0; i < wa; ++i)
+                for (long j = 0; j < wb; ++j) {
+                    if (a0 + i > b0 + j) continue;             // (below the diagonal of a diagonal block: the mirror writes it)
+                    S[(a0 + i) * D + b0 + j] = s[i][j];
+                    S[(b0 + j) * D + a0 + i] = s[i][j];
+                }
+        });
+    }
+    return PW_OK;
+}
+
+extern "C" int pw_hostpath_project(const pw_project_job* jobs, long n_jobs, const double* data, const double* transforms,
+                                   const double* mean, const double* vectors, double* proj, int threads) {
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_project_job& J = jobs[k];
+        const long T = (long)J.T, D = (long)J.D, K = (long)J.k;
+        const double* x = data + (long)J.x_first;
+        const double* tr = J.transform_first < 0 ? nullptr : transforms + (long)J.transform_first * COV_TRANSFORM_DOUBLES;
+        const double* m = mean + (long)J.mean_first;
+        const double* V = vectors + (long)J.v_first;
+        double* P = proj + (long)J.p_first;
+        constexpr long ROWS = 16;
+        cov_share((T + ROWS - 1) / ROWS, threads, [&](long p) {
+            std::vector<double> z((size_t)D);
+            for (long t = p * ROWS; t < std::min((p + 1) * ROWS, T); ++t) {
+                const double* trow = tr ? tr + t * COV_TRANSFORM_DOUBLES : nullptr;
+                for (long a = 0; a < D; ++a) z[a] = cov_y(x + t * D, trow, a) - m[a];
+                for (long j = 0; j < K; ++j) {
+                    double acc[COV_PROJ_ACC];
+                    for (int l = 0; l < COV_PROJ_ACC; ++l) acc[l] = 0.0;
+                    for (long a = 0; a < D; ++a) acc[a % COV_PROJ_ACC] = pw_fma(z[a], V[j * D + a], acc[a % COV_PROJ_ACC]);
+                    static_assert(COV_PROJ_ACC == SUP_ACC, "sup_fold folds SUP_ACC accumulators");
+                    P[t * K + j] = sup_fold(acc);
+                }
+            }
+        });
     }
     return PW_OK;
 }

@@ -394,6 +394,20 @@ class DLPOLY:
             return CL.cluster_frames_scan(dist, cutoff, device, frames=sel)
         return CL.cluster_frames(dist, cutoff, device, frames=sel)
 
+    def essential_dynamics(self, frames="all", weights="mass", reference="mean", n_modes: int = 10, swap_atoms=None,
+                           forcefield=None, device=None):
+        """The essential dynamics of the selected frames (``pywindow_amd.principal_modes``): the frames superposed onto
+        their mean structure (``reference="mean"``, iterated) or onto frame ``reference`` of the selection's rows, the
+        covariance of the superposed Cartesian coordinates taken on the GPU, its ``n_modes`` leading modes, the
+        projections of the frames on them, the per-atom RMSF and the cross-correlation map -- a
+        :class:`pywindow_amd.Modes` whose ``frames`` are the trajectory's frame numbers.  ``weights`` weigh the
+        superposition only; the covariance is the plain Cartesian one.  Same restrictions as :meth:`superposition`."""
+        from . import modes as MD
+
+        sel, coords = self._rigid_frames(frames, "essential_dynamics")
+        return MD.principal_modes(coords, self._weights(weights, swap_atoms, forcefield), reference, n_modes, device,
+                                  frames=sel)
+
     def track_windows(self, reference: int = 0, sites=None, min_cosine=None, weights="mass", swap_atoms=None,
                       forcefield=None, device=None):
         """Follow every window through the frames analysed so far: :meth:`superposition` of those frames onto frame
