@@ -347,11 +347,13 @@ typedef struct pw_cell_in {
     double tol;                /* bond tolerance, 0.4 */
 } pw_cell_in;
 
-#define PW_RB_NB_OVERFLOW 1     /* more than 32 atoms within max_dist of one atom */
-#define PW_RB_SEG_OVERFLOW 2    /* more than 32 bonded neighbours of one atom */
+#define PW_RB_NB_CAP 16         /* candidates kept per atom (csrc/pw_rebuild.hpp: RB_NB_CAP) */
+#define PW_RB_NB_OVERFLOW 1     /* more than PW_RB_NB_CAP candidate partners of one atom: (image, atom) pairs inside
+                                   max_dist and the pair's own bond range, with 2e-3 and rounding to spare */
+#define PW_RB_SEG_OVERFLOW 2    /* more than 2 * PW_RB_NB_CAP hits of one atom in one layer: cannot be raised */
 #define PW_RB_ATOMS_OVERFLOW 4  /* atoms_cap too small (retry with a larger one) */
 #define PW_RB_MOLS_OVERFLOW 8   /* mols_cap too small */
-#define PW_RB_THIN_CELL 16      /* a cell height is below max_dist */
+#define PW_RB_THIN_CELL 16      /* a perpendicular height of the cell, V / |b x c|, is below max_dist */
 
 typedef struct pw_cell_out {   /* caller-allocated */
     int32_t atoms_cap;         /* output atoms per frame */

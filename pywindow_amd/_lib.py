@@ -140,8 +140,23 @@ class CellOut(ctypes.Structure):
     ]
 
 
+# PW_RB_NB_CAP of the header = RB_NB_CAP of csrc/pw_rebuild.hpp (a static_assert in pw_rebuild.hip ties those two;
+# tests/test_rebuild_edges.py::test_status_text_states_the_constants ties this copy to them)
+RB_NB_CAP = 16
+RB_NB_OVERFLOW = 1
+RB_SEG_OVERFLOW = 2
 RB_ATOMS_OVERFLOW = 4
 RB_MOLS_OVERFLOW = 8
+RB_THIN_CELL = 16
+
+
+def rb_status_text(bits: int) -> str:
+    """What the PW_RB_* bits of a refused frame say (include/pywindow_amd.h)."""
+    names = ((RB_NB_OVERFLOW, f"{RB_NB_OVERFLOW} = more than {RB_NB_CAP} candidate partners of one atom"),
+             (RB_SEG_OVERFLOW, f"{RB_SEG_OVERFLOW} = more than {2 * RB_NB_CAP} hits of one atom in one layer"),
+             (RB_THIN_CELL, f"{RB_THIN_CELL} = a perpendicular height of the cell is below the bond cut-off"))
+    said = [text for bit, text in names if bits & bit]
+    return f"status bits {bits}: " + "; ".join(said or ["unknown"])
 
 #: numpy mirror of ``pw_unit_out`` (natural C alignment)
 UNIT_OUT_DTYPE = np.dtype(
@@ -1026,8 +1041,7 @@ class Context:
             raise PwHipError("pw_discrete_molecules: output does not fit (molecule larger than 2048 x the cell?)")
         bad = status & ~(RB_ATOMS_OVERFLOW | RB_MOLS_OVERFLOW)
         if bad.any():
-            raise PwHipError(f"pw_discrete_molecules: unsupported input (status bits {int(np.bitwise_or.reduce(bad))}: "
-                             "1/2 = more than 32 neighbours of one atom, 16 = cell thinner than the bond cut-off)")
+            raise PwHipError(f"pw_discrete_molecules: unsupported input ({rb_status_text(int(np.bitwise_or.reduce(bad)))})")
         return n_mol, off, src, img, xyz
 
     def resident_from_cells(self, topology, vdw, coords, lattice, lattice_inv, rebuild: bool):
@@ -1063,7 +1077,7 @@ class Context:
         if bad.any():
             if h:
                 load().pw_resident_free(self._h, h)
-            raise PwHipError(f"pw_resident_from_cells: unsupported input (status bits {int(np.bitwise_or.reduce(bad))})")
+            raise PwHipError(f"pw_resident_from_cells: unsupported input ({rb_status_text(int(np.bitwise_or.reduce(bad)))})")
         res = Resident._adopt(self, h, int(n_mol.sum())) if h else None
         return res, n_mol
 

@@ -16,6 +16,7 @@
 #include "../../include/pywindow_amd.h"
 #include "pw_host.hpp"
 #include "pw_rebuild.hpp"
+#include "pw_stat_host.hpp"
 #include "pw_team.hpp"
 
 using namespace pw;
@@ -26,9 +27,20 @@ extern "C" int pw_internal_pool(pw_context* ctx, size_t bytes, void** out);   //
 extern "C" int pw_internal_block_take(pw_context* ctx, size_t bytes, void** out, size_t* got);
 extern "C" void pw_internal_block_give(pw_context* ctx, void* p, size_t bytes);
 
+static_assert(RB_NB_CAP == PW_RB_NB_CAP, "the header states the candidate capacity");
+static_assert(RB_ST_NB_OVERFLOW == PW_RB_NB_OVERFLOW && RB_ST_SEG_OVERFLOW == PW_RB_SEG_OVERFLOW &&
+              RB_ST_ATOMS_OVERFLOW == PW_RB_ATOMS_OVERFLOW && RB_ST_MOLS_OVERFLOW == PW_RB_MOLS_OVERFLOW &&
+              RB_ST_THIN_CELL == PW_RB_THIN_CELL, "status bits of the header");
+
 namespace {
 
 constexpr int RB_WAVES = 4;
+
+// Test hook (pw_internal_rebuild_layout, below): which of the memory layouts a launch may use.  Bit 0: the visit bit
+// sets in team-shared memory (with them the one-wave walk, without them the stamp arrays and the four-barrier team
+// loop); bit 1: the scan coordinates, and the lists after them, in team-shared memory.  A cleared bit forbids; a
+// set bit leaves the choice to the sizes, as without the hook.  -1 (the start value): no restriction.
+std::atomic<int> g_layout{-1};
 
 __global__ void __launch_bounds__(RB_WAVES * 64)
 pw_rebuild_kernel(pw_cell_in in, pw_cell_out out, unsigned char* __restrict__ slabs, size_t slab_bytes,
@@ -192,16 +204,26 @@ int rebuild_on_device(pw_context* ctx, const pw_cell_in* in, int atoms_cap, int 
         RB_TRY(hipMemcpyAsync(d_inv, in->lattice_inv, sizeof(double) * 9 * F, hipMemcpyHostToDevice, st));
     }
     RB_TRY(hipMemsetAsync(d_counter, 0, sizeof(unsigned long long), st));
-    RB_TRY(hipMemsetAsync(dev->off, 0, sizeof(int) * F * (mols_cap + 1), st));
+    // the poison switch of the statistical entries (pw_stat_host.hpp) covers this launch too: the team slabs - which
+    // otherwise hold what the last call left - and every output array start as bytes 0xFF
+    const bool poison = scratch_poisoned();
+    RB_TRY(hipMemsetAsync(dev->off, poison ? 0xFF : 0, sizeof(int) * F * (mols_cap + 1), st));
+    RB_TRY(poison_scratch(poison, d_slabs, (size_t)grid * slab, st));
+    RB_TRY(poison_scratch(poison, dev->n_mol, sizeof(int) * F, st));
+    RB_TRY(poison_scratch(poison, dev->status, sizeof(int) * F, st));
+    RB_TRY(poison_scratch(poison, dev->src, sizeof(int) * F * atoms_cap, st));
+    RB_TRY(poison_scratch(poison, dev->img, (size_t)F * atoms_cap, st));
+    RB_TRY(poison_scratch(poison, dev->oxyz, sizeof(double) * 3 * F * atoms_cap, st));
     d_in.xyz = d_xyz; d_in.lattice = d_lat; d_in.lattice_inv = d_inv;
     d_in.cov = d_cov; d_in.mass = dev->mass; d_in.terminal = d_term;
     d_out.atoms_cap = atoms_cap; d_out.mols_cap = mols_cap;
     d_out.n_mol = dev->n_mol; d_out.status = dev->status; d_out.mol_offset = dev->off;
     d_out.src_atom = dev->src; d_out.src_image = (int8_t*)dev->img; d_out.xyz = dev->oxyz;
     // team-shared memory: the hit segments, and the two visit bit sets when they fit beside them
-    int with_bits = RebuildWs::fast_bytes(n, in->rebuild, true) <= 96 * 1024 ? 1 : 0;
+    const int layout = g_layout.load(std::memory_order_relaxed);
+    int with_bits = (layout & 1) && RebuildWs::fast_bytes(n, in->rebuild, true) <= 96 * 1024 ? 1 : 0;
     // ... and the single-precision coordinates of the candidate scan while two teams still fit a CU
-    int with_scan = RebuildWs::fast_bytes(n, in->rebuild, with_bits != 0, true) <= 79 * 1024 ? 1 : 0;
+    int with_scan = (layout & 2) && RebuildWs::fast_bytes(n, in->rebuild, with_bits != 0, true) <= 79 * 1024 ? 1 : 0;
     size_t lds = RebuildWs::fast_bytes(n, in->rebuild, with_bits != 0, with_scan != 0);
     {
         // the limit, not a request: set once per device (host threads may launch concurrently)
@@ -285,6 +307,11 @@ __global__ void rb_gather_kernel(long F, int atoms_cap, int mols_cap, const int*
 }
 
 }  // namespace
+
+// Test hook, not in the header (like pw_internal_poison_scratch): restrict the memory layouts of the launches that
+// follow (see g_layout), so that both device walks and all three layouts run at sizes a test can afford.  Process-wide;
+// -1 restores the automatic choice.
+extern "C" void pw_internal_rebuild_layout(int layout) { g_layout.store(layout < 0 ? -1 : (layout & 3), std::memory_order_relaxed); }
 
 extern "C" int pw_discrete_molecules(pw_context* ctx, const pw_cell_in* in, const pw_cell_out* out) {
     if (!args_ok(ctx, in) || !out || !out->n_mol || !out->status || !out->mol_offset || !out->src_atom ||

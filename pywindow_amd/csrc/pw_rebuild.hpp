@@ -42,6 +42,7 @@ constexpr int RB_LWORK = 512;      // layer width kept in team-shared memory (wi
 constexpr int RB_WF_TRUNCATED = 1;  // a neighbour candidate lay outside the 3x3x3 supercell
 constexpr int RB_WF_MARGINAL = 2;   // a distance within 1e-6 of a threshold of the bond test
 constexpr int RB_WF_REPEAT = 4;     // the same atom met in two images (or twice by value): not a finite molecule
+constexpr int RB_WF_OWN_COPY = 8;   // an atom whose copy in the central image is an item of its own (differs by value)
 constexpr int RB_CENTRAL = 13;     // image (0,0,0) in the a,b,c-nested 3x3x3 enumeration
 // a candidate entry: (image, atom), plus the outcome of the bond test when it cannot depend on the image
 // the pair is met in (see "bond tests made once")
@@ -52,11 +53,14 @@ constexpr int RB_NB_IMG_SHIFT = 24;            // entry = flags | image << 24 | 
 constexpr int RB_NB_Q_MASK = (1 << RB_NB_IMG_SHIFT) - 1;
 
 // status bits of one frame (pw_cell_out.status)
-constexpr int RB_ST_NB_OVERFLOW = 1;      // > RB_NB_CAP candidates around one atom
-constexpr int RB_ST_SEG_OVERFLOW = 2;     // > RB_SEG_CAP bonded neighbours of one atom
+constexpr int RB_ST_NB_OVERFLOW = 1;      // > RB_NB_CAP candidates around one atom: pairs that pass the single-precision screen
+constexpr int RB_ST_SEG_OVERFLOW = 2;     // > RB_SEG_CAP hits of one atom in one layer
+// An atom's list holds at most RB_NB_CAP entries and an entry gives at most two hits (as cell atom and as image atom),
+// so RB_ST_SEG_OVERFLOW cannot be raised: the bit stays in the interface, and the test stays in rb_expand.
+static_assert(2 * RB_NB_CAP <= RB_SEG_CAP, "an atom's hits of one layer fit its segment");
 constexpr int RB_ST_ATOMS_OVERFLOW = 4;   // output atom capacity exceeded
 constexpr int RB_ST_MOLS_OVERFLOW = 8;    // output molecule capacity exceeded
-constexpr int RB_ST_THIN_CELL = 16;       // a cell height is below max_dist: bonds could span two images
+constexpr int RB_ST_THIN_CELL = 16;       // a perpendicular height of the cell is below max_dist: bonds could span two images
 
 PW_HD inline int rb_atomic_add(int* p, int v) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -682,11 +686,23 @@ PW_HD inline void rebuild_frame(const RebuildFrame& fr, RebuildWs& w, const Rebu
                            pw_abs(sh.com[2]) <= 1.0;
             sh.bound[0] = centred ? -0.5 : 0.0;
             sh.bound[1] = centred ? 0.5 : 1.0;
-            // candidate lists assume a bond never spans two images
-            double h[3];
-            for (int c = 0; c < 3; ++c) h[c] = pw_abs(fr.lattice[3 * c + c]);
-            if (fr.rebuild && (h[0] < fr.max_dist || h[1] < fr.max_dist || h[2] < fr.max_dist))
-                w.status |= RB_ST_THIN_CELL;
+            // candidate lists assume a bond never spans two images: every pair of opposite faces at least max_dist
+            // apart.  That distance is the perpendicular height V / |b x c| (the diagonal lattice[c][c] overstates it
+            // in a sheared cell); V / |b x c| < max_dist is tested as V < max_dist * |b x c|, and a degenerate cell
+            // (V = 0, or not a number) is thin.
+            const double* L = fr.lattice;          // columns are the cell vectors
+            double cr[3][3];                       // b x c, c x a, a x b
+            for (int c = 0; c < 3; ++c) {
+                const int u = (c + 1) % 3, v = (c + 2) % 3;
+                cr[c][0] = L[3 + u] * L[6 + v] - L[6 + u] * L[3 + v];
+                cr[c][1] = L[6 + u] * L[v] - L[u] * L[6 + v];
+                cr[c][2] = L[u] * L[3 + v] - L[3 + u] * L[v];
+            }
+            const double vol = pw_abs(L[0] * cr[0][0] + L[3] * cr[0][1] + L[6] * cr[0][2]);
+            bool thin = !(vol > 0.0);
+            for (int c = 0; c < 3; ++c)
+                if (!(vol >= fr.max_dist * pw_sqrt(sq3(cr[c][0], cr[c][1], cr[c][2])))) thin = true;
+            if (fr.rebuild && thin) w.status |= RB_ST_THIN_CELL;
         } else {
             sh.origin[0] = sh.com[0] + 0.01; sh.origin[1] = sh.com[1] + 0.0; sh.origin[2] = sh.com[2] + 0.0;
         }
@@ -949,7 +965,10 @@ PW_HD inline void rebuild_frame(const RebuildFrame& fr, RebuildWs& w, const Rebu
         // shift is the image in which the first walk met the new start atom, the walk would retire
         // exactly the atoms it met in that image, and its centre of mass is the first one minus the
         // shift.  A walk predicted to be dropped - with 1e-6 to spare, against 1e-8 of coordinate
-        // rounding - is not made.
+        // rounding - is not made.  All of this holds only while every atom of the molecule is one list
+        // item with its copy in the central image: where the two differ by value (a coordinate on a tie
+        // of the eighth decimal) a later walk meets both, holds more atoms than the first and may well
+        // be kept, so a first walk through such an atom (RB_WF_OWN_COPY) predicts nothing.
         if (fr.rebuild) {
             if (tid == 0) {
                 int s0 = sh.start, c = WS.cage_of[s0], skip = 0;
@@ -1220,6 +1239,9 @@ PW_HD inline void rebuild_frame(const RebuildFrame& fr, RebuildWs& w, const Rebu
                     WS.cage_of[q] = mol_serial;
 #endif
                     if (old != 0) rb_atomic_or((int*)&sh.wflags, RB_WF_REPEAT);
+                    // the walk from another fragment meets this atom twice, as the cell atom and as its copy: it is
+                    // not this walk shifted
+                    if (!WS.alias[q]) rb_atomic_or((int*)&sh.wflags, RB_WF_OWN_COPY);
                     WS.cage_off[q] = (unsigned char)((ax + 1) * 9 + (ay + 1) * 3 + (az + 1));
                     int ao[3] = {ax, ay, az};
                     for (int a = 0; a < 3; ++a) {

@@ -820,6 +820,30 @@ def run_rebuild_limits(pool):
     np.savez_compressed(HERE / "rebuild_limits.npz", **arrays)
 
 
+def run_rebuild_edges(pool):
+    """The reference's discrete_molecules on the cases of tests/_rebuild_cases.py small enough for it (rebuilt where
+    the case is) -> rebuild_edges.npz: inputs, and per molecule the offsets, the source atoms and the coordinates."""
+    sys.path.insert(0, str(REPO / "tests"))
+    import _rebuild_cases as RC
+
+    todo = [c for c in RC.cases() if c["fixture"]]
+    res = dict(pool.map(rebuild_case, [(c["name"], c["system"]) for c in todo]))
+    arrays = {"names": np.array([c["name"] for c in todo])}
+    for c in todo:
+        name, out = c["name"], res[c["name"]]
+        prefix = "rebuild" if c["rebuild"] else "plain"
+        arrays[f"{name}__in_elements"] = c["system"]["elements"]
+        arrays[f"{name}__in_coordinates"] = c["system"]["coordinates"]
+        if "lattice" in c["system"]:
+            arrays[f"{name}__in_lattice"] = c["system"]["lattice"]
+        arrays[f"{name}__offset"] = out[f"{prefix}_offset"].astype(np.int32)
+        arrays[f"{name}__src"] = np.array([int(str(i).lstrip("CNOH")) for i in out[f"{prefix}_ids"]], dtype=np.int32)
+        arrays[f"{name}__xyz"] = out[f"{prefix}_xyz"]
+        assert list(out[f"{prefix}_elements"]) == list(c["system"]["elements"][arrays[f"{name}__src"]])
+        print("rebuild edges", name, c["n"], "->", len(out[f"{prefix}_offset"]) - 1, "molecules")
+    np.savez_compressed(HERE / "rebuild_edges.npz", **arrays)
+
+
 def run_rebuild(pool):
     pw = load_reference()
     cases = []
@@ -1084,7 +1108,7 @@ def run_history20():
 
 
 def main():
-    which = set(sys.argv[1:]) or {"static", "md20", "synth64", "periodic", "cc3base", "options", "rebuild", "ptraj", "optopt", "winopt", "shape", "tables", "history20", "axes", "nonporous", "cliffs", "json", "rebuild_limits"}
+    which = set(sys.argv[1:]) or {"static", "md20", "synth64", "periodic", "cc3base", "options", "rebuild", "ptraj", "optopt", "winopt", "shape", "tables", "history20", "axes", "nonporous", "cliffs", "json", "rebuild_limits", "rebuild_edges"}
     if "tables" in which:
         run_tables()
     if "history20" in which:
@@ -1124,6 +1148,8 @@ def main():
             run_rebuild(pool)
         if "rebuild_limits" in which:
             run_rebuild_limits(pool)
+        if "rebuild_edges" in which:
+            run_rebuild_edges(pool)
         if "ptraj" in which:
             run_ptraj(pool)
         if "optopt" in which:

@@ -12,7 +12,7 @@ extern "C" int hs_discrete_molecules(int n, const double* xyz, const double* lat
     size_t bytes = RebuildWs::bytes(n, rebuild, 1);
     unsigned char* base = (unsigned char*)aligned_alloc(64, (bytes + 63) & ~(size_t)63);
     if (!base) return -5;
-    memset(base, 0, bytes);
+    memset(base, 0xff, bytes);                  // ... nor on a zeroed slab: the pool hands out what the last call left
     RebuildWs* w = RebuildWs::carve(base, n, rebuild, 1);
     // with_bits: bit 0 = the visit bit sets, bit 1 = the scan coordinates in "team-shared" memory
     size_t fb = RebuildWs::fast_bytes(n, rebuild, (with_bits & 1) != 0, (with_bits & 2) != 0);
@@ -32,3 +32,9 @@ extern "C" int hs_discrete_molecules(int n, const double* xyz, const double* lat
     free(base);
     return 0;
 }
+// what tests/_rebuild_cases.py restates to tell which memory layout a launch takes
+extern "C" long hs_rebuild_fast_bytes(int n, int rebuild, int with_bits, int with_scan) {
+    return (long)RebuildWs::fast_bytes(n, rebuild, with_bits != 0, with_scan != 0);
+}
+extern "C" long hs_rebuild_shared_bytes() { return (long)sizeof(RebuildShared); }
+extern "C" long hs_rebuild_scan_bytes(int n) { return (long)RebuildWs::scan_bytes(n); }
