@@ -38,6 +38,7 @@ struct HostTeam {
     PW_HD static int bcast_i(int v, int /*src_lane*/) { return v; }
     PW_HD static int shfl_up_i(int v, int /*delta*/) { return v; }
     PW_HD static int uniform_i(int v) { return v; }
+    PW_HD static int incl_scan_i(int v) { return v; }
 };
 
 #if defined(__HIPCC__)

@@ -1308,9 +1308,10 @@ PW_NOINLINE PW_HD inline void ray_scan_multi(const Frame& F, int n, const double
 // rays from the centroid, which atoms the line meets.  An atom of radius r at distance |rel| can only be
 // met by rays inside a cone of half-angle asin(r / |rel|) about its direction -- some 1 % of the sphere --
 // and the rays of a golden spiral with a given polar angle are a contiguous index range.  So instead of
-// testing every (ray, atom) pair (P x N screens), one wave per atom walks the atom's index range, keeps
-// the rays inside the cone (one dot product each, conservative) as (ray, atom) pairs, and the exact
-// arithmetic of the reference then runs on the pairs only, one pair per lane.  A ray is stopped if any of
+// testing every (ray, atom) pair (P x N screens), the rays of the atom's index range that can lie inside the
+// cone are put to one dot product each (conservative) -- enumerated by their azimuth, a lane per piece of the
+// range (ConeLattice below), or where the cone has no window of azimuths, by one wave walking the range -- and
+// kept as (ray, atom) pairs; the exact arithmetic of the reference then runs on the pairs only, one pair per lane.  A ray is stopped if any of
 // its pairs says so and its farthest exit is the maximum over its pairs: both independent of the order in
 // which the pairs are visited, so the results are those of the dense scan, bit for bit.
 // Returns false (nothing written) when the pair list is too small or an index does not fit 16 bits.
@@ -1345,52 +1346,256 @@ struct PlanarRays {             // the average diameter's layout: x | y | z, P e
 };
 // per-atom cone data computed by one lane each (band of ray indices, threshold on dot(ray vector, rel))
 struct ConeBand { double thr; int klo, khi; };     // khi < 0: two-sided test (|dot|), khi = -khi - 1
+                                                   // klo < 0: narrowed in azimuth (ConeLattice), klo = ~klo
+
+// ---- the rays of a cone, enumerated on the spiral's lattice ------------------------------------------------
+// Ray k of the golden spiral has azimuth GOLDEN_ANGLE * k, i.e. frac(k * g) turns with g = GOLDEN_ANGLE / 2 pi, whatever
+// P is.  A cone of half-angle alpha about a direction d with rho = |d_xy| > sin(alpha) holds no pole and spans the
+// azimuths phi_d +- Delta, sin(Delta) = sin(alpha) / rho: its rays satisfy t(k) = frac(k * g - c) in [0, w) with
+// c = (phi_d - Delta) / 2 pi, w = Delta / pi.  The k with t(k) < w are a walk on a lattice: with s(q) = q g - round(q g)
+// at the Fibonacci numbers q = 1, 2, 3, 5, 8, ... (+0.382, -0.236, +0.146, -0.090, ...: alternating, |s_n| = |s_n+1| +
+// |s_n+2|) and |s_j| <= w < |s_j-1|, the two steps A, B in {q_j, q_j+1} with residues +a, -b (a, b <= w < a + b) give
+// the NEXT solution after k (three-distance theorem): k + A if t + a < w, else k + B if t - b >= 0, else k + A + B.
+// So a band of some 180 rays is ~20 candidates found by ~25 additions and compares of one lane, not three steps of a
+// whole wave.  The window is a superset (margins below), the test of a candidate is the walk's own dot test: the pairs
+// are the same set.  -DPW_NO_CONE_LATTICE compiles the walk alone (tests/test_cone_lattice.py: the same records).
+struct ConeLatticeTable {
+    static constexpr int N = 25;                   // q up to 121393 > 65536, team_ray_tests' limit on P
+    int q[N];
+    double s[N];                                   // signed: s[0] > 0 > s[1] ...
+    constexpr ConeLatticeTable() : q{}, s{} {
+        int a = 1, b = 2;
+        for (int i = 0; i < N; ++i) {
+            const double x = (double)a * (GOLDEN_ANGLE / TWO_PI);
+            q[i] = a;
+            s[i] = x - (double)(long)(x + 0.5);
+            const int c = a + b; a = b; b = c;
+        }
+    }
+};
+constexpr ConeLatticeTable CONE_LATTICE_TABLE{};
+constexpr double CONE_LATTICE_G = GOLDEN_ANGLE / TWO_PI;
+#ifndef PW_CONE_TARGET
+#define PW_CONE_TARGET 12
+#endif
+constexpr double CONE_TARGET = PW_CONE_TARGET;     // candidates a lane enumerates, about: a band is cut into pieces of that many
+// first: the number of the band's first piece; j: the step pair (q[j], q[j + 1]), < 0: not narrowed (the band walk);
+// plen: indices per piece
+struct ConeLattice { double c, w; int first; short j; unsigned short plen; };
+// The pieces of a narrowed band of `band` indices: the candidates are w * band of them (the spiral's azimuths are
+// equidistributed), so pieces of equal length hold equal work.  Returns their number, *plen their length.
+PW_HD inline int cone_pieces(int band, double w, unsigned short* plen) {
+    if (band <= 0) { *plen = 1; return 0; }
+    int want = (int)((double)band * w / CONE_TARGET) + 1;
+    if (want > band) want = band;
+    const int len = (band + want - 1) / want;
+    *plen = (unsigned short)len;
+    return (band + len - 1) / len;
+}
+// (the device's library functions or the host's: the window only has to hold the cone, and the margins are a million
+// times what the two can differ by)
+PW_HD inline double cone_asin(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return ::asin(x);
+#else
+    return __builtin_asin(x);
+#endif
+}
+PW_HD inline double cone_atan2(double y, double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return ::atan2(y, x);
+#else
+    return __builtin_atan2(y, x);
+#endif
+}
+// the window of the cone {u : R u . rel >= thr} (thr > 0) about rel = (rx, ry, rz), rr = |rel|^2
+PW_HD inline ConeLattice cone_lattice_window(double rx, double ry, double rz, double rr, double thr, double R) {
+    ConeLattice L;
+    L.c = 0.0; L.w = 1.0; L.j = -1; L.first = 0; L.plen = 1;
+    const double len = pw_sqrt(rr);
+    // cos(alpha), less what the rounding of a ray vector and of the dot product can amount to (some 1e-15)
+    const double ct = thr / (R * len) - 1e-12;
+    if (!(ct > 0.0)) return L;
+    const double sa = pw_sqrt(pw_max(1.0 - ct * ct, 0.0));
+    const double rho = pw_sqrt(rx * rx + ry * ry) / len;
+    if (!(rho > sa * (1.0 + 1e-6) + 1e-9)) return L;        // a pole inside the cone, or nearly: every azimuth
+    const double delta = cone_asin(sa / rho) * (1.0 + 1e-9) + 1e-9;
+    const double w = delta / ONE_PI;
+    int j = 0;
+    while (j + 1 < ConeLatticeTable::N && pw_abs(CONE_LATTICE_TABLE.s[j]) > w) ++j;
+    if (j + 1 >= ConeLatticeTable::N) return L;              // narrower than the table: no two steps for it
+    double c = (cone_atan2(ry, rx) - delta) / TWO_PI;
+    c -= __builtin_floor(c);
+    L.c = c < 1.0 ? c : 0.0;
+    L.w = w;
+    L.j = (short)j;
+    return L;
+}
+// the walk over the solutions of one window: k is a solution while k <= kend
+struct ConeLatticeWalk {
+    double t, w, a, b;
+    int k, A, B;
+    // the first solution at or after k0: stepping k by one turns t by g
+    PW_HD void enter(const ConeLattice& L, int k0, int kend) {
+        const int j = L.j, pos = j & 1 ? j + 1 : j, neg = j & 1 ? j : j + 1;
+        A = CONE_LATTICE_TABLE.q[pos]; a = CONE_LATTICE_TABLE.s[pos];
+        B = CONE_LATTICE_TABLE.q[neg]; b = -CONE_LATTICE_TABLE.s[neg];
+        w = L.w;
+        k = k0;
+        t = (double)k0 * CONE_LATTICE_G - L.c;
+        t -= __builtin_floor(t);
+        while (k <= kend && !(t < w)) {
+            ++k;
+            t += CONE_LATTICE_G;
+            if (t >= 1.0) t -= 1.0;
+        }
+    }
+    PW_HD void next() {
+        if (t + a < w) { k += A; t += a; }
+        else if (t - b >= 0.0) { k += B; t -= b; }
+        else { k += A + B; t = (t + a) - b; }
+    }
+};
+PW_HD inline ConeLattice* take_cone_lattice(ScratchArena& a, int n) {
+#ifdef PW_NO_CONE_LATTICE
+    (void)a; (void)n;
+    return nullptr;
+#else
+    return (ConeLattice*)a.take((size_t)(n + 1) * sizeof(ConeLattice));
+#endif
+}
+// The cone of one atom at rel = (rx, ry, rz) from the centre, radius vr; cn = |centre|.  narrow: give the band's window
+// of azimuths as well (L->j >= 0 and b->klo = ~klo where there is one).  Returns the number of pieces of a narrowed band.
+PW_HD inline __attribute__((always_inline)) int cone_of_atom(double rx, double ry, double rz, double vr, double cn, const Sphere& sp,
+                                                            bool narrow, ConeBand* out, ConeLattice* lat_out) {
+    const int P = sp.P;
+    ConeBand b;
+    ConeLattice L;
+    L.c = 0.0; L.w = 1.0; L.j = -1; L.first = 0; L.plen = 1;
+    int cnt = 0;
+    const double rr = sq3(rx, ry, rz);
+    // the line meets the sphere only if |rel|^2 - along^2 <= r^2 (with the margin of the dense screen)
+    const double a2 = rr - pw_fma(rr, 1e-12, (vr * vr) * (1.0 + 1e-12));
+    b.klo = 0; b.khi = -P;                     // every ray, two-sided
+    b.thr = -PW_INF;
+    if (a2 > 0.0) {
+        const double amin = pw_sqrt(a2) * (1.0 - 1e-9);      // smallest |along| of a meeting line
+        b.thr = amin * sp.R * (1.0 - 1e-9);
+        // an atom behind the centroid (along < 0) only counts if along > -(cen . u) >= -|cen|
+        // (utilities.py:1152-1155 compares distances from the ORIGIN): out of the question when the
+        // cone's smallest |along| exceeds |cen|
+        if (amin > cn + 1e-6) {
+            const double len = pw_sqrt(rr);
+            const double zd = rz / len, c = amin / len;
+            const double s_ = pw_sqrt(pw_max(1.0 - c * c, 0.0)) * (1.0 + 1e-9) + 1e-9;
+            const double rho = pw_sqrt(pw_max(1.0 - zd * zd, 0.0));
+            const double zhi = zd >= c ? 1.0 : pw_min(1.0, zd * c + rho * s_ + 1e-9);
+            const double zlo = zd <= -c ? -1.0 : pw_max(-1.0, zd * c - rho * s_ - 1e-9);
+            // z_k = start + k * step, step < 0
+            const double kh = (zlo - sp.start) / sp.step, kl = (zhi - sp.start) / sp.step;
+            b.klo = (int)pw_max(kl - 2.0, 0.0);
+            b.khi = (int)pw_min(kh + 3.0, (double)(P - 1));
+            // ... and of that band, the rays inside the cone's window of azimuths
+            if (narrow) {
+                L = cone_lattice_window(rx, ry, rz, rr, b.thr, sp.R);
+                if (L.j >= 0) {
+                    cnt = cone_pieces(b.khi - b.klo + 1, L.w, &L.plen);
+                    b.klo = ~b.klo;
+                }
+            }
+        }
+    }
+    *out = b;
+    *lat_out = L;
+    return cnt;
+}
 template <class T, bool FAR, class GETP>
 PW_HD inline __attribute__((always_inline)) bool team_ray_tests(const Frame& F, int n, const double* cen, const Sphere& sp,
                                                                GETP getp, ConeBand* bands, unsigned* pairs, int cap,
                                                                PW_LDS int* counts, unsigned char* flag,
-                                                               unsigned char hit_value, double* far) {
+                                                               unsigned char hit_value, double* far,
+                                                               ConeLattice* lat = nullptr) {
     const int P = sp.P;
     const int seg = cap / T::NWAVES;                 // every wave appends to a segment of its own: no atomics
     if (P >= 65536 || n >= 65536 || seg < 64) return false;
     const double c0 = cen[0], c1 = cen[1], c2 = cen[2];
     const double cn = norm3(c0, c1, c2);
-    // ---- the cones, one atom per lane ----
-    for (int i = T::tid(); i < n; i += T::SIZE) {
-        const double rx = F.x[i] - c0, ry = F.y[i] - c1, rz = F.z[i] - c2, vr = F.vdw[i];
-        const double rr = sq3(rx, ry, rz);
-        // the line meets the sphere only if |rel|^2 - along^2 <= r^2 (with the margin of the dense screen)
-        const double a2 = rr - pw_fma(rr, 1e-12, (vr * vr) * (1.0 + 1e-12));
+    // ---- the cones, one atom per lane; the pieces of the narrowed atoms' bands numbered by a prefix sum ----
+    int running = 0;                                 // pieces of the atoms before this pass (the same in every lane)
+    for (int base = 0; base < n; base += T::SIZE) {
+        const int i = base + T::tid();
         ConeBand b;
-        b.klo = 0; b.khi = -P;                     // every ray, two-sided
-        b.thr = -PW_INF;
-        if (a2 > 0.0) {
-            const double amin = pw_sqrt(a2) * (1.0 - 1e-9);      // smallest |along| of a meeting line
-            b.thr = amin * sp.R * (1.0 - 1e-9);
-            // an atom behind the centroid (along < 0) only counts if along > -(cen . u) >= -|cen|
-            // (utilities.py:1152-1155 compares distances from the ORIGIN): out of the question when the
-            // cone's smallest |along| exceeds |cen|
-            if (amin > cn + 1e-6) {
-                const double len = pw_sqrt(rr);
-                const double zd = rz / len, c = amin / len;
-                const double s_ = pw_sqrt(pw_max(1.0 - c * c, 0.0)) * (1.0 + 1e-9) + 1e-9;
-                const double rho = pw_sqrt(pw_max(1.0 - zd * zd, 0.0));
-                const double zhi = zd >= c ? 1.0 : pw_min(1.0, zd * c + rho * s_ + 1e-9);
-                const double zlo = zd <= -c ? -1.0 : pw_max(-1.0, zd * c - rho * s_ - 1e-9);
-                // z_k = start + k * step, step < 0
-                const double kh = (zlo - sp.start) / sp.step, kl = (zhi - sp.start) / sp.step;
-                b.klo = (int)pw_max(kl - 2.0, 0.0);
-                b.khi = (int)pw_min(kh + 3.0, (double)(P - 1));
-            }
+        ConeLattice L;
+        int cnt = 0;
+        if (i < n) {
+            cnt = cone_of_atom(F.x[i] - c0, F.y[i] - c1, F.z[i] - c2, F.vdw[i], cn, sp, lat != nullptr, &b, &L);
+            bands[i] = b;
         }
-        bands[i] = b;
+        if (lat != nullptr) {
+            const int inc = T::incl_scan_i(cnt);
+            if (T::lane() == T::WSIZE - 1) counts[T::wave()] = inc;
+            T::sync();
+            int at = running + inc - cnt;
+#pragma unroll
+            for (int w = 0; w < T::NWAVES; ++w) { const int cw = counts[w]; if (w < T::wave()) at += cw; running += cw; }
+            if (i < n) { L.first = at; lat[i] = L; }
+            T::sync();
+        }
     }
+    if (lat != nullptr && T::tid() == 0) lat[n].first = running;
     T::sync();
-    // ---- the rays inside each cone: one wave per atom walks the atom's index band ----
     int mine = 0;                                   // pairs appended by this wave so far (wave-uniform)
     unsigned* my = pairs + (size_t)T::wave() * seg;
+    // ---- the narrowed atoms: a lane per piece of a band enters the piece and steps from candidate to candidate ----
+    auto enumerate = [&](auto bands_, auto lat_, auto my_) __attribute__((always_inline)) {
+        for (int g0 = T::wave() * T::WSIZE; g0 < running; g0 += T::SIZE) {
+            const int g = g0 + T::lane();
+            ConeLatticeWalk wk;
+            wk.k = 1;
+            int kend = 0, i = 0;
+            double rx = 0.0, ry = 0.0, rz = 0.0, thr = 0.0;
+            if (g < running) {
+                int lo = 0, hi = n - 1;             // the atom of piece g: the first whose successor starts beyond g
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (lat_[mid + 1].first > g) hi = mid; else lo = mid + 1;
+                }
+                i = lo;
+                const ConeBand b = bands_[i];
+                const ConeLattice L = lat_[i];
+                const int k0 = ~b.klo + (g - L.first) * (int)L.plen;
+                kend = k0 + (int)L.plen - 1 < b.khi ? k0 + (int)L.plen - 1 : b.khi;
+                rx = F.x[i] - c0; ry = F.y[i] - c1; rz = F.z[i] - c2;
+                thr = b.thr;
+                wk.enter(L, k0, kend);
+            }
+            while (T::wave_any(wk.k <= kend)) {
+                const bool act = wk.k <= kend;
+                const int k = wk.k;
+                bool f = false;
+                if (act) {
+                    double px, py, pz;
+                    getp(k, &px, &py, &pz);
+                    const double dot = pw_fma(pz, rz, pw_fma(px, rx, py * ry));
+                    f = dot >= thr;
+                    wk.next();
+                }
+                const unsigned long long bal = T::ballot(f);
+                const int pos = mine + __builtin_popcountll(bal & ((1ull << T::lane()) - 1ull));
+                if (f && pos < seg) my_[pos] = ((unsigned)k << 16) | (unsigned)i;
+                mine += __builtin_popcountll(bal);
+            }
+        }
+    };
+    if (lat != nullptr) {
+        // (in team memory, the usual case: ds_* instructions, no flat access in the loop)
+        if (PW_IS_LDS(bands) && PW_IS_LDS(lat) && PW_IS_LDS(my)) enumerate(PW_AS_LDS(bands), PW_AS_LDS(lat), PW_AS_LDS(my));
+        else enumerate(bands, lat, my);
+    }
+    // ---- the rays inside each other cone: one wave per atom walks the atom's index band ----
     for (int i = T::wave(); i < n; i += T::NWAVES) {
         const ConeBand b = bands[i];
+        if (b.klo < 0) continue;
         const bool two_sided = b.khi < 0;
         const int khi = two_sided ? -b.khi - 1 : b.khi;
         const double rx = F.x[i] - c0, ry = F.y[i] - c1, rz = F.z[i] - c2;
@@ -2528,6 +2733,7 @@ PW_NOINLINE PW_HD inline void stage_average(UnitShared& sh, TeamWorkspace* ws, i
                 flag[k] = 0;
             });
             ConeBand* bands = (ConeBand*)a2.take((size_t)n * sizeof(ConeBand));
+            ConeLattice* lat = bands ? take_cone_lattice(a2, n) : nullptr;
             int cap = (int)(a2.left / 4);
             unsigned* pairs = (unsigned*)a2.take((size_t)cap * 4);
             if (cap < 4 * P) { pairs = (unsigned*)ws->knn; cap = 16 * ws->p_cap; }
@@ -2535,7 +2741,7 @@ PW_NOINLINE PW_HD inline void stage_average(UnitShared& sh, TeamWorkspace* ws, i
             // (apts comes from the arena: team memory)
             PlanarRays<decltype(PW_AS_LDS(apts))> getp{PW_AS_LDS(apts), P};
             if (bands)
-                done = team_ray_tests<T, true>(sh.S, n, cen, sp, getp, bands, pairs, cap, (PW_LDS int*)&v.red_i[0], flag, 1, vals);
+                done = team_ray_tests<T, true>(sh.S, n, cen, sp, getp, bands, pairs, cap, (PW_LDS int*)&v.red_i[0], flag, 1, vals, lat);
         }
     }
     if (done) {
@@ -3889,13 +4095,14 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
             for (int k = T::tid(); k < P; k += T::SIZE) flag[k] = 1;
             ScratchArena a2 = arena_mark;
             ConeBand* bands = (ConeBand*)a2.take((size_t)n * sizeof(ConeBand));
+            ConeLattice* lat = bands ? take_cone_lattice(a2, n) : nullptr;
             int cap = (int)(a2.left / 4);
             unsigned* pairs = (unsigned*)a2.take((size_t)cap * 4);
             if (cap < 4 * P) { pairs = (unsigned*)ws->knn; cap = 16 * ws->p_cap; }
             if (!bands && (size_t)n * sizeof(ConeBand) <= (size_t)ws->p_cap * 16) bands = (ConeBand*)(ws->knn + 8 * (size_t)ws->p_cap);
             auto run = [&](auto pts_) __attribute__((always_inline)) {
                 SpiralRays<decltype(pts_)> getp{pts_, Q4};
-                return team_ray_tests<T, false>(sh.S, n, cen, sp, getp, bands, pairs, cap, (PW_LDS int*)&v.red_i[0], flag, 0, nullptr);
+                return team_ray_tests<T, false>(sh.S, n, cen, sp, getp, bands, pairs, cap, (PW_LDS int*)&v.red_i[0], flag, 0, nullptr, lat);
             };
             if (bands) done = PW_IS_LDS(pts) ? run(PW_AS_LDS(pts)) : run(pts);
         }
