@@ -725,6 +725,65 @@ typedef struct pw_project_job {
 int pw_project(pw_context *ctx, const pw_project_job *jobs, int64_t n_jobs, const double *data, int64_t n_data,
                const pw_superpose_out *transforms, int64_t n_transforms, const double *mean, int64_t n_mean,
                const double *vectors, int64_t n_vectors, double *proj, int64_t n_proj);
+/* ---- the cavity of a cage: a voxel flood fill from the pore centre, closed at the windows ---------------------
+ * How much room is inside a cage, what shape it has and how it fluctuates: pore_volume is the volume of the largest
+ * inscribed sphere, a lower bound on the cavity; this is the region a probe's CENTRE can reach from a seed without
+ * crossing an atom or a plane laid through a window.  The reference has no counterpart.  Job k has
+ *     atoms   n >= 0 atoms xyz[atom_first .. +n) (rows of three doubles) with radii[radius_first .. +n), and a
+ *             probe radius probe >= 0;
+ *     a grid  of nx x ny x nz voxels, each 1 .. PW_CAVITY_MAX_G, with an origin o and a spacing h > 0: voxel
+ *             (i, j, l) has the centre x = o_x + (double)i * h, likewise y and z (one product, one addition, no fma);
+ *     planes  m >= 0 rows (a, b, c, d) planes[plane_first .. +m);
+ *     a seed  voxel (seed[0], seed[1], seed[2]) inside the grid.
+ * A voxel is FREE iff for every atom, with dx = x - X and so on,
+ *     (dx*dx + dy*dy) + dz*dz >= (radius + probe) * (radius + probe)           (equality is free),
+ * and OPEN iff it is free and ((a*x + b*y) + c*z) <= d holds for every plane.  The CAVITY is the 6-connected
+ * component of open voxels that contains the seed voxel; it is empty, and PW_CAV_SEED_CLOSED is set, if the seed
+ * voxel is not open.  All floating point is FP64 without contraction in exactly the association written.
+ * Row `out` of the result holds integers only: the voxels of the cavity (n_voxels) and of the open set (n_open);
+ * the cavity voxels with at least one of the six neighbours not in the cavity, a neighbour outside the grid counting
+ * as not in it (n_surface); the cavity voxels on a face of the grid (n_face: 0 means that the cavity is closed inside
+ * the box); the sums of i, j, l over the cavity (first) and of ii, jj, ll, ij, il, jl (second); the bounding box
+ * i_min, i_max, j_min, j_max, l_min, l_max, all -1 when the cavity is empty; and the flags.  Volume
+ * (n_voxels * h^3), centroid (o + h * first / n_voxels) and gyration tensor are the caller's few IEEE operations
+ * on these integers.  When mask_first >= 0 the cavity itself is written to mask[mask_first .. + ny * nz): one word
+ * a row (j, l) of the grid at index l * ny + j, bit i set iff voxel (i, j, l) is in the cavity.
+ * Every output is an integer, so the result is this definition itself on every device, launch geometry and run
+ * and on a device == -1 context (host threads), whatever else shares the call and however the jobs are cut into
+ * launches.  A row of the grid may skip an atom when dy*dy + dz*dz >= (radius + probe)^2, which is exact (rounding
+ * is monotone: pywindow_amd/csrc/pw_cavity.hpp); nothing else is culled, and there is no capacity in n or m.
+ * All pointers are host memory; n_points, n_radii, n_planes, n_out and n_mask are the rows of xyz, the entries of
+ * radii, the rows of planes, the rows of out and the words of mask (arrays no job uses may be null).  Jobs may share
+ * atoms, radii and planes but not rows of out or words of mask; entries no job owns are never touched.  A value a
+ * job reads that is not finite, h <= 0, a negative radius or probe, a dimension outside 1 .. PW_CAVITY_MAX_G, a
+ * seed outside the grid, a range outside an array or jobs that share outputs: PW_E_BAD_ARG (pw_last_error names
+ * the job and the reason), and nothing is launched or written.  Device work is queued on the context's stream,
+ * its memory allocated and freed in stream order; the call returns when the results are in place. */
+#define PW_CAVITY_MAX_G 64
+#define PW_CAV_SEED_CLOSED 1     /* the seed voxel is not open: the cavity is empty */
+typedef struct pw_cavity_job {
+    int64_t atom_first, n;      /* atoms = xyz[atom_first .. +n), n >= 0 */
+    int64_t radius_first;       /* their radii = radii[radius_first .. +n) */
+    int64_t plane_first, m;     /* planes = planes[plane_first .. +m), rows (a, b, c, d), m >= 0 */
+    int64_t mask_first;         /* mask[mask_first .. + ny*nz) is written, or -1: no mask */
+    int64_t out;                /* the job's row of the result */
+    double  origin[3];          /* the centre of voxel (0, 0, 0) */
+    double  spacing;            /* h > 0 */
+    double  probe;              /* >= 0 */
+    int32_t nx, ny, nz;         /* 1 .. PW_CAVITY_MAX_G */
+    int32_t seed[3];            /* the seed voxel (i, j, l) */
+} pw_cavity_job;
+typedef struct pw_cavity_out {
+    int64_t n_voxels, n_open, n_surface, n_face;
+    int64_t first[3];           /* sums of i, j, l over the cavity */
+    int64_t second[6];          /* sums of ii, jj, ll, ij, il, jl */
+    int32_t box[6];             /* i_min, i_max, j_min, j_max, l_min, l_max; -1 when the cavity is empty */
+    int32_t flags;              /* PW_CAV_* */
+    int32_t reserved;           /* padding to a multiple of 8 bytes; written as 0 */
+} pw_cavity_out;
+int pw_cavity(pw_context *ctx, const pw_cavity_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+              const double *radii, int64_t n_radii, const double *planes, int64_t n_planes, pw_cavity_out *out,
+              int64_t n_out, uint64_t *mask, int64_t n_mask);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

@@ -31,6 +31,7 @@ from .superposition import Superposition, rmsd_matrix, superpose, superpose_batc
 from .tracks import WindowTracks, track_windows  # noqa: E402
 from .clustering import Clusters, cluster_frames, cluster_frames_scan  # noqa: E402
 from .modes import Modes, covariance, principal_modes, project  # noqa: E402
+from .cavity import Cavity, cavity_grid, cavity_grid_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -86,6 +87,9 @@ __all__ = [
     "covariance",
     "project",
     "principal_modes",
+    "Cavity",
+    "cavity_grid",
+    "cavity_grid_batch",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

@@ -271,6 +271,23 @@ PROJECT_JOB_DTYPE = np.dtype(
 COV_CHUNK = 256
 COV_MAX_D = 3072
 
+#: numpy mirror of ``pw_cavity_job``
+CAVITY_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("radius_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
+     ("mask_first", np.int64), ("out", np.int64), ("origin", np.float64, (3,)), ("spacing", np.float64),
+     ("probe", np.float64), ("nx", np.int32), ("ny", np.int32), ("nz", np.int32), ("seed", np.int32, (3,))]
+)
+#: numpy mirror of ``pw_cavity_out``
+CAVITY_OUT_DTYPE = np.dtype(
+    [("n_voxels", np.int64), ("n_open", np.int64), ("n_surface", np.int64), ("n_face", np.int64),
+     ("first", np.int64, (3,)), ("second", np.int64, (6,)), ("box", np.int32, (6,)), ("flags", np.int32),
+     ("reserved", np.int32)]
+)
+assert CAVITY_JOB_DTYPE.itemsize == 120 and CAVITY_OUT_DTYPE.itemsize == 136
+#: ``PW_CAVITY_MAX_G``, ``PW_CAV_SEED_CLOSED``
+CAVITY_MAX_G = 64
+CAV_SEED_CLOSED = 1
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -361,6 +378,7 @@ EXPORTED_SYMBOLS = [
     "pw_cluster_gromos",
     "pw_covariance",
     "pw_project",
+    "pw_cavity",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -489,6 +507,9 @@ def load():
     L.pw_project.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
     L.pw_internal_covariance.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_internal_project.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_cavity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
+    L.pw_internal_cavity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64,
+                                     ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -992,6 +1013,48 @@ class Context:
             _stat_call("pw_internal_project", *args, ctypes.byref(ms))
             kernel_ms.append(float(ms.value))
         return proj
+
+    def cavity(self, jobs, xyz, radii, planes=None, out=None, mask=None, open_words=None, open_first=None,
+               workspace_bytes=None, kernel_ms=None):
+        """``pw_cavity``: the voxel flood fill of a batch of jobs (``CAVITY_JOB_DTYPE`` records indexing the rows of
+        ``xyz`` (rows of three), the entries of ``radii``, the rows of ``planes`` (rows of four), the rows of the result
+        and the words of ``mask``): ``(out, mask)``, ``out`` a ``CAVITY_OUT_DTYPE`` array -- ``out`` given: filled in
+        place, rows no job owns stay as they are -- and ``mask`` the uint64 words of the jobs with ``mask_first >= 0``
+        (``None`` when no job has one).  Whatever the entry refuses -- a value that is not finite, ``spacing <= 0``, a
+        negative radius or probe, a dimension outside ``1 .. CAVITY_MAX_G``, a seed outside the grid, a range outside
+        an array, jobs that share outputs --: ``ValueError`` with the library's message.  ``open_words`` /
+        ``open_first`` / ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the
+        device work by HIP events) go through the library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=CAVITY_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+        p = np.zeros((0, 4)) if planes is None else np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
+        rows = int(jobs["out"].max()) + 1 if len(jobs) else 0
+        if out is None:
+            out = np.zeros(max(rows, 0), dtype=CAVITY_OUT_DTYPE)
+        elif out.dtype != CAVITY_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
+            raise ValueError("out: a C-contiguous CAVITY_OUT_DTYPE array")
+        with_mask = jobs[jobs["mask_first"] >= 0]
+        if mask is None and len(with_mask):
+            size = (with_mask["mask_first"] + with_mask["ny"].astype(np.int64) * with_mask["nz"]).max()
+            mask = np.zeros(int(size), dtype=np.uint64)
+        elif mask is not None and (mask.dtype != np.uint64 or not mask.flags.c_contiguous or mask.ndim != 1):
+            raise ValueError("mask: a C-contiguous uint64 array")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), r.ctypes.data, len(r), p.ctypes.data, len(p),
+                out.ctypes.data, len(out), None if mask is None else mask.ctypes.data, 0 if mask is None else len(mask)]
+        if open_words is None and workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_cavity", *args)
+            return out, mask
+        w = None if open_words is None else np.ascontiguousarray(open_words, dtype=np.uint64).reshape(-1)
+        f = None if open_first is None else np.ascontiguousarray(open_first, dtype=np.int64).reshape(-1)
+        if (w is None) != (f is None) or (f is not None and len(f) != len(jobs)):
+            raise ValueError("open_words and open_first: both, with one entry of open_first per job")
+        ms = ctypes.c_float(0.0)
+        _stat_call("pw_internal_cavity", *args, None if w is None else w.ctypes.data, None if f is None else f.ctypes.data,
+                   0 if w is None else len(w), int(workspace_bytes or 0), ctypes.byref(ms))
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        return out, mask
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

@@ -19,6 +19,7 @@
 #include "pw_superpose.hpp"
 #include "pw_cluster.hpp"
 #include "pw_cov.hpp"
+#include "pw_cavity.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -891,6 +892,91 @@ extern "C" int pw_hostpath_project(const pw_project_job* jobs, long n_jobs, cons
             }
         });
     }
+    return PW_OK;
+}
+
+// pw_cavity on the host (pw_cavity.hip checks the arguments and sends device == -1 contexts here): the voxel, plane
+// and row-culling tests, the spread inside a word and the sums of a row of pw_cavity.hpp.  The threads share out the
+// jobs; a job is a plain loop over its rows -- classify, then sweeps forwards and backwards over the words until one
+// changes nothing (at most nx * ny * nz + 1 of them), then the sums of the rows.  A job's row of the result is its own.
+extern "C" int pw_hostpath_cavity(const pw_cavity_job* jobs, long n_jobs, const double* xyz, const double* radii,
+                                  const double* planes, pw_cavity_out* out, unsigned long long* mask,
+                                  const unsigned long long* open_words, const long* open_first, int threads) {
+    typedef cavity_word u64;
+    cov_share(n_jobs, threads, [&](long k) {
+        const pw_cavity_job& J = jobs[k];
+        const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
+        std::vector<u64> open((size_t)rows), fill((size_t)rows, 0);
+        if (open_first && open_first[k] >= 0) {
+            for (int r = 0; r < rows; ++r) open[r] = open_words[open_first[k] + r] & cavity_row_mask(nx);
+        } else {
+            const double* atoms = xyz + 3 * (long)J.atom_first;
+            const double* reach = radii + (long)J.radius_first;
+            const double* cuts = planes + 4 * (long)J.plane_first;
+            for (int r = 0; r < rows; ++r) {
+                const double y = cavity_coord(J.origin[1], r % ny, J.spacing), z = cavity_coord(J.origin[2], r / ny, J.spacing);
+                u64 word = cavity_row_mask(nx);
+                for (long a = 0; a < (long)J.n && word; ++a) {
+                    const double r2 = cavity_reach2(reach[a], J.probe);
+                    const double dy = y - atoms[3 * a + 1], dz = z - atoms[3 * a + 2];
+                    if (cavity_row_clear(dy, dz, r2)) continue;
+                    for (int i = 0; i < nx; ++i)
+                        if (!cavity_free(cavity_coord(J.origin[0], i, J.spacing) - atoms[3 * a], dy, dz, r2)) word &= ~(1ull << i);
+                }
+                for (long q = 0; q < (long)J.m && word; ++q)
+                    for (int i = 0; i < nx; ++i)
+                        if (!cavity_inside(cuts + 4 * q, cavity_coord(J.origin[0], i, J.spacing), y, z)) word &= ~(1ull << i);
+                open[r] = word;
+            }
+        }
+        const int seed_row = J.seed[2] * ny + J.seed[1];
+        const u64 seed_bit = 1ull << J.seed[0];
+        const bool seed_open = (open[seed_row] & seed_bit) != 0;
+        if (seed_open) fill[seed_row] = seed_bit;
+        auto word_of = [&](int j, int l) -> u64 { return j < 0 || j >= ny || l < 0 || l >= nz ? 0 : fill[l * ny + j]; };
+        auto visit = [&](int r) {
+            if (!open[r]) return false;
+            const int j = r % ny, l = r / ny;
+            const u64 g = cavity_fill_word(fill[r] | word_of(j - 1, l) | word_of(j + 1, l) | word_of(j, l - 1) | word_of(j, l + 1),
+                                           open[r]);
+            const bool changed = g != fill[r];
+            fill[r] = g;
+            return changed;
+        };
+        const long max_sweeps = (long)nx * ny * nz + 1;
+        for (long sweep = 0; seed_open && sweep < max_sweeps; ++sweep) {
+            bool changed = false;
+            for (int r = 0; r < rows; ++r) changed = visit(r) || changed;
+            for (int r = rows - 1; r >= 0; --r) changed = visit(r) || changed;
+            if (!changed) break;
+        }
+        pw_cavity_out o{};
+        u64 any = 0;
+        int box[4] = {CAVITY_MAX_G, -1, CAVITY_MAX_G, -1};
+        for (int r = 0; r < rows; ++r) {
+            o.n_open += cavity_popcount(open[r]);
+            const u64 f = fill[r];
+            if (J.mask_first >= 0) mask[(long)J.mask_first + r] = f;
+            if (!f) continue;
+            const int j = r % ny, l = r / ny;
+            CavityRow R;
+            cavity_row_sums(f, word_of(j - 1, l), word_of(j + 1, l), word_of(j, l - 1), word_of(j, l + 1), nx, ny, nz, j, l, R);
+            o.n_voxels += R.n;
+            o.n_surface += R.surface;
+            o.n_face += R.face;
+            for (int a = 0; a < 3; ++a) o.first[a] += R.first[a];
+            for (int a = 0; a < 6; ++a) o.second[a] += R.second[a];
+            any |= f;
+            box[0] = std::min(box[0], j); box[1] = std::max(box[1], j);
+            box[2] = std::min(box[2], l); box[3] = std::max(box[3], l);
+        }
+        o.box[0] = any ? __builtin_ctzll(any) : -1;
+        o.box[1] = any ? 63 - __builtin_clzll(any) : -1;
+        for (int a = 0; a < 4; ++a) o.box[2 + a] = any ? box[a] : -1;
+        o.flags = seed_open ? 0 : CAVITY_SEED_CLOSED;
+        o.reserved = 0;
+        out[(long)J.out] = o;
+    });
     return PW_OK;
 }
 

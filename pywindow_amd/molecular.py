@@ -204,6 +204,35 @@ class Molecule:
         self.properties["windows"] = {"diameters": None, "centre_of_mass": None}
         return None
 
+    def calculate_cavity(self, probe: float = 0.0, spacing: float = 0.5, close="windows", device=None) -> float:
+        """The volume of the cavity that the centre of a probe of radius ``probe`` reaches from the optimised pore
+        centre (``pywindow_amd.cavity_grid``, a voxel flood fill on the GPU), closed by planes through the windows of
+        ``calculate_windows`` (``close=None``: no planes) in a box of half the maximum diameter.  The reference has no
+        counterpart -- its ``pore_volume_opt`` is the inscribed sphere, a lower bound.  Sets ``properties["cavity"]``:
+        ``volume``, ``centre`` (the centroid), ``closed`` (``False``: the cavity reaches a face of the box, the volume
+        is that of the box's part of space), ``n_voxels``, ``spacing``, ``probe``; ``self.cavity`` keeps the
+        :class:`pywindow_amd.Cavity`.  ``full_analysis`` does not call it."""
+        from . import cavity as CV
+        from .element_data import VDW, element_ids
+        from .utilities import window_planes
+
+        if close not in ("windows", None):
+            raise ValueError('close: "windows" or None')
+        # (one launch for the stages this needs; the calls below read its record)
+        self._record(_lib.STAGE_BASIC | _lib.STAGE_OPT | (_lib.STAGE_WINDOWS if close == "windows" else 0))
+        self.calculate_pore_diameter_opt()
+        self.calculate_maximum_diameter()
+        planes = None
+        if close == "windows":
+            self.calculate_windows()
+            planes = window_planes(self.pore_opt_COM, self.properties["windows"]["centre_of_mass"])
+        self.cavity = CV.cavity_grid(self.coordinates, VDW[element_ids(self.elements)], self.pore_opt_COM, probe, spacing,
+                                     self.maximum_diameter / 2.0, planes, device=device)
+        self.properties["cavity"] = {
+            "volume": float(self.cavity.volume), "centre": self.cavity.centroid, "closed": bool(self.cavity.closed),
+            "n_voxels": int(self.cavity.n_voxels), "spacing": float(spacing), "probe": float(probe)}
+        return self.properties["cavity"]["volume"]
+
     def _align_to_principal_axes(self, align_molsys: bool = False) -> None:
         """Reference molecular.py:204-213.  There the result -- a ``(coordinates, rotations)`` tuple -- is
         assigned to ``self.coordinates[0]``, which numpy refuses; here the molecule takes the aligned

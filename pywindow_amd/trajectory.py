@@ -436,6 +436,54 @@ class DLPOLY:
         store.attach_tracks(tracks)
         return tracks
 
+    def cavity(self, probe: float = 0.0, spacing: float = 0.5, frames=None, close="windows", mask: bool = False,
+               device=None, swap_atoms=None, forcefield=None):
+        """The cavity of the cage in every frame analysed so far (``frames``: a selection of them), all frames in ONE
+        ``pw_cavity`` call on the GPU: a voxel flood fill from each record's optimised pore centre in a box of half the
+        record's maximum diameter, closed by planes through the record's windows (``close=None``: no planes) -- a
+        :class:`pywindow_amd.Cavity` whose fields are arrays over the frames and whose ``frames`` are the trajectory's
+        frame numbers.  A frame without windows gets no planes; its ``closed`` says what happened.
+        ``cavity().series("volume")`` goes into ``pywindow_amd.time_correlation``, ``lomb_scargle``,
+        ``gaussian_kde_1d``, ``gate_statistics`` and ``transition_counts``.  Non-modular, non-periodic analyses only."""
+        from . import cavity as CV
+        from .utilities import window_planes
+
+        if close not in ("windows", None):
+            raise ValueError('close: "windows" or None')
+        store = self.analysis_store
+        if store.modular or self.periodic:
+            raise ValueError("cavity: a periodic or modular trajectory is not supported yet (the atom order of a "
+                             "rebuilt molecule is not fixed across frames)")
+        unit_frames = [int(f) for f in store.unit_frame]
+        if not unit_frames:
+            raise ValueError("cavity: no frame has been analysed yet")
+        rows = list(range(len(unit_frames)))
+        if frames is not None:
+            want = self._select(frames)
+            missing = [f for f in want if f not in unit_frames]
+            if missing:
+                raise ValueError(f"cavity: frame {missing[0]} has not been analysed")
+            rows = [unit_frames.index(f) for f in want]
+        if not rows:
+            raise ValueError("cavity: no frames selected")
+        recs = store.records
+        need = _lib.STAGE_WINDOWS if close == "windows" else _lib.STAGE_OPT | _lib.STAGE_WINDOWS
+        if not store.stages & _lib.STAGE_BASIC or not store.stages & need:
+            raise ValueError("cavity: the analysis ran without the stages this needs (maximum diameter, optimised pore "
+                             f"centre{', windows' if close == 'windows' else ''}; stages = {store.stages})")
+        sel = [unit_frames[i] for i in rows]
+        coords = self._read_selected(sel, False)[0]
+        more = engine.extra_by_unit([store.extra]) if store.extra is not None and len(store.extra) else {}
+        planes = None
+        if close == "windows":
+            planes = []
+            for i in rows:
+                win = engine.windows_of(recs[i], more.get(i))
+                planes.append(None if win is None else window_planes(recs["pore_opt_c"][i], win[1]))
+        radii = VDW[element_ids(self.elements(swap_atoms, forcefield))]
+        return CV.cavity_grid_batch(coords, radii, np.asarray(recs["pore_opt_c"][rows], dtype=np.float64), probe, spacing,
+                                    np.asarray(recs["maxd"][rows], dtype=np.float64) / 2.0, planes, mask, device, frames=sel)
+
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
         selected frames, without building per-frame dicts."""

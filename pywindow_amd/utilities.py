@@ -158,6 +158,25 @@ def inertia_eigenvalues(elements, coordinates) -> np.ndarray:
     return np.array(_shape(elements, coordinates)["eigenvalues"])
 
 
+def window_planes(centre, window_centres) -> np.ndarray:
+    """One plane ``(a, b, c, d)`` per window for :func:`pywindow_amd.cavity_grid`: through the window centre ``w``,
+    normal to the line from ``centre`` to it, ``n = (w - c) / |w - c|`` and ``d = n . w``, so that ``n . x <= d`` is the
+    side of the cage's inside.  Plain numpy on the host; ``(0, 4)`` for no windows.  A window centre that coincides with
+    ``centre`` has no direction: ``ValueError``."""
+    c = np.asarray(centre, dtype=np.float64).reshape(3)
+    if window_centres is None:
+        return np.zeros((0, 4))
+    w = np.asarray(window_centres, dtype=np.float64).reshape(-1, 3)
+    if not len(w):
+        return np.zeros((0, 4))
+    v = w - c
+    length = np.sqrt((v * v).sum(axis=1))
+    if not (length > 0.0).all():
+        raise ValueError("window_planes: a window centre coincides with the centre")
+    n = v / length[:, None]
+    return np.concatenate([n, (n * w).sum(axis=1)[:, None]], axis=1)
+
+
 def circumcircle_window(coordinates, atom_set):
     """Reference utilities.py:1653-1676: ``(radius, centre)`` of the circle through three atoms,
     less a carbon van der Waals radius."""
