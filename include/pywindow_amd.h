@@ -784,6 +784,65 @@ typedef struct pw_cavity_out {
 int pw_cavity(pw_context *ctx, const pw_cavity_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
               const double *radii, int64_t n_radii, const double *planes, int64_t n_planes, pw_cavity_out *out,
               int64_t n_out, uint64_t *mask, int64_t n_mask);
+/* ---- the accessible surface of a cage, and which side of it faces the cavity ----------------------------------
+ * The solvent-accessible surface for a probe of a given radius by test points (Shrake and Rupley, 1973), every point
+ * attributed to the cavity or to the outside with the bit mask of pw_cavity.  The reference has no counterpart.
+ * The call has P = n_directions unit directions u_k = directions[3k .. 3k + 3), 1 <= P <= PW_SASA_MAX_POINTS, shared
+ * by its jobs.  Job k has
+ *     atoms   n >= 0 atoms xyz[atom_first .. +n) (rows of three doubles) with radii[radius_first .. +n), and a
+ *             probe radius probe >= 0;
+ *     a grid  when word_first >= 0: nx x ny x nz voxels, each 1 .. PW_CAVITY_MAX_G, with an origin o and a spacing
+ *             h > 0, and the ny * nz words words[word_first ..) in the layout of pw_cavity's mask -- row (j, l) at
+ *             index l * ny + j, bit i voxel i.  word_first == -1: no grid; origin, spacing and nx, ny, nz are not read.
+ * Atom i has the reach R_i = radius_i + probe and the test points p = X_i + R_i * u_k, component by component (one
+ * product, one addition, no fma).  A point is EXPOSED iff for every atom j != i (excluded by index, not by position)
+ *     (dx*dx + dy*dy) + dz*dz >= R_j * R_j,   dx = p_x - X_j,x, ...                (equality is exposed),
+ * so a second atom at the same position is another atom -- with a larger reach it buries every point --, and an atom
+ * of radius 0 with probe 0 buries nothing.  An exposed point is INSIDE iff the job has a grid and at least one of the up to eight
+ * voxels at the corners of the grid cell that holds p is set in the words: along x, i0 is the largest i in [0, nx)
+ * with o_x + (double)i * h <= p_x, or -1; the corners are i0 and i0 + 1, those outside [0, nx) dropped; y and z
+ * likewise.  Nothing is divided; bits at i >= nx are ignored; a point with no corner in the grid is not inside.
+ * All floating point is FP64 without contraction in exactly the association written.
+ * Written: exposed[count_first + i] and inside[count_first + i], the numbers of exposed and of inside points of atom
+ * i, and row `out` of the result with their sums over the job and the flags (PW_SASA_GRID: the job had a grid).
+ * Areas (4 pi R_i^2 exposed_i / P) are the caller's few IEEE operations on these integers.  Every output is an
+ * integer, so the result is this definition itself on every device, launch geometry and run and on a device == -1
+ * context (host threads).  An atom j is skipped for atom i only when the centres are further apart than the sum of
+ * the reaches by a margin that covers every rounding and the tolerance on |u| (pywindow_amd/csrc/pw_sasa.hpp has the
+ * rule and its proof; it is not applied when the job's largest magnitude is outside 2^-400 .. 2^400); there is no
+ * capacity in n.
+ * All pointers are host memory; n_points, n_radii, n_words, n_counts and n_out are the rows of xyz, the entries of
+ * radii, of words, of exposed and of inside (each n_counts) and the rows of out (arrays no job uses may be null).
+ * Jobs may share atoms, radii and words but not rows of out or entries of exposed / inside; entries no job owns are
+ * never touched.  A value a job reads that is not finite, a negative radius or probe, h <= 0, a dimension outside
+ * 1 .. PW_CAVITY_MAX_G, a range outside an array, jobs that share outputs: PW_E_BAD_ARG (pw_last_error names the
+ * job and the reason), and nothing is launched or written.  The directions are read by the jobs that have atoms: the
+ * first of them is the one named when P is outside its range, a direction is not finite or
+ * |((ux*ux + uy*uy) + uz*uz) - 1| > 1e-9 (the message names the direction too).  Device work is queued on the
+ * context's stream, its memory allocated and freed in stream order; the call returns when the results are in place. */
+#define PW_SASA_MAX_POINTS 4096
+#define PW_SASA_GRID 1            /* flags: the job had a grid */
+typedef struct pw_sasa_job {
+    int64_t atom_first, n;      /* atoms = xyz[atom_first .. +n), n >= 0 */
+    int64_t radius_first;       /* their radii = radii[radius_first .. +n) */
+    int64_t count_first;        /* exposed[count_first .. +n) and inside[count_first .. +n) are written */
+    int64_t word_first;         /* the grid's words = words[word_first .. + ny*nz), or -1: no grid */
+    int64_t out;                /* the job's row of the result */
+    double  origin[3];          /* the centre of voxel (0, 0, 0) */
+    double  spacing;            /* h > 0 */
+    double  probe;              /* >= 0 */
+    int32_t nx, ny, nz;         /* 1 .. PW_CAVITY_MAX_G */
+    int32_t reserved;           /* padding to a multiple of 8 bytes; not read */
+} pw_sasa_job;
+typedef struct pw_sasa_out {
+    int64_t exposed, inside;    /* sums of the per-atom counts */
+    int32_t flags;              /* PW_SASA_* */
+    int32_t reserved;           /* padding to a multiple of 8 bytes; written as 0 */
+} pw_sasa_out;
+int pw_sasa(pw_context *ctx, const pw_sasa_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+            const double *radii, int64_t n_radii, const double *directions, int64_t n_directions,
+            const uint64_t *words, int64_t n_words, int32_t *exposed, int32_t *inside, int64_t n_counts,
+            pw_sasa_out *out, int64_t n_out);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

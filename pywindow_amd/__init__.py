@@ -32,6 +32,7 @@ from .tracks import WindowTracks, track_windows  # noqa: E402
 from .clustering import Clusters, cluster_frames, cluster_frames_scan  # noqa: E402
 from .modes import Modes, covariance, principal_modes, project  # noqa: E402
 from .cavity import Cavity, cavity_grid, cavity_grid_batch  # noqa: E402
+from .surface import Surface, sphere_directions, surface_area, surface_area_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -90,6 +91,10 @@ __all__ = [
     "Cavity",
     "cavity_grid",
     "cavity_grid_batch",
+    "Surface",
+    "sphere_directions",
+    "surface_area",
+    "surface_area_batch",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

@@ -288,6 +288,19 @@ assert CAVITY_JOB_DTYPE.itemsize == 120 and CAVITY_OUT_DTYPE.itemsize == 136
 CAVITY_MAX_G = 64
 CAV_SEED_CLOSED = 1
 
+#: numpy mirror of ``pw_sasa_job``
+SASA_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("radius_first", np.int64), ("count_first", np.int64),
+     ("word_first", np.int64), ("out", np.int64), ("origin", np.float64, (3,)), ("spacing", np.float64),
+     ("probe", np.float64), ("nx", np.int32), ("ny", np.int32), ("nz", np.int32), ("reserved", np.int32)]
+)
+#: numpy mirror of ``pw_sasa_out``
+SASA_OUT_DTYPE = np.dtype([("exposed", np.int64), ("inside", np.int64), ("flags", np.int32), ("reserved", np.int32)])
+assert SASA_JOB_DTYPE.itemsize == 104 and SASA_OUT_DTYPE.itemsize == 24
+#: ``PW_SASA_MAX_POINTS``, ``PW_SASA_GRID``
+SASA_MAX_POINTS = 4096
+SASA_GRID = 1
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -379,6 +392,7 @@ EXPORTED_SYMBOLS = [
     "pw_covariance",
     "pw_project",
     "pw_cavity",
+    "pw_sasa",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -510,6 +524,9 @@ def load():
     L.pw_cavity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
     L.pw_internal_cavity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64,
                                      ctypes.POINTER(ctypes.c_float)]
+    L.pw_sasa.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64]
+    L.pw_internal_sasa.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i64, i64,
+                                   ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1055,6 +1072,49 @@ class Context:
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
         return out, mask
+
+    def sasa(self, jobs, xyz, radii, directions, words=None, out=None, exposed=None, inside=None, list_capacity=None,
+             lds_words=None, block_atoms=None, kernel_ms=None):
+        """``pw_sasa``: the exposed and the inside test points of every atom of a batch of jobs (``SASA_JOB_DTYPE``
+        records indexing the rows of ``xyz`` (rows of three), the entries of ``radii``, of ``words`` (uint64, a grid in
+        the layout of ``pw_cavity``'s mask; ``word_first = -1``: no grid), of ``exposed`` / ``inside`` and the rows of
+        the result) for the ``(P, 3)`` unit ``directions`` the jobs share: ``(out, exposed, inside)``, ``out`` a
+        ``SASA_OUT_DTYPE`` array and the counts int32 -- given: filled in place, entries no job owns stay as they are.
+        Whatever the entry refuses -- a value that is not finite, a negative radius or probe, ``spacing <= 0``, a
+        dimension outside ``1 .. CAVITY_MAX_G``, ``P`` outside ``1 .. SASA_MAX_POINTS``, a direction that is not a
+        unit vector to ``1e-9``, a range outside an array, jobs that share outputs --: ``ValueError`` with the
+        library's message.  ``list_capacity`` / ``lds_words`` / ``block_atoms`` / ``kernel_ms`` (a list that receives
+        the time of the kernel by HIP events) go through the library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=SASA_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+        u = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+        w = np.zeros(0, dtype=np.uint64) if words is None else np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+        if out is None:
+            out = np.zeros(int(jobs["out"].max()) + 1 if len(jobs) else 0, dtype=SASA_OUT_DTYPE)
+        elif out.dtype != SASA_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
+            raise ValueError("out: a C-contiguous SASA_OUT_DTYPE array")
+        size = int(max((jobs["count_first"] + jobs["n"]).max(), 0)) if len(jobs) else 0
+        counts = []
+        for given in (exposed, inside):
+            if given is None:
+                given = np.zeros(size, dtype=np.int32)
+            elif given.dtype != np.int32 or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError("exposed and inside: C-contiguous int32 arrays")
+            counts.append(given)
+        if len(counts[0]) != len(counts[1]):
+            raise ValueError("exposed and inside: the same length")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), r.ctypes.data, len(r), u.ctypes.data, len(u),
+                w.ctypes.data, len(w), counts[0].ctypes.data, counts[1].ctypes.data, len(counts[0]), out.ctypes.data, len(out)]
+        if list_capacity is None and lds_words is None and block_atoms is None and kernel_ms is None:
+            _stat_call("pw_sasa", *args)
+            return out, counts[0], counts[1]
+        ms = ctypes.c_float(0.0)
+        _stat_call("pw_internal_sasa", *args, int(list_capacity or 0), int(lds_words or 0), int(block_atoms or 0),
+                   ctypes.byref(ms))
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        return out, counts[0], counts[1]
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

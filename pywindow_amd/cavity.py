@@ -38,7 +38,9 @@ class Cavity:
     ``raw`` holds the integers of ``pw_cavity`` (``_lib.CAVITY_OUT_DTYPE``); ``origin`` is the centre of voxel
     ``(0, 0, 0)`` and ``shape`` the grid ``(nx, ny, nz)``; ``mask``, when asked for, is a ``(nz, ny, nx)`` bool array (a
     list of them for many frames).  ``closed``: the cavity touches no face of its box and the seed was open -- only then
-    is ``volume`` the volume of a cavity rather than of whatever part of space the box cut out."""
+    is ``volume`` the volume of a cavity rather than of whatever part of space the box cut out.  ``words``: with a
+    mask, the same voxels as ``pw_cavity`` wrote them -- ``ny * nz`` uint64 a frame, row ``(j, l)`` at ``l * ny + j``,
+    bit ``i`` voxel ``i`` -- which is what :func:`pywindow_amd.surface_area` hands on."""
 
     raw: np.ndarray
     origin: np.ndarray
@@ -47,6 +49,7 @@ class Cavity:
     probe: float
     mask: object = None
     frames: np.ndarray | None = None
+    words: object = None
 
     def _field(self, name):
         v = self.raw[name]
@@ -195,13 +198,13 @@ def cavity_grid_batch(xyz, radii, seeds, probe: float = 0.0, spacing: float = 0.
         at += len(p)
         words += g * g if mask else 0
     out, bits = engine.context(device).cavity(jobs, x.reshape(-1, 3), r, np.concatenate(cuts) if cuts else None)
-    masks = None
+    masks = words = None
     if mask:
-        masks = [unpack_mask(bits[int(j["mask_first"]):int(j["mask_first"]) + int(j["ny"]) * int(j["nz"])],
-                             int(j["nx"]), int(j["ny"]), int(j["nz"])) for j in jobs]
+        words = [bits[int(j["mask_first"]):int(j["mask_first"]) + int(j["ny"]) * int(j["nz"])] for j in jobs]
+        masks = [unpack_mask(w, int(j["nx"]), int(j["ny"]), int(j["nz"])) for w, j in zip(words, jobs)]
     shape = np.stack([jobs["nx"], jobs["ny"], jobs["nz"]], axis=1).astype(np.int64)
     return Cavity(out, jobs["origin"].copy(), shape, spacing, probe, masks,
-                  None if frames is None else np.array(frames, dtype=np.int64).reshape(-1))
+                  None if frames is None else np.array(frames, dtype=np.int64).reshape(-1), words)
 
 
 def cavity_grid(xyz, radii, seed, probe: float = 0.0, spacing: float = 0.5, half_width=None, planes=None,
@@ -224,4 +227,4 @@ def cavity_grid(xyz, radii, seed, probe: float = 0.0, spacing: float = 0.5, half
                              None if half_width is None else [half_width], None if planes is None else [planes], mask,
                              device)
     return Cavity(many.raw[0], many.origin[0], many.shape[0], many.spacing, many.probe,
-                  None if many.mask is None else many.mask[0])
+                  None if many.mask is None else many.mask[0], None, None if many.words is None else many.words[0])

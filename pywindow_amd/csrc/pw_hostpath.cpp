@@ -20,6 +20,7 @@
 #include "pw_cluster.hpp"
 #include "pw_cov.hpp"
 #include "pw_cavity.hpp"
+#include "pw_sasa.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -977,6 +978,66 @@ extern "C" int pw_hostpath_cavity(const pw_cavity_job* jobs, long n_jobs, const 
         o.reserved = 0;
         out[(long)J.out] = o;
     });
+    return PW_OK;
+}
+
+// pw_sasa on the host (pw_sasa.hip checks the arguments and sends device == -1 contexts here): the test point, the
+// exposure test, the cell search, the corner test and the culling rule of pw_sasa.hpp.  The threads share out pieces of
+// SASA_HOST_ATOMS atoms of a job; an atom collects the atoms that sasa_far does not rule out and runs its P points
+// down that list.  An atom's counts are its own; a job's row is summed from them afterwards, in order.
+extern "C" int pw_hostpath_sasa(const pw_sasa_job* jobs, long n_jobs, const double* xyz, const double* radii,
+                                const double* directions, long P, const unsigned long long* words, int* exposed,
+                                int* inside, pw_sasa_out* out, int threads) {
+    constexpr long SASA_HOST_ATOMS = 16;
+    struct Piece { long job, a_begin, a_end; };
+    std::vector<Piece> pieces;
+    std::vector<double> slack((size_t)n_jobs);
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_sasa_job& J = jobs[k];
+        slack[k] = J.n ? sasa_slack(sasa_magnitude(xyz + 3 * (long)J.atom_first, radii + (long)J.radius_first, (long)J.n, J.probe)) : -1.0;
+        for (long a = 0; a < (long)J.n; a += SASA_HOST_ATOMS) pieces.push_back({k, a, std::min(a + SASA_HOST_ATOMS, (long)J.n)});
+    }
+    cov_share((long)pieces.size(), threads, [&](long p) {
+        const Piece& piece = pieces[p];
+        const pw_sasa_job& J = jobs[piece.job];
+        const double* atoms = xyz + 3 * (long)J.atom_first;
+        const double* reach = radii + (long)J.radius_first;
+        const bool grid = J.word_first >= 0;
+        const cavity_word* w = grid ? words + (long)J.word_first : nullptr;
+        std::vector<double> near;
+        for (long i = piece.a_begin; i < piece.a_end; ++i) {
+            const double Xi = atoms[3 * i], Yi = atoms[3 * i + 1], Zi = atoms[3 * i + 2], Ri = sasa_reach(reach[i], J.probe);
+            near.clear();
+            for (long a = 0; a < (long)J.n; ++a) {
+                const double R = sasa_reach(reach[a], J.probe);
+                if (a == i || sasa_far(Xi - atoms[3 * a], Yi - atoms[3 * a + 1], Zi - atoms[3 * a + 2], Ri, R, slack[piece.job])) continue;
+                near.insert(near.end(), {atoms[3 * a], atoms[3 * a + 1], atoms[3 * a + 2], R * R});
+            }
+            int n_exposed = 0, n_inside = 0;
+            for (long k = 0; k < P; ++k) {
+                const double px = sasa_point(Xi, Ri, directions[3 * k]), py = sasa_point(Yi, Ri, directions[3 * k + 1]),
+                             pz = sasa_point(Zi, Ri, directions[3 * k + 2]);
+                bool open = true;
+                for (size_t e = 0; e < near.size() && open; e += 4)
+                    open = sasa_exposed(px - near[e], py - near[e + 1], pz - near[e + 2], near[e + 3]);
+                if (!open) continue;
+                ++n_exposed;
+                if (grid && sasa_inside(px, py, pz, J.origin, J.spacing, J.nx, J.ny, J.nz, [&](int r) { return w[r]; })) ++n_inside;
+            }
+            exposed[(long)J.count_first + i] = n_exposed;
+            inside[(long)J.count_first + i] = n_inside;
+        }
+    });
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_sasa_job& J = jobs[k];
+        pw_sasa_out o{};
+        for (long i = 0; i < (long)J.n; ++i) {
+            o.exposed += exposed[(long)J.count_first + i];
+            o.inside += inside[(long)J.count_first + i];
+        }
+        o.flags = J.word_first >= 0 ? SASA_GRID : 0;
+        out[(long)J.out] = o;
+    }
     return PW_OK;
 }
 

@@ -204,14 +204,15 @@ class Molecule:
         self.properties["windows"] = {"diameters": None, "centre_of_mass": None}
         return None
 
-    def calculate_cavity(self, probe: float = 0.0, spacing: float = 0.5, close="windows", device=None) -> float:
+    def calculate_cavity(self, probe: float = 0.0, spacing: float = 0.5, close="windows", device=None,
+                         mask: bool = False) -> float:
         """The volume of the cavity that the centre of a probe of radius ``probe`` reaches from the optimised pore
         centre (``pywindow_amd.cavity_grid``, a voxel flood fill on the GPU), closed by planes through the windows of
         ``calculate_windows`` (``close=None``: no planes) in a box of half the maximum diameter.  The reference has no
         counterpart -- its ``pore_volume_opt`` is the inscribed sphere, a lower bound.  Sets ``properties["cavity"]``:
         ``volume``, ``centre`` (the centroid), ``closed`` (``False``: the cavity reaches a face of the box, the volume
         is that of the box's part of space), ``n_voxels``, ``spacing``, ``probe``; ``self.cavity`` keeps the
-        :class:`pywindow_amd.Cavity`.  ``full_analysis`` does not call it."""
+        :class:`pywindow_amd.Cavity` (``mask=True``: with its voxels).  ``full_analysis`` does not call it."""
         from . import cavity as CV
         from .element_data import VDW, element_ids
         from .utilities import window_planes
@@ -227,11 +228,38 @@ class Molecule:
             self.calculate_windows()
             planes = window_planes(self.pore_opt_COM, self.properties["windows"]["centre_of_mass"])
         self.cavity = CV.cavity_grid(self.coordinates, VDW[element_ids(self.elements)], self.pore_opt_COM, probe, spacing,
-                                     self.maximum_diameter / 2.0, planes, device=device)
+                                     self.maximum_diameter / 2.0, planes, mask, device)
         self.properties["cavity"] = {
             "volume": float(self.cavity.volume), "centre": self.cavity.centroid, "closed": bool(self.cavity.closed),
             "n_voxels": int(self.cavity.n_voxels), "spacing": float(spacing), "probe": float(probe)}
         return self.properties["cavity"]["volume"]
+
+    def calculate_surface_area(self, probe: float = 0.0, points: int = 960, side=None, device=None) -> float:
+        """The solvent-accessible surface area for a probe of radius ``probe`` (``pywindow_amd.surface_area``, Shrake
+        and Rupley's test points on the GPU, ``points`` an atom).  ``side=None``: the whole surface, no analysis is
+        run.  ``side="internal"`` / ``"external"``: the part that faces the cavity / the outside -- the analysis and
+        ``calculate_cavity(probe)`` run first, with the same planes through the windows, and the cavity's voxels say
+        which side an exposed point is on.  The reference has no counterpart.  Sets ``properties["surface_area"]``:
+        ``area``, ``internal_area`` and ``external_area`` (``None`` without a side), ``closed`` (the cavity's),
+        ``probe``, ``points``; ``self.surface`` keeps the :class:`pywindow_amd.Surface`.  ``full_analysis`` does not
+        call it."""
+        from . import surface as SF
+        from .element_data import VDW, element_ids
+
+        if side not in (None, "internal", "external"):
+            raise ValueError('side: None, "internal" or "external"')
+        cav = None
+        if side is not None:
+            self.calculate_cavity(probe=probe, device=device, mask=True)
+            cav = self.cavity
+        self.surface = SF.surface_area(self.coordinates, VDW[element_ids(self.elements)], probe, points, cav, device)
+        sided = side is not None
+        self.properties["surface_area"] = {
+            "area": float(self.surface.area),
+            "internal_area": float(self.surface.internal_area) if sided else None,
+            "external_area": float(self.surface.external_area) if sided else None,
+            "closed": bool(self.surface.closed) if sided else None, "probe": float(probe), "points": int(points)}
+        return self.properties["surface_area"][{None: "area", "internal": "internal_area", "external": "external_area"}[side]]
 
     def _align_to_principal_axes(self, align_molsys: bool = False) -> None:
         """Reference molecular.py:204-213.  There the result -- a ``(coordinates, rotations)`` tuple -- is

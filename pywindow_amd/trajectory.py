@@ -484,6 +484,33 @@ class DLPOLY:
         return CV.cavity_grid_batch(coords, radii, np.asarray(recs["pore_opt_c"][rows], dtype=np.float64), probe, spacing,
                                     np.asarray(recs["maxd"][rows], dtype=np.float64) / 2.0, planes, mask, device, frames=sel)
 
+    def surface(self, probe: float = 0.0, points: int = 960, frames=None, cavity: bool = True, device=None,
+                swap_atoms=None, forcefield=None):
+        """The accessible surface of the cage in every frame, all frames in ONE ``pw_sasa`` call on the GPU
+        (``pywindow_amd.surface_area_batch``): a :class:`pywindow_amd.Surface` whose fields are arrays over the frames
+        and whose ``frames`` are the trajectory's frame numbers.  ``cavity=True``: the frames analysed so far
+        (``frames``: a selection of them), each with its cavity for the same probe (:meth:`cavity`, closed at the
+        windows, one ``pw_cavity`` call), so that ``internal_area`` and ``external_area`` are told apart and ``valid``
+        of a series is the cavity's ``closed``.  ``cavity=False``: the whole surface only, of any frames (``None``:
+        all) -- no analysis is needed.  ``surface().series("internal_area")`` goes into
+        ``pywindow_amd.time_correlation``, ``lomb_scargle``, ``gaussian_kde_1d``, ``gate_statistics`` and
+        ``transition_counts``.  Non-modular, non-periodic trajectories only."""
+        from . import surface as SF
+
+        cav = None
+        if cavity:
+            cav = self.cavity(probe=probe, frames=frames, mask=True, device=device, swap_atoms=swap_atoms, forcefield=forcefield)
+            sel = [int(f) for f in cav.frames]
+        else:
+            if self.periodic:
+                raise ValueError("surface: a periodic trajectory is not supported yet (its molecules are not rebuilt here)")
+            sel = self._select("all" if frames is None else frames)
+        if not sel:
+            raise ValueError("surface: no frames selected")
+        coords = self._read_selected(sel, False)[0]
+        radii = VDW[element_ids(self.elements(swap_atoms, forcefield))]
+        return SF.surface_area_batch(coords, radii, probe, points, cav, device, frames=sel)
+
     def analysis_records(self, frames="all", swap_atoms=None, forcefield=None, device=None) -> np.ndarray:
         """Columnar results: the structured record array (``_lib.UNIT_OUT_DTYPE``) for the
         selected frames, without building per-frame dicts."""
