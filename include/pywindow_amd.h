@@ -843,6 +843,70 @@ int pw_sasa(pw_context *ctx, const pw_sasa_job *jobs, int64_t n_jobs, const doub
             const double *radii, int64_t n_radii, const double *directions, int64_t n_directions,
             const uint64_t *words, int64_t n_words, int32_t *exposed, int32_t *inside, int64_t n_counts,
             pw_sasa_out *out, int64_t n_out);
+/* ---- pore sizes: the probe-swept cavity for a ladder of probes ---------------------------------------------------
+ * The room a guest of radius p can actually fill (the probe-occupiable volume: the reach of the probe's centre
+ * dilated by the probe sphere; Ongari et al., Langmuir 2017) and the geometric pore size distribution (for every
+ * point of the void the largest sphere that contains it, fits between the atoms and can be brought there from the
+ * pore centre; Gelb and Gubbins 1999), whose cumulative form at radius p is that volume.  The reference has no
+ * counterpart.  Job k has the atoms, radii, planes, grid (nx, ny, nz in 1 .. PW_CAVITY_MAX_G, origin o, spacing
+ * h > 0) and seed voxel of a pw_cavity job, and L = n_levels probe radii probes[probe_first .. +L),
+ * 1 <= L <= PW_PORES_MAX_LEVELS, each finite and >= 0, strictly ascending: p_0 < p_1 < ... < p_{L-1}.  Per level l:
+ *     reach_l   the cavity of pw_cavity for the probe p_l -- the same voxel centres, (radius + p_l)^2, free and open
+ *               tests in the same association, the 6-connected fill from the seed voxel; it is empty, and
+ *               PW_CAV_SEED_CLOSED is in the level's flags, if the seed voxel is not open at that level;
+ *     K_l       the largest integer k in [0, PW_PORES_MAX_K2] with (double)k * (h * h) <= p_l * p_l, each product
+ *               rounded once (the left side is monotone in k: a bisection, nothing is divided);
+ *     swept_l   the voxels v of the grid for which some c in reach_l has
+ *               (v_i-c_i)^2 + (v_j-c_j)^2 + (v_l-c_l)^2 <= K_l in integers.  Voxels outside the grid do not exist:
+ *               nothing wraps and nothing reaches bits >= nx.
+ * domain = reach_0, and for v in domain cover(v) is the largest l with v in swept_l, or none.  Integers only are
+ * written.  Row level_first + l of levels: n_reach and n_face (pw_cavity's n_voxels and n_face for p_l),
+ * n_swept = |swept_l & domain|, n_largest = #{v in domain : cover(v) = l}, k2 = K_l and the flags.  Row `out` of
+ * out: n_domain, n_none = #{v in domain without a cover} and n_levels, with n_domain = n_none + sum_l n_largest_l.
+ * (A ball holds its centre whatever K is, so swept_0 holds reach_0: n_swept_0 = n_domain and n_none = 0 under this
+ * definition.)  When mask_first >= 0 the words of swept_l & domain go to mask[mask_first + l * ny * nz ..), level
+ * after level, each in the layout of pw_cavity's mask.  Volumes are the caller's count * h^3.  The resolution in p
+ * is the grid's: a probe below h has K = 0 and sweeps nothing beyond its centres, and the raw n_swept need not be
+ * monotone in p on a grid -- the reverse cumulative sum of n_largest is.
+ * Every output is an integer and the sweep has no floating point (pywindow_amd/csrc/pw_pores.hpp), so the result is
+ * this definition itself on every device, launch geometry and run and on a device == -1 context (host threads).
+ * All pointers are host memory; n_points, n_radii, n_planes, n_probes, n_levels, n_out and n_mask are the rows of
+ * xyz, the entries of radii, the rows of planes, the entries of probes, the rows of levels and of out and the words of
+ * mask (arrays no job uses may be null).  Jobs may share atoms, radii, planes and probes but not rows of out, rows
+ * of levels or words of mask; entries no job owns are never touched.  What pw_cavity refuses, L outside its range,
+ * a probe that is not finite or negative, probes not strictly ascending, a range outside an array or jobs that
+ * share outputs: PW_E_BAD_ARG (pw_last_error names the job and the reason), and nothing is launched or written.
+ * Device work is queued on the context's stream, its memory allocated and freed in stream order; the call returns
+ * when the results are in place. */
+#define PW_PORES_MAX_LEVELS 64
+#define PW_PORES_MAX_K2 11907     /* 3 * 63 * 63: the squared distance of opposite corners of a 64^3 grid */
+typedef struct pw_pores_job {
+    int64_t atom_first, n;          /* atoms = xyz[atom_first .. +n), n >= 0 */
+    int64_t radius_first;           /* their radii = radii[radius_first .. +n) */
+    int64_t plane_first, m;         /* planes = planes[plane_first .. +m), rows (a, b, c, d), m >= 0 */
+    int64_t probe_first, n_levels;  /* the ladder = probes[probe_first .. +n_levels) */
+    int64_t level_first;            /* levels[level_first .. +n_levels) is written */
+    int64_t mask_first;             /* mask[mask_first .. + n_levels*ny*nz) is written, or -1: no mask */
+    int64_t out;                    /* the job's row of out */
+    double  origin[3];              /* the centre of voxel (0, 0, 0) */
+    double  spacing;                /* h > 0 */
+    int32_t nx, ny, nz;             /* 1 .. PW_CAVITY_MAX_G */
+    int32_t seed[3];                /* the seed voxel (i, j, l) */
+} pw_pores_job;
+typedef struct pw_pores_level {
+    int64_t n_reach, n_face;        /* pw_cavity's n_voxels and n_face for this probe */
+    int64_t n_swept;                /* |swept_l & domain| */
+    int64_t n_largest;              /* #{v in domain : cover(v) = l} */
+    int32_t k2;                     /* K_l */
+    int32_t flags;                  /* PW_CAV_SEED_CLOSED */
+} pw_pores_level;
+typedef struct pw_pores_out {
+    int64_t n_domain, n_none, n_levels;
+} pw_pores_out;
+int pw_pore_sizes(pw_context *ctx, const pw_pores_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+                  const double *radii, int64_t n_radii, const double *planes, int64_t n_planes, const double *probes,
+                  int64_t n_probes, pw_pores_level *levels, int64_t n_levels, pw_pores_out *out, int64_t n_out,
+                  uint64_t *mask, int64_t n_mask);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

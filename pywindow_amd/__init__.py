@@ -33,6 +33,7 @@ from .clustering import Clusters, cluster_frames, cluster_frames_scan  # noqa: E
 from .modes import Modes, covariance, principal_modes, project  # noqa: E402
 from .cavity import Cavity, cavity_grid, cavity_grid_batch  # noqa: E402
 from .surface import Surface, sphere_directions, surface_area, surface_area_batch  # noqa: E402
+from .pores import PoreSizes, pore_size_distribution, pore_size_distribution_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -95,6 +96,9 @@ __all__ = [
     "sphere_directions",
     "surface_area",
     "surface_area_batch",
+    "PoreSizes",
+    "pore_size_distribution",
+    "pore_size_distribution_batch",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

@@ -301,6 +301,22 @@ assert SASA_JOB_DTYPE.itemsize == 104 and SASA_OUT_DTYPE.itemsize == 24
 SASA_MAX_POINTS = 4096
 SASA_GRID = 1
 
+#: numpy mirror of ``pw_pores_job``
+PORES_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("radius_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
+     ("probe_first", np.int64), ("n_levels", np.int64), ("level_first", np.int64), ("mask_first", np.int64),
+     ("out", np.int64), ("origin", np.float64, (3,)), ("spacing", np.float64), ("nx", np.int32), ("ny", np.int32),
+     ("nz", np.int32), ("seed", np.int32, (3,))]
+)
+#: numpy mirrors of ``pw_pores_level`` and ``pw_pores_out``
+PORES_LEVEL_DTYPE = np.dtype([("n_reach", np.int64), ("n_face", np.int64), ("n_swept", np.int64), ("n_largest", np.int64),
+                              ("k2", np.int32), ("flags", np.int32)])
+PORES_OUT_DTYPE = np.dtype([("n_domain", np.int64), ("n_none", np.int64), ("n_levels", np.int64)])
+assert PORES_JOB_DTYPE.itemsize == 136 and PORES_LEVEL_DTYPE.itemsize == 40 and PORES_OUT_DTYPE.itemsize == 24
+#: ``PW_PORES_MAX_LEVELS``, ``PW_PORES_MAX_K2``
+PORES_MAX_LEVELS = 64
+PORES_MAX_K2 = 3 * 63 * 63
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -393,6 +409,7 @@ EXPORTED_SYMBOLS = [
     "pw_project",
     "pw_cavity",
     "pw_sasa",
+    "pw_pore_sizes",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -527,6 +544,9 @@ def load():
     L.pw_sasa.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64]
     L.pw_internal_sasa.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i64, i64,
                                    ctypes.POINTER(ctypes.c_float)]
+    L.pw_pore_sizes.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
+    L.pw_internal_pore_sizes.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp,
+                                         i64, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1115,6 +1135,57 @@ class Context:
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
         return out, counts[0], counts[1]
+
+    def pore_sizes(self, jobs, xyz, radii, probes, planes=None, levels=None, out=None, mask=None, open_words=None,
+                   open_first=None, workspace_bytes=None, kernel_ms=None):
+        """``pw_pore_sizes``: the probe-swept cavity of a batch of jobs for their ladders of probes
+        (``PORES_JOB_DTYPE`` records indexing the rows of ``xyz`` (rows of three), the entries of ``radii`` and of
+        ``probes``, the rows of ``planes`` (rows of four), the rows of the two results and the words of ``mask``):
+        ``(levels, out, mask)``, ``levels`` a ``PORES_LEVEL_DTYPE`` array with ``n_levels`` rows a job from its
+        ``level_first``, ``out`` a ``PORES_OUT_DTYPE`` array -- given: filled in place, rows no job owns stay as they
+        are -- and ``mask`` the uint64 words of the jobs with ``mask_first >= 0``, ``n_levels * ny * nz`` a job, level
+        after level (``None`` when no job has one).  Whatever the entry refuses -- what ``pw_cavity`` refuses,
+        ``n_levels`` outside ``1 .. PORES_MAX_LEVELS``, a probe that is not finite or negative, probes that do not
+        ascend strictly, a range outside an array, jobs that share outputs --: ``ValueError`` with the library's
+        message.  ``open_words`` / ``open_first`` (ready-made open words, ``n_levels * ny * nz`` a job) /
+        ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the device work by HIP events) go through
+        the library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=PORES_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(probes, dtype=np.float64).reshape(-1)
+        p = np.zeros((0, 4)) if planes is None else np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
+        if out is None:
+            out = np.zeros(max(int(jobs["out"].max()) + 1, 0) if len(jobs) else 0, dtype=PORES_OUT_DTYPE)
+        elif out.dtype != PORES_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
+            raise ValueError("out: a C-contiguous PORES_OUT_DTYPE array")
+        if levels is None:
+            levels = np.zeros(max(int((jobs["level_first"] + jobs["n_levels"]).max()), 0) if len(jobs) else 0,
+                              dtype=PORES_LEVEL_DTYPE)
+        elif levels.dtype != PORES_LEVEL_DTYPE or not levels.flags.c_contiguous or levels.ndim != 1:
+            raise ValueError("levels: a C-contiguous PORES_LEVEL_DTYPE array")
+        with_mask = jobs[jobs["mask_first"] >= 0]
+        if mask is None and len(with_mask):
+            size = (with_mask["mask_first"] + with_mask["n_levels"] * with_mask["ny"].astype(np.int64) * with_mask["nz"]).max()
+            mask = np.zeros(max(int(size), 0), dtype=np.uint64)
+        elif mask is not None and (mask.dtype != np.uint64 or not mask.flags.c_contiguous or mask.ndim != 1):
+            raise ValueError("mask: a C-contiguous uint64 array")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), r.ctypes.data, len(r), p.ctypes.data, len(p),
+                q.ctypes.data, len(q), levels.ctypes.data, len(levels), out.ctypes.data, len(out),
+                None if mask is None else mask.ctypes.data, 0 if mask is None else len(mask)]
+        if open_words is None and workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_pore_sizes", *args)
+            return levels, out, mask
+        w = None if open_words is None else np.ascontiguousarray(open_words, dtype=np.uint64).reshape(-1)
+        f = None if open_first is None else np.ascontiguousarray(open_first, dtype=np.int64).reshape(-1)
+        if (w is None) != (f is None) or (f is not None and len(f) != len(jobs)):
+            raise ValueError("open_words and open_first: both, with one entry of open_first per job")
+        ms = ctypes.c_float(0.0)
+        _stat_call("pw_internal_pore_sizes", *args, None if w is None else w.ctypes.data,
+                   None if f is None else f.ctypes.data, 0 if w is None else len(w), int(workspace_bytes or 0), ctypes.byref(ms))
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        return levels, out, mask
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

@@ -7,7 +7,8 @@ point without entering an atom's van der Waals sphere (grown by the probe) and w
 window (:func:`pywindow_amd.utilities.window_planes`).  It is counted on a grid of at most 64 voxels an axis; every
 output of the kernel is an integer, so the result is the same on the device and on the explicit host path
 (``device=-1``), and volume, centroid and gyration tensor are a few IEEE operations on those integers.  The volume is
-that of the probe centre's reach, not the probe-swept (dilated) one.  The reference has no counterpart.
+that of the probe centre's reach; the probe-swept (dilated) one is :mod:`pywindow_amd.pores`.  The reference has no
+counterpart.
 
 * :func:`cavity_grid` -- one frame, or many frames in one call; :class:`Cavity` -- the result, whose
   :meth:`Cavity.series` goes straight into :func:`pywindow_amd.time_correlation`, :func:`pywindow_amd.lomb_scargle`,

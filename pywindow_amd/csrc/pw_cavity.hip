@@ -1,5 +1,6 @@
 // pw_cavity.hip -- gfx950 kernel and the C ABI entry of the cavity of a cage (include/pywindow_amd.h: pw_cavity;
-// definition of the result, the bit layout and why the culling is exact in pw_cavity.hpp).
+// definition of the result, the bit layout and why the culling is exact in pw_cavity.hpp; the classify and fill steps
+// themselves in pw_cavity_dev.hpp, which pw_pores.hip shares).
 //
 // pw_cavity_kernel, a workgroup of four waves a job, everything of the job in LDS: two bit grids of ny * nz words,
 // `open` and `fill`, and a few integers of reduction scratch, as dynamic LDS sized by the largest job of the launch
@@ -26,7 +27,7 @@
 #include <vector>
 
 #include "../../include/pywindow_amd.h"
-#include "pw_cavity.hpp"
+#include "pw_cavity_dev.hpp"
 #include "pw_stat_host.hpp"
 
 using namespace pw;
@@ -42,7 +43,6 @@ namespace {
 
 typedef cavity_word u64;
 
-constexpr int CAV_THREADS = 256;
 constexpr int CAV_SUMS = 14;                                     // n_voxels, n_open, n_surface, n_face, first, second
 constexpr size_t CAV_SCRATCH_BYTES = 8 * (CAV_SUMS + 1) + 4 * 4 + 8;   // the sums, the OR of the words, j / l min / max
 constexpr size_t cav_lds_bytes(long rows) { return 16 * (size_t)rows + ((CAV_SCRATCH_BYTES + 15) & ~(size_t)15); }
@@ -56,11 +56,6 @@ struct CavJobDev {
     int nx, ny, nz, seed[3];
 };
 
-// the value that lane `from` of the wave holds; `from` is the wave's
-__device__ inline double cav_lane(double v, int from) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), from), __builtin_amdgcn_readlane(__double2loint(v), from));
-}
-
 __global__ void __launch_bounds__(CAV_THREADS)
 pw_cavity_kernel(const CavJobDev* __restrict__ jobs, const double* __restrict__ xyz, const double* __restrict__ radii,
                  const double* __restrict__ planes, u64* __restrict__ ws, pw_cavity_out* __restrict__ out) {
@@ -71,93 +66,21 @@ pw_cavity_kernel(const CavJobDev* __restrict__ jobs, const double* __restrict__ 
     u64* s_fill = s_open + rows;
     unsigned long long* s_sum = s_fill + rows;                  // [CAV_SUMS], then the OR of the cavity's words
     int* s_box = (int*)(s_sum + CAV_SUMS + 1);                  // j_min, j_max, l_min, l_max
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const u64 xmask = cavity_row_mask(nx);
+    const int tid = threadIdx.x;
 
     // ---- classify
-    if (D.open_first >= 0) {
-        for (int r = tid; r < rows; r += CAV_THREADS) {
-            s_open[r] = ws[D.open_first + r] & xmask;
-            s_fill[r] = 0;
-        }
-    } else {
-        const long n = D.n, m = D.m;
-        const double* atoms = xyz + 3 * D.atom_first;
-        const double* reach = radii + D.radius_first;
-        const double* cuts = planes + 4 * D.plane_first;
-        const double h = D.h, probe = D.probe, oy = D.o[1], oz = D.o[2];
-        const double x = cavity_coord(D.o[0], lane, h);
-        for (int r = wave; r < rows; r += CAV_THREADS / 64) {
-            const double y = cavity_coord(oy, r % ny, h), z = cavity_coord(oz, r / ny, h);
-            bool open = lane < nx;
-            // 64 atoms at a time, lane a holding atom base + a: one ballot of the row test says which of them this row
-            // has to look at -- a few of a cage's -- and those go to every lane through the lane-read
-            for (long base = 0; base < n; base += 64) {
-                if (!__ballot(open)) break;                          // (no voxel of the row is open any more)
-                const long a = base + lane;
-                double X = 0.0, Y = 0.0, Z = 0.0, r2 = 0.0;
-                bool near = false;
-                if (a < n) {
-                    X = atoms[3 * a]; Y = atoms[3 * a + 1]; Z = atoms[3 * a + 2];
-                    r2 = cavity_reach2(reach[a], probe);
-                    near = !cavity_row_clear(y - Y, z - Z, r2);
-                }
-                for (u64 todo = __ballot(near); todo; todo &= todo - 1) {   // (at most 64 bits, one fewer a turn)
-                    const int b = __ffsll((long long)todo) - 1;
-                    open = open && cavity_free(x - cav_lane(X, b), y - cav_lane(Y, b), z - cav_lane(Z, b), cav_lane(r2, b));
-                }
-            }
-            for (long base = 0; base < m; base += 64) {
-                const long q = base + lane;
-                double pa = 0.0, pb = 0.0, pc = 0.0, pd = 0.0;
-                if (q < m) {
-                    pa = cuts[4 * q]; pb = cuts[4 * q + 1]; pc = cuts[4 * q + 2]; pd = cuts[4 * q + 3];
-                }
-                const int count = m - base < 64 ? (int)(m - base) : 64;
-                for (int b = 0; b < count; ++b)
-                    open = open && cavity_inside(cav_lane(pa, b), cav_lane(pb, b), cav_lane(pc, b), cav_lane(pd, b), x, y, z);
-            }
-            const u64 word = __ballot(open);
-            if (lane == 0) {
-                s_open[r] = word;
-                s_fill[r] = 0;
-            }
-        }
-    }
+    if (D.open_first >= 0)
+        cav_load_open(ws + D.open_first, nx, rows, s_open, s_fill);
+    else
+        cav_classify(xyz + 3 * D.atom_first, radii + D.radius_first, D.n, planes + 4 * D.plane_first, D.m, D.o[0], D.o[1],
+                     D.o[2], D.h, D.probe, nx, ny, rows, s_open, s_fill);
     if (tid <= CAV_SUMS) s_sum[tid] = 0;
     if (tid < 4) s_box[tid] = (tid & 1) ? -1 : CAVITY_MAX_G;
     __syncthreads();
-    bool seed_open = false;                                          // (thread 0's, for the flags)
-    if (tid == 0) {
-        const int seed_row = D.seed[2] * ny + D.seed[1];
-        const u64 seed_bit = 1ull << D.seed[0];
-        seed_open = (s_open[seed_row] & seed_bit) != 0;
-        if (seed_open) s_fill[seed_row] = seed_bit;
-    }
-    __syncthreads();
+    const bool seed_open = cav_seed(D.seed, ny, s_open, s_fill);     // (thread 0's, for the flags)
 
     // ---- fill
-    const long max_sweeps = (long)nx * ny * nz + 1;
-    for (long sweep = 0; sweep < max_sweeps; ++sweep) {
-        int changed = 0;
-        for (int r = tid; r < rows; r += CAV_THREADS) {
-            const u64 o = s_open[r];
-            if (!o) continue;
-            const int j = r % ny, l = r / ny;
-            const u64 f = s_fill[r];                                 // (only this thread stores it)
-            u64 from = f;
-            if (j > 0) from |= __hip_atomic_load(s_fill + r - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (j + 1 < ny) from |= __hip_atomic_load(s_fill + r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (l > 0) from |= __hip_atomic_load(s_fill + r - ny, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (l + 1 < nz) from |= __hip_atomic_load(s_fill + r + ny, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            const u64 g = cavity_fill_word(from, o);
-            if (g != f) {
-                __hip_atomic_store(s_fill + r, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                changed = 1;
-            }
-        }
-        if (!__syncthreads_or(changed)) break;                       // (the same answer in every thread)
-    }
+    cav_fill(s_open, s_fill, nx, ny, nz);
 
     // ---- reduce
     for (int r = tid; r < rows; r += CAV_THREADS) {

@@ -88,6 +88,12 @@ PW_HD inline void cavity_word_sums(cavity_word w, long& count, long& sum, long& 
     sum2 = s2;
 }
 
+// the voxels of row (j, l) of the cavity, word f, that lie on a face of the grid
+PW_HD inline long cavity_row_face(cavity_word f, int nx, int ny, int nz, int j, int l) {
+    const bool edge_row = j == 0 || j == ny - 1 || l == 0 || l == nz - 1;
+    return cavity_popcount(edge_row ? f : f & (1ull | (1ull << (nx - 1))));
+}
+
 // what a row of the cavity adds to a job's result.  f: the row's word; ym, yp (rows j -+ 1) and zm, zp (rows l -+ 1):
 // the neighbour rows' words, 0 outside the grid.  The sums are in the order of pw_cavity_out.
 struct CavityRow {
@@ -100,10 +106,9 @@ PW_HD inline void cavity_row_sums(cavity_word f, cavity_word ym, cavity_word yp,
     long n, si, sii;
     cavity_word_sums(f, n, si, sii);
     const cavity_word inner = f & (f << 1) & (f >> 1) & ym & yp & zm & zp;   // (bit nx of f is zero, and so is "bit -1")
-    const bool edge_row = j == 0 || j == ny - 1 || l == 0 || l == nz - 1;
     r.n = n;
     r.surface = cavity_popcount(f & ~inner);
-    r.face = edge_row ? n : cavity_popcount(f & (1ull | (1ull << (nx - 1))));
+    r.face = cavity_row_face(f, nx, ny, nz, j, l);
     r.first[0] = si;
     r.first[1] = n * j;
     r.first[2] = n * l;

@@ -21,6 +21,7 @@
 #include "pw_cov.hpp"
 #include "pw_cavity.hpp"
 #include "pw_sasa.hpp"
+#include "pw_pores.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -900,6 +901,66 @@ extern "C" int pw_hostpath_project(const pw_project_job* jobs, long n_jobs, cons
 // and row-culling tests, the spread inside a word and the sums of a row of pw_cavity.hpp.  The threads share out the
 // jobs; a job is a plain loop over its rows -- classify, then sweeps forwards and backwards over the words until one
 // changes nothing (at most nx * ny * nz + 1 of them), then the sums of the rows.  A job's row of the result is its own.
+namespace {
+// a grid and what it is classified against (the fields that pw_cavity_job and pw_pores_job have in common)
+struct CavityHostGrid {
+    const double *atoms, *reach, *cuts;
+    long n, m;
+    const double* origin;
+    double h;
+    int nx, ny, nz;
+    const int* seed;
+};
+
+// the open words of the grid for a probe
+void cavity_host_open(const CavityHostGrid& G, double probe, std::vector<cavity_word>& open) {
+    const int nx = G.nx, ny = G.ny, rows = G.ny * G.nz;
+    for (int r = 0; r < rows; ++r) {
+        const double y = cavity_coord(G.origin[1], r % ny, G.h), z = cavity_coord(G.origin[2], r / ny, G.h);
+        cavity_word word = cavity_row_mask(nx);
+        for (long a = 0; a < G.n && word; ++a) {
+            const double r2 = cavity_reach2(G.reach[a], probe);
+            const double dy = y - G.atoms[3 * a + 1], dz = z - G.atoms[3 * a + 2];
+            if (cavity_row_clear(dy, dz, r2)) continue;
+            for (int i = 0; i < nx; ++i)
+                if (!cavity_free(cavity_coord(G.origin[0], i, G.h) - G.atoms[3 * a], dy, dz, r2)) word &= ~(1ull << i);
+        }
+        for (long q = 0; q < G.m && word; ++q)
+            for (int i = 0; i < nx; ++i)
+                if (!cavity_inside(G.cuts + 4 * q, cavity_coord(G.origin[0], i, G.h), y, z)) word &= ~(1ull << i);
+        open[r] = word;
+    }
+}
+
+// the component of the open words that holds the seed voxel into `fill`; false, and fill all zero, if the seed is closed
+bool cavity_host_fill(const CavityHostGrid& G, const std::vector<cavity_word>& open, std::vector<cavity_word>& fill) {
+    const int nx = G.nx, ny = G.ny, nz = G.nz, rows = ny * nz;
+    std::fill(fill.begin(), fill.end(), 0);
+    const int seed_row = G.seed[2] * ny + G.seed[1];
+    const cavity_word seed_bit = 1ull << G.seed[0];
+    const bool seed_open = (open[seed_row] & seed_bit) != 0;
+    if (seed_open) fill[seed_row] = seed_bit;
+    auto word_of = [&](int j, int l) -> cavity_word { return j < 0 || j >= ny || l < 0 || l >= nz ? 0 : fill[l * ny + j]; };
+    auto visit = [&](int r) {
+        if (!open[r]) return false;
+        const int j = r % ny, l = r / ny;
+        const cavity_word g = cavity_fill_word(fill[r] | word_of(j - 1, l) | word_of(j + 1, l) | word_of(j, l - 1) | word_of(j, l + 1),
+                                               open[r]);
+        const bool changed = g != fill[r];
+        fill[r] = g;
+        return changed;
+    };
+    const long max_sweeps = (long)nx * ny * nz + 1;
+    for (long sweep = 0; seed_open && sweep < max_sweeps; ++sweep) {
+        bool changed = false;
+        for (int r = 0; r < rows; ++r) changed = visit(r) || changed;
+        for (int r = rows - 1; r >= 0; --r) changed = visit(r) || changed;
+        if (!changed) break;
+    }
+    return seed_open;
+}
+}  // namespace
+
 extern "C" int pw_hostpath_cavity(const pw_cavity_job* jobs, long n_jobs, const double* xyz, const double* radii,
                                   const double* planes, pw_cavity_out* out, unsigned long long* mask,
                                   const unsigned long long* open_words, const long* open_first, int threads) {
@@ -907,50 +968,16 @@ extern "C" int pw_hostpath_cavity(const pw_cavity_job* jobs, long n_jobs, const 
     cov_share(n_jobs, threads, [&](long k) {
         const pw_cavity_job& J = jobs[k];
         const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
+        const CavityHostGrid G{xyz + 3 * (long)J.atom_first, radii + (long)J.radius_first, planes + 4 * (long)J.plane_first,
+                               (long)J.n, (long)J.m, J.origin, J.spacing, nx, ny, nz, J.seed};
         std::vector<u64> open((size_t)rows), fill((size_t)rows, 0);
         if (open_first && open_first[k] >= 0) {
             for (int r = 0; r < rows; ++r) open[r] = open_words[open_first[k] + r] & cavity_row_mask(nx);
         } else {
-            const double* atoms = xyz + 3 * (long)J.atom_first;
-            const double* reach = radii + (long)J.radius_first;
-            const double* cuts = planes + 4 * (long)J.plane_first;
-            for (int r = 0; r < rows; ++r) {
-                const double y = cavity_coord(J.origin[1], r % ny, J.spacing), z = cavity_coord(J.origin[2], r / ny, J.spacing);
-                u64 word = cavity_row_mask(nx);
-                for (long a = 0; a < (long)J.n && word; ++a) {
-                    const double r2 = cavity_reach2(reach[a], J.probe);
-                    const double dy = y - atoms[3 * a + 1], dz = z - atoms[3 * a + 2];
-                    if (cavity_row_clear(dy, dz, r2)) continue;
-                    for (int i = 0; i < nx; ++i)
-                        if (!cavity_free(cavity_coord(J.origin[0], i, J.spacing) - atoms[3 * a], dy, dz, r2)) word &= ~(1ull << i);
-                }
-                for (long q = 0; q < (long)J.m && word; ++q)
-                    for (int i = 0; i < nx; ++i)
-                        if (!cavity_inside(cuts + 4 * q, cavity_coord(J.origin[0], i, J.spacing), y, z)) word &= ~(1ull << i);
-                open[r] = word;
-            }
+            cavity_host_open(G, J.probe, open);
         }
-        const int seed_row = J.seed[2] * ny + J.seed[1];
-        const u64 seed_bit = 1ull << J.seed[0];
-        const bool seed_open = (open[seed_row] & seed_bit) != 0;
-        if (seed_open) fill[seed_row] = seed_bit;
+        const bool seed_open = cavity_host_fill(G, open, fill);
         auto word_of = [&](int j, int l) -> u64 { return j < 0 || j >= ny || l < 0 || l >= nz ? 0 : fill[l * ny + j]; };
-        auto visit = [&](int r) {
-            if (!open[r]) return false;
-            const int j = r % ny, l = r / ny;
-            const u64 g = cavity_fill_word(fill[r] | word_of(j - 1, l) | word_of(j + 1, l) | word_of(j, l - 1) | word_of(j, l + 1),
-                                           open[r]);
-            const bool changed = g != fill[r];
-            fill[r] = g;
-            return changed;
-        };
-        const long max_sweeps = (long)nx * ny * nz + 1;
-        for (long sweep = 0; seed_open && sweep < max_sweeps; ++sweep) {
-            bool changed = false;
-            for (int r = 0; r < rows; ++r) changed = visit(r) || changed;
-            for (int r = rows - 1; r >= 0; --r) changed = visit(r) || changed;
-            if (!changed) break;
-        }
         pw_cavity_out o{};
         u64 any = 0;
         int box[4] = {CAVITY_MAX_G, -1, CAVITY_MAX_G, -1};
@@ -977,6 +1004,64 @@ extern "C" int pw_hostpath_cavity(const pw_cavity_job* jobs, long n_jobs, const 
         o.flags = seed_open ? 0 : CAVITY_SEED_CLOSED;
         o.reserved = 0;
         out[(long)J.out] = o;
+    });
+    return PW_OK;
+}
+
+// pw_pore_sizes on the host (pw_pores.hip checks the arguments and sends device == -1 contexts here): a level's reach
+// by the steps of pw_cavity above, K, the spread and the swept word of a row of pw_pores.hpp.  The threads share out
+// the jobs; a job runs its levels from the first to the last, keeps every level's swept words inside the domain, and
+// then hands every voxel of the domain to the largest level that covers it, from the last level down.
+extern "C" int pw_hostpath_pore_sizes(const pw_pores_job* jobs, long n_jobs, const double* xyz, const double* radii,
+                                      const double* planes, const double* probes, pw_pores_level* levels,
+                                      pw_pores_out* out, unsigned long long* mask, const unsigned long long* open_words,
+                                      const long* open_first, int threads) {
+    typedef cavity_word u64;
+    cov_share(n_jobs, threads, [&](long k) {
+        const pw_pores_job& J = jobs[k];
+        const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz, L = (int)J.n_levels;
+        const u64 xmask = cavity_row_mask(nx);
+        const CavityHostGrid G{xyz + 3 * (long)J.atom_first, radii + (long)J.radius_first, planes + 4 * (long)J.plane_first,
+                               (long)J.n, (long)J.m, J.origin, J.spacing, nx, ny, nz, J.seed};
+        std::vector<u64> open((size_t)rows), fill((size_t)rows), domain((size_t)rows, 0), swept((size_t)L * rows, 0);
+        pw_pores_level* LV = levels + (long)J.level_first;
+        for (int lv = 0; lv < L; ++lv) {
+            const double probe = probes[(long)J.probe_first + lv];
+            if (open_first && open_first[k] >= 0) {
+                for (int r = 0; r < rows; ++r) open[r] = open_words[open_first[k] + (long)lv * rows + r] & xmask;
+            } else {
+                cavity_host_open(G, probe, open);
+            }
+            const bool seed_open = cavity_host_fill(G, open, fill);
+            if (lv == 0) domain = fill;
+            pw_pores_level o{};
+            o.k2 = pores_k2(probe, J.spacing);
+            o.flags = seed_open ? 0 : CAVITY_SEED_CLOSED;
+            u64* mine = swept.data() + (size_t)lv * rows;
+            for (int r = 0; r < rows; ++r) {
+                const int j = r % ny, l = r / ny;
+                o.n_reach += cavity_popcount(fill[r]);
+                o.n_face += cavity_row_face(fill[r], nx, ny, nz, j, l);
+                if (seed_open && domain[r])
+                    mine[r] = pores_dilate_row([&](int s) { return fill[s]; }, j, l, ny, nz, o.k2, xmask) & domain[r];
+                o.n_swept += cavity_popcount(mine[r]);
+            }
+            LV[lv] = o;
+        }
+        std::vector<u64> assigned((size_t)rows, 0);
+        for (int lv = L - 1; lv >= 0; --lv)
+            for (int r = 0; r < rows; ++r) {
+                const u64 taken = swept[(size_t)lv * rows + r] & ~assigned[r];
+                LV[lv].n_largest += cavity_popcount(taken);
+                assigned[r] |= taken;
+            }
+        pw_pores_out total{0, 0, L};
+        for (int r = 0; r < rows; ++r) {
+            total.n_domain += cavity_popcount(domain[r]);
+            total.n_none += cavity_popcount(domain[r] & ~assigned[r]);
+        }
+        out[(long)J.out] = total;
+        if (J.mask_first >= 0) memcpy(mask + (long)J.mask_first, swept.data(), sizeof(u64) * swept.size());
     });
     return PW_OK;
 }

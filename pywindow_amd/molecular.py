@@ -204,6 +204,23 @@ class Molecule:
         self.properties["windows"] = {"diameters": None, "centre_of_mass": None}
         return None
 
+    def _cavity_planes(self, close):
+        """The analysis that :meth:`calculate_cavity` and :meth:`calculate_pore_size_distribution` stand on -- the
+        optimised pore centre, the maximum diameter and, for ``close="windows"``, the windows -- and the planes through
+        the windows (``close=None``: none)."""
+        from .utilities import window_planes
+
+        if close not in ("windows", None):
+            raise ValueError('close: "windows" or None')
+        # (one launch for the stages this needs; the calls below read its record)
+        self._record(_lib.STAGE_BASIC | _lib.STAGE_OPT | (_lib.STAGE_WINDOWS if close == "windows" else 0))
+        self.calculate_pore_diameter_opt()
+        self.calculate_maximum_diameter()
+        if close != "windows":
+            return None
+        self.calculate_windows()
+        return window_planes(self.pore_opt_COM, self.properties["windows"]["centre_of_mass"])
+
     def calculate_cavity(self, probe: float = 0.0, spacing: float = 0.5, close="windows", device=None,
                          mask: bool = False) -> float:
         """The volume of the cavity that the centre of a probe of radius ``probe`` reaches from the optimised pore
@@ -215,24 +232,37 @@ class Molecule:
         :class:`pywindow_amd.Cavity` (``mask=True``: with its voxels).  ``full_analysis`` does not call it."""
         from . import cavity as CV
         from .element_data import VDW, element_ids
-        from .utilities import window_planes
 
-        if close not in ("windows", None):
-            raise ValueError('close: "windows" or None')
-        # (one launch for the stages this needs; the calls below read its record)
-        self._record(_lib.STAGE_BASIC | _lib.STAGE_OPT | (_lib.STAGE_WINDOWS if close == "windows" else 0))
-        self.calculate_pore_diameter_opt()
-        self.calculate_maximum_diameter()
-        planes = None
-        if close == "windows":
-            self.calculate_windows()
-            planes = window_planes(self.pore_opt_COM, self.properties["windows"]["centre_of_mass"])
+        planes = self._cavity_planes(close)
         self.cavity = CV.cavity_grid(self.coordinates, VDW[element_ids(self.elements)], self.pore_opt_COM, probe, spacing,
                                      self.maximum_diameter / 2.0, planes, mask, device)
         self.properties["cavity"] = {
             "volume": float(self.cavity.volume), "centre": self.cavity.centroid, "closed": bool(self.cavity.closed),
             "n_voxels": int(self.cavity.n_voxels), "spacing": float(spacing), "probe": float(probe)}
         return self.properties["cavity"]["volume"]
+
+    def calculate_pore_size_distribution(self, probes=None, spacing: float = 0.5, close="windows", device=None):
+        """The pore sizes of the cage (``pywindow_amd.pore_size_distribution``, on the GPU): for a ladder of probe
+        radii (``None``: ``0, spacing / 2, spacing, ...`` up to half the maximum diameter, at most 64) the volume a
+        probe can occupy and the geometric pore size distribution, seeded at the optimised pore centre and closed by
+        planes through the windows exactly as :meth:`calculate_cavity` (``close=None``: no planes), on the same grid.
+        The reference has no counterpart.  Sets ``properties["pore_size_distribution"]``: ``probes``, ``diameter``,
+        ``occupiable_volume``, ``histogram``, ``cumulative``, ``mean_diameter``, ``median_diameter``,
+        ``largest_probe``, ``closed``, ``spacing``; ``self.pore_sizes`` keeps the :class:`pywindow_amd.PoreSizes`,
+        which is returned.  ``full_analysis`` does not call it."""
+        from . import pores as PS
+        from .element_data import VDW, element_ids
+
+        planes = self._cavity_planes(close)
+        ps = PS.pore_size_distribution(self.coordinates, VDW[element_ids(self.elements)], self.pore_opt_COM, probes, spacing,
+                                       self.maximum_diameter / 2.0, planes, False, device)
+        self.pore_sizes = ps
+        self.properties["pore_size_distribution"] = {
+            "probes": ps.probes, "diameter": ps.diameter, "occupiable_volume": ps.occupiable_volume,
+            "histogram": ps.histogram, "cumulative": ps.cumulative, "mean_diameter": float(ps.mean_diameter),
+            "median_diameter": float(ps.median_diameter), "largest_probe": float(ps.largest_probe),
+            "closed": bool(ps.closed), "spacing": float(spacing)}
+        return ps
 
     def calculate_surface_area(self, probe: float = 0.0, points: int = 960, side=None, device=None) -> float:
         """The solvent-accessible surface area for a probe of radius ``probe`` (``pywindow_amd.surface_area``, Shrake

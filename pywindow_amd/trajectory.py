@@ -436,40 +436,33 @@ class DLPOLY:
         store.attach_tracks(tracks)
         return tracks
 
-    def cavity(self, probe: float = 0.0, spacing: float = 0.5, frames=None, close="windows", mask: bool = False,
-               device=None, swap_atoms=None, forcefield=None):
-        """The cavity of the cage in every frame analysed so far (``frames``: a selection of them), all frames in ONE
-        ``pw_cavity`` call on the GPU: a voxel flood fill from each record's optimised pore centre in a box of half the
-        record's maximum diameter, closed by planes through the record's windows (``close=None``: no planes) -- a
-        :class:`pywindow_amd.Cavity` whose fields are arrays over the frames and whose ``frames`` are the trajectory's
-        frame numbers.  A frame without windows gets no planes; its ``closed`` says what happened.
-        ``cavity().series("volume")`` goes into ``pywindow_amd.time_correlation``, ``lomb_scargle``,
-        ``gaussian_kde_1d``, ``gate_statistics`` and ``transition_counts``.  Non-modular, non-periodic analyses only."""
-        from . import cavity as CV
+    def _cavity_inputs(self, what: str, frames, close, swap_atoms, forcefield):
+        """What :meth:`cavity` and :meth:`pore_sizes` hand to their kernels for the analysed frames (``frames``: a
+        selection of them): ``(frame numbers, coordinates, radii, seeds, half widths, planes)``."""
         from .utilities import window_planes
 
         if close not in ("windows", None):
             raise ValueError('close: "windows" or None')
         store = self.analysis_store
         if store.modular or self.periodic:
-            raise ValueError("cavity: a periodic or modular trajectory is not supported yet (the atom order of a "
+            raise ValueError(f"{what}: a periodic or modular trajectory is not supported yet (the atom order of a "
                              "rebuilt molecule is not fixed across frames)")
         unit_frames = [int(f) for f in store.unit_frame]
         if not unit_frames:
-            raise ValueError("cavity: no frame has been analysed yet")
+            raise ValueError(f"{what}: no frame has been analysed yet")
         rows = list(range(len(unit_frames)))
         if frames is not None:
             want = self._select(frames)
             missing = [f for f in want if f not in unit_frames]
             if missing:
-                raise ValueError(f"cavity: frame {missing[0]} has not been analysed")
+                raise ValueError(f"{what}: frame {missing[0]} has not been analysed")
             rows = [unit_frames.index(f) for f in want]
         if not rows:
-            raise ValueError("cavity: no frames selected")
+            raise ValueError(f"{what}: no frames selected")
         recs = store.records
         need = _lib.STAGE_WINDOWS if close == "windows" else _lib.STAGE_OPT | _lib.STAGE_WINDOWS
         if not store.stages & _lib.STAGE_BASIC or not store.stages & need:
-            raise ValueError("cavity: the analysis ran without the stages this needs (maximum diameter, optimised pore "
+            raise ValueError(f"{what}: the analysis ran without the stages this needs (maximum diameter, optimised pore "
                              f"centre{', windows' if close == 'windows' else ''}; stages = {store.stages})")
         sel = [unit_frames[i] for i in rows]
         coords = self._read_selected(sel, False)[0]
@@ -481,8 +474,37 @@ class DLPOLY:
                 win = engine.windows_of(recs[i], more.get(i))
                 planes.append(None if win is None else window_planes(recs["pore_opt_c"][i], win[1]))
         radii = VDW[element_ids(self.elements(swap_atoms, forcefield))]
-        return CV.cavity_grid_batch(coords, radii, np.asarray(recs["pore_opt_c"][rows], dtype=np.float64), probe, spacing,
-                                    np.asarray(recs["maxd"][rows], dtype=np.float64) / 2.0, planes, mask, device, frames=sel)
+        return (sel, coords, radii, np.asarray(recs["pore_opt_c"][rows], dtype=np.float64),
+                np.asarray(recs["maxd"][rows], dtype=np.float64) / 2.0, planes)
+
+    def cavity(self, probe: float = 0.0, spacing: float = 0.5, frames=None, close="windows", mask: bool = False,
+               device=None, swap_atoms=None, forcefield=None):
+        """The cavity of the cage in every frame analysed so far (``frames``: a selection of them), all frames in ONE
+        ``pw_cavity`` call on the GPU: a voxel flood fill from each record's optimised pore centre in a box of half the
+        record's maximum diameter, closed by planes through the record's windows (``close=None``: no planes) -- a
+        :class:`pywindow_amd.Cavity` whose fields are arrays over the frames and whose ``frames`` are the trajectory's
+        frame numbers.  A frame without windows gets no planes; its ``closed`` says what happened.
+        ``cavity().series("volume")`` goes into ``pywindow_amd.time_correlation``, ``lomb_scargle``,
+        ``gaussian_kde_1d``, ``gate_statistics`` and ``transition_counts``.  Non-modular, non-periodic analyses only."""
+        from . import cavity as CV
+
+        sel, coords, radii, seeds, half_widths, planes = self._cavity_inputs("cavity", frames, close, swap_atoms, forcefield)
+        return CV.cavity_grid_batch(coords, radii, seeds, probe, spacing, half_widths, planes, mask, device, frames=sel)
+
+    def pore_sizes(self, probes=None, spacing: float = 0.5, frames=None, close="windows", masks: bool = False,
+                   device=None, swap_atoms=None, forcefield=None):
+        """The pore sizes of the cage in every frame analysed so far (``frames``: a selection of them), all frames in
+        ONE ``pw_pore_sizes`` call on the GPU (``pywindow_amd.pore_size_distribution_batch``): for the ladder ``probes``
+        (``None``: ``0, spacing / 2, spacing, ...`` up to the largest box's half width, at most 64) the
+        probe-occupiable volume and the geometric pore size distribution, seeded, boxed and closed exactly as
+        :meth:`cavity` -- a :class:`pywindow_amd.PoreSizes` whose fields are arrays over the frames and whose
+        ``frames`` are the trajectory's frame numbers.  ``pore_sizes().series("occupiable_volume", level=l)`` goes into
+        ``pywindow_amd.time_correlation``, ``lomb_scargle``, ``gaussian_kde_1d``, ``gate_statistics`` and
+        ``transition_counts``.  Non-modular, non-periodic analyses only."""
+        from . import pores as PS
+
+        sel, coords, radii, seeds, half_widths, planes = self._cavity_inputs("pore_sizes", frames, close, swap_atoms, forcefield)
+        return PS.pore_size_distribution_batch(coords, radii, seeds, probes, spacing, half_widths, planes, masks, device, frames=sel)
 
     def surface(self, probe: float = 0.0, points: int = 960, frames=None, cavity: bool = True, device=None,
                 swap_atoms=None, forcefield=None):
