@@ -907,6 +907,79 @@ int pw_pore_sizes(pw_context *ctx, const pw_pores_job *jobs, int64_t n_jobs, con
                   const double *radii, int64_t n_radii, const double *planes, int64_t n_planes, const double *probes,
                   int64_t n_probes, pw_pores_level *levels, int64_t n_levels, pw_pores_out *out, int64_t n_out,
                   uint64_t *mask, int64_t n_mask);
+/* ---- guest affinity: the Lennard-Jones energy map of a cavity and its Boltzmann sums -----------------------------
+ * How strongly a cage holds a one-site guest: the Boltzmann-weighted volume of the cavity (the helium void volume,
+ * the Henry coefficient), the mean and the minimum binding energy and an energy histogram, at up to
+ * PW_AFF_MAX_LEVELS temperatures in one pass.  The reference has no counterpart.  Job k has
+ *     atoms   n >= 0 atoms xyz[atom_first .. +n) (rows of three doubles) with rows (A, B) coef[coef_first .. +n),
+ *             finite, 0 <= A, B <= 1e100.  A = 4 eps sigma^12 and B = 4 eps sigma^6 are the caller's (units included);
+ *     a grid  nx x ny x nz voxels, each 1 .. PW_CAVITY_MAX_G, origin o and spacing h > 0 exactly as pw_cavity: voxel
+ *             (i, j, l) has the centre x = o_x + (double)i * h, likewise y and z;
+ *     region  the ny * nz words words[word_first ..) in the layout of pw_cavity's mask -- row (j, l) at l * ny + j, bit
+ *             i voxel i, bits at i >= nx ignored; word_first == -1: every voxel of the grid;
+ *     core2 >= 1e-6 and cutoff2 (0.0: no cutoff, otherwise > core2), both finite;
+ *     L = n_betas inverse temperatures betas[beta_first .. +L), 1 <= L <= PW_AFF_MAX_LEVELS, finite and >= 0;
+ *     E = n_edges histogram edges edges[edge_first .. +E), 0 <= E <= PW_AFF_MAX_EDGES, finite, strictly ascending.
+ * ORDER.  The voxels of the region are ranked by (l, j, i) ascending; V is their number.
+ * ENERGY.  Per voxel, the atoms in index order, dx = x - X and so on, r2 = (dx*dx + dy*dy) + dz*dz.  The voxel is
+ * BLOCKED iff some atom has r2 <= core2.  An atom COUNTS iff cutoff2 == 0.0 or r2 <= cutoff2; an atom that does not
+ * count is skipped, not added as zero.  For a counting atom q = 1.0 / r2 (correctly rounded), s = (q*q)*q,
+ * u = s * (A*s - B), U = U + u, from +0.0.  The bounds keep U of a voxel that is not blocked finite.
+ * WEIGHT.  Per beta and voxel that is not blocked: x = -(beta * U); if x > 700.0 then x = 700.0 and PW_AFF_CLAMPED
+ * is set in the job's flags; w = pw_exp(x) (pywindow_amd/csrc/pw_math.hpp); the terms are z = w and e = w * U.
+ * SUMS.  Chunk c holds the ranks 64c .. 64c + 63; a slot whose rank is >= V or whose voxel is blocked holds +0.0.
+ * Within a chunk, for k = 1, 2, 4, 8, 16, 32 in turn, slot[t] = slot[t] + slot[t + k] for every t that is a multiple
+ * of 2k; the chunk's sum is slot[0].  The total starts at +0.0 and takes the chunk sums in chunk order.  There are
+ * no floating-point atomics.  All floating point is FP64 without contraction in exactly the association written, so
+ * the result is the same bytes on every device, launch geometry and run and on a device == -1 context (host
+ * threads), whatever else shares the call and however the jobs are cut into launches.
+ * Written: row `out` (n_voxels = V, n_blocked, u_min -- the smallest U of a voxel that is not blocked, ties to the
+ * lowest rank; +inf and min_voxel = -1 when there is none --, min_voxel = (i, j, l) and the flags); rows
+ * levels[level_first + b] = (Z_b, E_b), the totals of z and e; hist[hist_first + k] = #{v not blocked :
+ * U_v < edge_k}, by comparisons; and, when energy_first >= 0, energies[energy_first + rank] = U, +inf where blocked.
+ * The Boltzmann volume Z h^3, the mean energy E / Z and everything built on them are the caller's.
+ * All pointers are host memory; n_points, n_coef, n_words, n_betas, n_edges, n_energies, n_levels, n_hist and n_out
+ * are the rows of xyz and of coef, the entries of words, betas, edges and energies, the rows of levels, the entries of
+ * hist and the rows of out (arrays no job uses may be null).  Jobs may share every input but no row of out or of
+ * levels and no entry of hist or energies; entries no job owns are never touched.  A value a job reads that is not
+ * finite or outside its bounds, a dimension or a count outside its range, a range outside an array or jobs that
+ * share outputs: PW_E_BAD_ARG (pw_last_error names the job -- of two that share, the later -- and the reason), and
+ * nothing is launched or written.  Device work is queued on the context's stream, its memory allocated and freed in
+ * stream order; there is no capacity in n; the call returns when the results are in place. */
+#define PW_AFF_MAX_LEVELS 8
+#define PW_AFF_MAX_EDGES 16
+#define PW_AFF_CLAMPED 1          /* flags: some -(beta * U) was above 700 and was taken as 700 */
+typedef struct pw_affinity_job {
+    int64_t atom_first, n;          /* atoms = xyz[atom_first .. +n), n >= 0 */
+    int64_t coef_first;             /* their rows (A, B) = coef[coef_first .. +n) */
+    int64_t word_first;             /* the region = words[word_first .. + ny*nz), or -1: every voxel */
+    int64_t beta_first, n_betas;    /* betas[beta_first .. +n_betas) */
+    int64_t edge_first, n_edges;    /* edges[edge_first .. +n_edges) */
+    int64_t level_first;            /* levels[level_first .. +n_betas) is written */
+    int64_t hist_first;             /* hist[hist_first .. +n_edges) is written */
+    int64_t energy_first;           /* energies[energy_first .. +V) is written, or -1: no energy map */
+    int64_t out;                    /* the job's row of out */
+    double  origin[3];              /* the centre of voxel (0, 0, 0) */
+    double  spacing;                /* h > 0 */
+    double  core2;                  /* >= 1e-6 */
+    double  cutoff2;                /* 0.0: none; otherwise > core2 */
+    int32_t nx, ny, nz;             /* 1 .. PW_CAVITY_MAX_G */
+    int32_t reserved;               /* padding to a multiple of 8 bytes; not read */
+} pw_affinity_job;
+typedef struct pw_affinity_level {
+    double z, e;                    /* sum of w, sum of w * U */
+} pw_affinity_level;
+typedef struct pw_affinity_out {
+    int64_t n_voxels, n_blocked;
+    double  u_min;
+    int32_t min_voxel[3];           /* (i, j, l), or -1 */
+    int32_t flags;                  /* PW_AFF_* */
+} pw_affinity_out;
+int pw_affinity(pw_context *ctx, const pw_affinity_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+                const double *coef, int64_t n_coef, const uint64_t *words, int64_t n_words, const double *betas,
+                int64_t n_betas, const double *edges, int64_t n_edges, double *energies, int64_t n_energies,
+                pw_affinity_level *levels, int64_t n_levels, int64_t *hist, int64_t n_hist, pw_affinity_out *out,
+                int64_t n_out);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

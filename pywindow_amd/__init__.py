@@ -34,6 +34,7 @@ from .modes import Modes, covariance, principal_modes, project  # noqa: E402
 from .cavity import Cavity, cavity_grid, cavity_grid_batch  # noqa: E402
 from .surface import Surface, sphere_directions, surface_area, surface_area_batch  # noqa: E402
 from .pores import PoreSizes, pore_size_distribution, pore_size_distribution_batch  # noqa: E402
+from .affinity import Affinity, guest_affinity, guest_affinity_batch, lj_coefficients  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -99,6 +100,10 @@ __all__ = [
     "PoreSizes",
     "pore_size_distribution",
     "pore_size_distribution_batch",
+    "Affinity",
+    "guest_affinity",
+    "guest_affinity_batch",
+    "lj_coefficients",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

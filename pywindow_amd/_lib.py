@@ -317,6 +317,24 @@ assert PORES_JOB_DTYPE.itemsize == 136 and PORES_LEVEL_DTYPE.itemsize == 40 and 
 PORES_MAX_LEVELS = 64
 PORES_MAX_K2 = 3 * 63 * 63
 
+#: numpy mirror of ``pw_affinity_job``
+AFFINITY_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("word_first", np.int64),
+     ("beta_first", np.int64), ("n_betas", np.int64), ("edge_first", np.int64), ("n_edges", np.int64),
+     ("level_first", np.int64), ("hist_first", np.int64), ("energy_first", np.int64), ("out", np.int64),
+     ("origin", np.float64, (3,)), ("spacing", np.float64), ("core2", np.float64), ("cutoff2", np.float64),
+     ("nx", np.int32), ("ny", np.int32), ("nz", np.int32), ("reserved", np.int32)]
+)
+#: numpy mirrors of ``pw_affinity_level`` and ``pw_affinity_out``
+AFFINITY_LEVEL_DTYPE = np.dtype([("z", np.float64), ("e", np.float64)])
+AFFINITY_OUT_DTYPE = np.dtype([("n_voxels", np.int64), ("n_blocked", np.int64), ("u_min", np.float64),
+                               ("min_voxel", np.int32, (3,)), ("flags", np.int32)])
+assert AFFINITY_JOB_DTYPE.itemsize == 160 and AFFINITY_LEVEL_DTYPE.itemsize == 16 and AFFINITY_OUT_DTYPE.itemsize == 40
+#: ``PW_AFF_MAX_LEVELS``, ``PW_AFF_MAX_EDGES``, ``PW_AFF_CLAMPED``
+AFF_MAX_LEVELS = 8
+AFF_MAX_EDGES = 16
+AFF_CLAMPED = 1
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -410,6 +428,7 @@ EXPORTED_SYMBOLS = [
     "pw_cavity",
     "pw_sasa",
     "pw_pore_sizes",
+    "pw_affinity",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -547,6 +566,9 @@ def load():
     L.pw_pore_sizes.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
     L.pw_internal_pore_sizes.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp,
                                          i64, i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_affinity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
+    L.pw_internal_affinity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
+                                       vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1186,6 +1208,51 @@ class Context:
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
         return levels, out, mask
+
+    def affinity(self, jobs, xyz, coef, betas, words=None, edges=None, out=None, levels=None, hist=None, energies=None,
+                 workspace_bytes=None, kernel_ms=None):
+        """``pw_affinity``: the Lennard-Jones energy map of the regions of a batch of jobs and its Boltzmann sums
+        (``AFFINITY_JOB_DTYPE`` records indexing the rows of ``xyz`` (rows of three) and of ``coef`` (rows ``(A, B)``),
+        the entries of ``words`` (uint64, a region in the layout of ``pw_cavity``'s mask; ``word_first = -1``: every
+        voxel), of ``betas`` and of ``edges``, and the rows and entries of the results):
+        ``(out, levels, hist, energies)`` -- ``out`` an ``AFFINITY_OUT_DTYPE`` array, ``levels`` an
+        ``AFFINITY_LEVEL_DTYPE`` array with ``n_betas`` rows a job from its ``level_first``, ``hist`` int64 with
+        ``n_edges`` counts a job from its ``hist_first`` and ``energies`` float64 (given: filled in place, entries no
+        job owns stay as they are; a job with ``energy_first >= 0`` needs ``energies`` given, since only the library
+        counts the voxels of a region).  Whatever the entry refuses -- a value that is not finite or outside its
+        bounds, a count or a dimension outside its range, a range outside an array, jobs that share outputs --:
+        ``ValueError`` with the library's message.  ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time
+        of the device work by HIP events) go through the library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=AFFINITY_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
+        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        w = np.zeros(0, dtype=np.uint64) if words is None else np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+        e = np.zeros(0) if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+
+        def result(given, dtype, size, name):
+            if given is None:
+                return np.zeros(max(int(size), 0), dtype=dtype)
+            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError(f"{name}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+            return given
+
+        some = len(jobs) > 0
+        out = result(out, AFFINITY_OUT_DTYPE, jobs["out"].max() + 1 if some else 0, "out")
+        levels = result(levels, AFFINITY_LEVEL_DTYPE, (jobs["level_first"] + jobs["n_betas"]).max() if some else 0, "levels")
+        hist = result(hist, np.int64, (jobs["hist_first"] + jobs["n_edges"]).max() if some else 0, "hist")
+        energies = result(energies, np.float64, 0, "energies")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), w.ctypes.data, len(w),
+                b.ctypes.data, len(b), e.ctypes.data, len(e), energies.ctypes.data, len(energies), levels.ctypes.data,
+                len(levels), hist.ctypes.data, len(hist), out.ctypes.data, len(out)]
+        if workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_affinity", *args)
+            return out, levels, hist, energies
+        ms = ctypes.c_float(0.0)
+        _stat_call("pw_internal_affinity", *args, int(workspace_bytes or 0), ctypes.byref(ms))
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        return out, levels, hist, energies
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

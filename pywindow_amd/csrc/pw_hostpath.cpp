@@ -19,6 +19,7 @@
 #include "pw_superpose.hpp"
 #include "pw_cluster.hpp"
 #include "pw_cov.hpp"
+#include "pw_affinity.hpp"
 #include "pw_cavity.hpp"
 #include "pw_sasa.hpp"
 #include "pw_pores.hpp"
@@ -1123,6 +1124,150 @@ extern "C" int pw_hostpath_sasa(const pw_sasa_job* jobs, long n_jobs, const doub
         o.flags = J.word_first >= 0 ? SASA_GRID : 0;
         out[(long)J.out] = o;
     }
+    return PW_OK;
+}
+
+// pw_affinity on the host (pw_affinity.hip checks the arguments, counts the voxels of every region and sends
+// device == -1 contexts here): the pair term, the blocked and counts tests, the weight with its clamp, the chunk tree and
+// the search of a rank's voxel of pw_affinity.hpp.  The threads share out (job, chunk) pieces, each of which leaves the
+// partial of pw_affinity.hpp; then one ordered reduce a job.
+extern "C" int pw_hostpath_affinity(const pw_affinity_job* jobs, long n_jobs, const long* voxels, const double* xyz,
+                                    const double* coef, const unsigned long long* words, const double* betas,
+                                    const double* edges, double* energies, pw_affinity_level* levels, long long* hist,
+                                    pw_affinity_out* out, int threads) {
+    typedef cavity_word u64;
+    struct Plan { long piece_first, part_first, prefix_first; };
+    std::vector<Plan> plan((size_t)n_jobs + 1);
+    long pieces = 0, part_words = 0, prefix_ints = 0;
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_affinity_job& J = jobs[k];
+        plan[k] = Plan{pieces, part_words, prefix_ints};
+        const long chunks = (voxels[k] + AFF_CHUNK - 1) / AFF_CHUNK;
+        pieces += chunks;
+        part_words += chunks * aff_part_words((int)J.n_betas, (int)J.n_edges);
+        if (J.word_first >= 0) prefix_ints += (long)J.ny * J.nz + 1;
+    }
+    plan[n_jobs] = Plan{pieces, part_words, prefix_ints};
+    std::vector<u64> part((size_t)part_words);
+    std::vector<int> prefix((size_t)prefix_ints);
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_affinity_job& J = jobs[k];
+        if (J.word_first < 0) continue;
+        int* p = prefix.data() + plan[k].prefix_first;
+        const int rows = J.ny * J.nz;
+        p[0] = 0;
+        for (int r = 0; r < rows; ++r) p[r + 1] = p[r] + cavity_popcount(words[(long)J.word_first + r] & cavity_row_mask(J.nx));
+    }
+    // the voxel of a rank of job k
+    auto voxel_of = [&](long k, long rank, int& i, int& row) {
+        const pw_affinity_job& J = jobs[k];
+        const u64* w = J.word_first >= 0 ? words + (long)J.word_first : nullptr;
+        const int* p = prefix.data() + plan[k].prefix_first;
+        aff_voxel(rank, J.word_first >= 0, J.nx, J.ny * J.nz, [&](int r) { return w[r]; }, [&](int r) { return p[r]; }, i, row);
+    };
+    cov_share(pieces, threads, [&](long piece) {
+        long k = 0, hi = n_jobs;                                     // the last job with piece_first <= piece
+        while (hi - k > 1) {
+            const long mid = (k + hi) / 2;
+            if (plan[mid].piece_first <= piece) k = mid; else hi = mid;
+        }
+        const pw_affinity_job& J = jobs[k];
+        const int L = (int)J.n_betas, E = (int)J.n_edges, stride = aff_part_words(L, E);
+        const long chunk = piece - plan[k].piece_first, V = voxels[k];
+        const double* atoms = xyz + 3 * (long)J.atom_first;
+        const double* ab = coef + 2 * (long)J.coef_first;
+        double U[AFF_CHUNK], slot_z[AFF_CHUNK], slot_e[AFF_CHUNK];
+        bool live[AFF_CHUNK];
+        long n_blocked = 0;
+        for (int t = 0; t < AFF_CHUNK; ++t) {
+            const long rank = chunk * AFF_CHUNK + t;
+            U[t] = 0.0;
+            live[t] = false;
+            if (rank >= V) continue;
+            int i, row;
+            voxel_of(k, rank, i, row);
+            const double x = cavity_coord(J.origin[0], i, J.spacing), y = cavity_coord(J.origin[1], row % J.ny, J.spacing),
+                         z = cavity_coord(J.origin[2], row / J.ny, J.spacing);
+            double u_sum = 0.0;
+            bool blocked = false;
+            for (long a = 0; a < (long)J.n && !blocked; ++a) {
+                const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
+                blocked = aff_blocked(r2, J.core2);
+                if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
+            }
+            n_blocked += blocked;
+            live[t] = !blocked;
+            U[t] = u_sum;
+            if (J.energy_first >= 0) energies[(long)J.energy_first + rank] = blocked ? aff_inf() : u_sum;
+        }
+        u64* P = part.data() + plan[k].part_first + chunk * stride;
+        bool clamped = false;
+        for (int b = 0; b < L; ++b) {
+            for (int t = 0; t < AFF_CHUNK; ++t) {
+                slot_z[t] = slot_e[t] = 0.0;
+                if (!live[t]) continue;
+                const double w = aff_weight(betas[(long)J.beta_first + b], U[t], POW_EXP_TAB, clamped);
+                slot_z[t] = w;
+                slot_e[t] = w * U[t];
+            }
+            P[2 * b] = pw_d2bits(aff_tree(slot_z));
+            P[2 * b + 1] = pw_d2bits(aff_tree(slot_e));
+        }
+        double m = aff_inf();
+        long m_rank = chunk * AFF_CHUNK;
+        for (int t = 0; t < AFF_CHUNK; ++t)
+            if (live[t] && U[t] < m) {
+                m = U[t];
+                m_rank = chunk * AFF_CHUNK + t;
+            }
+        P[2 * L] = pw_d2bits(m);
+        P[2 * L + 1] = (u64)m_rank;
+        P[2 * L + 2] = (u64)n_blocked;
+        P[2 * L + 3] = clamped ? (u64)AFF_CLAMPED : 0ull;
+        for (int e = 0; e < E; ++e) {
+            long below = 0;
+            for (int t = 0; t < AFF_CHUNK; ++t) below += live[t] && U[t] < edges[(long)J.edge_first + e];
+            P[2 * L + AFF_PART_FIXED + e] = (u64)below;
+        }
+    });
+    cov_share(n_jobs, threads, [&](long k) {
+        const pw_affinity_job& J = jobs[k];
+        const int L = (int)J.n_betas, E = (int)J.n_edges, stride = aff_part_words(L, E);
+        const long chunks = plan[k + 1].piece_first - plan[k].piece_first;
+        const u64* P = part.data() + plan[k].part_first;
+        for (int b = 0; b < L; ++b) {
+            double sz = 0.0, se = 0.0;
+            for (long c = 0; c < chunks; ++c) {
+                sz = sz + pw_bits2d(P[c * stride + 2 * b]);
+                se = se + pw_bits2d(P[c * stride + 2 * b + 1]);
+            }
+            levels[(long)J.level_first + b] = pw_affinity_level{sz, se};
+        }
+        pw_affinity_out o{voxels[k], 0, aff_inf(), {-1, -1, -1}, 0};
+        long rank = -1;
+        for (long c = 0; c < chunks; ++c) {
+            const double v = pw_bits2d(P[c * stride + 2 * L]);
+            if (v < o.u_min) {
+                o.u_min = v;
+                rank = (long)P[c * stride + 2 * L + 1];
+            }
+            o.n_blocked += (long)P[c * stride + 2 * L + 2];
+            o.flags |= (int)P[c * stride + 2 * L + 3];
+        }
+        if (rank >= 0) {
+            int i, row;
+            voxel_of(k, rank, i, row);
+            o.min_voxel[0] = i;
+            o.min_voxel[1] = row % J.ny;
+            o.min_voxel[2] = row / J.ny;
+        }
+        out[(long)J.out] = o;
+        for (int e = 0; e < E; ++e) {
+            long long s = 0;
+            for (long c = 0; c < chunks; ++c) s += (long long)P[c * stride + 2 * L + AFF_PART_FIXED + e];
+            hist[(long)J.hist_first + e] = s;
+        }
+    });
     return PW_OK;
 }
 

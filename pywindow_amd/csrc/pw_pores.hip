@@ -182,23 +182,6 @@ struct PoresGroup {
 
 int pores_bad(long k, const char* what) { return stat_bad("pw_pore_sizes", k, what); }
 
-// of spans (first, length, job) that must not overlap: the earliest job that shares an entry with a job before it, or -1
-long pores_shared(std::vector<std::array<long, 3>>& spans) {
-    std::sort(spans.begin(), spans.end());
-    long bad = -1, end = -1, owner = -1;                             // the furthest end so far and the job it belongs to
-    for (const auto& s : spans) {
-        if (s[0] < end) {
-            const long later = s[2] > owner ? s[2] : owner;
-            if (bad < 0 || later < bad) bad = later;
-        }
-        if (s[0] + s[1] > end) {
-            end = s[0] + s[1];
-            owner = s[2];
-        }
-    }
-    return bad;
-}
-
 // Everything is checked before anything is launched or written.  open_first (may be null; an entry -1: classify) names
 // the ready-made open words of a job, level after level, in open_words[0 .. n_open_words).
 int pores_check(const pw_pores_job* jobs, long n_jobs, const double* xyz, long n_points, const double* radii, long n_radii,
@@ -249,17 +232,17 @@ int pores_check(const pw_pores_job* jobs, long n_jobs, const double* xyz, long n
     // outputs of two jobs: the later of the two is named
     std::vector<std::array<long, 3>> spans;
     for (long k = 0; k < n_jobs; ++k) spans.push_back({(long)jobs[k].out, 1, k});
-    long bad = pores_shared(spans);
+    long bad = stat_shared(spans);
     if (bad >= 0) return pores_bad(bad, "shares its row of out with an earlier job");
     spans.clear();
     for (long k = 0; k < n_jobs; ++k) spans.push_back({(long)jobs[k].level_first, (long)jobs[k].n_levels, k});
-    bad = pores_shared(spans);
+    bad = stat_shared(spans);
     if (bad >= 0) return pores_bad(bad, "shares rows of levels with an earlier job");
     spans.clear();
     for (long k = 0; k < n_jobs; ++k)
         if (jobs[k].mask_first >= 0)
             spans.push_back({(long)jobs[k].mask_first, (long)jobs[k].n_levels * jobs[k].ny * jobs[k].nz, k});
-    bad = pores_shared(spans);
+    bad = stat_shared(spans);
     if (bad >= 0) return pores_bad(bad, "shares words of mask with an earlier job");
     return PW_OK;
 }

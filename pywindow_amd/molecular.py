@@ -264,6 +264,29 @@ class Molecule:
             "closed": bool(ps.closed), "spacing": float(spacing)}
         return ps
 
+    def calculate_guest_affinity(self, guest="Xe", temperature: float = 298.0, spacing: float = 0.5, close="windows",
+                                 device=None):
+        """How strongly the cage holds a one-site Lennard-Jones guest (``pywindow_amd.guest_affinity``, on the GPU):
+        the guest's energy with the UFF atoms of the cage at every voxel of the cavity of ``calculate_cavity(probe=0)``
+        -- seeded, boxed and closed in the same way (``close=None``: no planes) --, a voxel within 0.5 Angstrom of an
+        atom left out (``core2 = 0.25``), and the Boltzmann sums over them at ``temperature`` (K).  ``guest``: a name
+        of ``pywindow_amd.affinity.GUESTS`` or a ``(sigma, eps_kJ_per_mol)`` pair.  The reference has no counterpart.
+        Sets ``properties["guest_affinity"]``: ``guest``, ``temperature``, ``boltzmann_volume``, ``henry``,
+        ``mean_energy``, ``heat``, ``min_energy``, ``min_position``, ``closed``, ``spacing``; ``self.affinity`` keeps
+        the :class:`pywindow_amd.Affinity`, which is returned.  ``full_analysis`` does not call it."""
+        from . import affinity as AF
+
+        self.calculate_cavity(probe=0.0, spacing=spacing, close=close, device=device, mask=True)
+        af = AF.guest_affinity(self.coordinates, self.elements, guest, [temperature], cavity=self.cavity, core2=0.25,
+                               device=device)
+        self.affinity = af
+        self.properties["guest_affinity"] = {
+            "guest": guest, "temperature": float(temperature), "boltzmann_volume": float(af.boltzmann_volume[0]),
+            "henry": float(af.henry[0]), "mean_energy": float(af.mean_energy[0]), "heat": float(af.heat[0]),
+            "min_energy": float(af.min_energy), "min_position": af.min_position, "closed": bool(af.closed),
+            "spacing": float(spacing)}
+        return af
+
     def calculate_surface_area(self, probe: float = 0.0, points: int = 960, side=None, device=None) -> float:
         """The solvent-accessible surface area for a probe of radius ``probe`` (``pywindow_amd.surface_area``, Shrake
         and Rupley's test points on the GPU, ``points`` an atom).  ``side=None``: the whole surface, no analysis is

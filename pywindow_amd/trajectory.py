@@ -506,6 +506,23 @@ class DLPOLY:
         sel, coords, radii, seeds, half_widths, planes = self._cavity_inputs("pore_sizes", frames, close, swap_atoms, forcefield)
         return PS.pore_size_distribution_batch(coords, radii, seeds, probes, spacing, half_widths, planes, masks, device, frames=sel)
 
+    def affinity(self, guest="Xe", temperatures=298.0, spacing: float = 0.5, frames=None, close="windows", edges=None,
+                 energies: bool = False, device=None, swap_atoms=None, forcefield=None):
+        """The affinity of the cage for a one-site Lennard-Jones guest in every frame analysed so far (``frames``: a
+        selection of them): one ``pw_cavity`` call for the probe-0 cavities, seeded, boxed and closed exactly as
+        :meth:`cavity`, then ALL frames in ONE ``pw_affinity`` call on the GPU
+        (``pywindow_amd.guest_affinity_batch``, UFF atoms, ``core2 = 0.25``) -- a :class:`pywindow_amd.Affinity` whose
+        fields are arrays over the frames and whose ``frames`` are the trajectory's frame numbers.
+        ``affinity().series("boltzmann_volume")`` goes into ``pywindow_amd.time_correlation``, ``lomb_scargle``,
+        ``gaussian_kde_1d``, ``gate_statistics`` and ``transition_counts``.  Non-modular, non-periodic analyses only."""
+        from . import affinity as AF
+        from . import cavity as CV
+
+        sel, coords, radii, seeds, half_widths, planes = self._cavity_inputs("affinity", frames, close, swap_atoms, forcefield)
+        cav = CV.cavity_grid_batch(coords, radii, seeds, 0.0, spacing, half_widths, planes, True, device, frames=sel)
+        return AF.guest_affinity_batch(coords, self.elements(swap_atoms, forcefield), guest, temperatures, cavity=cav,
+                                       edges=edges, energies=energies, core2=0.25, device=device, frames=sel)
+
     def surface(self, probe: float = 0.0, points: int = 960, frames=None, cavity: bool = True, device=None,
                 swap_atoms=None, forcefield=None):
         """The accessible surface of the cage in every frame, all frames in ONE ``pw_sasa`` call on the GPU
