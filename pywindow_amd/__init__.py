@@ -35,6 +35,7 @@ from .cavity import Cavity, cavity_grid, cavity_grid_batch  # noqa: E402
 from .surface import Surface, sphere_directions, surface_area, surface_area_batch  # noqa: E402
 from .pores import PoreSizes, pore_size_distribution, pore_size_distribution_batch  # noqa: E402
 from .affinity import Affinity, guest_affinity, guest_affinity_batch, lj_coefficients  # noqa: E402
+from .passage import Passage, guest_passage, guest_passage_batch, passage_field  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -104,6 +105,10 @@ __all__ = [
     "guest_affinity",
     "guest_affinity_batch",
     "lj_coefficients",
+    "Passage",
+    "guest_passage",
+    "guest_passage_batch",
+    "passage_field",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

@@ -335,6 +335,23 @@ AFF_MAX_LEVELS = 8
 AFF_MAX_EDGES = 16
 AFF_CLAMPED = 1
 
+#: numpy mirror of ``pw_passage_job``
+PASSAGE_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
+     ("field_first", np.int64), ("out_first", np.int64), ("origin", np.float64, (3,)), ("spacing", np.float64),
+     ("core2", np.float64), ("cutoff2", np.float64), ("nx", np.int32), ("ny", np.int32), ("nz", np.int32),
+     ("seed", np.int32, (3,))]
+)
+#: numpy mirror of ``pw_passage_out``
+PASSAGE_OUT_DTYPE = np.dtype(
+    [("barrier", np.float64), ("well", np.float64), ("u_seed", np.float64), ("n_fill", np.int64), ("n_basin", np.int64),
+     ("saddle", np.int32, (3,)), ("well_voxel", np.int32, (3,)), ("flags", np.int32), ("reserved", np.int32)]
+)
+assert PASSAGE_JOB_DTYPE.itemsize == 128 and PASSAGE_OUT_DTYPE.itemsize == 72
+#: ``PW_PAS_SEED_CLOSED``, ``PW_PAS_NO_EXIT``
+PAS_SEED_CLOSED = 1
+PAS_NO_EXIT = 2
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -429,6 +446,7 @@ EXPORTED_SYMBOLS = [
     "pw_sasa",
     "pw_pore_sizes",
     "pw_affinity",
+    "pw_passage",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -569,6 +587,9 @@ def load():
     L.pw_affinity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
     L.pw_internal_affinity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
                                        vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_passage.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
+    L.pw_internal_passage.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64,
+                                      ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1253,6 +1274,43 @@ class Context:
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
         return out, levels, hist, energies
+
+    def passage(self, jobs, xyz=None, coef=None, planes=None, field=None, out=None, workspace_bytes=None, kernel_ms=None,
+                fills=None, grids=None):
+        """``pw_passage``: the barrier between the seed voxel and the faces of the box of every job of a batch, one row
+        per plane left out (``PASSAGE_JOB_DTYPE`` records indexing the rows of ``xyz`` (rows of three), of ``coef``
+        (rows ``(A, B)``) and of ``planes`` (rows of four), the entries of ``field`` and the rows of the result): a
+        ``PASSAGE_OUT_DTYPE`` array with ``max(m, 1)`` rows a job from its ``out_first`` -- ``out`` given: filled in
+        place, rows no job owns stay as they are.  Whatever the entry refuses -- what ``pw_cavity`` and ``pw_affinity``
+        refuse for the same fields, a field value that is ``-inf`` or not a number, a range outside an array, jobs that
+        share rows --: ``ValueError`` with the library's message.  ``workspace_bytes`` / ``kernel_ms`` (a list that
+        receives the time of the device work by HIP events) / ``fills`` (an int32 array as long as ``out`` that
+        receives the number of flood fills of every row) / ``grids`` (3: the kernel without its fourth bit grid, for
+        the measurement of what that grid buys; the result does not depend on it) go through the library's measurement
+        entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=PASSAGE_JOB_DTYPE).reshape(-1)
+        x = np.zeros((0, 3)) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        c = np.zeros((0, 2)) if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
+        p = np.zeros((0, 4)) if planes is None else np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
+        f = np.zeros(0) if field is None else np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
+        if out is None:
+            rows = int((jobs["out_first"] + np.maximum(jobs["m"], 1)).max()) if len(jobs) else 0
+            out = np.zeros(max(rows, 0), dtype=PASSAGE_OUT_DTYPE)
+        elif out.dtype != PASSAGE_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
+            raise ValueError("out: a C-contiguous PASSAGE_OUT_DTYPE array")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), p.ctypes.data, len(p),
+                f.ctypes.data, len(f), out.ctypes.data, len(out)]
+        if workspace_bytes is None and kernel_ms is None and fills is None and grids is None:
+            _stat_call("pw_passage", *args)
+            return out
+        if fills is not None and (fills.dtype != np.int32 or not fills.flags.c_contiguous or fills.shape != out.shape):
+            raise ValueError("fills: a C-contiguous int32 array as long as out")
+        ms = ctypes.c_float(0.0)
+        _stat_call("pw_internal_passage", *args, int(workspace_bytes or 0), ctypes.byref(ms),
+                   None if fills is None else fills.ctypes.data, int(grids or 0))
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        return out
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

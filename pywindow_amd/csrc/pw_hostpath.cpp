@@ -23,6 +23,7 @@
 #include "pw_cavity.hpp"
 #include "pw_sasa.hpp"
 #include "pw_pores.hpp"
+#include "pw_passage.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -1268,6 +1269,167 @@ extern "C" int pw_hostpath_affinity(const pw_affinity_job* jobs, long n_jobs, co
             hist[(long)J.hist_first + e] = s;
         }
     });
+    return PW_OK;
+}
+
+// pw_passage on the host (pw_passage.hip checks the arguments and sends device == -1 contexts here): the pair terms of
+// pw_affinity.hpp, the plane test and the fill of pw_cavity.hpp, the keys and the bisection of pw_passage.hpp.  Jobs go
+// in order in batches whose maps fit PAS_WORKSPACE_BYTES; within a batch the threads first share out slabs of
+// PAS_HOST_SLAB voxels of the maps of the jobs without a field of their own, then the (job, row) pieces.  A piece builds
+// its held words, then runs level after level: the allowed words from the map, the fill, the face test.
+extern "C" int pw_hostpath_passage(const pw_passage_job* jobs, long n_jobs, const double* xyz, const double* coef,
+                                   const double* planes, const double* field, pw_passage_out* out, int* fills,
+                                   int threads) {
+    typedef cavity_word u64;
+    constexpr long PAS_HOST_SLAB = 4096;
+    struct Piece { long job, a, b; };                                // a slab [a, b) of a map, or row a of a job
+    std::vector<double> maps;
+    std::vector<long> map_first((size_t)n_jobs);
+    for (long first = 0; first < n_jobs;) {
+        long last = first, words = 0;
+        std::vector<Piece> slabs, pieces;
+        for (; last < n_jobs; ++last) {
+            const pw_passage_job& J = jobs[last];
+            const long V = (long)J.nx * J.ny * J.nz;
+            if (last > first && J.field_first == -1 && words + V > PAS_WORKSPACE_BYTES / 8) break;
+            map_first[last] = words;
+            if (J.field_first == -1) {                               // (a caller's field is read in place)
+                words += V;
+                for (long a = 0; a < V; a += PAS_HOST_SLAB) slabs.push_back({last, a, std::min(a + PAS_HOST_SLAB, V)});
+            }
+            for (long k = 0; k < pas_rows_out((long)J.m); ++k) pieces.push_back({last, k, 0});
+        }
+        maps.resize((size_t)words);
+        cov_share((long)slabs.size(), threads, [&](long s) {
+            const Piece& piece = slabs[s];
+            const pw_passage_job& J = jobs[piece.job];
+            const double* atoms = xyz + 3 * (long)J.atom_first;
+            const double* ab = coef + 2 * (long)J.coef_first;
+            double* U = maps.data() + map_first[piece.job];
+            for (long rank = piece.a; rank < piece.b; ++rank) {
+                const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx);
+                const double x = cavity_coord(J.origin[0], i, J.spacing), y = cavity_coord(J.origin[1], row % J.ny, J.spacing),
+                             z = cavity_coord(J.origin[2], row / J.ny, J.spacing);
+                double u_sum = 0.0;
+                bool blocked = false;
+                for (long a = 0; a < (long)J.n && !blocked; ++a) {
+                    const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
+                    blocked = aff_blocked(r2, J.core2);
+                    if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
+                }
+                U[rank] = blocked ? aff_inf() : u_sum;
+            }
+        });
+        cov_share((long)pieces.size(), threads, [&](long p) {
+            const pw_passage_job& J = jobs[pieces[p].job];
+            const long k = pieces[p].a;
+            const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
+            const double* U = J.field_first == -1 ? maps.data() + map_first[pieces[p].job] : field + (long)J.field_first;
+            const double* cuts = planes + 4 * (long)J.plane_first;
+            const CavityHostGrid G{nullptr, nullptr, nullptr, 0, 0, J.origin, J.spacing, nx, ny, nz, J.seed};
+            std::vector<u64> held((size_t)rows), open((size_t)rows), fill((size_t)rows);
+            for (int r = 0; r < rows; ++r) {
+                const double y = cavity_coord(J.origin[1], r % ny, J.spacing), z = cavity_coord(J.origin[2], r / ny, J.spacing);
+                u64 word = cavity_row_mask(nx);
+                for (long q = 0; q < (long)J.m && word; ++q) {
+                    if (q == k) continue;
+                    for (int i = 0; i < nx; ++i)
+                        if (!cavity_inside(cuts + 4 * q, cavity_coord(J.origin[0], i, J.spacing), y, z)) word &= ~(1ull << i);
+                }
+                held[r] = word;
+            }
+            const int seed_row = J.seed[2] * ny + J.seed[1];
+            const long seed_rank = (long)seed_row * nx + J.seed[0];
+            const u64 seed_key = pas_key(U[seed_rank]);
+            pw_passage_out o{};
+            o.u_seed = U[seed_rank];
+            int n_fills = 0;
+            // the level `mid`: open, below, above as the kernel's level pass; then the fill; true iff it is on a face
+            u64 below = 0, above = PAS_KEY_NONE;
+            auto level = [&](u64 mid) {
+                below = 0;
+                above = PAS_KEY_NONE;
+                for (int r = 0; r < rows; ++r) {
+                    u64 word = 0;
+                    for (u64 todo = held[r]; todo; todo &= todo - 1) {
+                        const int i = __builtin_ctzll(todo);
+                        const u64 key = pas_key(U[(long)r * nx + i]);
+                        if (key <= mid) {
+                            word |= 1ull << i;
+                            below = std::max(below, key);
+                        } else if (key < PAS_KEY_INF) {
+                            above = std::min(above, key);
+                        }
+                    }
+                    open[r] = word;
+                }
+                cavity_host_fill(G, open, fill);
+                ++n_fills;
+                long face = 0;
+                for (int r = 0; r < rows; ++r) face += cavity_row_face(fill[r], nx, ny, nz, r % ny, r / ny);
+                return face != 0;
+            };
+            auto count = [&]() {
+                long n = 0;
+                for (int r = 0; r < rows; ++r) n += cavity_popcount(fill[r]);
+                return n;
+            };
+            if (!((held[seed_row] >> J.seed[0]) & 1ull) || seed_key == PAS_KEY_INF) {
+                o.barrier = o.well = aff_inf();
+                for (int a = 0; a < 3; ++a) o.saddle[a] = o.well_voxel[a] = -1;
+                o.flags = PAS_SEED_CLOSED;
+            } else {
+                u64 B = PAS_KEY_NONE;
+                if (!level(PAS_KEY_INF - 1)) {
+                    o.flags = PAS_NO_EXIT;
+                    o.n_fill = o.n_basin = count();
+                } else {
+                    u64 lo = seed_key, hi = below;
+                    for (int step = 0; step < PAS_MAX_STEPS && lo < hi; ++step) {
+                        const u64 mid = lo + ((hi - lo) >> 1);
+                        if (level(mid)) {
+                            hi = below;
+                        } else {
+                            if (above > hi) break;
+                            lo = above;
+                        }
+                    }
+                    B = hi;
+                    if (seed_key < B) {
+                        level(B - 1);
+                        o.n_basin = count();
+                    }
+                    level(B);
+                    o.n_fill = count();
+                }
+                u64 well_key = PAS_KEY_NONE;
+                long well_rank = -1, saddle_rank = -1;
+                for (int r = 0; r < rows; ++r)
+                    for (u64 todo = fill[r]; todo; todo &= todo - 1) {
+                        const long rank = (long)r * nx + __builtin_ctzll(todo);
+                        const u64 key = pas_key(U[rank]);
+                        if (key < well_key) {
+                            well_key = key;
+                            well_rank = rank;
+                        }
+                        if (key == B && saddle_rank < 0) saddle_rank = rank;
+                    }
+                o.barrier = saddle_rank >= 0 ? U[saddle_rank] : aff_inf();
+                o.well = U[well_rank];
+                const long ranks[2] = {saddle_rank, well_rank};
+                for (int w = 0; w < 2; ++w) {
+                    int* v = w ? o.well_voxel : o.saddle;
+                    const long row = ranks[w] / nx;
+                    v[0] = ranks[w] >= 0 ? (int)(ranks[w] - row * nx) : -1;
+                    v[1] = ranks[w] >= 0 ? (int)(row % ny) : -1;
+                    v[2] = ranks[w] >= 0 ? (int)(row / ny) : -1;
+                }
+            }
+            out[(long)J.out_first + k] = o;
+            if (fills) fills[(long)J.out_first + k] = n_fills;
+        });
+        first = last;
+    }
     return PW_OK;
 }
 

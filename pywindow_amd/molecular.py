@@ -287,6 +287,29 @@ class Molecule:
             "spacing": float(spacing)}
         return af
 
+    def calculate_guest_passage(self, guest="Xe", spacing: float = 0.5, close="windows", device=None):
+        """What it costs a one-site Lennard-Jones guest to leave the cage through each window
+        (``pywindow_amd.guest_passage``, on the GPU): the guest's energy with the UFF atoms of the cage at every voxel
+        of the box of ``calculate_cavity`` -- the same grid, seed and planes through the windows --, and per window,
+        with the other windows' planes shut, the lowest energy level that connects the pore centre to the outside
+        (``barrier``), the lowest energy inside it (``well``) and their difference, the activation energy of the hop for
+        the cage as it stands.  ``close=None``: one row without planes, the cheapest way out of the box.  ``guest``: a
+        name of ``pywindow_amd.affinity.GUESTS`` or a ``(sigma, eps_kJ_per_mol)`` pair.  The reference has no
+        counterpart.  Sets ``properties["guest_passage"]``: ``guest``, ``barrier``, ``well``, ``activation``,
+        ``saddle_position``, ``free_exit``, ``no_exit``, ``n_windows``, ``spacing``; ``self.passage`` keeps the
+        :class:`pywindow_amd.Passage`, which is returned.  ``full_analysis`` does not call it."""
+        from . import passage as PA
+
+        planes = self._cavity_planes(close)
+        ps = PA.guest_passage(self.coordinates, self.elements, guest, self.pore_opt_COM, planes, spacing,
+                              self.maximum_diameter / 2.0, core2=0.25, device=device)
+        self.passage = ps
+        self.properties["guest_passage"] = {
+            "guest": guest, "barrier": ps.barrier.copy(), "well": ps.well.copy(), "activation": ps.activation,
+            "saddle_position": ps.saddle_position, "free_exit": ps.free_exit, "no_exit": ps.no_exit,
+            "n_windows": int(ps.n_windows), "spacing": float(spacing)}
+        return ps
+
     def calculate_surface_area(self, probe: float = 0.0, points: int = 960, side=None, device=None) -> float:
         """The solvent-accessible surface area for a probe of radius ``probe`` (``pywindow_amd.surface_area``, Shrake
         and Rupley's test points on the GPU, ``points`` an atom).  ``side=None``: the whole surface, no analysis is

@@ -523,6 +523,21 @@ class DLPOLY:
         return AF.guest_affinity_batch(coords, self.elements(swap_atoms, forcefield), guest, temperatures, cavity=cav,
                                        edges=edges, energies=energies, core2=0.25, device=device, frames=sel)
 
+    def passage(self, guest="Xe", spacing: float = 0.5, frames=None, device=None, close="windows", swap_atoms=None,
+                forcefield=None):
+        """The barrier a one-site Lennard-Jones guest crosses at every window in every frame analysed so far
+        (``frames``: a selection of them), ALL frames in ONE ``pw_passage`` call on the GPU
+        (``pywindow_amd.guest_passage_batch``, UFF atoms, ``core2 = 0.25``), seeded, boxed and closed exactly as
+        :meth:`cavity` -- a :class:`pywindow_amd.Passage` whose fields are ``(frames, windows)`` arrays, the columns in
+        the order of each frame's ``windows``, and whose ``frames`` are the trajectory's frame numbers.
+        ``passage().series("activation")`` goes into ``pywindow_amd.time_correlation``, ``lomb_scargle``,
+        ``gaussian_kde_1d``, ``gate_statistics`` and ``transition_counts``.  Non-modular, non-periodic analyses only."""
+        from . import passage as PA
+
+        sel, coords, radii, seeds, half_widths, planes = self._cavity_inputs("passage", frames, close, swap_atoms, forcefield)
+        return PA.guest_passage_batch(coords, self.elements(swap_atoms, forcefield), guest, seeds, planes, spacing,
+                                      half_widths, core2=0.25, device=device, frames=sel)
+
     def surface(self, probe: float = 0.0, points: int = 960, frames=None, cavity: bool = True, device=None,
                 swap_atoms=None, forcefield=None):
         """The accessible surface of the cage in every frame, all frames in ONE ``pw_sasa`` call on the GPU
