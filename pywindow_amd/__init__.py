@@ -36,6 +36,7 @@ from .surface import Surface, sphere_directions, surface_area, surface_area_batc
 from .pores import PoreSizes, pore_size_distribution, pore_size_distribution_batch  # noqa: E402
 from .affinity import Affinity, guest_affinity, guest_affinity_batch, lj_coefficients  # noqa: E402
 from .passage import Passage, guest_passage, guest_passage_batch, passage_field  # noqa: E402
+from .hopping import Hopping, guest_hopping, guest_hopping_batch, window_frame  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -109,6 +110,10 @@ __all__ = [
     "guest_passage",
     "guest_passage_batch",
     "passage_field",
+    "Hopping",
+    "guest_hopping",
+    "guest_hopping_batch",
+    "window_frame",
     "max_dim",
     "molecular_weight",
     "opt_pore_diameter",

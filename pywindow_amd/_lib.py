@@ -352,6 +352,22 @@ assert PASSAGE_JOB_DTYPE.itemsize == 128 and PASSAGE_OUT_DTYPE.itemsize == 72
 PAS_SEED_CLOSED = 1
 PAS_NO_EXIT = 2
 
+#: numpy mirror of ``pw_hop_job``
+HOP_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
+     ("field_first", np.int64), ("beta_first", np.int64), ("n_betas", np.int64), ("slab_first", np.int64),
+     ("sum_first", np.int64), ("word_first", np.int64), ("out", np.int64), ("origin", np.float64, (3,)),
+     ("spacing", np.float64), ("core2", np.float64), ("cutoff2", np.float64), ("cap", np.float64), ("nx", np.int32),
+     ("ny", np.int32), ("nz", np.int32), ("seed", np.int32, (2,)), ("reserved", np.int32)]
+)
+#: numpy mirrors of ``pw_hop_slab`` and ``pw_hop_out``; the sums are ``AFFINITY_LEVEL_DTYPE`` rows
+HOP_SLAB_DTYPE = np.dtype([("n", np.int64), ("n_face", np.int64), ("u_min", np.float64), ("min_i", np.int32),
+                           ("min_j", np.int32)])
+HOP_OUT_DTYPE = np.dtype([("n", np.int64), ("flags", np.int32), ("reserved", np.int32)])
+assert HOP_JOB_DTYPE.itemsize == 176 and HOP_SLAB_DTYPE.itemsize == 32 and HOP_OUT_DTYPE.itemsize == 16
+#: ``PW_HOP_CLAMPED``
+HOP_CLAMPED = 1
+
 #: numpy mirror of ``pw_extra_window``: a window beyond the W_MAX a record holds
 EXTRA_WINDOW_DTYPE = np.dtype(
     [("unit", np.int64), ("index", np.int32), ("reserved", np.int32), ("d", np.float64), ("c", np.float64, (3,))],
@@ -447,6 +463,7 @@ EXPORTED_SYMBOLS = [
     "pw_pore_sizes",
     "pw_affinity",
     "pw_passage",
+    "pw_hop",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -590,6 +607,8 @@ def load():
     L.pw_passage.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
     L.pw_internal_passage.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64,
                                       ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int]
+    L.pw_hop.argtypes = [vp, vp, i64] + [vp, i64] * 9
+    L.pw_internal_hop.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1311,6 +1330,57 @@ class Context:
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
         return out
+
+    def hop(self, jobs, betas, xyz=None, coef=None, planes=None, field=None, slabs=None, sums=None, out=None, words=None,
+            workspace_bytes=None, kernel_ms=None):
+        """``pw_hop``: per slab of the grid of every job of a batch, the 2-D component of allowed voxels round the seed
+        column and its Boltzmann sums (``HOP_JOB_DTYPE`` records indexing the rows of ``xyz`` (rows of three), of ``coef``
+        (rows ``(A, B)``) and of ``planes`` (rows of four), the entries of ``field`` and of ``betas`` and the rows and
+        entries of the results): ``(slabs, sums, out, words)`` -- ``slabs`` a ``HOP_SLAB_DTYPE`` array with ``nz`` rows
+        a job from its ``slab_first``, ``sums`` an ``AFFINITY_LEVEL_DTYPE`` array with ``nz * n_betas`` rows a job from
+        its ``sum_first``, ``out`` a ``HOP_OUT_DTYPE`` array and ``words`` the uint64 words of the jobs with
+        ``word_first >= 0``, ``ny * nz`` a job (``None`` when no job has one); given: filled in place, entries no job
+        owns stay as they are.  Whatever the entry refuses -- what ``pw_passage`` refuses for the same fields, a cap
+        that is not finite, a seed column outside the grid, a beta that is negative or not finite, a range outside an
+        array, jobs that share outputs --: ``ValueError`` with the library's message.  ``workspace_bytes`` /
+        ``kernel_ms`` (a list that receives ``(total, field kernels, slab kernels)`` in ms by HIP events) go through the
+        library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=HOP_JOB_DTYPE).reshape(-1)
+        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        x = np.zeros((0, 3)) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        c = np.zeros((0, 2)) if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
+        p = np.zeros((0, 4)) if planes is None else np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
+        f = np.zeros(0) if field is None else np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
+
+        def result(given, dtype, size, name):
+            if given is None:
+                return np.zeros(max(int(size), 0), dtype=dtype)
+            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError(f"{name}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+            return given
+
+        some = len(jobs) > 0
+        nz = jobs["nz"].astype(np.int64)
+        slabs = result(slabs, HOP_SLAB_DTYPE, (jobs["slab_first"] + nz).max() if some else 0, "slabs")
+        sums = result(sums, AFFINITY_LEVEL_DTYPE, (jobs["sum_first"] + nz * jobs["n_betas"]).max() if some else 0, "sums")
+        out = result(out, HOP_OUT_DTYPE, jobs["out"].max() + 1 if some else 0, "out")
+        with_words = jobs[jobs["word_first"] >= 0]
+        if words is None and len(with_words):
+            size = (with_words["word_first"] + with_words["ny"].astype(np.int64) * with_words["nz"]).max()
+            words = np.zeros(max(int(size), 0), dtype=np.uint64)
+        elif words is not None:
+            words = result(words, np.uint64, 0, "words")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), p.ctypes.data, len(p),
+                f.ctypes.data, len(f), b.ctypes.data, len(b), slabs.ctypes.data, len(slabs), sums.ctypes.data, len(sums),
+                out.ctypes.data, len(out), None if words is None else words.ctypes.data, 0 if words is None else len(words)]
+        if workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_hop", *args)
+            return slabs, sums, out, words
+        ms = (ctypes.c_float * 3)()
+        _stat_call("pw_internal_hop", *args, int(workspace_bytes or 0), ms)
+        if kernel_ms is not None:
+            kernel_ms.append((float(ms[0]), float(ms[1]), float(ms[2])))
+        return slabs, sums, out, words
 
     def circumcircle(self, coordinates, atom_sets):
         """``pw_circumcircle``: (diameters (K,), centres (K, 3)) for K atom triples of one molecule."""

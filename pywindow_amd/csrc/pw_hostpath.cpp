@@ -24,6 +24,7 @@
 #include "pw_sasa.hpp"
 #include "pw_pores.hpp"
 #include "pw_passage.hpp"
+#include "pw_hop.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -1428,6 +1429,147 @@ extern "C" int pw_hostpath_passage(const pw_passage_job* jobs, long n_jobs, cons
             out[(long)J.out_first + k] = o;
             if (fills) fills[(long)J.out_first + k] = n_fills;
         });
+        first = last;
+    }
+    return PW_OK;
+}
+
+// pw_hop on the host (pw_hop.hip checks the arguments and sends device == -1 contexts here): the pair terms of
+// pw_affinity.hpp, the plane test of pw_cavity.hpp, the fill, the minimum and the sums of pw_hop.hpp.  Jobs go in order
+// in batches whose maps fit HOP_WORKSPACE_BYTES; within a batch the threads first share out slabs of HOP_HOST_SLAB voxels
+// of the maps of the jobs without a field of their own, then the (job, slab) pieces; a job's row of out is put together
+// from its pieces' counts and flags afterwards.
+extern "C" int pw_hostpath_hop(const pw_hop_job* jobs, long n_jobs, const double* xyz, const double* coef,
+                               const double* planes, const double* field, const double* betas, pw_hop_slab* slabs,
+                               pw_affinity_level* sums, pw_hop_out* out, unsigned long long* words, int threads) {
+    typedef cavity_word u64;
+    constexpr long HOP_HOST_SLAB = 4096;
+    struct Piece { long job, a, b; };                                // a slab [a, b) of a map, or slab a of a job
+    std::vector<double> maps;
+    std::vector<long> map_first((size_t)n_jobs);
+    for (long first = 0; first < n_jobs;) {
+        long last = first, map_words = 0;
+        std::vector<Piece> slices, pieces;
+        for (; last < n_jobs; ++last) {
+            const pw_hop_job& J = jobs[last];
+            const long V = (long)J.nx * J.ny * J.nz;
+            if (last > first && J.field_first == -1 && map_words + V > HOP_WORKSPACE_BYTES / 8) break;
+            map_first[last] = map_words;
+            if (J.field_first == -1) {                               // (a caller's field is read in place)
+                map_words += V;
+                for (long a = 0; a < V; a += HOP_HOST_SLAB) slices.push_back({last, a, std::min(a + HOP_HOST_SLAB, V)});
+            }
+            for (long l = 0; l < J.nz; ++l) pieces.push_back({last, l, 0});
+        }
+        maps.resize((size_t)map_words);
+        std::vector<int> piece_flags(pieces.size(), 0);
+        cov_share((long)slices.size(), threads, [&](long s) {
+            const Piece& piece = slices[s];
+            const pw_hop_job& J = jobs[piece.job];
+            const double* atoms = xyz + 3 * (long)J.atom_first;
+            const double* ab = coef + 2 * (long)J.coef_first;
+            double* U = maps.data() + map_first[piece.job];
+            for (long rank = piece.a; rank < piece.b; ++rank) {
+                const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx);
+                const double x = cavity_coord(J.origin[0], i, J.spacing), y = cavity_coord(J.origin[1], row % J.ny, J.spacing),
+                             z = cavity_coord(J.origin[2], row / J.ny, J.spacing);
+                double u_sum = 0.0;
+                bool blocked = false;
+                for (long a = 0; a < (long)J.n && !blocked; ++a) {
+                    const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
+                    blocked = aff_blocked(r2, J.core2);
+                    if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
+                }
+                U[rank] = blocked ? aff_inf() : u_sum;
+            }
+        });
+        cov_share((long)pieces.size(), threads, [&](long p) {
+            const pw_hop_job& J = jobs[pieces[p].job];
+            const int l = (int)pieces[p].a, nx = J.nx, ny = J.ny, L = (int)J.n_betas;
+            const double* U = (J.field_first == -1 ? maps.data() + map_first[pieces[p].job] : field + (long)J.field_first) +
+                              (long)l * ny * nx;
+            const double* cuts = planes + 4 * (long)J.plane_first;
+            const double z = cavity_coord(J.origin[2], l, J.spacing);
+            u64 open[CAVITY_MAX_G], fill[CAVITY_MAX_G];
+            for (int j = 0; j < ny; ++j) {
+                const double y = cavity_coord(J.origin[1], j, J.spacing);
+                u64 word = 0;
+                for (int i = 0; i < nx; ++i) {
+                    bool ok = hop_admits(U[(long)j * nx + i], J.cap);
+                    const double x = cavity_coord(J.origin[0], i, J.spacing);
+                    for (long q = 0; q < (long)J.m && ok; ++q) ok = cavity_inside(cuts + 4 * q, x, y, z);
+                    if (ok) word |= 1ull << i;
+                }
+                open[j] = word;
+                fill[j] = 0;
+            }
+            fill[J.seed[1]] = open[J.seed[1]] & (1ull << J.seed[0]);
+            const long max_sweeps = (long)nx * ny + 1;
+            for (long sweep = 0; sweep < max_sweeps; ++sweep) {
+                bool changed = false;
+                for (int j = 0; j < ny; ++j) {                       // (in place: a row may see this sweep's neighbour)
+                    const u64 from = fill[j] | (j > 0 ? fill[j - 1] : 0) | (j + 1 < ny ? fill[j + 1] : 0);
+                    const u64 g = hop_fill_word(from, open[j]);
+                    changed = changed || g != fill[j];
+                    fill[j] = g;
+                }
+                if (!changed) break;
+            }
+            pw_hop_slab s{0, 0, aff_inf(), -1, -1};
+            int best_pos = 0x7fffffff;
+            for (int j = 0; j < ny; ++j) {
+                s.n += cavity_popcount(fill[j]);
+                s.n_face += hop_row_face(fill[j], nx, ny, j);
+                if (words && J.word_first >= 0) words[(long)J.word_first + (long)l * ny + j] = fill[j];
+            }
+            // the voxels in rank order, 64 a chunk
+            double z_total[AFF_MAX_LEVELS], e_total[AFF_MAX_LEVELS], u[AFF_CHUNK], slot_z[AFF_CHUNK], slot_e[AFF_CHUNK];
+            for (int b = 0; b < L; ++b) z_total[b] = e_total[b] = 0.0;
+            bool clamped = false;
+            int held = 0, j = 0;
+            u64 todo = ny ? fill[0] : 0;
+            for (long done = 0; done < s.n;) {
+                for (held = 0; held < AFF_CHUNK && done < s.n;) {
+                    while (!todo) todo = fill[++j];                  // (done < n: a voxel is left in a later row)
+                    const int i = __builtin_ctzll(todo);
+                    todo &= todo - 1;
+                    u[held] = U[(long)j * nx + i];
+                    if (hop_before(u[held], j * 64 + i, s.u_min, best_pos)) {
+                        s.u_min = u[held];
+                        best_pos = j * 64 + i;
+                    }
+                    ++held;
+                    ++done;
+                }
+                for (int b = 0; b < L; ++b) {
+                    for (int t = 0; t < AFF_CHUNK; ++t) {
+                        slot_z[t] = slot_e[t] = 0.0;
+                        if (t >= held) continue;
+                        const double w = aff_weight(betas[(long)J.beta_first + b], u[t], POW_EXP_TAB, clamped);
+                        slot_z[t] = w;
+                        slot_e[t] = w * u[t];
+                    }
+                    z_total[b] = z_total[b] + aff_tree(slot_z);
+                    e_total[b] = e_total[b] + aff_tree(slot_e);
+                }
+            }
+            if (s.n) {
+                s.min_i = best_pos & 63;
+                s.min_j = best_pos >> 6;
+            }
+            slabs[(long)J.slab_first + l] = s;
+            for (int b = 0; b < L; ++b) sums[(long)J.sum_first + (long)l * L + b] = pw_affinity_level{z_total[b], e_total[b]};
+            piece_flags[(size_t)p] = clamped ? HOP_CLAMPED : 0;
+        });
+        for (size_t p = 0; p < pieces.size();) {                     // (a job's pieces follow one another)
+            const pw_hop_job& J = jobs[pieces[p].job];
+            pw_hop_out o{0, 0, 0};
+            for (long l = 0; l < J.nz; ++l, ++p) {
+                o.n += slabs[(long)J.slab_first + l].n;
+                o.flags |= piece_flags[p];
+            }
+            out[(long)J.out] = o;
+        }
         first = last;
     }
     return PW_OK;

@@ -35,6 +35,7 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_cavity_dev.hpp"
+#include "pw_field_dev.hpp"
 #include "pw_passage.hpp"
 #include "pw_stat_host.hpp"
 
@@ -71,38 +72,7 @@ struct PasJobDev {
 __global__ void __launch_bounds__(AFF_CHUNK)
 pw_passage_field_kernel(const PasJobDev* __restrict__ jobs, int n_jobs, long total, const double* __restrict__ xyz,
                         const double* __restrict__ coef, u64* __restrict__ ws) {
-    __shared__ double s_xyz[3 * PAS_FIELD_TILE];
-    __shared__ double s_coef[2 * PAS_FIELD_TILE];
-    const int lane = threadIdx.x;
-    for (long item = blockIdx.x; item < total; item += gridDim.x) {
-        const int k = stat_find(n_jobs, item, [&](int q) { return jobs[q].item_first; });
-        const PasJobDev& J = jobs[k];
-        const long chunk = item - J.item_first, rank = chunk * AFF_CHUNK + lane;
-        const bool valid = rank < J.V;
-        const int nx = J.nx, ny = J.ny;
-        const int row = valid ? (int)(rank / nx) : 0, i = valid ? (int)(rank - (long)row * nx) : 0;
-        const double x = cavity_coord(J.o[0], i, J.h), y = cavity_coord(J.o[1], row % ny, J.h),
-                     z = cavity_coord(J.o[2], row / ny, J.h);
-        const double core2 = J.core2, cutoff2 = J.cutoff2;
-        const double* atoms = xyz + 3 * J.atom_first;
-        const double* rows_ab = coef + 2 * J.coef_first;
-        double U = 0.0;
-        bool blocked = false;
-        for (long a0 = 0; a0 < J.n; a0 += PAS_FIELD_TILE) {
-            const int len = (int)(J.n - a0 < PAS_FIELD_TILE ? J.n - a0 : PAS_FIELD_TILE);
-            __syncthreads();                                         // (the atoms staged before are done with)
-            for (int t = lane; t < 3 * len; t += AFF_CHUNK) s_xyz[t] = atoms[3 * a0 + t];
-            for (int t = lane; t < 2 * len; t += AFF_CHUNK) s_coef[t] = rows_ab[2 * a0 + t];
-            __syncthreads();
-            for (int t = 0; t < len; ++t) {
-                const double r2 = aff_r2(x - s_xyz[3 * t], y - s_xyz[3 * t + 1], z - s_xyz[3 * t + 2]);
-                blocked = blocked || aff_blocked(r2, core2);
-                const double u = aff_pair(r2, s_coef[2 * t], s_coef[2 * t + 1]);
-                U = aff_counts(r2, cutoff2) ? U + u : U;
-            }
-        }
-        if (valid) ws[J.map_first + rank] = pw_d2bits(blocked ? aff_inf() : U);
-    }
+    field_items(jobs, n_jobs, total, xyz, coef, ws);                 // (pw_field_dev.hpp, shared with pw_hop.hip)
 }
 
 // held: a wave takes rows (j, l), lane i is voxel i; every plane but `skip`, 64 at a time.  LOW: the kernel keeps s_low

@@ -310,6 +310,29 @@ class Molecule:
             "n_windows": int(ps.n_windows), "spacing": float(spacing)}
         return ps
 
+    def calculate_guest_hopping(self, guest="Xe", temperature: float = 298.0, spacing: float = 0.25, device=None):
+        """How fast a one-site Lennard-Jones guest hops out of the cage through each window
+        (``pywindow_amd.guest_hopping``, on the GPU): the free-energy profile of the guest along the line from the
+        optimised pore centre through every window of ``calculate_windows``, the other windows' planes shut, and the
+        transition-state-theory rate ``sqrt(k_B T / 2 pi m) * area / well_volume`` at ``temperature`` (K) for the cage
+        as it stands.  ``guest``: a name of ``pywindow_amd.affinity.GUESTS``.  The reference has no counterpart.  Sets
+        ``properties["guest_hopping"]``: ``guest``, ``temperature``, ``rate``, ``free_barrier``, ``area``,
+        ``well_volume``, ``escape_rate``, ``valid``, ``free_exit``, ``n_windows``, ``spacing``; ``self.hopping`` keeps
+        the :class:`pywindow_amd.Hopping`, which is returned.  ``full_analysis`` does not call it."""
+        from . import hopping as HP
+
+        self._cavity_planes("windows")
+        hp = HP.guest_hopping(self.coordinates, self.elements, guest, self.pore_opt_COM,
+                              self.properties["windows"]["centre_of_mass"], [temperature], spacing, device=device)
+        self.hopping = hp
+        self.properties["guest_hopping"] = {
+            "guest": guest, "temperature": float(temperature), "rate": hp.rate[:, 0].copy(),
+            "free_barrier": hp.free_barrier[:, 0].copy(), "area": hp.area[:, 0].copy(),
+            "well_volume": hp.well_volume[:, 0].copy(), "escape_rate": float(hp.escape_rate[0]),
+            "valid": hp.valid[:, 0].copy(), "free_exit": hp.free_exit[:, 0].copy(), "n_windows": int(hp.n_windows[0]),
+            "spacing": float(spacing)}
+        return hp
+
     def calculate_surface_area(self, probe: float = 0.0, points: int = 960, side=None, device=None) -> float:
         """The solvent-accessible surface area for a probe of radius ``probe`` (``pywindow_amd.surface_area``, Shrake
         and Rupley's test points on the GPU, ``points`` an atom).  ``side=None``: the whole surface, no analysis is

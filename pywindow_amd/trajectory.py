@@ -436,9 +436,10 @@ class DLPOLY:
         store.attach_tracks(tracks)
         return tracks
 
-    def _cavity_inputs(self, what: str, frames, close, swap_atoms, forcefield):
+    def _cavity_inputs(self, what: str, frames, close, swap_atoms, forcefield, centres: bool = False):
         """What :meth:`cavity` and :meth:`pore_sizes` hand to their kernels for the analysed frames (``frames``: a
-        selection of them): ``(frame numbers, coordinates, radii, seeds, half widths, planes)``."""
+        selection of them): ``(frame numbers, coordinates, radii, seeds, half widths, planes)`` -- with ``centres`` the
+        window centres of every frame in place of the planes through them (:meth:`hopping`)."""
         from .utilities import window_planes
 
         if close not in ("windows", None):
@@ -472,6 +473,9 @@ class DLPOLY:
             planes = []
             for i in rows:
                 win = engine.windows_of(recs[i], more.get(i))
+                if centres:
+                    planes.append(None if win is None else np.asarray(win[1], dtype=np.float64).reshape(-1, 3))
+                    continue
                 planes.append(None if win is None else window_planes(recs["pore_opt_c"][i], win[1]))
         radii = VDW[element_ids(self.elements(swap_atoms, forcefield))]
         return (sel, coords, radii, np.asarray(recs["pore_opt_c"][rows], dtype=np.float64),
@@ -537,6 +541,24 @@ class DLPOLY:
         sel, coords, radii, seeds, half_widths, planes = self._cavity_inputs("passage", frames, close, swap_atoms, forcefield)
         return PA.guest_passage_batch(coords, self.elements(swap_atoms, forcefield), guest, seeds, planes, spacing,
                                       half_widths, core2=0.25, device=device, frames=sel)
+
+    def hopping(self, guest="Xe", temperatures=298.0, frames=None, spacing: float = 0.25, device=None, swap_atoms=None,
+                forcefield=None):
+        """The free-energy profile of a one-site Lennard-Jones guest through every window and the hopping rate built on
+        it in every frame analysed so far (``frames``: a selection of them), every (frame, window) a job of ONE
+        ``pw_hop`` call on the GPU (``pywindow_amd.guest_hopping_batch``, UFF atoms, ``core2 = 0.25``): each record's
+        optimised pore centre and window centres -- a :class:`pywindow_amd.Hopping` whose fields are arrays over
+        (frames, windows), the columns in the order of each frame's ``windows``, and whose ``frames`` are the
+        trajectory's frame numbers.  The breathing of a window, not the mean structure, sets the rate:
+        ``hopping().mean_rate()`` is the ensemble rate and ``hopping().series("rate")`` goes into
+        ``pywindow_amd.time_correlation``, ``lomb_scargle``, ``gaussian_kde_1d``, ``gate_statistics`` and
+        ``transition_counts``.  Non-modular, non-periodic analyses only."""
+        from . import hopping as HP
+
+        sel, coords, radii, seeds, half_widths, wins = self._cavity_inputs("hopping", frames, "windows", swap_atoms, forcefield,
+                                                                           centres=True)
+        return HP.guest_hopping_batch(coords, self.elements(swap_atoms, forcefield), guest, seeds, wins, temperatures,
+                                      spacing, core2=0.25, device=device, frames=sel)
 
     def surface(self, probe: float = 0.0, points: int = 960, frames=None, cavity: bool = True, device=None,
                 swap_atoms=None, forcefield=None):
