@@ -1115,6 +1115,80 @@ int pw_hop(pw_context *ctx, const pw_hop_job *jobs, int64_t n_jobs, const double
            const double *coef, int64_t n_coef, const double *planes, int64_t n_planes, const double *field,
            int64_t n_field, const double *betas, int64_t n_betas, pw_hop_slab *slabs, int64_t n_slabs,
            pw_affinity_level *sums, int64_t n_sums, pw_hop_out *out, int64_t n_out, uint64_t *words, int64_t n_words);
+/* ---- rigid linear guests: the orientation-averaged affinity of a cavity ------------------------------------------
+ * pw_affinity for a guest that is not a sphere: a rigid linear molecule (N2, CO2, O2 -- sites on one axis, optional
+ * point charges) inserted at every voxel of a region in every one of M orientations, the Boltzmann sums averaged over
+ * the orientations.  The reference has no counterpart.  Job k has the grid, the region (word_first, or -1: every
+ * voxel), core2, cutoff2 and the L = n_betas betas exactly as a pw_affinity job, n >= 0 atoms xyz[atom_first .. +n), and
+ *     sites   S = n_sites offsets t_s = offsets[site_first .. +S) along the guest's axis, 1 <= S <= PW_RIGID_MAX_SITES,
+ *             each finite with |t_s| <= 16;
+ *     rows    (A, B, C) per (site, atom), coef[coef_first + s*n + a], three doubles a row: 0 <= A, B <= 1e100, C finite
+ *             with |C| <= 1e100 (C = q_a q_s / (4 pi eps_0) in the caller's units);
+ *     charged 0 or 1: with 0 the column C is neither read nor evaluated;
+ *     dirs    M = n_dirs directions dirs[dir_first .. +M), 1 <= M <= PW_RIGID_MAX_DIRS, three doubles each, every
+ *             component finite and within [-1, 1].  The directions are data: nothing normalises them or checks their
+ *             length;
+ *     map_level  -1, or 0 <= map_level < L together with map_first >= 0.
+ * POSE (v, o).  Voxel v has the centre (x, y, z) as in pw_cavity; orientation o the direction (dx, dy, dz).  Site s sits
+ * at px = x + (t_s * dx), likewise py and pz: the product is rounded, then the sum; no contraction.  Per site the atoms
+ * go in index order: r2 as in pw_affinity from (px - X, py - Y, pz - Z); the POSE is BLOCKED iff r2 <= core2 for any
+ * (site, atom); an atom COUNTS for a site iff cutoff2 == 0.0 or r2 <= cutoff2; for a counting atom u is pw_affinity's
+ * pair term from (A, B) and, when charged, u = u + C / sqrt(r2), the square root and the division correctly rounded;
+ * U_s = U_s + u from +0.0.  The pose's energy is U = U_0, then U = U + U_s for s = 1 .. S-1.
+ * WEIGHT.  Per beta and pose that is not blocked: w as in pw_affinity's WEIGHT from (beta, U), the clamp at 700 and
+ * PW_AFF_CLAMPED in the job's flags included; the terms are z = w and e = w * U.
+ * VOXEL.  Per beta zs = +0.0 and es = +0.0; for o = 0 .. M-1 in order zs = zs + z and es = es + e, blocked poses
+ * skipped; zbar = zs * inv_M and ebar = es * inv_M with inv_M = 1.0 / (double)M.  umin_v is the smallest U of the
+ * voxel's poses that are not blocked, by strict < in o order, +inf without one.  A voxel whose poses are all blocked is
+ * DEAD.
+ * SUMS.  Exactly pw_affinity's SUMS on the slots zbar and ebar: ranks by (l, j, i), chunks of 64 ranks, the tree k = 1,
+ * 2, 4, 8, 16, 32, the chunk sums added in chunk order from +0.0; no floating-point atomics.  FP64 without contraction in
+ * the association written: the same bytes on every device, launch geometry and run and on a device == -1 context.
+ * Written: row `out` (n_voxels, n_blocked_poses, n_dead, u_min -- the smallest pose energy, ties to the lowest rank
+ * and then the lowest o; +inf with min_voxel = min_dir = -1 without one --, min_voxel = (i, j, l), min_dir = o, the
+ * flags); rows levels[level_first + b] = (Z_b, E_b), the totals of zbar and ebar; and, when map_level >= 0, per rank
+ * the two doubles maps[map_first + 2*rank] = zbar at that level and maps[map_first + 2*rank + 1] = umin_v.
+ * With S = 1, t_0 = 0, M = 1 and charged = 0 every output shared with pw_affinity is pw_affinity's bytes.
+ * All pointers are host memory; n_points, n_coef, n_offsets, n_dirs, n_words, n_betas, n_maps, n_levels and n_out are
+ * the rows of xyz, of coef (three doubles) and the entries of offsets, the rows of dirs, the entries of words, betas
+ * and maps (doubles), the rows of levels and of out.  Jobs may share every input but no row of out or of levels and no
+ * entry of maps; entries no job owns are never touched.  What is refused, and how, is as in pw_affinity
+ * (PW_E_BAD_ARG, pw_last_error names the job -- of two that share, the later -- and the reason; nothing is launched
+ * or written). */
+#define PW_RIGID_MAX_SITES 8
+#define PW_RIGID_MAX_DIRS 1024
+typedef struct pw_rigid_job {
+    int64_t atom_first, n;          /* atoms = xyz[atom_first .. +n), n >= 0 */
+    int64_t coef_first;             /* rows (A, B, C) = coef[coef_first .. + n_sites*n), row s*n + a */
+    int64_t word_first;             /* the region = words[word_first .. + ny*nz), or -1: every voxel */
+    int64_t beta_first, n_betas;    /* betas[beta_first .. +n_betas) */
+    int64_t site_first, n_sites;    /* offsets[site_first .. +n_sites) */
+    int64_t dir_first, n_dirs;      /* dirs[dir_first .. +n_dirs), rows of three */
+    int64_t level_first;            /* levels[level_first .. +n_betas) is written */
+    int64_t map_first;              /* maps[map_first .. + 2*V) is written when map_level >= 0 */
+    int64_t out;                    /* the job's row of out */
+    double  origin[3];              /* the centre of voxel (0, 0, 0) */
+    double  spacing;                /* h > 0 */
+    double  core2;                  /* >= 1e-6 */
+    double  cutoff2;                /* 0.0: none; otherwise > core2 */
+    int32_t nx, ny, nz;             /* 1 .. PW_CAVITY_MAX_G */
+    int32_t charged;                /* 0 or 1 */
+    int32_t map_level;              /* -1: no map; otherwise the beta whose zbar is written */
+    int32_t reserved;               /* padding to a multiple of 8 bytes; not read */
+} pw_rigid_job;
+typedef struct pw_rigid_out {
+    int64_t n_voxels, n_blocked_poses, n_dead;
+    double  u_min;
+    int32_t min_voxel[3];           /* (i, j, l), or -1 */
+    int32_t min_dir;                /* o, or -1 */
+    int32_t flags;                  /* PW_AFF_* */
+    int32_t reserved;               /* padding to a multiple of 8 bytes; written as 0 */
+} pw_rigid_out;
+int pw_rigid_affinity(pw_context *ctx, const pw_rigid_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+                      const double *coef, int64_t n_coef, const double *offsets, int64_t n_offsets, const double *dirs,
+                      int64_t n_dirs, const uint64_t *words, int64_t n_words, const double *betas, int64_t n_betas,
+                      double *maps, int64_t n_maps, pw_affinity_level *levels, int64_t n_levels, pw_rigid_out *out,
+                      int64_t n_out);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

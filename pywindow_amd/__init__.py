@@ -35,6 +35,14 @@ from .cavity import Cavity, cavity_grid, cavity_grid_batch  # noqa: E402
 from .surface import Surface, sphere_directions, surface_area, surface_area_batch  # noqa: E402
 from .pores import PoreSizes, pore_size_distribution, pore_size_distribution_batch  # noqa: E402
 from .affinity import Affinity, guest_affinity, guest_affinity_batch, lj_coefficients  # noqa: E402
+from .rigid import (  # noqa: E402
+    RIGID_GUESTS,
+    RigidAffinity,
+    RigidGuest,
+    rigid_coefficients,
+    rigid_guest_affinity,
+    rigid_guest_affinity_batch,
+)
 from .passage import Passage, guest_passage, guest_passage_batch, passage_field  # noqa: E402
 from .hopping import Hopping, guest_hopping, guest_hopping_batch, window_frame  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
@@ -106,6 +114,12 @@ __all__ = [
     "guest_affinity",
     "guest_affinity_batch",
     "lj_coefficients",
+    "RIGID_GUESTS",
+    "RigidAffinity",
+    "RigidGuest",
+    "rigid_coefficients",
+    "rigid_guest_affinity",
+    "rigid_guest_affinity_batch",
     "Passage",
     "guest_passage",
     "guest_passage_batch",

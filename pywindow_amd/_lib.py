@@ -335,6 +335,23 @@ AFF_MAX_LEVELS = 8
 AFF_MAX_EDGES = 16
 AFF_CLAMPED = 1
 
+#: numpy mirrors of ``pw_rigid_job`` and ``pw_rigid_out``; the levels are ``AFFINITY_LEVEL_DTYPE`` rows
+RIGID_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("word_first", np.int64),
+     ("beta_first", np.int64), ("n_betas", np.int64), ("site_first", np.int64), ("n_sites", np.int64),
+     ("dir_first", np.int64), ("n_dirs", np.int64), ("level_first", np.int64), ("map_first", np.int64), ("out", np.int64),
+     ("origin", np.float64, (3,)), ("spacing", np.float64), ("core2", np.float64), ("cutoff2", np.float64),
+     ("nx", np.int32), ("ny", np.int32), ("nz", np.int32), ("charged", np.int32), ("map_level", np.int32),
+     ("reserved", np.int32)]
+)
+RIGID_OUT_DTYPE = np.dtype([("n_voxels", np.int64), ("n_blocked_poses", np.int64), ("n_dead", np.int64),
+                            ("u_min", np.float64), ("min_voxel", np.int32, (3,)), ("min_dir", np.int32),
+                            ("flags", np.int32), ("reserved", np.int32)])
+assert RIGID_JOB_DTYPE.itemsize == 176 and RIGID_OUT_DTYPE.itemsize == 56
+#: ``PW_RIGID_MAX_SITES``, ``PW_RIGID_MAX_DIRS``
+RIGID_MAX_SITES = 8
+RIGID_MAX_DIRS = 1024
+
 #: numpy mirror of ``pw_passage_job``
 PASSAGE_JOB_DTYPE = np.dtype(
     [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
@@ -464,6 +481,7 @@ EXPORTED_SYMBOLS = [
     "pw_affinity",
     "pw_passage",
     "pw_hop",
+    "pw_rigid_affinity",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -609,6 +627,8 @@ def load():
                                       ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int]
     L.pw_hop.argtypes = [vp, vp, i64] + [vp, i64] * 9
     L.pw_internal_hop.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9
+    L.pw_internal_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1293,6 +1313,50 @@ class Context:
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
         return out, levels, hist, energies
+
+    def rigid_affinity(self, jobs, xyz, coef, offsets, dirs, betas, words=None, out=None, levels=None, maps=None,
+                       workspace_bytes=None, kernel_ms=None):
+        """``pw_rigid_affinity``: the orientation-averaged affinity of the regions of a batch of jobs for a rigid linear
+        guest (``RIGID_JOB_DTYPE`` records indexing the rows of ``xyz`` (rows of three), of ``coef`` (rows
+        ``(A, B, C)``, row ``s * n + a`` of a job) and of ``dirs`` (rows of three), the entries of ``offsets``, of
+        ``words`` (uint64, a region in the layout of ``pw_cavity``'s mask; ``word_first = -1``: every voxel) and of
+        ``betas``, and the rows and entries of the results): ``(out, levels, maps)`` -- ``out`` a ``RIGID_OUT_DTYPE``
+        array, ``levels`` an ``AFFINITY_LEVEL_DTYPE`` array with ``n_betas`` rows a job from its ``level_first`` and
+        ``maps`` float64, two entries a voxel of a job with ``map_level >= 0`` (given: filled in place, entries no job
+        owns stay as they are; such a job needs ``maps`` given, since only the library counts the voxels of a
+        region).  Whatever the entry refuses: ``ValueError`` with the library's message.  ``workspace_bytes`` /
+        ``kernel_ms`` (a list that receives the time of the device work by HIP events) go through the library's
+        measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=RIGID_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        w = np.zeros(0, dtype=np.uint64) if words is None else np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
+
+        def result(given, dtype, size, name):
+            if given is None:
+                return np.zeros(max(int(size), 0), dtype=dtype)
+            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError(f"{name}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+            return given
+
+        some = len(jobs) > 0
+        out = result(out, RIGID_OUT_DTYPE, jobs["out"].max() + 1 if some else 0, "out")
+        levels = result(levels, AFFINITY_LEVEL_DTYPE, (jobs["level_first"] + jobs["n_betas"]).max() if some else 0, "levels")
+        maps = result(maps, np.float64, 0, "maps")
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), t.ctypes.data, len(t),
+                d.ctypes.data, len(d), w.ctypes.data, len(w), b.ctypes.data, len(b), maps.ctypes.data, len(maps),
+                levels.ctypes.data, len(levels), out.ctypes.data, len(out)]
+        if workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_rigid_affinity", *args)
+            return out, levels, maps
+        ms = ctypes.c_float(0.0)
+        _stat_call("pw_internal_rigid_affinity", *args, int(workspace_bytes or 0), ctypes.byref(ms))
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        return out, levels, maps
 
     def passage(self, jobs, xyz=None, coef=None, planes=None, field=None, out=None, workspace_bytes=None, kernel_ms=None,
                 fills=None, grids=None):

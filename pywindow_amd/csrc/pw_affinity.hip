@@ -1,7 +1,8 @@
 // pw_affinity.hip -- gfx950 kernels and the C ABI entry of the Lennard-Jones energy map of a cavity and its Boltzmann
 // sums (include/pywindow_amd.h: pw_affinity; definition of the result in pw_affinity.hpp).  Three kernels a launch group:
-//   prefix   a workgroup a job that has a mask: the exclusive prefix of the popcounts of its ny * nz words (bits at
-//            i >= nx dropped), rows + 1 integers in the workspace.  A thread takes at most 16 consecutive rows.
+//   prefix   (pw_affinity_dev.hpp, shared with pw_rigid.hip) a workgroup a job that has a mask: the exclusive prefix of
+//            the popcounts of its ny * nz words (bits at i >= nx dropped), rows + 1 integers in the workspace.  A thread
+//            takes at most 16 consecutive rows.
 //   main     a work item is (job, chunk of 64 ranks) and a wavefront takes one item after the other; the job of an item
 //            is found by binary search in the prefix of work items, so one launch serves any mix of grids.  A lane is a
 //            rank: to a row by binary search in the job's prefix (at most 12 steps), then to the bit inside the word
@@ -25,6 +26,7 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_affinity.hpp"
+#include "pw_affinity_dev.hpp"
 #include "pw_stat_host.hpp"
 
 using namespace pw;
@@ -43,8 +45,6 @@ namespace {
 
 typedef cavity_word u64;
 
-constexpr int AFF_PREFIX_THREADS = 256;
-
 // a job as the kernels read it: firsts relative to the spans of the arrays that were uploaded
 struct AffJobDev {
     long atom_first, n, coef_first;
@@ -59,30 +59,6 @@ struct AffJobDev {
     double o[3], h, core2, cutoff2;
     int nx, ny, nz, L, E, reserved;
 };
-
-__global__ void __launch_bounds__(AFF_PREFIX_THREADS)
-pw_affinity_prefix_kernel(const AffJobDev* __restrict__ jobs, const u64* __restrict__ words, u64* __restrict__ ws) {
-    __shared__ int s_sum[AFF_PREFIX_THREADS];
-    const AffJobDev& J = jobs[blockIdx.x];
-    if (J.prefix_first < 0) return;                                  // (the same in every thread)
-    const int rows = J.ny * J.nz, t = threadIdx.x;
-    const int per = (rows + AFF_PREFIX_THREADS - 1) / AFF_PREFIX_THREADS;   // <= 16
-    const int begin = t * per < rows ? t * per : rows, end = begin + per < rows ? begin + per : rows;
-    const u64 xmask = cavity_row_mask(J.nx);
-    const u64* w = words + J.word_first;
-    int* prefix = (int*)(ws + J.prefix_first);
-    int mine = 0;
-    for (int r = begin; r < end; ++r) mine += cavity_popcount(w[r] & xmask);
-    s_sum[t] = mine;
-    __syncthreads();
-    int base = 0;
-    for (int q = 0; q < t; ++q) base += s_sum[q];
-    for (int r = begin; r < end; ++r) {
-        prefix[r] = base;
-        base += cavity_popcount(w[r] & xmask);
-    }
-    if (t == AFF_PREFIX_THREADS - 1) prefix[rows] = base;            // (the last thread's rows end at `rows`: the total)
-}
 
 __global__ void __launch_bounds__(AFF_CHUNK)
 pw_affinity_kernel(const AffJobDev* __restrict__ jobs, int n_jobs, long total, const double* __restrict__ xyz,
@@ -445,7 +421,7 @@ int affinity(pw_context* ctx, const pw_affinity_job* jobs, int64_t n_jobs, const
                 if (devs[k].energy_first >= 0) widen(e_lo_ws, e_hi_ws, devs[k].energy_first, devs[k].V);
             }
             if (any_mask) {
-                hipLaunchKernelGGL(pw_affinity_prefix_kernel, dim3(n_group), dim3(AFF_PREFIX_THREADS), 0, st, d_jobs + G.first,
+                hipLaunchKernelGGL(pw_region_prefix_kernel<AffJobDev>, dim3(n_group), dim3(AFF_PREFIX_THREADS), 0, st, d_jobs + G.first,
                                    d_words, d_ws);
                 STAT_TRY(hipGetLastError());
             }

@@ -20,6 +20,7 @@
 #include "pw_cluster.hpp"
 #include "pw_cov.hpp"
 #include "pw_affinity.hpp"
+#include "pw_rigid.hpp"
 #include "pw_cavity.hpp"
 #include "pw_sasa.hpp"
 #include "pw_pores.hpp"
@@ -1269,6 +1270,164 @@ extern "C" int pw_hostpath_affinity(const pw_affinity_job* jobs, long n_jobs, co
             for (long c = 0; c < chunks; ++c) s += (long long)P[c * stride + 2 * L + AFF_PART_FIXED + e];
             hist[(long)J.hist_first + e] = s;
         }
+    });
+    return PW_OK;
+}
+
+// pw_rigid_affinity on the host (pw_rigid.hip checks the arguments, counts the voxels of every region and sends
+// device == -1 contexts here): the site position, the charged pair term and the fold over the orientations of
+// pw_rigid.hpp on the pair term, the tests, the weight, the chunk tree and the search of a rank's voxel of
+// pw_affinity.hpp.  The threads share out (job, chunk) pieces, each of which leaves the partial of pw_rigid.hpp; then one
+// ordered reduce a job.
+extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const long* voxels, const double* xyz,
+                                 const double* coef, const double* offsets, const double* dirs,
+                                 const unsigned long long* words, const double* betas, double* maps,
+                                 pw_affinity_level* levels, pw_rigid_out* out, int threads) {
+    typedef cavity_word u64;
+    struct Plan { long piece_first, part_first, prefix_first; };
+    std::vector<Plan> plan((size_t)n_jobs + 1);
+    long pieces = 0, part_words = 0, prefix_ints = 0;
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_rigid_job& J = jobs[k];
+        plan[k] = Plan{pieces, part_words, prefix_ints};
+        const long chunks = (voxels[k] + AFF_CHUNK - 1) / AFF_CHUNK;
+        pieces += chunks;
+        part_words += chunks * rigid_part_words((int)J.n_betas);
+        if (J.word_first >= 0) prefix_ints += (long)J.ny * J.nz + 1;
+    }
+    plan[n_jobs] = Plan{pieces, part_words, prefix_ints};
+    std::vector<u64> part((size_t)part_words);
+    std::vector<int> prefix((size_t)prefix_ints);
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_rigid_job& J = jobs[k];
+        if (J.word_first < 0) continue;
+        int* p = prefix.data() + plan[k].prefix_first;
+        const int rows = J.ny * J.nz;
+        p[0] = 0;
+        for (int r = 0; r < rows; ++r) p[r + 1] = p[r] + cavity_popcount(words[(long)J.word_first + r] & cavity_row_mask(J.nx));
+    }
+    auto voxel_of = [&](long k, long rank, int& i, int& row) {
+        const pw_rigid_job& J = jobs[k];
+        const u64* w = J.word_first >= 0 ? words + (long)J.word_first : nullptr;
+        const int* p = prefix.data() + plan[k].prefix_first;
+        aff_voxel(rank, J.word_first >= 0, J.nx, J.ny * J.nz, [&](int r) { return w[r]; }, [&](int r) { return p[r]; }, i, row);
+    };
+    cov_share(pieces, threads, [&](long piece) {
+        long k = 0, hi = n_jobs;                                     // the last job with piece_first <= piece
+        while (hi - k > 1) {
+            const long mid = (k + hi) / 2;
+            if (plan[mid].piece_first <= piece) k = mid; else hi = mid;
+        }
+        const pw_rigid_job& J = jobs[k];
+        const int L = (int)J.n_betas, S = (int)J.n_sites, M = (int)J.n_dirs, stride = rigid_part_words(L);
+        const long chunk = piece - plan[k].piece_first, V = voxels[k], n = (long)J.n;
+        const bool charged = J.charged != 0;
+        const double* atoms = xyz + 3 * (long)J.atom_first;
+        const double* abc = coef + 3 * (long)J.coef_first;
+        const double* ts = offsets + (long)J.site_first;
+        const double* dd = dirs + 3 * (long)J.dir_first;
+        const double inv_M = rigid_inv(M);
+        double slot_z[AFF_MAX_LEVELS][AFF_CHUNK], slot_e[AFF_MAX_LEVELS][AFF_CHUNK];
+        double m = aff_inf();
+        long m_rank = chunk * AFF_CHUNK, m_dir = 0, n_blocked = 0, n_dead = 0;
+        bool clamped = false;
+        for (int t = 0; t < AFF_CHUNK; ++t) {
+            for (int b = 0; b < L; ++b) slot_z[b][t] = slot_e[b][t] = 0.0;
+            const long rank = chunk * AFF_CHUNK + t;
+            if (rank >= V) continue;
+            int i, row;
+            voxel_of(k, rank, i, row);
+            const double x = cavity_coord(J.origin[0], i, J.spacing), y = cavity_coord(J.origin[1], row % J.ny, J.spacing),
+                         z = cavity_coord(J.origin[2], row / J.ny, J.spacing);
+            RigidFold fold[AFF_MAX_LEVELS];
+            double umin_v = aff_inf();
+            int n_live = 0;
+            for (int o = 0; o < M; ++o) {
+                bool blocked = false;
+                double U = 0.0;
+                for (int s = 0; s < S && !blocked; ++s) {
+                    const double px = rigid_site(x, ts[s], dd[3 * o]), py = rigid_site(y, ts[s], dd[3 * o + 1]),
+                                 pz = rigid_site(z, ts[s], dd[3 * o + 2]);
+                    const double* rows = abc + 3 * (long)s * n;
+                    double Us = 0.0;
+                    for (long a = 0; a < n && !blocked; ++a) {
+                        const double r2 = aff_r2(px - atoms[3 * a], py - atoms[3 * a + 1], pz - atoms[3 * a + 2]);
+                        blocked = aff_blocked(r2, J.core2);
+                        if (blocked || !aff_counts(r2, J.cutoff2)) continue;
+                        Us = Us + (charged ? rigid_pair<true>(r2, rows[3 * a], rows[3 * a + 1], rows[3 * a + 2])
+                                           : rigid_pair<false>(r2, rows[3 * a], rows[3 * a + 1], 0.0));
+                    }
+                    U = s ? U + Us : Us;
+                }
+                if (blocked) {
+                    ++n_blocked;
+                    continue;
+                }
+                ++n_live;
+                if (U < umin_v) umin_v = U;
+                if (U < m) {
+                    m = U;
+                    m_rank = rank;
+                    m_dir = o;
+                }
+                for (int b = 0; b < L; ++b) fold[b].add(aff_weight(betas[(long)J.beta_first + b], U, POW_EXP_TAB, clamped), U);
+            }
+            n_dead += n_live == 0;
+            for (int b = 0; b < L; ++b) {
+                slot_z[b][t] = fold[b].zbar(inv_M);
+                slot_e[b][t] = fold[b].ebar(inv_M);
+            }
+            if (J.map_level >= 0) {
+                maps[(long)J.map_first + 2 * rank] = fold[J.map_level].zbar(inv_M);
+                maps[(long)J.map_first + 2 * rank + 1] = umin_v;
+            }
+        }
+        u64* P = part.data() + plan[k].part_first + chunk * stride;
+        for (int b = 0; b < L; ++b) {
+            P[2 * b] = pw_d2bits(aff_tree(slot_z[b]));
+            P[2 * b + 1] = pw_d2bits(aff_tree(slot_e[b]));
+        }
+        P[2 * L] = pw_d2bits(m);
+        P[2 * L + 1] = (u64)m_rank;
+        P[2 * L + 2] = (u64)m_dir;
+        P[2 * L + 3] = (u64)n_blocked;
+        P[2 * L + 4] = (u64)n_dead;
+        P[2 * L + 5] = clamped ? (u64)AFF_CLAMPED : 0ull;
+    });
+    cov_share(n_jobs, threads, [&](long k) {
+        const pw_rigid_job& J = jobs[k];
+        const int L = (int)J.n_betas, stride = rigid_part_words(L);
+        const long chunks = plan[k + 1].piece_first - plan[k].piece_first;
+        const u64* P = part.data() + plan[k].part_first;
+        for (int b = 0; b < L; ++b) {
+            double sz = 0.0, se = 0.0;
+            for (long c = 0; c < chunks; ++c) {
+                sz = sz + pw_bits2d(P[c * stride + 2 * b]);
+                se = se + pw_bits2d(P[c * stride + 2 * b + 1]);
+            }
+            levels[(long)J.level_first + b] = pw_affinity_level{sz, se};
+        }
+        pw_rigid_out o{voxels[k], 0, 0, aff_inf(), {-1, -1, -1}, -1, 0, 0};
+        long rank = -1;
+        for (long c = 0; c < chunks; ++c) {
+            const double v = pw_bits2d(P[c * stride + 2 * L]);
+            if (v < o.u_min) {
+                o.u_min = v;
+                rank = (long)P[c * stride + 2 * L + 1];
+                o.min_dir = (int)P[c * stride + 2 * L + 2];
+            }
+            o.n_blocked_poses += (long)P[c * stride + 2 * L + 3];
+            o.n_dead += (long)P[c * stride + 2 * L + 4];
+            o.flags |= (int)P[c * stride + 2 * L + 5];
+        }
+        if (rank >= 0) {
+            int i, row;
+            voxel_of(k, rank, i, row);
+            o.min_voxel[0] = i;
+            o.min_voxel[1] = row % J.ny;
+            o.min_voxel[2] = row / J.ny;
+        }
+        out[(long)J.out] = o;
     });
     return PW_OK;
 }

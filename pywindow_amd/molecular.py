@@ -287,6 +287,33 @@ class Molecule:
             "spacing": float(spacing)}
         return af
 
+    def calculate_rigid_guest_affinity(self, guest="CO2", temperature: float = 298.0, spacing: float = 0.5, close="windows",
+                                       directions=None, charges=None, device=None):
+        """How strongly the cage holds a rigid linear guest -- N2, CO2, O2 -- averaged over its orientations
+        (``pywindow_amd.rigid_guest_affinity``, on the GPU): the guest's centre at every voxel of the cavity of
+        ``calculate_cavity(probe=0)`` -- seeded, boxed and closed as in :meth:`calculate_guest_affinity` --, in every
+        one of ``directions`` (``None``: ``pywindow_amd.sphere_directions`` of ``pywindow_amd.rigid.M_DEFAULT``), a
+        pose with a site within 0.5 Angstrom of an atom left out (``core2 = 0.25``).  ``guest``: a name of
+        ``pywindow_amd.rigid.RIGID_GUESTS`` or a :class:`pywindow_amd.RigidGuest`.  ``charges``: the framework's
+        partial charges in e, one per atom; ``None``: no electrostatics at all (the bundled cage model carries no
+        charges, and the guest's then do nothing).  The reference has no counterpart.  Sets
+        ``properties["rigid_guest_affinity"]``: ``guest``, ``temperature``, ``boltzmann_volume``, ``henry``,
+        ``mean_energy``, ``heat``, ``min_energy``, ``min_position``, ``min_direction``, ``closed``, ``spacing``;
+        ``self.rigid_affinity`` keeps the :class:`pywindow_amd.RigidAffinity`, which is returned.  ``full_analysis``
+        does not call it."""
+        from . import rigid as RG
+
+        self.calculate_cavity(probe=0.0, spacing=spacing, close=close, device=device, mask=True)
+        af = RG.rigid_guest_affinity(self.coordinates, self.elements, guest, [temperature], cavity=self.cavity,
+                                     directions=directions, charges=charges, core2=0.25, device=device)
+        self.rigid_affinity = af
+        self.properties["rigid_guest_affinity"] = {
+            "guest": guest, "temperature": float(temperature), "boltzmann_volume": float(af.boltzmann_volume[0]),
+            "henry": float(af.henry[0]), "mean_energy": float(af.mean_energy[0]), "heat": float(af.heat[0]),
+            "min_energy": float(af.min_energy), "min_position": af.min_position, "min_direction": af.min_direction,
+            "closed": bool(af.closed), "spacing": float(spacing)}
+        return af
+
     def calculate_guest_passage(self, guest="Xe", spacing: float = 0.5, close="windows", device=None):
         """What it costs a one-site Lennard-Jones guest to leave the cage through each window
         (``pywindow_amd.guest_passage``, on the GPU): the guest's energy with the UFF atoms of the cage at every voxel

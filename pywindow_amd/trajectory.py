@@ -527,6 +527,22 @@ class DLPOLY:
         return AF.guest_affinity_batch(coords, self.elements(swap_atoms, forcefield), guest, temperatures, cavity=cav,
                                        edges=edges, energies=energies, core2=0.25, device=device, frames=sel)
 
+    def rigid_affinity(self, guest="CO2", temperatures=298.0, spacing: float = 0.5, frames=None, close="windows",
+                       directions=None, charges=None, device=None, swap_atoms=None, forcefield=None):
+        """The orientation-averaged affinity of the cage for a rigid linear guest (N2, CO2, O2) in every frame analysed
+        so far (``frames``: a selection of them): one ``pw_cavity`` call for the probe-0 cavities, seeded, boxed and
+        closed exactly as :meth:`cavity`, then ALL frames in ONE ``pw_rigid_affinity`` call on the GPU
+        (``pywindow_amd.rigid_guest_affinity_batch``, UFF atoms, ``core2 = 0.25``; ``charges``: the framework's partial
+        charges, ``None``: no electrostatics) -- a :class:`pywindow_amd.RigidAffinity` whose fields are arrays over the
+        frames and whose ``frames`` are the trajectory's frame numbers.  Non-modular, non-periodic analyses only."""
+        from . import cavity as CV
+        from . import rigid as RG
+
+        sel, coords, radii, seeds, half_widths, planes = self._cavity_inputs("rigid_affinity", frames, close, swap_atoms, forcefield)
+        cav = CV.cavity_grid_batch(coords, radii, seeds, 0.0, spacing, half_widths, planes, True, device, frames=sel)
+        return RG.rigid_guest_affinity_batch(coords, self.elements(swap_atoms, forcefield), guest, temperatures, cavity=cav,
+                                             directions=directions, charges=charges, core2=0.25, device=device, frames=sel)
+
     def passage(self, guest="Xe", spacing: float = 0.5, frames=None, device=None, close="windows", swap_atoms=None,
                 forcefield=None):
         """The barrier a one-site Lennard-Jones guest crosses at every window in every frame analysed so far

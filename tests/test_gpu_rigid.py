@@ -1,0 +1,134 @@
+"""Rigid linear guests on the device: pw_rigid_affinity on gfx950 against the host path (device = -1) and against the
+definition (tests/_rigid_cases.py: reference), as BYTES -- the order of every sum is part of the definition, so neither
+the launch geometry, which kernel instance serves a job, how the jobs are gathered into launches nor what the workspace
+held before may show.  numpy only; tests/test_rigid.py holds the host path to the definition."""
+import numpy as np
+import pytest
+
+import _affinity_cases as A
+import _rigid_cases as C
+import _stat_edges as S
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def host():
+    from pywindow_amd import _lib
+
+    return _lib.Context(-1, host_threads=16)
+
+
+@pytest.fixture(autouse=True)
+def poison_off_afterwards():
+    yield
+    S.set_poison(False)
+
+
+def test_the_case_list(hip_ctx, host):
+    """Device == host path == definition, job by job and as one batch with holes, and two consecutive device calls agree."""
+    for c in C.cases():
+        packed = C.pack([c])
+        rc, got = C.raw(hip_ctx, packed)
+        want = C.expected([c], host)
+        assert rc == 0 and C.same(got, want), (c.name, C.first_difference(got, want))
+        assert C.same(got, C.raw(host, packed)[1]), c.name
+    jobs = C.cases()
+    packed = C.pack(jobs, hole=3)
+    rc, got = C.raw(hip_ctx, packed)
+    want = C.expected(jobs, host, hole=3)
+    assert rc == 0 and C.same(got, want), C.first_difference(got, want)
+    assert C.same(got, C.raw(host, packed)[1]) and C.same(got, C.raw(hip_ctx, packed)[1])
+    rows = np.frombuffer(got[0].tobytes(), dtype=np.uint8).reshape(len(got[0]), -1)
+    assert (rows == C.SENTINEL).all(axis=1).sum() == 3 * len(jobs)
+
+
+@pytest.mark.parametrize("workspace_bytes", (1, 100_000, 0))
+def test_workspaces_poison_and_a_call_of_other_shapes_before(hip_ctx, host, workspace_bytes):
+    """Through pw_internal_rigid_affinity with every job a launch of its own, with 100 kB a launch and with the default;
+    the workspace and the compact result filled with 0xFF before the first kernel or not; with maps and without; right
+    after a call of other shapes and values: the same bytes, and entries nobody owns untouched."""
+    jobs = C.cases()
+    for maps in (True, False):
+        packed = C.pack(jobs, hole=1, maps=maps)
+        want = C.expected(jobs, host, hole=1, maps=maps)
+        for poison in (False, True):
+            assert C.raw(hip_ctx, C.pack(C.other_shapes()))[0] == 0
+            S.set_poison(poison)
+            rc, got = C.raw(hip_ctx, packed, workspace_bytes=workspace_bytes)
+            S.set_poison(False)
+            assert rc == 0 and C.same(got, want), (workspace_bytes, maps, poison, C.first_difference(got, want))
+
+
+def test_a_batch_of_64_mixed_jobs(hip_ctx, host):
+    jobs = C.mixed_batch()
+    assert len(jobs) == 64 and len({c.dims for c in jobs}) > 10 and {len(c.betas) for c in jobs} >= {1, 8}
+    assert {len(c.offsets) for c in jobs} >= {1, 2, 3, 5, 8} and {c.charged for c in jobs} == {0, 1}
+    packed = C.pack(jobs, hole=1)
+    rc, got = C.raw(hip_ctx, packed)
+    want = C.expected(jobs, host, hole=1)
+    assert rc == 0 and C.same(got, want), C.first_difference(got, want)
+    assert C.same(got, C.raw(host, packed)[1])
+    rc, again = C.raw(hip_ctx, packed, workspace_bytes=30_000)
+    assert rc == 0 and C.same(again, want)
+
+
+def test_256_chunks_go_through_the_reduce(hip_ctx, host):
+    """One 64 x 64 x 4 grid without a mask, 8 orientations, 2 sites and 8 atoms."""
+    c = C.grid_case()[0]
+    packed = C.pack([c])
+    rc, got = C.raw(hip_ctx, packed)
+    want = C.expected([c], host)
+    assert rc == 0 and C.same(got, want), C.first_difference(got, want)
+    assert int(got[0]["n_voxels"][0]) == 64 * 256
+
+
+def test_one_site_one_direction_is_pw_affinity_on_the_device(hip_ctx):
+    """Every job of tests/_affinity_cases.py as S = 1, t = 0, M = 1, uncharged, one batch: the device's pw_affinity bytes
+    in every shared field."""
+    jobs = A.cases()
+    rc, (out, levels, _) = C.raw(hip_ctx, C.pack([C.from_affinity(c) for c in jobs]))
+    rc_a, (out_a, levels_a, _, _) = A.raw(hip_ctx, A.pack(jobs, energies=False))
+    assert rc == 0 and rc_a == 0 and levels.tobytes() == levels_a.tobytes()
+    for name in ("n_voxels", "u_min", "min_voxel", "flags"):
+        assert out[name].tobytes() == out_a[name].tobytes(), name
+    assert np.array_equal(out["n_blocked_poses"], out_a["n_blocked"]) and np.array_equal(out["n_dead"], out_a["n_blocked"])
+
+
+def test_bad_arguments_never_launch(hip_ctx):
+    from pywindow_amd import _lib
+
+    for packed, sizes, what in C.bad_batches():
+        for budget in (None, 1):
+            rc, got = C.raw(hip_ctx, packed, workspace_bytes=budget, sizes=sizes)
+            assert rc == -2 and C.same(got, C.blank_of(packed)), what
+            message = _lib.load().pw_last_error().decode()
+            assert message.startswith("pw_rigid_affinity: job 1: ") and what in message, (what, message)
+
+
+def test_molecule_and_dlpoly_on_jittered_cc3_frames(hip_ctx, tmp_path):
+    """Molecule.calculate_rigid_guest_affinity and DLPOLY.rigid_affinity on 8 jittered CC3 frames, uncharged and with
+    framework charges: device against host."""
+    import pywindow_amd as pw
+    from pywindow_amd import synth
+
+    elements, base = synth.load_cc3_base()
+    frames = [synth.noisy_frame(base, 700 + t, sigma=0.04) for t in range(8)]
+    rng = np.random.default_rng(3)
+    q = rng.uniform(-0.4, 0.4, len(elements))
+    q -= q.mean()
+    dirs = pw.sphere_directions(16)
+    for charges in (None, q):
+        got = []
+        for device in (0, -1):
+            mol = pw.Molecule({"elements": elements, "coordinates": frames[0]}, "cc3", 0)
+            got.append(mol.calculate_rigid_guest_affinity("CO2", 298.0, directions=dirs, charges=charges, device=device))
+        assert got[0].raw.tobytes() == got[1].raw.tobytes() and got[0].levels.tobytes() == got[1].levels.tobytes()
+        assert got[0].closed and got[0].min_energy < 0.0 and got[0].charged == (charges is not None)
+    traj = pw.DLPOLY(synth.write_history(tmp_path / "HISTORY", elements, frames))
+    traj.analysis()
+    for charges in (None, q):
+        dev = traj.rigid_affinity("N2", [298.0, 195.0], directions=dirs, charges=charges, device=0)
+        ref = traj.rigid_affinity("N2", [298.0, 195.0], directions=dirs, charges=charges, device=-1)
+        assert dev.raw.shape == (8,) and dev.raw.tobytes() == ref.raw.tobytes() and dev.levels.tobytes() == ref.levels.tobytes()
+        assert dev.closed.all() and len(set(dev.n_voxels.tolist())) > 3 and dev.series("heat")[1].all()
