@@ -27,7 +27,7 @@
 #include "../../include/pywindow_amd.h"
 #include "pw_affinity.hpp"
 #include "pw_affinity_dev.hpp"
-#include "pw_stat_host.hpp"
+#include "pw_grid_host.hpp"
 
 using namespace pw;
 
@@ -193,12 +193,8 @@ pw_affinity_reduce_kernel(const AffJobDev* __restrict__ jobs, const u64* __restr
     }
 }
 
-// jobs [first, last) go in one launch and share one workspace of `words` 8-byte words; `items` is their chunks
-struct AffGroup {
-    long first, last, words, items;
-};
-
-int aff_bad(long k, const char* what) { return stat_bad("pw_affinity", k, what); }
+const char* const ENTRY = "pw_affinity";
+int aff_bad(long k, const char* what) { return stat_bad(ENTRY, k, what); }
 
 // Everything is checked before anything is launched or written.  V[k]: the voxels of job k's region
 int aff_check(const pw_affinity_job* jobs, long n_jobs, const double* xyz, long n_points, const double* coef, long n_coef,
@@ -207,76 +203,47 @@ int aff_check(const pw_affinity_job* jobs, long n_jobs, const double* xyz, long 
               long n_hist, long n_out, std::vector<long>& V) {
     for (long k = 0; k < n_jobs; ++k) {
         const pw_affinity_job& J = jobs[k];
-        if (J.nx < 1 || J.nx > CAVITY_MAX_G || J.ny < 1 || J.ny > CAVITY_MAX_G || J.nz < 1 || J.nz > CAVITY_MAX_G)
-            return aff_bad(k, "a dimension outside 1 .. PW_CAVITY_MAX_G (64)");
+        GRID_CHECK(grid_dims_check(ENTRY, k, J.nx, J.ny, J.nz));
         const long rows = (long)J.ny * J.nz, L = (long)J.n_betas, E = (long)J.n_edges;
         if (J.n < 0) return aff_bad(k, "a negative count");
-        if (L < 1 || L > AFF_MAX_LEVELS) return aff_bad(k, "n_betas outside 1 .. PW_AFF_MAX_LEVELS (8)");
+        GRID_CHECK(grid_n_betas_check(ENTRY, k, L));
         if (E < 0 || E > AFF_MAX_EDGES) return aff_bad(k, "n_edges outside 0 .. PW_AFF_MAX_EDGES (16)");
-        if (J.atom_first < 0 || J.n > n_points || J.atom_first > n_points - J.n) return aff_bad(k, "atoms outside xyz");
-        if (J.coef_first < 0 || J.n > n_coef || J.coef_first > n_coef - J.n) return aff_bad(k, "coefficients outside coef");
-        if (J.word_first < -1 || (J.word_first >= 0 && (rows > n_words || J.word_first > n_words - rows)))
+        if (span_outside(J.atom_first, J.n, n_points)) return aff_bad(k, "atoms outside xyz");
+        if (span_outside(J.coef_first, J.n, n_coef)) return aff_bad(k, "coefficients outside coef");
+        if (J.word_first < -1 || (J.word_first >= 0 && span_outside(J.word_first, rows, n_words)))
             return aff_bad(k, "the words are outside their array");
-        if (J.beta_first < 0 || L > n_betas || J.beta_first > n_betas - L) return aff_bad(k, "betas outside the array");
-        if (J.edge_first < 0 || E > n_edges || J.edge_first > n_edges - E) return aff_bad(k, "edges outside the array");
-        if (J.level_first < 0 || L > n_levels || J.level_first > n_levels - L) return aff_bad(k, "the rows are outside levels");
-        if (J.hist_first < 0 || E > n_hist || J.hist_first > n_hist - E) return aff_bad(k, "the counts are outside hist");
-        if (J.out < 0 || J.out >= n_out) return aff_bad(k, "the row is outside out");
+        if (span_outside(J.beta_first, L, n_betas)) return aff_bad(k, "betas outside the array");
+        if (span_outside(J.edge_first, E, n_edges)) return aff_bad(k, "edges outside the array");
+        if (span_outside(J.level_first, L, n_levels)) return aff_bad(k, "the rows are outside levels");
+        if (span_outside(J.hist_first, E, n_hist)) return aff_bad(k, "the counts are outside hist");
+        if (span_outside(J.out, 1, n_out)) return aff_bad(k, "the row is outside out");
         if ((J.n && (!xyz || !coef)) || (J.word_first >= 0 && !words) || !betas || (E && (!edges || !hist)) || !levels ||
             (J.energy_first >= 0 && !energies))
             return aff_bad(k, "null array");
-        long count = (long)J.nx * rows;
-        if (J.word_first >= 0) {
-            count = 0;
-            for (long r = 0; r < rows; ++r) count += cavity_popcount(words[J.word_first + r] & cavity_row_mask(J.nx));
-        }
-        V[k] = count;
-        if (J.energy_first < -1 || (J.energy_first >= 0 && (count > n_energies || J.energy_first > n_energies - count)))
+        V[k] = grid_region_voxels(J.word_first >= 0 ? words + J.word_first : nullptr, J.nx, rows);
+        if (J.energy_first < -1 || (J.energy_first >= 0 && span_outside(J.energy_first, V[k], n_energies)))
             return aff_bad(k, "the energies are outside their array");
-        if (!pw_finite(J.origin[0]) || !pw_finite(J.origin[1]) || !pw_finite(J.origin[2]) || !pw_finite(J.spacing))
-            return aff_bad(k, "the origin or the spacing is not finite");
-        if (!(J.spacing > 0.0)) return aff_bad(k, "spacing <= 0");
-        if (!pw_finite(J.core2) || !(J.core2 >= AFF_MIN_CORE2)) return aff_bad(k, "core2 below 1e-6 or not finite");
-        if (!pw_finite(J.cutoff2) || !(J.cutoff2 == 0.0 || J.cutoff2 > J.core2))
-            return aff_bad(k, "cutoff2 is neither 0 nor above core2");
-        for (long b = 0; b < L; ++b) {
-            const double beta = betas[J.beta_first + b];
-            if (!pw_finite(beta) || beta < 0.0) return aff_bad(k, "a beta is negative or not finite");
-        }
+        GRID_CHECK(grid_frame_check(ENTRY, k, J.origin, J.spacing));
+        GRID_CHECK(grid_core_check(ENTRY, k, J.core2, J.cutoff2));
+        GRID_CHECK(grid_betas_check(ENTRY, k, betas, J.beta_first, L));
         for (long e = 0; e < E; ++e) {
             const double edge = edges[J.edge_first + e];
             if (!pw_finite(edge)) return aff_bad(k, "an edge is not finite");
             if (e && !(edge > edges[J.edge_first + e - 1])) return aff_bad(k, "the edges are not strictly ascending");
         }
-        for (long a = 0; a < J.n; ++a) {
-            const double* p = xyz + 3 * (J.atom_first + a);
-            if (!pw_finite(p[0]) || !pw_finite(p[1]) || !pw_finite(p[2])) return aff_bad(k, "a coordinate is not finite");
-            const double* c = coef + 2 * (J.coef_first + a);
-            if (!pw_finite(c[0]) || !pw_finite(c[1])) return aff_bad(k, "a coefficient is not finite");
-            if (c[0] < 0.0 || c[1] < 0.0 || c[0] > AFF_MAX_COEF || c[1] > AFF_MAX_COEF)
-                return aff_bad(k, "a coefficient outside 0 .. 1e100");
+        for (long a = 0; a < J.n; ++a) {                             // (atom by atom: its coordinates, then its row)
+            GRID_CHECK(grid_xyz_check(ENTRY, k, xyz, J.atom_first + a, 1));
+            GRID_CHECK(grid_coef_check(ENTRY, k, coef, J.coef_first + a, 1, 2, false));
         }
     }
-    // outputs of two jobs: the later of the two is named
-    std::vector<std::array<long, 3>> spans;
-    for (long k = 0; k < n_jobs; ++k) spans.push_back({(long)jobs[k].out, 1, k});
-    long bad = stat_shared(spans);
-    if (bad >= 0) return aff_bad(bad, "shares its row of out with an earlier job");
-    spans.clear();
-    for (long k = 0; k < n_jobs; ++k) spans.push_back({(long)jobs[k].level_first, (long)jobs[k].n_betas, k});
-    bad = stat_shared(spans);
-    if (bad >= 0) return aff_bad(bad, "shares rows of levels with an earlier job");
-    spans.clear();
-    for (long k = 0; k < n_jobs; ++k)
-        if (jobs[k].n_edges) spans.push_back({(long)jobs[k].hist_first, (long)jobs[k].n_edges, k});
-    bad = stat_shared(spans);
-    if (bad >= 0) return aff_bad(bad, "shares counts of hist with an earlier job");
-    spans.clear();
-    for (long k = 0; k < n_jobs; ++k)
-        if (jobs[k].energy_first >= 0 && V[k]) spans.push_back({(long)jobs[k].energy_first, V[k], k});
-    bad = stat_shared(spans);
-    if (bad >= 0) return aff_bad(bad, "shares energies with an earlier job");
-    return PW_OK;
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares its row of out with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].out, 1}; }));
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares rows of levels with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].level_first, (long)jobs[k].n_betas}; }));
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares counts of hist with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].hist_first, (long)jobs[k].n_edges}; }));
+    return shared_output(ENTRY, n_jobs, "shares energies with an earlier job",
+                         [&](long k) { return OutSpan{(long)jobs[k].energy_first, jobs[k].energy_first >= 0 ? V[k] : 0}; });
 }
 
 // workspace_bytes: the budget of the prefixes, partials and energy maps of the jobs of one launch (0:
@@ -308,31 +275,24 @@ int affinity(pw_context* ctx, const pw_affinity_job* jobs, int64_t n_jobs, const
     // the spans of the arrays that the jobs read, and the plan: jobs in order, gathered into launches while their
     // prefixes, partials and energy maps fit the budget
     const long budget_words = (workspace_bytes ? (long)workspace_bytes : AFF_WORKSPACE_BYTES) / 8;
-    long a_lo = -1, a_hi = 0, c_lo = -1, c_hi = 0, w_lo = -1, w_hi = 0, b_lo = -1, b_hi = 0, e_lo = -1, e_hi = 0;
-    auto widen = [](long& lo, long& hi, long first, long count) {
-        if (count == 0) return;
-        if (lo < 0 || first < lo) lo = first;
-        if (first + count > hi) hi = first + count;
-    };
+    Span atoms, rows_ab, region, beta_span, edge_span;
     for (long k = 0; k < N; ++k) {
         const pw_affinity_job& J = jobs[k];
-        widen(a_lo, a_hi, (long)J.atom_first, (long)J.n);
-        widen(c_lo, c_hi, (long)J.coef_first, (long)J.n);
-        if (J.word_first >= 0) widen(w_lo, w_hi, (long)J.word_first, (long)J.ny * J.nz);
-        widen(b_lo, b_hi, (long)J.beta_first, (long)J.n_betas);
-        widen(e_lo, e_hi, (long)J.edge_first, (long)J.n_edges);
+        atoms.widen((long)J.atom_first, (long)J.n);
+        rows_ab.widen((long)J.coef_first, (long)J.n);
+        if (J.word_first >= 0) region.widen((long)J.word_first, (long)J.ny * J.nz);
+        beta_span.widen((long)J.beta_first, (long)J.n_betas);
+        edge_span.widen((long)J.edge_first, (long)J.n_edges);
     }
-    for (long* lo : {&a_lo, &c_lo, &w_lo, &b_lo, &e_lo})
-        if (*lo < 0) *lo = 0;
-    const long n_beta_span = b_hi - b_lo, n_edge_span = e_hi - e_lo;
+    const long n_beta_span = beta_span.count(), n_edge_span = edge_span.count();
     std::vector<double> params((size_t)(n_beta_span + n_edge_span));
-    memcpy(params.data(), betas + b_lo, sizeof(double) * (size_t)n_beta_span);
-    if (n_edge_span) memcpy(params.data() + n_beta_span, edges + e_lo, sizeof(double) * (size_t)n_edge_span);
+    memcpy(params.data(), betas + beta_span.lo_or_zero(), sizeof(double) * (size_t)n_beta_span);
+    if (n_edge_span) memcpy(params.data() + n_beta_span, edges + edge_span.lo, sizeof(double) * (size_t)n_edge_span);
 
     std::vector<AffJobDev> devs((size_t)N);
-    std::vector<AffGroup> groups;
-    AffGroup cur{0, 0, 0, 0};
-    long max_words = 0, n_level_rows = 0, n_counts = 0;
+    std::vector<LaunchGroup> groups;
+    LaunchGroup cur;
+    long n_level_rows = 0, n_counts = 0;
     for (long k = 0; k < N; ++k) {
         const pw_affinity_job& J = jobs[k];
         const long rows = (long)J.ny * J.nz, L = (long)J.n_betas, E = (long)J.n_edges;
@@ -340,23 +300,20 @@ int affinity(pw_context* ctx, const pw_affinity_job* jobs, int64_t n_jobs, const
         const bool masked = J.word_first >= 0;
         const long prefix_words = masked ? (rows + 2) / 2 : 0, part_words = chunks * aff_part_words((int)L, (int)E),
                    energy_words = J.energy_first >= 0 ? V[k] : 0, need = prefix_words + part_words + energy_words;
-        if (cur.last > cur.first && cur.words + need + 1 > budget_words) {   // (a word more a job: no job is free)
-            groups.push_back(cur);
-            cur = AffGroup{cur.last, cur.last, 0, 0};
-        }
+        place(groups, cur, budget_words, need + 1);                  // (a word more a job: no job is free)
         AffJobDev& D = devs[k];
-        D.atom_first = J.n ? (long)J.atom_first - a_lo : 0;
+        D.atom_first = atoms.rel((long)J.atom_first, (long)J.n);
         D.n = (long)J.n;
-        D.coef_first = J.n ? (long)J.coef_first - c_lo : 0;
-        D.word_first = masked ? (long)J.word_first - w_lo : -1;
+        D.coef_first = rows_ab.rel((long)J.coef_first, (long)J.n);
+        D.word_first = masked ? (long)J.word_first - region.lo : -1;
         D.prefix_first = masked ? cur.words : -1;
         D.part_first = cur.words + prefix_words;
         D.energy_first = J.energy_first >= 0 ? cur.words + prefix_words + part_words : -1;
         D.item_first = cur.items;
         D.chunks = chunks;
         D.V = V[k];
-        D.beta_first = (long)J.beta_first - b_lo;
-        D.edge_first = n_beta_span + (E ? (long)J.edge_first - e_lo : 0);
+        D.beta_first = beta_span.rel((long)J.beta_first, L);
+        D.edge_first = n_beta_span + edge_span.rel((long)J.edge_first, E);
         D.level_first = n_level_rows;
         D.hist_first = n_counts;
         for (int a = 0; a < 3; ++a) D.o[a] = J.origin[a];
@@ -364,15 +321,14 @@ int affinity(pw_context* ctx, const pw_affinity_job* jobs, int64_t n_jobs, const
         D.nx = J.nx; D.ny = J.ny; D.nz = J.nz; D.L = (int)L; D.E = (int)E; D.reserved = 0;
         n_level_rows += L;
         n_counts += E;
-        cur.words += need + 1; cur.items += chunks; cur.last += 1;
-        max_words = cur.words > max_words ? cur.words : max_words;
+        cur.words += need + 1; cur.cost += need + 1; cur.items += chunks; cur.last += 1;
     }
     groups.push_back(cur);
 
     // the compact result of the call: the rows of out in job order, then the rows of levels, then the counts
     const size_t out_bytes = sizeof(pw_affinity_out) * (size_t)N, levels_bytes = sizeof(pw_affinity_level) * (size_t)n_level_rows,
                  hist_bytes = sizeof(long long) * (size_t)n_counts, res_bytes = out_bytes + levels_bytes + hist_bytes,
-                 ws_bytes = sizeof(u64) * (size_t)max_words;
+                 ws_bytes = sizeof(u64) * (size_t)most_words(groups);
     std::vector<unsigned char> res(res_bytes);
     std::vector<std::vector<double>> maps(groups.size());            // the energy maps of a launch, as its workspace has them
 
@@ -388,23 +344,17 @@ int affinity(pw_context* ctx, const pw_affinity_job* jobs, int64_t n_jobs, const
         u64 *d_words, *d_ws;
         unsigned char* d_res;
         STAT_TRY(buf.alloc(&d_jobs, sizeof(AffJobDev) * (size_t)N));
-        STAT_TRY(buf.alloc(&d_xyz, sizeof(double) * 3 * (size_t)(a_hi - a_lo)));
-        STAT_TRY(buf.alloc(&d_coef, sizeof(double) * 2 * (size_t)(c_hi - c_lo)));
-        STAT_TRY(buf.alloc(&d_words, sizeof(u64) * (size_t)(w_hi - w_lo)));
+        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(AffJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
+        STAT_TRY(atoms.upload(buf, &d_xyz, xyz, 3));
+        STAT_TRY(rows_ab.upload(buf, &d_coef, coef, 2));
+        STAT_TRY(region.upload(buf, &d_words, words, 1));
         STAT_TRY(buf.alloc(&d_params, sizeof(double) * params.size()));
+        STAT_TRY(hipMemcpyAsync(d_params, params.data(), sizeof(double) * params.size(), hipMemcpyHostToDevice, st));
         STAT_TRY(buf.alloc(&d_ws, ws_bytes));
         STAT_TRY(buf.alloc(&d_res, res_bytes));
         const bool poison = scratch_poisoned();                      // (test hook, pw_stat_host.hpp)
         STAT_TRY(poison_scratch(poison, d_ws, ws_bytes, st));
         STAT_TRY(poison_scratch(poison, d_res, res_bytes, st));
-        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(AffJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
-        if (a_hi > a_lo)
-            STAT_TRY(hipMemcpyAsync(d_xyz, xyz + 3 * a_lo, sizeof(double) * 3 * (size_t)(a_hi - a_lo), hipMemcpyHostToDevice, st));
-        if (c_hi > c_lo)
-            STAT_TRY(hipMemcpyAsync(d_coef, coef + 2 * c_lo, sizeof(double) * 2 * (size_t)(c_hi - c_lo), hipMemcpyHostToDevice, st));
-        if (w_hi > w_lo)
-            STAT_TRY(hipMemcpyAsync(d_words, words + w_lo, sizeof(u64) * (size_t)(w_hi - w_lo), hipMemcpyHostToDevice, st));
-        STAT_TRY(hipMemcpyAsync(d_params, params.data(), sizeof(double) * params.size(), hipMemcpyHostToDevice, st));
         pw_affinity_out* d_out = (pw_affinity_out*)d_res;
         double* d_levels = (double*)(d_res + out_bytes);
         long long* d_hist = (long long*)(d_res + out_bytes + levels_bytes);
@@ -412,13 +362,13 @@ int affinity(pw_context* ctx, const pw_affinity_job* jobs, int64_t n_jobs, const
         // (launches follow one another on the stream, so the next one may take the workspace over once the energy maps
         // of this one are on their way)
         for (size_t g = 0; g < groups.size(); ++g) {
-            const AffGroup& G = groups[g];
+            const LaunchGroup& G = groups[g];
             const unsigned n_group = (unsigned)(G.last - G.first);
             bool any_mask = false;
-            long e_lo_ws = -1, e_hi_ws = 0;
+            Span maps_ws;                                            // the energy maps of the group in its workspace
             for (long k = G.first; k < G.last; ++k) {
                 any_mask = any_mask || devs[k].prefix_first >= 0;
-                if (devs[k].energy_first >= 0) widen(e_lo_ws, e_hi_ws, devs[k].energy_first, devs[k].V);
+                if (devs[k].energy_first >= 0) maps_ws.widen(devs[k].energy_first, devs[k].V);
             }
             if (any_mask) {
                 hipLaunchKernelGGL(pw_region_prefix_kernel<AffJobDev>, dim3(n_group), dim3(AFF_PREFIX_THREADS), 0, st, d_jobs + G.first,
@@ -434,12 +384,12 @@ int affinity(pw_context* ctx, const pw_affinity_job* jobs, int64_t n_jobs, const
             hipLaunchKernelGGL(pw_affinity_reduce_kernel, dim3(n_group), dim3(AFF_CHUNK), 0, st, d_jobs + G.first, d_words,
                                d_ws, d_out + G.first, d_levels, d_hist);
             STAT_TRY(hipGetLastError());
-            if (e_lo_ws >= 0) {
-                maps[g].resize((size_t)(e_hi_ws - e_lo_ws));
-                STAT_TRY(hipMemcpyAsync(maps[g].data(), d_ws + e_lo_ws, sizeof(double) * maps[g].size(), hipMemcpyDeviceToHost, st));
+            if (maps_ws.lo >= 0) {
+                maps[g].resize((size_t)maps_ws.count());
+                STAT_TRY(hipMemcpyAsync(maps[g].data(), d_ws + maps_ws.lo, sizeof(double) * maps[g].size(), hipMemcpyDeviceToHost, st));
                 // (energy_first of the group's jobs becomes relative to that copy)
                 for (long k = G.first; k < G.last; ++k)
-                    if (devs[k].energy_first >= 0) devs[k].energy_first -= e_lo_ws;
+                    if (devs[k].energy_first >= 0) devs[k].energy_first -= maps_ws.lo;
             }
         }
         STAT_TRY(ev.stop(st));

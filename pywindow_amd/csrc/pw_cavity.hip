@@ -28,7 +28,7 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_cavity_dev.hpp"
-#include "pw_stat_host.hpp"
+#include "pw_grid_host.hpp"
 
 using namespace pw;
 
@@ -124,13 +124,8 @@ pw_cavity_kernel(const CavJobDev* __restrict__ jobs, const double* __restrict__ 
     }
 }
 
-// jobs [first, last) go in one launch and share one workspace of `words` words; `cost` is what they take of the
-// budget (a word more a job than they use: no job is free); the largest of them has `rows` rows
-struct CavGroup {
-    long first, last, words, cost, rows;
-};
-
-int cav_bad(long k, const char* what) { return stat_bad("pw_cavity", k, what); }
+const char* const ENTRY = "pw_cavity";
+int cav_bad(long k, const char* what) { return stat_bad(ENTRY, k, what); }
 
 // Everything is checked before anything is launched or written.  open_first (may be null; an entry -1: classify) names
 // ready-made open words of a job in open_words[0 .. n_open_words).
@@ -139,45 +134,37 @@ int cav_check(const pw_cavity_job* jobs, long n_jobs, const double* xyz, long n_
               const long* open_first, long n_open_words) {
     for (long k = 0; k < n_jobs; ++k) {
         const pw_cavity_job& J = jobs[k];
-        if (J.nx < 1 || J.nx > CAVITY_MAX_G || J.ny < 1 || J.ny > CAVITY_MAX_G || J.nz < 1 || J.nz > CAVITY_MAX_G)
-            return cav_bad(k, "a dimension outside 1 .. PW_CAVITY_MAX_G (64)");
+        GRID_CHECK(grid_dims_check(ENTRY, k, J.nx, J.ny, J.nz));
         if (J.seed[0] < 0 || J.seed[0] >= J.nx || J.seed[1] < 0 || J.seed[1] >= J.ny || J.seed[2] < 0 || J.seed[2] >= J.nz)
             return cav_bad(k, "the seed is outside the grid");
         const long rows = (long)J.ny * J.nz;
         if (J.n < 0 || J.m < 0) return cav_bad(k, "a negative count");
-        if (J.atom_first < 0 || J.n > n_points || J.atom_first > n_points - J.n) return cav_bad(k, "atoms outside xyz");
-        if (J.radius_first < 0 || J.n > n_radii || J.radius_first > n_radii - J.n) return cav_bad(k, "radii outside the array");
-        if (J.plane_first < 0 || J.m > n_planes || J.plane_first > n_planes - J.m) return cav_bad(k, "planes outside the array");
-        if (J.out < 0 || J.out >= n_out) return cav_bad(k, "the row is outside out");
-        if (J.mask_first < -1 || (J.mask_first >= 0 && (rows > n_mask || J.mask_first > n_mask - rows)))
+        if (span_outside(J.atom_first, J.n, n_points)) return cav_bad(k, "atoms outside xyz");
+        if (span_outside(J.radius_first, J.n, n_radii)) return cav_bad(k, "radii outside the array");
+        if (span_outside(J.plane_first, J.m, n_planes)) return cav_bad(k, "planes outside the array");
+        if (span_outside(J.out, 1, n_out)) return cav_bad(k, "the row is outside out");
+        if (J.mask_first < -1 || (J.mask_first >= 0 && span_outside(J.mask_first, rows, n_mask)))
             return cav_bad(k, "the words are outside mask");
         if ((J.n && (!xyz || !radii)) || (J.m && !planes) || (J.mask_first >= 0 && !mask)) return cav_bad(k, "null array");
-        if (open_first && open_first[k] != -1 &&
-            (!open_words || open_first[k] < 0 || rows > n_open_words || open_first[k] > n_open_words - rows))
+        if (open_first && open_first[k] != -1 && (!open_words || span_outside(open_first[k], rows, n_open_words)))
             return cav_bad(k, "the open words are outside their array");
         if (!pw_finite(J.origin[0]) || !pw_finite(J.origin[1]) || !pw_finite(J.origin[2]) || !pw_finite(J.spacing) ||
             !pw_finite(J.probe))
             return cav_bad(k, "the origin, the spacing or the probe is not finite");
         if (!(J.spacing > 0.0)) return cav_bad(k, "spacing <= 0");
         if (J.probe < 0.0) return cav_bad(k, "a negative probe");
-        for (long a = 0; a < J.n; ++a) {
-            const double* p = xyz + 3 * (J.atom_first + a);
-            if (!pw_finite(p[0]) || !pw_finite(p[1]) || !pw_finite(p[2])) return cav_bad(k, "a coordinate is not finite");
-            const double r = radii[J.radius_first + a];
-            if (!pw_finite(r)) return cav_bad(k, "a radius is not finite");
-            if (r < 0.0) return cav_bad(k, "a negative radius");
+        for (long a = 0; a < J.n; ++a) {                             // (atom by atom: its coordinates, then its radius)
+            GRID_CHECK(grid_xyz_check(ENTRY, k, xyz, J.atom_first + a, 1));
+            GRID_CHECK(grid_radii_check(ENTRY, k, radii, J.radius_first + a, 1));
         }
-        for (long q = 0; q < 4 * J.m; ++q)
-            if (!pw_finite(planes[4 * J.plane_first + q])) return cav_bad(k, "a plane is not finite");
+        GRID_CHECK(grid_planes_check(ENTRY, k, planes, J.plane_first, J.m));
     }
-    // outputs of two jobs: the later of the two is named
-    std::vector<std::pair<long, long>> rows_of((size_t)n_jobs);
-    for (long k = 0; k < n_jobs; ++k) rows_of[k] = {(long)jobs[k].out, k};
-    std::sort(rows_of.begin(), rows_of.end());
+    // outputs of two jobs: the later of the two is named.  (Of rows, all of length 1, stat_shared names the second
+    // lowest job of a row that is shared, as the sweep over equal neighbours did.  The words of mask keep their sweep,
+    // which orders spans of one first by job where stat_shared orders them by length.)
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares its row of out with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].out, 1}; }));
     long bad = -1;
-    for (long i = 1; i < n_jobs; ++i)
-        if (rows_of[i].first == rows_of[i - 1].first && (bad < 0 || rows_of[i].second < bad)) bad = rows_of[i].second;
-    if (bad >= 0) return cav_bad(bad, "shares its row of out with an earlier job");
     std::vector<std::pair<long, long>> spans;
     for (long k = 0; k < n_jobs; ++k)
         if (jobs[k].mask_first >= 0) spans.push_back({(long)jobs[k].mask_first, k});
@@ -225,38 +212,26 @@ int cavity(pw_context* ctx, const pw_cavity_job* jobs, int64_t n_jobs, const dou
     // the spans of the arrays that the jobs read, and the plan: jobs in order, gathered into launches while their
     // open words and masks fit the budget
     const long budget_words = (workspace_bytes ? (long)workspace_bytes : CAVITY_WORKSPACE_BYTES) / 8;
-    long a_lo = -1, a_hi = 0, r_lo = -1, r_hi = 0, p_lo = -1, p_hi = 0;
-    auto widen = [](long& lo, long& hi, long first, long count) {
-        if (count == 0) return;
-        if (lo < 0 || first < lo) lo = first;
-        if (first + count > hi) hi = first + count;
-    };
+    Span atoms, atom_radii, windows;
     for (long k = 0; k < N; ++k) {
-        widen(a_lo, a_hi, (long)jobs[k].atom_first, (long)jobs[k].n);
-        widen(r_lo, r_hi, (long)jobs[k].radius_first, (long)jobs[k].n);
-        widen(p_lo, p_hi, (long)jobs[k].plane_first, (long)jobs[k].m);
+        atoms.widen((long)jobs[k].atom_first, (long)jobs[k].n);
+        atom_radii.widen((long)jobs[k].radius_first, (long)jobs[k].n);
+        windows.widen((long)jobs[k].plane_first, (long)jobs[k].m);
     }
-    if (a_lo < 0) a_lo = a_hi = 0;
-    if (r_lo < 0) r_lo = r_hi = 0;
-    if (p_lo < 0) p_lo = p_hi = 0;
     std::vector<CavJobDev> devs((size_t)N);
-    std::vector<CavGroup> groups;
-    CavGroup cur{0, 0, 0, 0, 0};
-    long max_words = 0;
+    std::vector<LaunchGroup> groups;
+    LaunchGroup cur;
     for (long k = 0; k < N; ++k) {
         const pw_cavity_job& J = jobs[k];
         const long rows = (long)J.ny * J.nz;
         const bool given = open_first && open_first[k] >= 0;
         const long words = (given ? rows : 0) + (J.mask_first >= 0 ? rows : 0);
-        if (cur.last > cur.first && cur.cost + words + 1 > budget_words) {
-            groups.push_back(cur);
-            cur = CavGroup{cur.last, cur.last, 0, 0, 0};
-        }
+        place(groups, cur, budget_words, words + 1);                 // (a word more a job than it uses: no job is free)
         CavJobDev& D = devs[k];
-        D.atom_first = J.n ? (long)J.atom_first - a_lo : 0;
+        D.atom_first = atoms.rel((long)J.atom_first, (long)J.n);
         D.n = (long)J.n;
-        D.radius_first = J.n ? (long)J.radius_first - r_lo : 0;
-        D.plane_first = J.m ? (long)J.plane_first - p_lo : 0;
+        D.radius_first = atom_radii.rel((long)J.radius_first, (long)J.n);
+        D.plane_first = windows.rel((long)J.plane_first, (long)J.m);
         D.m = (long)J.m;
         D.mask_first = J.mask_first >= 0 ? cur.words : -1;           // (masks of neighbours side by side: one copy)
         D.open_first = given ? cur.words + (J.mask_first >= 0 ? rows : 0) : -1;
@@ -266,7 +241,6 @@ int cavity(pw_context* ctx, const pw_cavity_job* jobs, int64_t n_jobs, const dou
         }
         D.h = J.spacing; D.probe = J.probe; D.nx = J.nx; D.ny = J.ny; D.nz = J.nz;
         cur.words += words; cur.cost += words + 1; cur.last += 1; cur.rows = rows > cur.rows ? rows : cur.rows;
-        max_words = cur.words > max_words ? cur.words : max_words;
     }
     groups.push_back(cur);
 
@@ -283,27 +257,21 @@ int cavity(pw_context* ctx, const pw_cavity_job* jobs, int64_t n_jobs, const dou
         double *d_xyz, *d_radii, *d_planes;
         u64* d_ws;
         pw_cavity_out* d_out;
-        const size_t ws_bytes = sizeof(u64) * (size_t)max_words, out_bytes = sizeof(pw_cavity_out) * (size_t)N;
+        const size_t ws_bytes = sizeof(u64) * (size_t)most_words(groups), out_bytes = sizeof(pw_cavity_out) * (size_t)N;
         STAT_TRY(buf.alloc(&d_jobs, sizeof(CavJobDev) * (size_t)N));
-        STAT_TRY(buf.alloc(&d_xyz, sizeof(double) * 3 * (size_t)(a_hi - a_lo)));
-        STAT_TRY(buf.alloc(&d_radii, sizeof(double) * (size_t)(r_hi - r_lo)));
-        STAT_TRY(buf.alloc(&d_planes, sizeof(double) * 4 * (size_t)(p_hi - p_lo)));
+        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(CavJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
+        STAT_TRY(atoms.upload(buf, &d_xyz, xyz, 3));
+        STAT_TRY(atom_radii.upload(buf, &d_radii, radii, 1));
+        STAT_TRY(windows.upload(buf, &d_planes, planes, 4));
         STAT_TRY(buf.alloc(&d_ws, ws_bytes));
         STAT_TRY(buf.alloc(&d_out, out_bytes));
         const bool poison = scratch_poisoned();                      // (test hook, pw_stat_host.hpp)
         STAT_TRY(poison_scratch(poison, d_ws, ws_bytes, st));
         STAT_TRY(poison_scratch(poison, d_out, out_bytes, st));
-        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(CavJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
-        if (a_hi > a_lo)
-            STAT_TRY(hipMemcpyAsync(d_xyz, xyz + 3 * a_lo, sizeof(double) * 3 * (size_t)(a_hi - a_lo), hipMemcpyHostToDevice, st));
-        if (r_hi > r_lo)
-            STAT_TRY(hipMemcpyAsync(d_radii, radii + r_lo, sizeof(double) * (size_t)(r_hi - r_lo), hipMemcpyHostToDevice, st));
-        if (p_hi > p_lo)
-            STAT_TRY(hipMemcpyAsync(d_planes, planes + 4 * p_lo, sizeof(double) * 4 * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
         STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one may take the workspace over once the masks of
         // this one are on their way; neighbours in the workspace and in the caller's array travel in one copy)
-        for (const CavGroup& G : groups) {
+        for (const LaunchGroup& G : groups) {
             for (long k = G.first; k < G.last; ++k)
                 if (devs[k].open_first >= 0)
                     STAT_TRY(hipMemcpyAsync(d_ws + devs[k].open_first, open_words + open_first[k],

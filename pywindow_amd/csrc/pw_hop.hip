@@ -30,7 +30,7 @@
 #include "pw_cavity_dev.hpp"
 #include "pw_field_dev.hpp"
 #include "pw_hop.hpp"
-#include "pw_stat_host.hpp"
+#include "pw_grid_host.hpp"
 
 using namespace pw;
 
@@ -204,13 +204,8 @@ pw_hop_kernel(const HopJobDev* __restrict__ jobs, int n_jobs, const double* __re
     if (D.resw_first >= 0 && lane < ny) res[D.resw_first + (long)l * ny + lane] = fill;
 }
 
-// jobs [first, last) go in one launch and share one workspace of `words` 8-byte words; `items` is the chunks of their
-// field kernel, `blocks` their slabs
-struct HopGroup {
-    long first, last, words, items, blocks;
-};
-
-int hop_bad(long k, const char* what) { return stat_bad("pw_hop", k, what); }
+const char* const ENTRY = "pw_hop";
+int hop_bad(long k, const char* what) { return stat_bad(ENTRY, k, what); }
 
 // Everything is checked before anything is launched or written
 int hop_check(const pw_hop_job* jobs, long n_jobs, const double* xyz, long n_points, const double* coef, long n_coef,
@@ -219,69 +214,50 @@ int hop_check(const pw_hop_job* jobs, long n_jobs, const double* xyz, long n_poi
               const uint64_t* words, long n_words) {
     for (long k = 0; k < n_jobs; ++k) {
         const pw_hop_job& J = jobs[k];
-        if (J.nx < 1 || J.nx > CAVITY_MAX_G || J.ny < 1 || J.ny > CAVITY_MAX_G || J.nz < 1 || J.nz > CAVITY_MAX_G)
-            return hop_bad(k, "a dimension outside 1 .. PW_CAVITY_MAX_G (64)");
+        GRID_CHECK(grid_dims_check(ENTRY, k, J.nx, J.ny, J.nz));
         if (J.seed[0] < 0 || J.seed[0] >= J.nx || J.seed[1] < 0 || J.seed[1] >= J.ny)
             return hop_bad(k, "the seed column is outside the grid");
         const long rows = (long)J.ny * J.nz, V = rows * J.nx, L = (long)J.n_betas;
         const bool lj = J.field_first == -1;
         if (J.n < 0 || J.m < 0) return hop_bad(k, "a negative count");
-        if (L < 1 || L > AFF_MAX_LEVELS) return hop_bad(k, "n_betas outside 1 .. PW_AFF_MAX_LEVELS (8)");
-        if (lj && (J.atom_first < 0 || J.n > n_points || J.atom_first > n_points - J.n)) return hop_bad(k, "atoms outside xyz");
-        if (lj && (J.coef_first < 0 || J.n > n_coef || J.coef_first > n_coef - J.n)) return hop_bad(k, "coefficients outside coef");
-        if (J.plane_first < 0 || J.m > n_planes || J.plane_first > n_planes - J.m) return hop_bad(k, "planes outside the array");
-        if (J.field_first < -1 || (!lj && (V > n_field || J.field_first > n_field - V)))
-            return hop_bad(k, "the field is outside its array");
-        if (J.beta_first < 0 || L > n_betas || J.beta_first > n_betas - L) return hop_bad(k, "betas outside the array");
-        if (J.slab_first < 0 || J.nz > n_slabs || J.slab_first > n_slabs - J.nz) return hop_bad(k, "the rows are outside slabs");
-        if (J.sum_first < 0 || J.nz * L > n_sums || J.sum_first > n_sums - J.nz * L) return hop_bad(k, "the pairs are outside sums");
-        if (J.word_first < -1 || (J.word_first >= 0 && (rows > n_words || J.word_first > n_words - rows)))
+        GRID_CHECK(grid_n_betas_check(ENTRY, k, L));
+        if (lj && span_outside(J.atom_first, J.n, n_points)) return hop_bad(k, "atoms outside xyz");
+        if (lj && span_outside(J.coef_first, J.n, n_coef)) return hop_bad(k, "coefficients outside coef");
+        if (span_outside(J.plane_first, J.m, n_planes)) return hop_bad(k, "planes outside the array");
+        if (J.field_first < -1 || (!lj && span_outside(J.field_first, V, n_field))) return hop_bad(k, "the field is outside its array");
+        if (span_outside(J.beta_first, L, n_betas)) return hop_bad(k, "betas outside the array");
+        if (span_outside(J.slab_first, J.nz, n_slabs)) return hop_bad(k, "the rows are outside slabs");
+        if (span_outside(J.sum_first, J.nz * L, n_sums)) return hop_bad(k, "the pairs are outside sums");
+        if (J.word_first < -1 || (J.word_first >= 0 && span_outside(J.word_first, rows, n_words)))
             return hop_bad(k, "the words are outside their array");
-        if (J.out < 0 || J.out >= n_out) return hop_bad(k, "the row is outside out");
+        if (span_outside(J.out, 1, n_out)) return hop_bad(k, "the row is outside out");
         if ((lj && J.n && (!xyz || !coef)) || (J.m && !planes) || (!lj && !field) || !betas || !slabs || !sums ||
             (J.word_first >= 0 && !words))
             return hop_bad(k, "null array");
-        if (!pw_finite(J.origin[0]) || !pw_finite(J.origin[1]) || !pw_finite(J.origin[2]) || !pw_finite(J.spacing))
-            return hop_bad(k, "the origin or the spacing is not finite");
-        if (!(J.spacing > 0.0)) return hop_bad(k, "spacing <= 0");
+        GRID_CHECK(grid_frame_check(ENTRY, k, J.origin, J.spacing));
         if (!pw_finite(J.cap)) return hop_bad(k, "the cap is not finite");
-        for (long b = 0; b < L; ++b)
-            if (!pw_finite(betas[J.beta_first + b]) || betas[J.beta_first + b] < 0.0) return hop_bad(k, "a beta is negative or not finite");
-        for (long q = 0; q < 4 * J.m; ++q)
-            if (!pw_finite(planes[4 * J.plane_first + q])) return hop_bad(k, "a plane is not finite");
+        GRID_CHECK(grid_betas_check(ENTRY, k, betas, J.beta_first, L));
+        GRID_CHECK(grid_planes_check(ENTRY, k, planes, J.plane_first, J.m));
         if (!lj) {
-            for (long v = 0; v < V; ++v)
-                if (!pas_value_ok(field[J.field_first + v])) return hop_bad(k, "a field value is -inf or not a number");
+            GRID_CHECK(grid_field_check(ENTRY, k, field, J.field_first, V));
             continue;
         }
-        if (!pw_finite(J.core2) || !(J.core2 >= AFF_MIN_CORE2)) return hop_bad(k, "core2 below 1e-6 or not finite");
-        if (!pw_finite(J.cutoff2) || !(J.cutoff2 == 0.0 || J.cutoff2 > J.core2))
-            return hop_bad(k, "cutoff2 is neither 0 nor above core2");
-        for (long a = 0; a < J.n; ++a) {
-            const double* p = xyz + 3 * (J.atom_first + a);
-            if (!pw_finite(p[0]) || !pw_finite(p[1]) || !pw_finite(p[2])) return hop_bad(k, "a coordinate is not finite");
-            const double* c = coef + 2 * (J.coef_first + a);
-            if (!pw_finite(c[0]) || !pw_finite(c[1])) return hop_bad(k, "a coefficient is not finite");
-            if (c[0] < 0.0 || c[1] < 0.0 || c[0] > AFF_MAX_COEF || c[1] > AFF_MAX_COEF)
-                return hop_bad(k, "a coefficient outside 0 .. 1e100");
+        GRID_CHECK(grid_core_check(ENTRY, k, J.core2, J.cutoff2));
+        for (long a = 0; a < J.n; ++a) {                             // (atom by atom: its coordinates, then its row)
+            GRID_CHECK(grid_xyz_check(ENTRY, k, xyz, J.atom_first + a, 1));
+            GRID_CHECK(grid_coef_check(ENTRY, k, coef, J.coef_first + a, 1, 2, false));
         }
     }
-    // outputs of two jobs: the later of the two is named
-    const char* what[4] = {"shares rows of slabs with an earlier job", "shares pairs of sums with an earlier job",
-                           "shares a row of out with an earlier job", "shares words with an earlier job"};
-    for (int kind = 0; kind < 4; ++kind) {
-        std::vector<std::array<long, 3>> spans;
-        for (long k = 0; k < n_jobs; ++k) {
-            const pw_hop_job& J = jobs[k];
-            if (kind == 0) spans.push_back({(long)J.slab_first, (long)J.nz, k});
-            if (kind == 1) spans.push_back({(long)J.sum_first, (long)J.nz * (long)J.n_betas, k});
-            if (kind == 2) spans.push_back({(long)J.out, 1, k});
-            if (kind == 3 && J.word_first >= 0) spans.push_back({(long)J.word_first, (long)J.ny * J.nz, k});
-        }
-        const long bad = stat_shared(spans);
-        if (bad >= 0) return hop_bad(bad, what[kind]);
-    }
-    return PW_OK;
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares rows of slabs with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].slab_first, (long)jobs[k].nz}; }));
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares pairs of sums with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].sum_first, (long)jobs[k].nz * (long)jobs[k].n_betas}; }));
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares a row of out with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].out, 1}; }));
+    return shared_output(ENTRY, n_jobs, "shares words with an earlier job", [&](long k) {
+        const pw_hop_job& J = jobs[k];
+        return OutSpan{(long)J.word_first, J.word_first >= 0 ? (long)J.ny * J.nz : 0};
+    });
 }
 
 // the marks between the kernels of a call, for the measurement entry: mark() records an event, the times of the odd and
@@ -340,47 +316,37 @@ int hop(pw_context* ctx, const pw_hop_job* jobs, int64_t n_jobs, const double* x
     // the spans of the arrays that the jobs read, and the plan: jobs in order, gathered into launches while their maps
     // fit the budget
     const long budget_words = (workspace_bytes ? (long)workspace_bytes : HOP_WORKSPACE_BYTES) / 8;
-    long a_lo = -1, a_hi = 0, c_lo = -1, c_hi = 0, p_lo = -1, p_hi = 0, b_lo = -1, b_hi = 0;
-    auto widen = [](long& lo, long& hi, long first, long count) {
-        if (count == 0) return;
-        if (lo < 0 || first < lo) lo = first;
-        if (first + count > hi) hi = first + count;
-    };
+    Span atoms, rows_ab, windows, beta_span;
     for (long k = 0; k < N; ++k) {
         const pw_hop_job& J = jobs[k];
         if (J.field_first == -1) {
-            widen(a_lo, a_hi, (long)J.atom_first, (long)J.n);
-            widen(c_lo, c_hi, (long)J.coef_first, (long)J.n);
+            atoms.widen((long)J.atom_first, (long)J.n);
+            rows_ab.widen((long)J.coef_first, (long)J.n);
         }
-        widen(p_lo, p_hi, (long)J.plane_first, (long)J.m);
-        widen(b_lo, b_hi, (long)J.beta_first, (long)J.n_betas);
+        windows.widen((long)J.plane_first, (long)J.m);
+        beta_span.widen((long)J.beta_first, (long)J.n_betas);
     }
-    for (long* lo : {&a_lo, &c_lo, &p_lo, &b_lo})
-        if (*lo < 0) *lo = 0;
     std::vector<HopJobDev> devs((size_t)N);
-    std::vector<HopGroup> groups;
-    HopGroup cur{0, 0, 0, 0, 0};
-    long max_words = 0, res_words = 0;
+    std::vector<LaunchGroup> groups;
+    LaunchGroup cur;
+    long res_words = 0;
     for (long k = 0; k < N; ++k) {
         const pw_hop_job& J = jobs[k];
         const long rows = (long)J.ny * J.nz, V = rows * J.nx;
         const bool lj = J.field_first == -1;
-        if (cur.last > cur.first && cur.words + V > budget_words) {
-            groups.push_back(cur);
-            cur = HopGroup{cur.last, cur.last, 0, 0, 0};
-        }
+        place(groups, cur, budget_words, V);
         HopJobDev& D = devs[k];
-        D.atom_first = lj && J.n ? (long)J.atom_first - a_lo : 0;
         D.n = lj ? (long)J.n : 0;
-        D.coef_first = lj && J.n ? (long)J.coef_first - c_lo : 0;
-        D.plane_first = J.m ? (long)J.plane_first - p_lo : 0;
+        D.atom_first = atoms.rel((long)J.atom_first, D.n);
+        D.coef_first = rows_ab.rel((long)J.coef_first, D.n);
+        D.plane_first = windows.rel((long)J.plane_first, (long)J.m);
         D.m = (long)J.m;
         D.map_first = cur.words;
         D.item_first = cur.items;
         D.chunks = lj ? (V + AFF_CHUNK - 1) / AFF_CHUNK : 0;
         D.slab_first = cur.blocks;
         D.V = V;
-        D.beta_first = (long)J.beta_first - b_lo;
+        D.beta_first = (long)J.beta_first - beta_span.lo;
         D.res_first = res_words;
         res_words += (long)J.nz * hop_record_words((int)J.n_betas);
         D.resw_first = J.word_first >= 0 ? res_words : -1;
@@ -388,12 +354,11 @@ int hop(pw_context* ctx, const pw_hop_job* jobs, int64_t n_jobs, const double* x
         for (int a = 0; a < 3; ++a) D.o[a] = J.origin[a];
         D.h = J.spacing; D.core2 = J.core2; D.cutoff2 = J.cutoff2; D.cap = J.cap;
         D.nx = J.nx; D.ny = J.ny; D.nz = J.nz; D.L = (int)J.n_betas; D.si = J.seed[0]; D.sj = J.seed[1];
-        cur.words += V; cur.items += D.chunks; cur.blocks += J.nz; cur.last += 1;
-        max_words = cur.words > max_words ? cur.words : max_words;
+        cur.words += V; cur.cost += V; cur.items += D.chunks; cur.blocks += J.nz; cur.last += 1;
     }
     groups.push_back(cur);
 
-    const size_t ws_bytes = sizeof(u64) * (size_t)max_words, res_bytes = sizeof(u64) * (size_t)res_words;
+    const size_t ws_bytes = sizeof(u64) * (size_t)most_words(groups), res_bytes = sizeof(u64) * (size_t)res_words;
     std::vector<u64> res((size_t)res_words);
 
     DeviceScope dev_scope_;
@@ -408,26 +373,19 @@ int hop(pw_context* ctx, const pw_hop_job* jobs, int64_t n_jobs, const double* x
         double *d_xyz, *d_coef, *d_planes, *d_betas;
         u64 *d_ws, *d_res;
         STAT_TRY(buf.alloc(&d_jobs, sizeof(HopJobDev) * (size_t)N));
-        STAT_TRY(buf.alloc(&d_xyz, sizeof(double) * 3 * (size_t)(a_hi - a_lo)));
-        STAT_TRY(buf.alloc(&d_coef, sizeof(double) * 2 * (size_t)(c_hi - c_lo)));
-        STAT_TRY(buf.alloc(&d_planes, sizeof(double) * 4 * (size_t)(p_hi - p_lo)));
-        STAT_TRY(buf.alloc(&d_betas, sizeof(double) * (size_t)(b_hi - b_lo)));
+        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(HopJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
+        STAT_TRY(atoms.upload(buf, &d_xyz, xyz, 3));
+        STAT_TRY(rows_ab.upload(buf, &d_coef, coef, 2));
+        STAT_TRY(windows.upload(buf, &d_planes, planes, 4));
+        STAT_TRY(beta_span.upload(buf, &d_betas, betas, 1));         // (every job has a beta: never empty)
         STAT_TRY(buf.alloc(&d_ws, ws_bytes));
         STAT_TRY(buf.alloc(&d_res, res_bytes));
         const bool poison = scratch_poisoned();                      // (test hook, pw_stat_host.hpp)
         STAT_TRY(poison_scratch(poison, d_ws, ws_bytes, st));
         STAT_TRY(poison_scratch(poison, d_res, res_bytes, st));
-        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(HopJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
-        if (a_hi > a_lo)
-            STAT_TRY(hipMemcpyAsync(d_xyz, xyz + 3 * a_lo, sizeof(double) * 3 * (size_t)(a_hi - a_lo), hipMemcpyHostToDevice, st));
-        if (c_hi > c_lo)
-            STAT_TRY(hipMemcpyAsync(d_coef, coef + 2 * c_lo, sizeof(double) * 2 * (size_t)(c_hi - c_lo), hipMemcpyHostToDevice, st));
-        if (p_hi > p_lo)
-            STAT_TRY(hipMemcpyAsync(d_planes, planes + 4 * p_lo, sizeof(double) * 4 * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
-        STAT_TRY(hipMemcpyAsync(d_betas, betas + b_lo, sizeof(double) * (size_t)(b_hi - b_lo), hipMemcpyHostToDevice, st));
         STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one takes the workspace over when this one is done)
-        for (const HopGroup& G : groups) {
+        for (const LaunchGroup& G : groups) {
             const unsigned n_group = (unsigned)(G.last - G.first);
             for (long k = G.first; k < G.last; ++k)
                 if (jobs[k].field_first >= 0)

@@ -37,7 +37,7 @@
 #include "pw_cavity_dev.hpp"
 #include "pw_field_dev.hpp"
 #include "pw_passage.hpp"
-#include "pw_stat_host.hpp"
+#include "pw_grid_host.hpp"
 
 using namespace pw;
 
@@ -348,62 +348,40 @@ pw_passage_kernel(const PasJobDev* __restrict__ jobs, int n_jobs, const double* 
     }
 }
 
-// jobs [first, last) go in one launch and share one workspace of `words` 8-byte words; `items` is the chunks of their
-// field kernel, `blocks` their rows, and the largest of them has `rows` rows of the grid
-struct PasGroup {
-    long first, last, words, items, blocks, rows;
-};
-
-int pas_bad(long k, const char* what) { return stat_bad("pw_passage", k, what); }
+const char* const ENTRY = "pw_passage";
+int pas_bad(long k, const char* what) { return stat_bad(ENTRY, k, what); }
 
 // Everything is checked before anything is launched or written
 int pas_check(const pw_passage_job* jobs, long n_jobs, const double* xyz, long n_points, const double* coef, long n_coef,
               const double* planes, long n_planes, const double* field, long n_field, long n_out) {
     for (long k = 0; k < n_jobs; ++k) {
         const pw_passage_job& J = jobs[k];
-        if (J.nx < 1 || J.nx > CAVITY_MAX_G || J.ny < 1 || J.ny > CAVITY_MAX_G || J.nz < 1 || J.nz > CAVITY_MAX_G)
-            return pas_bad(k, "a dimension outside 1 .. PW_CAVITY_MAX_G (64)");
+        GRID_CHECK(grid_dims_check(ENTRY, k, J.nx, J.ny, J.nz));
         if (J.seed[0] < 0 || J.seed[0] >= J.nx || J.seed[1] < 0 || J.seed[1] >= J.ny || J.seed[2] < 0 || J.seed[2] >= J.nz)
             return pas_bad(k, "the seed is outside the grid");
         const long V = (long)J.nx * J.ny * J.nz;
         const bool lj = J.field_first == -1;
         if (J.n < 0 || J.m < 0) return pas_bad(k, "a negative count");
-        if (lj && (J.atom_first < 0 || J.n > n_points || J.atom_first > n_points - J.n)) return pas_bad(k, "atoms outside xyz");
-        if (lj && (J.coef_first < 0 || J.n > n_coef || J.coef_first > n_coef - J.n)) return pas_bad(k, "coefficients outside coef");
-        if (J.plane_first < 0 || J.m > n_planes || J.plane_first > n_planes - J.m) return pas_bad(k, "planes outside the array");
-        if (J.field_first < -1 || (!lj && (V > n_field || J.field_first > n_field - V)))
-            return pas_bad(k, "the field is outside its array");
-        const long R = pas_rows_out((long)J.m);
-        if (J.out_first < 0 || R > n_out || J.out_first > n_out - R) return pas_bad(k, "the rows are outside out");
+        if (lj && span_outside(J.atom_first, J.n, n_points)) return pas_bad(k, "atoms outside xyz");
+        if (lj && span_outside(J.coef_first, J.n, n_coef)) return pas_bad(k, "coefficients outside coef");
+        if (span_outside(J.plane_first, J.m, n_planes)) return pas_bad(k, "planes outside the array");
+        if (J.field_first < -1 || (!lj && span_outside(J.field_first, V, n_field))) return pas_bad(k, "the field is outside its array");
+        if (span_outside(J.out_first, pas_rows_out((long)J.m), n_out)) return pas_bad(k, "the rows are outside out");
         if ((lj && J.n && (!xyz || !coef)) || (J.m && !planes) || (!lj && !field)) return pas_bad(k, "null array");
-        if (!pw_finite(J.origin[0]) || !pw_finite(J.origin[1]) || !pw_finite(J.origin[2]) || !pw_finite(J.spacing))
-            return pas_bad(k, "the origin or the spacing is not finite");
-        if (!(J.spacing > 0.0)) return pas_bad(k, "spacing <= 0");
-        for (long q = 0; q < 4 * J.m; ++q)
-            if (!pw_finite(planes[4 * J.plane_first + q])) return pas_bad(k, "a plane is not finite");
+        GRID_CHECK(grid_frame_check(ENTRY, k, J.origin, J.spacing));
+        GRID_CHECK(grid_planes_check(ENTRY, k, planes, J.plane_first, J.m));
         if (!lj) {
-            for (long v = 0; v < V; ++v)
-                if (!pas_value_ok(field[J.field_first + v])) return pas_bad(k, "a field value is -inf or not a number");
+            GRID_CHECK(grid_field_check(ENTRY, k, field, J.field_first, V));
             continue;
         }
-        if (!pw_finite(J.core2) || !(J.core2 >= AFF_MIN_CORE2)) return pas_bad(k, "core2 below 1e-6 or not finite");
-        if (!pw_finite(J.cutoff2) || !(J.cutoff2 == 0.0 || J.cutoff2 > J.core2))
-            return pas_bad(k, "cutoff2 is neither 0 nor above core2");
-        for (long a = 0; a < J.n; ++a) {
-            const double* p = xyz + 3 * (J.atom_first + a);
-            if (!pw_finite(p[0]) || !pw_finite(p[1]) || !pw_finite(p[2])) return pas_bad(k, "a coordinate is not finite");
-            const double* c = coef + 2 * (J.coef_first + a);
-            if (!pw_finite(c[0]) || !pw_finite(c[1])) return pas_bad(k, "a coefficient is not finite");
-            if (c[0] < 0.0 || c[1] < 0.0 || c[0] > AFF_MAX_COEF || c[1] > AFF_MAX_COEF)
-                return pas_bad(k, "a coefficient outside 0 .. 1e100");
+        GRID_CHECK(grid_core_check(ENTRY, k, J.core2, J.cutoff2));
+        for (long a = 0; a < J.n; ++a) {                             // (atom by atom: its coordinates, then its row)
+            GRID_CHECK(grid_xyz_check(ENTRY, k, xyz, J.atom_first + a, 1));
+            GRID_CHECK(grid_coef_check(ENTRY, k, coef, J.coef_first + a, 1, 2, false));
         }
     }
-    // outputs of two jobs: the later of the two is named
-    std::vector<std::array<long, 3>> spans;
-    for (long k = 0; k < n_jobs; ++k) spans.push_back({(long)jobs[k].out_first, (long)pas_rows_out((long)jobs[k].m), k});
-    const long bad = stat_shared(spans);
-    if (bad >= 0) return pas_bad(bad, "shares rows of out with an earlier job");
-    return PW_OK;
+    return shared_output(ENTRY, n_jobs, "shares rows of out with an earlier job",
+                         [&](long k) { return OutSpan{(long)jobs[k].out_first, (long)pas_rows_out((long)jobs[k].m)}; });
 }
 
 // workspace_bytes: the budget of the maps of the jobs of one launch (0: PAS_WORKSPACE_BYTES; at 1 every job is a launch
@@ -431,40 +409,30 @@ int passage(pw_context* ctx, const pw_passage_job* jobs, int64_t n_jobs, const d
     // the spans of the arrays that the jobs read, and the plan: jobs in order, gathered into launches while their maps
     // fit the budget
     const long budget_words = (workspace_bytes ? (long)workspace_bytes : PAS_WORKSPACE_BYTES) / 8;
-    long a_lo = -1, a_hi = 0, c_lo = -1, c_hi = 0, p_lo = -1, p_hi = 0;
-    auto widen = [](long& lo, long& hi, long first, long count) {
-        if (count == 0) return;
-        if (lo < 0 || first < lo) lo = first;
-        if (first + count > hi) hi = first + count;
-    };
+    Span atoms, rows_ab, windows;
     for (long k = 0; k < N; ++k) {
         const pw_passage_job& J = jobs[k];
         if (J.field_first == -1) {
-            widen(a_lo, a_hi, (long)J.atom_first, (long)J.n);
-            widen(c_lo, c_hi, (long)J.coef_first, (long)J.n);
+            atoms.widen((long)J.atom_first, (long)J.n);
+            rows_ab.widen((long)J.coef_first, (long)J.n);
         }
-        widen(p_lo, p_hi, (long)J.plane_first, (long)J.m);
+        windows.widen((long)J.plane_first, (long)J.m);
     }
-    for (long* lo : {&a_lo, &c_lo, &p_lo})
-        if (*lo < 0) *lo = 0;
     std::vector<PasJobDev> devs((size_t)N);
-    std::vector<PasGroup> groups;
+    std::vector<LaunchGroup> groups;
     std::vector<long> res_first((size_t)N);
-    PasGroup cur{0, 0, 0, 0, 0, 0};
-    long max_words = 0, n_rows = 0;
+    LaunchGroup cur;
+    long n_rows = 0;
     for (long k = 0; k < N; ++k) {
         const pw_passage_job& J = jobs[k];
         const long rows = (long)J.ny * J.nz, V = rows * J.nx, R = pas_rows_out((long)J.m);
         const bool lj = J.field_first == -1;
-        if (cur.last > cur.first && cur.words + V > budget_words) {
-            groups.push_back(cur);
-            cur = PasGroup{cur.last, cur.last, 0, 0, 0, 0};
-        }
+        place(groups, cur, budget_words, V);
         PasJobDev& D = devs[k];
-        D.atom_first = lj && J.n ? (long)J.atom_first - a_lo : 0;
         D.n = lj ? (long)J.n : 0;
-        D.coef_first = lj && J.n ? (long)J.coef_first - c_lo : 0;
-        D.plane_first = J.m ? (long)J.plane_first - p_lo : 0;
+        D.atom_first = atoms.rel((long)J.atom_first, D.n);
+        D.coef_first = rows_ab.rel((long)J.coef_first, D.n);
+        D.plane_first = windows.rel((long)J.plane_first, (long)J.m);
         D.m = (long)J.m;
         D.map_first = cur.words;
         D.item_first = cur.items;
@@ -478,12 +446,12 @@ int passage(pw_context* ctx, const pw_passage_job* jobs, int64_t n_jobs, const d
         D.h = J.spacing; D.core2 = J.core2; D.cutoff2 = J.cutoff2; D.nx = J.nx; D.ny = J.ny; D.nz = J.nz;
         res_first[k] = n_rows;
         n_rows += R;
-        cur.words += V; cur.items += D.chunks; cur.blocks += R; cur.last += 1; cur.rows = rows > cur.rows ? rows : cur.rows;
-        max_words = cur.words > max_words ? cur.words : max_words;
+        cur.words += V; cur.cost += V; cur.items += D.chunks; cur.blocks += R; cur.last += 1;
+        cur.rows = rows > cur.rows ? rows : cur.rows;
     }
     groups.push_back(cur);
 
-    const size_t ws_bytes = sizeof(u64) * (size_t)max_words, res_bytes = sizeof(pw_passage_out) * (size_t)n_rows;
+    const size_t ws_bytes = sizeof(u64) * (size_t)most_words(groups), res_bytes = sizeof(pw_passage_out) * (size_t)n_rows;
     std::vector<pw_passage_out> res((size_t)n_rows);
 
     DeviceScope dev_scope_;
@@ -501,25 +469,19 @@ int passage(pw_context* ctx, const pw_passage_job* jobs, int64_t n_jobs, const d
         u64* d_ws;
         pw_passage_out* d_res;
         STAT_TRY(buf.alloc(&d_jobs, sizeof(PasJobDev) * (size_t)N));
-        STAT_TRY(buf.alloc(&d_xyz, sizeof(double) * 3 * (size_t)(a_hi - a_lo)));
-        STAT_TRY(buf.alloc(&d_coef, sizeof(double) * 2 * (size_t)(c_hi - c_lo)));
-        STAT_TRY(buf.alloc(&d_planes, sizeof(double) * 4 * (size_t)(p_hi - p_lo)));
+        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(PasJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
+        STAT_TRY(atoms.upload(buf, &d_xyz, xyz, 3));
+        STAT_TRY(rows_ab.upload(buf, &d_coef, coef, 2));
+        STAT_TRY(windows.upload(buf, &d_planes, planes, 4));
         STAT_TRY(buf.alloc(&d_ws, ws_bytes));
         STAT_TRY(buf.alloc(&d_res, res_bytes));
         const bool poison = scratch_poisoned();                      // (test hook, pw_stat_host.hpp)
         STAT_TRY(poison_scratch(poison, d_ws, ws_bytes, st));
         STAT_TRY(poison_scratch(poison, d_res, res_bytes, st));
-        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(PasJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
-        if (a_hi > a_lo)
-            STAT_TRY(hipMemcpyAsync(d_xyz, xyz + 3 * a_lo, sizeof(double) * 3 * (size_t)(a_hi - a_lo), hipMemcpyHostToDevice, st));
-        if (c_hi > c_lo)
-            STAT_TRY(hipMemcpyAsync(d_coef, coef + 2 * c_lo, sizeof(double) * 2 * (size_t)(c_hi - c_lo), hipMemcpyHostToDevice, st));
-        if (p_hi > p_lo)
-            STAT_TRY(hipMemcpyAsync(d_planes, planes + 4 * p_lo, sizeof(double) * 4 * (size_t)(p_hi - p_lo), hipMemcpyHostToDevice, st));
         STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one takes the workspace over when this one is done)
         long row0 = 0;
-        for (const PasGroup& G : groups) {
+        for (const LaunchGroup& G : groups) {
             const unsigned n_group = (unsigned)(G.last - G.first);
             for (long k = G.first; k < G.last; ++k)
                 if (jobs[k].field_first >= 0)

@@ -26,7 +26,7 @@
 #include "../../include/pywindow_amd.h"
 #include "pw_affinity_dev.hpp"
 #include "pw_rigid.hpp"
-#include "pw_stat_host.hpp"
+#include "pw_grid_host.hpp"
 
 using namespace pw;
 
@@ -304,12 +304,8 @@ void rigid_launch(int cls, unsigned blocks, size_t lds, hipStream_t st, const Ri
 #undef RIGID_GO
 }
 
-// jobs [first, last) go in one launch and share one workspace of `words` 8-byte words; `items` is their chunks
-struct RigidGroup {
-    long first, last, words, items;
-};
-
-int rigid_bad(long k, const char* what) { return stat_bad("pw_rigid_affinity", k, what); }
+const char* const ENTRY = "pw_rigid_affinity";
+int rigid_bad(long k, const char* what) { return stat_bad(ENTRY, k, what); }
 
 // Everything is checked before anything is launched or written.  V[k]: the voxels of job k's region
 int rigid_check(const pw_rigid_job* jobs, long n_jobs, const double* xyz, long n_points, const double* coef, long n_coef,
@@ -318,47 +314,32 @@ int rigid_check(const pw_rigid_job* jobs, long n_jobs, const double* xyz, long n
                 long n_levels, long n_out, std::vector<long>& V) {
     for (long k = 0; k < n_jobs; ++k) {
         const pw_rigid_job& J = jobs[k];
-        if (J.nx < 1 || J.nx > CAVITY_MAX_G || J.ny < 1 || J.ny > CAVITY_MAX_G || J.nz < 1 || J.nz > CAVITY_MAX_G)
-            return rigid_bad(k, "a dimension outside 1 .. PW_CAVITY_MAX_G (64)");
+        GRID_CHECK(grid_dims_check(ENTRY, k, J.nx, J.ny, J.nz));
         const long rows = (long)J.ny * J.nz, L = (long)J.n_betas, S = (long)J.n_sites, M = (long)J.n_dirs;
         if (J.n < 0) return rigid_bad(k, "a negative count");
-        if (L < 1 || L > AFF_MAX_LEVELS) return rigid_bad(k, "n_betas outside 1 .. PW_AFF_MAX_LEVELS (8)");
+        GRID_CHECK(grid_n_betas_check(ENTRY, k, L));
         if (S < 1 || S > RIGID_MAX_SITES) return rigid_bad(k, "n_sites outside 1 .. PW_RIGID_MAX_SITES (8)");
         if (M < 1 || M > RIGID_MAX_DIRS) return rigid_bad(k, "n_dirs outside 1 .. PW_RIGID_MAX_DIRS (1024)");
         if (J.charged != 0 && J.charged != 1) return rigid_bad(k, "charged is neither 0 nor 1");
         if (J.map_level < -1 || J.map_level >= L) return rigid_bad(k, "map_level outside -1 .. n_betas - 1");
         if (J.map_level >= 0 && J.map_first < 0) return rigid_bad(k, "map_level >= 0 with map_first < 0");
-        if (J.atom_first < 0 || J.n > n_points || J.atom_first > n_points - J.n) return rigid_bad(k, "atoms outside xyz");
-        if (J.coef_first < 0 || S * J.n > n_coef || J.coef_first > n_coef - S * J.n)   // (n <= n_points: no overflow)
-            return rigid_bad(k, "coefficients outside coef");
-        if (J.site_first < 0 || S > n_offsets || J.site_first > n_offsets - S) return rigid_bad(k, "sites outside offsets");
-        if (J.dir_first < 0 || M > n_dirs || J.dir_first > n_dirs - M) return rigid_bad(k, "directions outside dirs");
-        if (J.word_first < -1 || (J.word_first >= 0 && (rows > n_words || J.word_first > n_words - rows)))
+        if (span_outside(J.atom_first, J.n, n_points)) return rigid_bad(k, "atoms outside xyz");
+        if (span_outside(J.coef_first, S * J.n, n_coef)) return rigid_bad(k, "coefficients outside coef");   // (n <= n_points: no overflow)
+        if (span_outside(J.site_first, S, n_offsets)) return rigid_bad(k, "sites outside offsets");
+        if (span_outside(J.dir_first, M, n_dirs)) return rigid_bad(k, "directions outside dirs");
+        if (J.word_first < -1 || (J.word_first >= 0 && span_outside(J.word_first, rows, n_words)))
             return rigid_bad(k, "the words are outside their array");
-        if (J.beta_first < 0 || L > n_betas || J.beta_first > n_betas - L) return rigid_bad(k, "betas outside the array");
-        if (J.level_first < 0 || L > n_levels || J.level_first > n_levels - L) return rigid_bad(k, "the rows are outside levels");
-        if (J.out < 0 || J.out >= n_out) return rigid_bad(k, "the row is outside out");
+        if (span_outside(J.beta_first, L, n_betas)) return rigid_bad(k, "betas outside the array");
+        if (span_outside(J.level_first, L, n_levels)) return rigid_bad(k, "the rows are outside levels");
+        if (span_outside(J.out, 1, n_out)) return rigid_bad(k, "the row is outside out");
         if ((J.n && (!xyz || !coef)) || (J.word_first >= 0 && !words) || !betas || !offsets || !dirs || !levels ||
             (J.map_level >= 0 && !maps))
             return rigid_bad(k, "null array");
-        long count = (long)J.nx * rows;
-        if (J.word_first >= 0) {
-            count = 0;
-            for (long r = 0; r < rows; ++r) count += cavity_popcount(words[J.word_first + r] & cavity_row_mask(J.nx));
-        }
-        V[k] = count;
-        if (J.map_level >= 0 && (2 * count > n_maps || J.map_first > n_maps - 2 * count))
-            return rigid_bad(k, "the maps are outside their array");
-        if (!pw_finite(J.origin[0]) || !pw_finite(J.origin[1]) || !pw_finite(J.origin[2]) || !pw_finite(J.spacing))
-            return rigid_bad(k, "the origin or the spacing is not finite");
-        if (!(J.spacing > 0.0)) return rigid_bad(k, "spacing <= 0");
-        if (!pw_finite(J.core2) || !(J.core2 >= AFF_MIN_CORE2)) return rigid_bad(k, "core2 below 1e-6 or not finite");
-        if (!pw_finite(J.cutoff2) || !(J.cutoff2 == 0.0 || J.cutoff2 > J.core2))
-            return rigid_bad(k, "cutoff2 is neither 0 nor above core2");
-        for (long b = 0; b < L; ++b) {
-            const double beta = betas[J.beta_first + b];
-            if (!pw_finite(beta) || beta < 0.0) return rigid_bad(k, "a beta is negative or not finite");
-        }
+        V[k] = grid_region_voxels(J.word_first >= 0 ? words + J.word_first : nullptr, J.nx, rows);
+        if (J.map_level >= 0 && span_outside(J.map_first, 2 * V[k], n_maps)) return rigid_bad(k, "the maps are outside their array");
+        GRID_CHECK(grid_frame_check(ENTRY, k, J.origin, J.spacing));
+        GRID_CHECK(grid_core_check(ENTRY, k, J.core2, J.cutoff2));
+        GRID_CHECK(grid_betas_check(ENTRY, k, betas, J.beta_first, L));
         for (long s = 0; s < S; ++s) {
             const double t = offsets[J.site_first + s];
             if (!pw_finite(t) || pw_abs(t) > RIGID_MAX_OFFSET) return rigid_bad(k, "an offset is not finite or beyond 16");
@@ -367,34 +348,15 @@ int rigid_check(const pw_rigid_job* jobs, long n_jobs, const double* xyz, long n
             const double d = dirs[3 * J.dir_first + c];
             if (!pw_finite(d) || pw_abs(d) > 1.0) return rigid_bad(k, "a direction's component is not finite or outside -1 .. 1");
         }
-        for (long a = 0; a < J.n; ++a) {
-            const double* p = xyz + 3 * (J.atom_first + a);
-            if (!pw_finite(p[0]) || !pw_finite(p[1]) || !pw_finite(p[2])) return rigid_bad(k, "a coordinate is not finite");
-        }
-        for (long r = 0; r < S * J.n; ++r) {
-            const double* c = coef + 3 * (J.coef_first + r);
-            if (!pw_finite(c[0]) || !pw_finite(c[1])) return rigid_bad(k, "a coefficient is not finite");
-            if (c[0] < 0.0 || c[1] < 0.0 || c[0] > AFF_MAX_COEF || c[1] > AFF_MAX_COEF)
-                return rigid_bad(k, "a coefficient outside 0 .. 1e100");
-            if (J.charged && (!pw_finite(c[2]) || pw_abs(c[2]) > AFF_MAX_COEF))
-                return rigid_bad(k, "a charge term is not finite or beyond 1e100");
-        }
+        GRID_CHECK(grid_xyz_check(ENTRY, k, xyz, J.atom_first, J.n));   // (every coordinate, then every row)
+        GRID_CHECK(grid_coef_check(ENTRY, k, coef, J.coef_first, S * J.n, 3, J.charged != 0));
     }
-    // outputs of two jobs: the later of the two is named
-    std::vector<std::array<long, 3>> spans;
-    for (long k = 0; k < n_jobs; ++k) spans.push_back({(long)jobs[k].out, 1, k});
-    long bad = stat_shared(spans);
-    if (bad >= 0) return rigid_bad(bad, "shares its row of out with an earlier job");
-    spans.clear();
-    for (long k = 0; k < n_jobs; ++k) spans.push_back({(long)jobs[k].level_first, (long)jobs[k].n_betas, k});
-    bad = stat_shared(spans);
-    if (bad >= 0) return rigid_bad(bad, "shares rows of levels with an earlier job");
-    spans.clear();
-    for (long k = 0; k < n_jobs; ++k)
-        if (jobs[k].map_level >= 0 && V[k]) spans.push_back({(long)jobs[k].map_first, 2 * V[k], k});
-    bad = stat_shared(spans);
-    if (bad >= 0) return rigid_bad(bad, "shares maps with an earlier job");
-    return PW_OK;
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares its row of out with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].out, 1}; }));
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares rows of levels with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].level_first, (long)jobs[k].n_betas}; }));
+    return shared_output(ENTRY, n_jobs, "shares maps with an earlier job",
+                         [&](long k) { return OutSpan{(long)jobs[k].map_first, jobs[k].map_level >= 0 ? 2 * V[k] : 0}; });
 }
 
 // workspace_bytes: the budget of the prefixes, partials and maps of the jobs of one launch (0: RIGID_WORKSPACE_BYTES; at 1
@@ -425,35 +387,27 @@ int rigid(pw_context* ctx, const pw_rigid_job* jobs, int64_t n_jobs, const doubl
     // the spans of the arrays that the jobs read, and the plan: jobs in order, gathered into launches while their
     // prefixes, partials and maps fit the budget
     const long budget_words = (workspace_bytes ? (long)workspace_bytes : RIGID_WORKSPACE_BYTES) / 8;
-    long a_lo = -1, a_hi = 0, c_lo = -1, c_hi = 0, w_lo = -1, w_hi = 0, b_lo = -1, b_hi = 0, s_lo = -1, s_hi = 0, d_lo = -1,
-         d_hi = 0;
-    auto widen = [](long& lo, long& hi, long first, long count) {
-        if (count == 0) return;
-        if (lo < 0 || first < lo) lo = first;
-        if (first + count > hi) hi = first + count;
-    };
+    Span atoms, rows_abq, region, beta_span, site_span, dir_span;
     for (long k = 0; k < N; ++k) {
         const pw_rigid_job& J = jobs[k];
-        widen(a_lo, a_hi, (long)J.atom_first, (long)J.n);
-        widen(c_lo, c_hi, (long)J.coef_first, (long)J.n_sites * (long)J.n);
-        if (J.word_first >= 0) widen(w_lo, w_hi, (long)J.word_first, (long)J.ny * J.nz);
-        widen(b_lo, b_hi, (long)J.beta_first, (long)J.n_betas);
-        widen(s_lo, s_hi, (long)J.site_first, (long)J.n_sites);
-        widen(d_lo, d_hi, (long)J.dir_first, (long)J.n_dirs);
+        atoms.widen((long)J.atom_first, (long)J.n);
+        rows_abq.widen((long)J.coef_first, (long)J.n_sites * (long)J.n);
+        if (J.word_first >= 0) region.widen((long)J.word_first, (long)J.ny * J.nz);
+        beta_span.widen((long)J.beta_first, (long)J.n_betas);
+        site_span.widen((long)J.site_first, (long)J.n_sites);
+        dir_span.widen((long)J.dir_first, (long)J.n_dirs);
     }
-    for (long* lo : {&a_lo, &c_lo, &w_lo, &b_lo, &s_lo, &d_lo})
-        if (*lo < 0) *lo = 0;
-    // betas, offsets and directions travel as one array
-    const long n_beta_span = b_hi - b_lo, n_site_span = s_hi - s_lo, n_dir_span = d_hi - d_lo;
+    // betas, offsets and directions travel as one array (every job has some of each: the three spans have a lo)
+    const long n_beta_span = beta_span.count(), n_site_span = site_span.count(), n_dir_span = dir_span.count();
     std::vector<double> params((size_t)(n_beta_span + n_site_span + 3 * n_dir_span));
-    memcpy(params.data(), betas + b_lo, sizeof(double) * (size_t)n_beta_span);
-    memcpy(params.data() + n_beta_span, offsets + s_lo, sizeof(double) * (size_t)n_site_span);
-    memcpy(params.data() + n_beta_span + n_site_span, dirs + 3 * d_lo, sizeof(double) * 3 * (size_t)n_dir_span);
+    memcpy(params.data(), betas + beta_span.lo, sizeof(double) * (size_t)n_beta_span);
+    memcpy(params.data() + n_beta_span, offsets + site_span.lo, sizeof(double) * (size_t)n_site_span);
+    memcpy(params.data() + n_beta_span + n_site_span, dirs + 3 * dir_span.lo, sizeof(double) * 3 * (size_t)n_dir_span);
 
     std::vector<RigidJobDev> devs((size_t)N);
-    std::vector<RigidGroup> groups;
-    RigidGroup cur{0, 0, 0, 0};
-    long max_words = 0, n_level_rows = 0;
+    std::vector<LaunchGroup> groups;
+    LaunchGroup cur;
+    long n_level_rows = 0;
     for (long k = 0; k < N; ++k) {
         const pw_rigid_job& J = jobs[k];
         const long rows = (long)J.ny * J.nz, L = (long)J.n_betas;
@@ -461,24 +415,21 @@ int rigid(pw_context* ctx, const pw_rigid_job* jobs, int64_t n_jobs, const doubl
         const bool masked = J.word_first >= 0;
         const long prefix_words = masked ? (rows + 2) / 2 : 0, part_words = chunks * rigid_part_words((int)L),
                    map_words = J.map_level >= 0 ? 2 * V[k] : 0, need = prefix_words + part_words + map_words;
-        if (cur.last > cur.first && cur.words + need + 1 > budget_words) {   // (a word more a job: no job is free)
-            groups.push_back(cur);
-            cur = RigidGroup{cur.last, cur.last, 0, 0};
-        }
+        place(groups, cur, budget_words, need + 1);                  // (a word more a job: no job is free)
         RigidJobDev& D = devs[k];
-        D.atom_first = J.n ? (long)J.atom_first - a_lo : 0;
+        D.atom_first = atoms.rel((long)J.atom_first, (long)J.n);
         D.n = (long)J.n;
-        D.coef_first = J.n ? (long)J.coef_first - c_lo : 0;
-        D.word_first = masked ? (long)J.word_first - w_lo : -1;
+        D.coef_first = rows_abq.rel((long)J.coef_first, (long)J.n);
+        D.word_first = masked ? (long)J.word_first - region.lo : -1;
         D.prefix_first = masked ? cur.words : -1;
         D.part_first = cur.words + prefix_words;
         D.map_first = J.map_level >= 0 ? cur.words + prefix_words + part_words : -1;
         D.item_first = cur.items;
         D.chunks = chunks;
         D.V = V[k];
-        D.beta_first = (long)J.beta_first - b_lo;
-        D.site_first = (long)J.site_first - s_lo;
-        D.dir_first = (long)J.dir_first - d_lo;
+        D.beta_first = (long)J.beta_first - beta_span.lo;
+        D.site_first = (long)J.site_first - site_span.lo;
+        D.dir_first = (long)J.dir_first - dir_span.lo;
         D.level_first = n_level_rows;
         for (int a = 0; a < 3; ++a) D.o[a] = J.origin[a];
         D.h = J.spacing; D.core2 = J.core2; D.cutoff2 = J.cutoff2;
@@ -486,14 +437,13 @@ int rigid(pw_context* ctx, const pw_rigid_job* jobs, int64_t n_jobs, const doubl
         D.cls = rigid_class((int)J.n_sites, J.charged != 0);
         D.map_level = J.map_level;
         n_level_rows += L;
-        cur.words += need + 1; cur.items += chunks; cur.last += 1;
-        max_words = cur.words > max_words ? cur.words : max_words;
+        cur.words += need + 1; cur.cost += need + 1; cur.items += chunks; cur.last += 1;
     }
     groups.push_back(cur);
 
     // the compact result of the call: the rows of out in job order, then the rows of levels
     const size_t out_bytes = sizeof(pw_rigid_out) * (size_t)N, levels_bytes = sizeof(pw_affinity_level) * (size_t)n_level_rows,
-                 res_bytes = out_bytes + levels_bytes, ws_bytes = sizeof(u64) * (size_t)max_words;
+                 res_bytes = out_bytes + levels_bytes, ws_bytes = sizeof(u64) * (size_t)most_words(groups);
     std::vector<unsigned char> res(res_bytes);
     std::vector<std::vector<double>> got(groups.size());             // the maps of a launch, as its workspace has them
 
@@ -509,23 +459,17 @@ int rigid(pw_context* ctx, const pw_rigid_job* jobs, int64_t n_jobs, const doubl
         u64 *d_words, *d_ws;
         unsigned char* d_res;
         STAT_TRY(buf.alloc(&d_jobs, sizeof(RigidJobDev) * (size_t)N));
-        STAT_TRY(buf.alloc(&d_xyz, sizeof(double) * 3 * (size_t)(a_hi - a_lo)));
-        STAT_TRY(buf.alloc(&d_coef, sizeof(double) * 3 * (size_t)(c_hi - c_lo)));
-        STAT_TRY(buf.alloc(&d_words, sizeof(u64) * (size_t)(w_hi - w_lo)));
+        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(RigidJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
+        STAT_TRY(atoms.upload(buf, &d_xyz, xyz, 3));
+        STAT_TRY(rows_abq.upload(buf, &d_coef, coef, 3));
+        STAT_TRY(region.upload(buf, &d_words, words, 1));
         STAT_TRY(buf.alloc(&d_params, sizeof(double) * params.size()));
+        STAT_TRY(hipMemcpyAsync(d_params, params.data(), sizeof(double) * params.size(), hipMemcpyHostToDevice, st));
         STAT_TRY(buf.alloc(&d_ws, ws_bytes));
         STAT_TRY(buf.alloc(&d_res, res_bytes));
         const bool poison = scratch_poisoned();                      // (test hook, pw_stat_host.hpp)
         STAT_TRY(poison_scratch(poison, d_ws, ws_bytes, st));
         STAT_TRY(poison_scratch(poison, d_res, res_bytes, st));
-        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(RigidJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
-        if (a_hi > a_lo)
-            STAT_TRY(hipMemcpyAsync(d_xyz, xyz + 3 * a_lo, sizeof(double) * 3 * (size_t)(a_hi - a_lo), hipMemcpyHostToDevice, st));
-        if (c_hi > c_lo)
-            STAT_TRY(hipMemcpyAsync(d_coef, coef + 3 * c_lo, sizeof(double) * 3 * (size_t)(c_hi - c_lo), hipMemcpyHostToDevice, st));
-        if (w_hi > w_lo)
-            STAT_TRY(hipMemcpyAsync(d_words, words + w_lo, sizeof(u64) * (size_t)(w_hi - w_lo), hipMemcpyHostToDevice, st));
-        STAT_TRY(hipMemcpyAsync(d_params, params.data(), sizeof(double) * params.size(), hipMemcpyHostToDevice, st));
         pw_rigid_out* d_out = (pw_rigid_out*)d_res;
         double* d_levels = (double*)(d_res + out_bytes);
         const double *d_betas = d_params, *d_offsets = d_params + n_beta_span, *d_dirs = d_params + n_beta_span + n_site_span;
@@ -533,14 +477,14 @@ int rigid(pw_context* ctx, const pw_rigid_job* jobs, int64_t n_jobs, const doubl
         // (launches follow one another on the stream, so the next one may take the workspace over once the maps of this
         // one are on their way)
         for (size_t g = 0; g < groups.size(); ++g) {
-            const RigidGroup& G = groups[g];
+            const LaunchGroup& G = groups[g];
             const unsigned n_group = (unsigned)(G.last - G.first);
             bool any_mask = false, needed[RIGID_CLASSES] = {};
-            long m_lo_ws = -1, m_hi_ws = 0;
+            Span maps_ws;                                            // the maps of the group in its workspace
             int max_M = 1;
             for (long k = G.first; k < G.last; ++k) {
                 any_mask = any_mask || devs[k].prefix_first >= 0;
-                if (devs[k].map_first >= 0) widen(m_lo_ws, m_hi_ws, devs[k].map_first, 2 * devs[k].V);
+                if (devs[k].map_first >= 0) maps_ws.widen(devs[k].map_first, 2 * devs[k].V);
                 if (devs[k].chunks) {
                     needed[devs[k].cls] = true;
                     max_M = devs[k].M > max_M ? devs[k].M : max_M;
@@ -563,12 +507,12 @@ int rigid(pw_context* ctx, const pw_rigid_job* jobs, int64_t n_jobs, const doubl
             hipLaunchKernelGGL(pw_rigid_reduce_kernel, dim3(n_group), dim3(AFF_CHUNK), 0, st, d_jobs + G.first, d_words, d_ws,
                                d_out + G.first, d_levels);
             STAT_TRY(hipGetLastError());
-            if (m_lo_ws >= 0) {
-                got[g].resize((size_t)(m_hi_ws - m_lo_ws));
-                STAT_TRY(hipMemcpyAsync(got[g].data(), d_ws + m_lo_ws, sizeof(double) * got[g].size(), hipMemcpyDeviceToHost, st));
+            if (maps_ws.lo >= 0) {
+                got[g].resize((size_t)maps_ws.count());
+                STAT_TRY(hipMemcpyAsync(got[g].data(), d_ws + maps_ws.lo, sizeof(double) * got[g].size(), hipMemcpyDeviceToHost, st));
                 // (map_first of the group's jobs becomes relative to that copy)
                 for (long k = G.first; k < G.last; ++k)
-                    if (devs[k].map_first >= 0) devs[k].map_first -= m_lo_ws;
+                    if (devs[k].map_first >= 0) devs[k].map_first -= maps_ws.lo;
             }
         }
         STAT_TRY(ev.stop(st));

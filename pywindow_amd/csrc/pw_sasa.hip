@@ -33,7 +33,7 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_sasa.hpp"
-#include "pw_stat_host.hpp"
+#include "pw_grid_host.hpp"
 
 using namespace pw;
 
@@ -188,7 +188,8 @@ pw_sasa_kernel(const SasaBlock* __restrict__ blocks, const SasaJobDev* __restric
     if (tid == 0 && B.a_begin == 0) row->flags = grid ? SASA_GRID : 0;
 }
 
-int sasa_bad(long k, const char* what) { return stat_bad("pw_sasa", k, what); }
+const char* const ENTRY = "pw_sasa";
+int sasa_bad(long k, const char* what) { return stat_bad(ENTRY, k, what); }
 
 // Everything is checked before anything is launched or written.
 int sasa_check(const pw_sasa_job* jobs, long n_jobs, const double* xyz, long n_points, const double* radii, long n_radii,
@@ -199,32 +200,21 @@ int sasa_check(const pw_sasa_job* jobs, long n_jobs, const double* xyz, long n_p
         const pw_sasa_job& J = jobs[k];
         const bool grid = J.word_first != -1;
         if (J.n < 0) return sasa_bad(k, "a negative count");
-        if (J.atom_first < 0 || J.n > n_points || J.atom_first > n_points - J.n) return sasa_bad(k, "atoms outside xyz");
-        if (J.radius_first < 0 || J.n > n_radii || J.radius_first > n_radii - J.n) return sasa_bad(k, "radii outside the array");
-        if (J.count_first < 0 || J.n > n_counts || J.count_first > n_counts - J.n)
-            return sasa_bad(k, "the counts are outside exposed and inside");
-        if (J.out < 0 || J.out >= n_out) return sasa_bad(k, "the row is outside out");
+        if (span_outside(J.atom_first, J.n, n_points)) return sasa_bad(k, "atoms outside xyz");
+        if (span_outside(J.radius_first, J.n, n_radii)) return sasa_bad(k, "radii outside the array");
+        if (span_outside(J.count_first, J.n, n_counts)) return sasa_bad(k, "the counts are outside exposed and inside");
+        if (span_outside(J.out, 1, n_out)) return sasa_bad(k, "the row is outside out");
         if (grid) {
-            if (J.nx < 1 || J.nx > CAVITY_MAX_G || J.ny < 1 || J.ny > CAVITY_MAX_G || J.nz < 1 || J.nz > CAVITY_MAX_G)
-                return sasa_bad(k, "a dimension outside 1 .. PW_CAVITY_MAX_G (64)");
-            const long rows = (long)J.ny * J.nz;
-            if (J.word_first < 0 || rows > n_words || J.word_first > n_words - rows)
-                return sasa_bad(k, "the words are outside their array");
+            GRID_CHECK(grid_dims_check(ENTRY, k, J.nx, J.ny, J.nz));
+            if (span_outside(J.word_first, (long)J.ny * J.nz, n_words)) return sasa_bad(k, "the words are outside their array");
         }
         if ((J.n && (!xyz || !radii || !exposed || !inside || !directions)) || (grid && !words)) return sasa_bad(k, "null array");
         if (!pw_finite(J.probe)) return sasa_bad(k, "the probe is not finite");
         if (J.probe < 0.0) return sasa_bad(k, "a negative probe");
-        if (grid) {
-            if (!pw_finite(J.origin[0]) || !pw_finite(J.origin[1]) || !pw_finite(J.origin[2]) || !pw_finite(J.spacing))
-                return sasa_bad(k, "the origin or the spacing is not finite");
-            if (!(J.spacing > 0.0)) return sasa_bad(k, "spacing <= 0");
-        }
-        for (long a = 0; a < J.n; ++a) {
-            const double* p = xyz + 3 * (J.atom_first + a);
-            if (!pw_finite(p[0]) || !pw_finite(p[1]) || !pw_finite(p[2])) return sasa_bad(k, "a coordinate is not finite");
-            const double r = radii[J.radius_first + a];
-            if (!pw_finite(r)) return sasa_bad(k, "a radius is not finite");
-            if (r < 0.0) return sasa_bad(k, "a negative radius");
+        if (grid) GRID_CHECK(grid_frame_check(ENTRY, k, J.origin, J.spacing));
+        for (long a = 0; a < J.n; ++a) {                             // (atom by atom: its coordinates, then its radius)
+            GRID_CHECK(grid_xyz_check(ENTRY, k, xyz, J.atom_first + a, 1));
+            GRID_CHECK(grid_radii_check(ENTRY, k, radii, J.radius_first + a, 1));
         }
         if (J.n && !directions_checked) {
             if (P < 1 || P > SASA_MAX_POINTS)
@@ -240,14 +230,13 @@ int sasa_check(const pw_sasa_job* jobs, long n_jobs, const double* xyz, long n_p
             directions_checked = true;
         }
     }
-    // outputs of two jobs: the later of the two is named
-    std::vector<std::pair<long, long>> rows_of((size_t)n_jobs);
-    for (long k = 0; k < n_jobs; ++k) rows_of[k] = {(long)jobs[k].out, k};
-    std::sort(rows_of.begin(), rows_of.end());
+    // outputs of two jobs: the later of the two is named.  (Of rows, all of length 1, stat_shared names the second
+    // lowest job of a row that is shared, as the sweep over equal neighbours did.  The counts keep their sweep, which
+    // orders spans of one first by job where stat_shared orders them by length: with three jobs at one first and the
+    // lengths 1, 3, 2 this one names job 1 and stat_shared job 2 -- tests/test_sasa.py holds every such case.)
+    GRID_CHECK(shared_output(ENTRY, n_jobs, "shares its row of out with an earlier job",
+                             [&](long k) { return OutSpan{(long)jobs[k].out, 1}; }));
     long bad = -1;
-    for (long i = 1; i < n_jobs; ++i)
-        if (rows_of[i].first == rows_of[i - 1].first && (bad < 0 || rows_of[i].second < bad)) bad = rows_of[i].second;
-    if (bad >= 0) return sasa_bad(bad, "shares its row of out with an earlier job");
     std::vector<std::pair<long, long>> spans;
     for (long k = 0; k < n_jobs; ++k)
         if (jobs[k].n > 0) spans.push_back({(long)jobs[k].count_first, k});
@@ -295,20 +284,12 @@ int sasa(pw_context* ctx, const pw_sasa_job* jobs, int64_t n_jobs, const double*
     const long stage = lds_words == 0 ? SASA_LDS_WORDS : lds_words < 0 ? 0 : std::min<long>((long)lds_words, CAVITY_MAX_G * CAVITY_MAX_G);
     const long per_block = block_atoms ? (long)block_atoms : SASA_BLOCK_ATOMS;
     // the spans of the arrays that the jobs read, the compacted counts and the workgroups
-    long a_lo = -1, a_hi = 0, r_lo = -1, r_hi = 0, w_lo = -1, w_hi = 0;
-    auto widen = [](long& lo, long& hi, long first, long count) {
-        if (count == 0) return;
-        if (lo < 0 || first < lo) lo = first;
-        if (first + count > hi) hi = first + count;
-    };
+    Span atoms, atom_radii, region;
     for (long k = 0; k < N; ++k) {
-        widen(a_lo, a_hi, (long)jobs[k].atom_first, (long)jobs[k].n);
-        widen(r_lo, r_hi, (long)jobs[k].radius_first, (long)jobs[k].n);
-        if (jobs[k].word_first >= 0) widen(w_lo, w_hi, (long)jobs[k].word_first, (long)jobs[k].ny * jobs[k].nz);
+        atoms.widen((long)jobs[k].atom_first, (long)jobs[k].n);
+        atom_radii.widen((long)jobs[k].radius_first, (long)jobs[k].n);
+        if (jobs[k].word_first >= 0) region.widen((long)jobs[k].word_first, (long)jobs[k].ny * jobs[k].nz);
     }
-    if (a_lo < 0) a_lo = a_hi = 0;
-    if (r_lo < 0) r_lo = r_hi = 0;
-    if (w_lo < 0) w_lo = w_hi = 0;
     std::vector<SasaJobDev> devs((size_t)N);
     std::vector<SasaBlock> blocks;
     long total = 0, lds_rows = 0;
@@ -317,11 +298,11 @@ int sasa(pw_context* ctx, const pw_sasa_job* jobs, int64_t n_jobs, const double*
         const bool grid = J.word_first >= 0;
         const long rows = grid ? (long)J.ny * J.nz : 0;
         SasaJobDev& D = devs[k];
-        D.atom_first = J.n ? (long)J.atom_first - a_lo : 0;
+        D.atom_first = atoms.rel((long)J.atom_first, (long)J.n);
         D.n = (long)J.n;
-        D.radius_first = J.n ? (long)J.radius_first - r_lo : 0;
+        D.radius_first = atom_radii.rel((long)J.radius_first, (long)J.n);
         D.count_first = total;
-        D.word_first = grid ? (long)J.word_first - w_lo : -1;
+        D.word_first = grid ? (long)J.word_first - region.lo : -1;
         for (int a = 0; a < 3; ++a) D.o[a] = grid ? J.origin[a] : 0.0;
         D.h = grid ? J.spacing : 1.0;
         D.probe = J.probe;
@@ -355,23 +336,17 @@ int sasa(pw_context* ctx, const pw_sasa_job* jobs, int64_t n_jobs, const double*
         const size_t counts_bytes = sizeof(int) * 2 * (size_t)total, out_bytes = sizeof(pw_sasa_out) * (size_t)N;
         STAT_TRY(buf.alloc(&d_blocks, sizeof(SasaBlock) * blocks.size()));
         STAT_TRY(buf.alloc(&d_jobs, sizeof(SasaJobDev) * (size_t)N));
-        STAT_TRY(buf.alloc(&d_xyz, sizeof(double) * 3 * (size_t)(a_hi - a_lo)));
-        STAT_TRY(buf.alloc(&d_radii, sizeof(double) * (size_t)(r_hi - r_lo)));
+        STAT_TRY(hipMemcpyAsync(d_blocks, blocks.data(), sizeof(SasaBlock) * blocks.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(SasaJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
+        STAT_TRY(atoms.upload(buf, &d_xyz, xyz, 3));
+        STAT_TRY(atom_radii.upload(buf, &d_radii, radii, 1));
         STAT_TRY(buf.alloc(&d_dirs, sizeof(double) * dirs.size()));
-        STAT_TRY(buf.alloc(&d_words, sizeof(u64) * (size_t)(w_hi - w_lo)));
+        if (Pd) STAT_TRY(hipMemcpyAsync(d_dirs, dirs.data(), sizeof(double) * dirs.size(), hipMemcpyHostToDevice, st));
+        STAT_TRY(region.upload(buf, &d_words, words, 1));
         STAT_TRY(buf.alloc(&d_counts, counts_bytes));
         STAT_TRY(buf.alloc(&d_out, out_bytes));
         STAT_TRY(poison_scratch(scratch_poisoned(), d_counts, counts_bytes, st));    // (test hook, pw_stat_host.hpp)
         STAT_TRY(hipMemsetAsync(d_out, 0, out_bytes, st));           // (the rows are sums by atomics: they start at 0)
-        STAT_TRY(hipMemcpyAsync(d_blocks, blocks.data(), sizeof(SasaBlock) * blocks.size(), hipMemcpyHostToDevice, st));
-        STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(SasaJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
-        if (a_hi > a_lo)
-            STAT_TRY(hipMemcpyAsync(d_xyz, xyz + 3 * a_lo, sizeof(double) * 3 * (size_t)(a_hi - a_lo), hipMemcpyHostToDevice, st));
-        if (r_hi > r_lo)
-            STAT_TRY(hipMemcpyAsync(d_radii, radii + r_lo, sizeof(double) * (size_t)(r_hi - r_lo), hipMemcpyHostToDevice, st));
-        if (Pd) STAT_TRY(hipMemcpyAsync(d_dirs, dirs.data(), sizeof(double) * dirs.size(), hipMemcpyHostToDevice, st));
-        if (w_hi > w_lo)
-            STAT_TRY(hipMemcpyAsync(d_words, words + w_lo, sizeof(u64) * (size_t)(w_hi - w_lo), hipMemcpyHostToDevice, st));
         STAT_TRY(ev.start(st));
         hipLaunchKernelGGL(pw_sasa_kernel, dim3((unsigned)blocks.size()), dim3(SASA_THREADS), sasa_lds_bytes(lds_rows), st,
                            d_blocks, d_jobs, d_xyz, d_radii, d_dirs, (int)Pd, d_words, d_counts, total, d_out, cap);

@@ -1,5 +1,6 @@
 // pw_stat_host.hpp -- what the translation units of the statistical entries (pw_kde.hip, pw_kdew.hip, pw_corr.hip,
-// pw_dft.hip, pw_gate.hip, pw_trans.hip, pw_superpose.hip, pw_cluster.hip, pw_cov.hip, pw_cavity.hip, pw_sasa.hip, pw_pores.hip, pw_affinity.hip, pw_rigid.hip, pw_passage.hip, pw_hop.hip) share on the host side of a call: device
+// pw_dft.hip, pw_gate.hip, pw_trans.hip, pw_superpose.hip, pw_cluster.hip, pw_cov.hip) and, through pw_grid_host.hpp,
+// those of the grid entries (listed there) share on the host side of a call: device
 // memory and events of one call, the two ways an entry reports a failure, the search of a work item's slab and the
 // poison switch.  Not for pw_hostpath.cpp: this is HIP.
 #pragma once

@@ -119,3 +119,26 @@ def test_molecule_and_dlpoly_on_jittered_cc3_frames(hip_ctx, tmp_path):
     assert dev.raw.shape == (8,) and dev.raw.tobytes() == ref.raw.tobytes() and dev.levels.tobytes() == ref.levels.tobytes()
     assert np.array_equal(dev.counts, ref.counts) and all(a.tobytes() == b.tobytes() for a, b in zip(dev.energies, ref.energies))
     assert dev.closed.all() and len(set(dev.n_voxels.tolist())) > 3 and dev.series("heat")[1].all()
+
+
+def test_every_budget_with_padded_inputs_and_outputs_in_reverse(hip_ctx, host):
+    """Three jobs of tiny grids with 0, 1 and 5 atoms, the second with a mask, at every budget of a launch from one word
+    to all their words and eight more (tests/_grid_sweep.py): every place where the planner can close a launch group.
+    Nothing of the inputs starts at 0 and the outputs go to the jobs from the back to the front."""
+    import _grid_sweep as G
+
+    betas, edges = ((0.4,), (0.2, 0.9), (0.3,)), ((), (-0.5, 0.5), (0.0,))
+    jobs = [C.Case(f"sweep-{k}", d, *C.shell_atoms(n, d, 1.0, 70 + k), words=C.words_with(d, 7, 70) if k == 1 else None,
+                   betas=betas[k], edges=edges[k]) for k, (d, n) in enumerate(zip(G.DIMS, G.ATOMS))]
+    pads = [C.Case(f"pad-{k}", (2, 2, 2), *C.shell_atoms(2, (2, 2, 2), 1.0, 80 + k), words=C.words_with((2, 2, 2), 3, 80 + k),
+                   betas=(0.1, 0.2), edges=(0.0,)) for k in range(3)]
+    order, at = G.interleaved(pads, jobs)
+    packed = list(C.pack(order, hole=1))
+    rec = packed[0] = np.ascontiguousarray(packed[0][at])
+    assert (rec["n"] == G.ATOMS).all() and (rec["atom_first"][1:] > 0).all() and (rec["coef_first"][1:] > 0).all()
+    assert rec["word_first"][1] > 0 and (rec["beta_first"] > 0).all() and (rec["edge_first"][1:] > 0).all()
+    assert all((np.diff(rec[name]) < 0).all() for name in ("out", "level_first", "hist_first", "energy_first"))
+    V = [packed[10][q] for q in at]
+    words = [((c.dims[1] * c.dims[2] + 2) // 2 if c.words is not None else 0)
+             + -(-v // 64) * (2 * len(c.betas) + 4 + len(c.edges)) + v + 1 for c, v in zip(jobs, V)]
+    G.budget_sweep(C, hip_ctx, host, tuple(packed), words)

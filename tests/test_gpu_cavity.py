@@ -119,3 +119,29 @@ def test_the_public_layer_on_jittered_cc3_frames(hip_ctx):
     assert np.array_equal(dev.volume, ref.volume) and np.array_equal(dev.gyration, ref.gyration)
     assert dev.closed.all() and (dev.volume > recs["pore_vol_opt"]).all() and len(set(dev.n_voxels.tolist())) > 5
     assert np.array_equal(dev.series("volume")[1], dev.n_face == 0)
+
+
+def test_every_budget_with_padded_inputs_and_outputs_in_reverse(hip_ctx, host):
+    """Three jobs of tiny grids with 0, 1 and 5 atoms -- the first with ready-made open words, the second without a
+    mask -- at every budget of a launch from one word to all their words and eight more (tests/_grid_sweep.py): every
+    place where the planner can close a launch group.  Nothing of the inputs starts at 0 and the outputs go to the jobs
+    from the back to the front."""
+    import _grid_sweep as G
+
+    rng = np.random.default_rng(70)
+    planes = (None, [[1.0, 0.0, 0.0, 2.5]], [[0.0, 1.0, 0.0, 1.5], [0.0, 0.0, 1.0, 9.0]])
+    jobs = [C.Case(f"sweep-{k}", d, (0, 0, 0), *C.random_atoms(n, d, 70 + k, 1.0, radius=(0.2, 0.6)), probe=0.1 * k, h=1.0,
+                   planes=planes[k], words=rng.integers(0, 1 << d[0], d[1] * d[2], dtype=np.uint64) if k == 0 else None)
+            for k, (d, n) in enumerate(zip(G.DIMS, G.ATOMS))]
+    pads = [C.Case(f"pad-{k}", (2, 2, 2), (1, 1, 1), *C.random_atoms(2, (2, 2, 2), 80 + k, 1.0), h=1.0, planes=[[1.0, 1.0, 0.0, 5.0]],
+                   words=np.full(4, 3, dtype=np.uint64)) for k in range(3)]
+    order, at = G.interleaved(pads, jobs)
+    packed = list(C.pack(order, hole=1))
+    rec = packed[0] = np.ascontiguousarray(packed[0][at])
+    open_first = packed[7] = np.ascontiguousarray(packed[7][at])
+    rec["mask_first"][1] = -1
+    assert (rec["n"] == G.ATOMS).all() and (rec["atom_first"][1:] > 0).all() and (rec["radius_first"][1:] > 0).all()
+    assert (rec["plane_first"][1:] > 0).all() and open_first[0] > 0 and (open_first[1:] == -1).all()
+    assert (np.diff(rec["out"]) < 0).all() and rec["mask_first"][0] > rec["mask_first"][2] > 0
+    words = [c.dims[1] * c.dims[2] * (int(c.words is not None) + int(k != 1)) + 1 for k, c in enumerate(jobs)]
+    G.budget_sweep(C, hip_ctx, host, tuple(packed), words)

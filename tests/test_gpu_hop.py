@@ -168,3 +168,27 @@ def test_molecule_and_dlpoly_on_jittered_cc3_frames(hip_ctx, tmp_path):
     assert valid.any() and (values[valid] == best[valid]).all() and (dev.series("escape_rate")[0][valid] >= values[valid]).all()
     print("rates", dev.rate[:, :, 0], "mean", dev.mean_rate())
     assert same_hopping(traj.hopping("Kr", 298.0, frames=[1, 5], device=0), traj.hopping("Kr", 298.0, frames=[1, 5], device=-1))
+
+
+def test_every_budget_with_padded_inputs_and_outputs_in_reverse(hip_ctx, host):
+    """Three jobs of tiny grids -- the first with a field of its caller's, the others with 1 and 5 atoms; one, no and
+    two planes; one, two and one betas; the second without words -- at every budget of a launch from one word to all
+    their words and eight more (tests/_grid_sweep.py): every place where the planner can close a launch group.  Nothing
+    of the inputs starts at 0 and the outputs go to the jobs from the back to the front."""
+    import _affinity_cases as A
+    import _grid_sweep as G
+
+    planes = ([[1.0, 0.0, 0.0, 1.5]], None, [[0.0, 1.0, 0.0, 0.5], [0.0, 0.0, 1.0, 1.5]])
+    betas = ((0.4,), (0.2, 0.9), (0.3,))
+    jobs = [C.Case(f"sweep-{k}", d, (0, 0), C.random_field(d, 70) if k == 0 else None, *A.shell_atoms(n, d, 1.0, 70 + k),
+                   planes=planes[k], betas=betas[k], words=k != 1) for k, (d, n) in enumerate(zip(G.DIMS, G.ATOMS))]
+    pads = [C.Case(f"pad-{k}", (2, 2, 2), (1, 1), C.random_field((2, 2, 2), 80 + k), *A.shell_atoms(2, (2, 2, 2), 1.0, 80 + k),
+                   planes=[[1.0, 1.0, 0.0, 5.0]], betas=(0.1, 0.2)) for k in range(3)]
+    order, at = G.interleaved(pads, jobs)
+    packed = list(C.pack(order, hole=1))
+    rec = packed[0] = np.ascontiguousarray(packed[0][at])
+    assert (rec["n"] == G.ATOMS).all() and (rec["atom_first"][1:] > 0).all() and (rec["coef_first"][1:] > 0).all()
+    assert rec["plane_first"][0] > 0 and rec["plane_first"][2] > 0 and (rec["beta_first"] > 0).all()
+    assert rec["field_first"][0] > 0 and (rec["field_first"][1:] == -1).all() and rec["word_first"][1] == -1
+    assert all((np.diff(rec[name]) < 0).all() for name in ("slab_first", "sum_first", "out")) and rec["word_first"][0] > rec["word_first"][2] > 0
+    G.budget_sweep(C, hip_ctx, host, tuple(packed), [d[0] * d[1] * d[2] for d in G.DIMS])

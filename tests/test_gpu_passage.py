@@ -161,3 +161,25 @@ def test_molecule_and_dlpoly_on_jittered_cc3_frames(hip_ctx, tmp_path):
     values, valid = dev.series("activation")
     assert valid.all() and len(set(values.tolist())) > 3 and (values == dev.activation.min(axis=1)).all()
     assert traj.passage("Kr", frames=[1, 5], device=0).raw.tobytes() == traj.passage("Kr", frames=[1, 5], device=-1).raw.tobytes()
+
+
+def test_every_budget_with_padded_inputs_and_outputs_in_reverse(hip_ctx, host):
+    """Three jobs of tiny grids -- the first with a field of its caller's, the others with 1 and 5 atoms; one, no and
+    two planes -- at every budget of a launch from one word to all their words and eight more (tests/_grid_sweep.py):
+    every place where the planner can close a launch group.  Nothing of the inputs starts at 0 and the rows of out go
+    to the jobs from the back to the front."""
+    import _affinity_cases as A
+    import _grid_sweep as G
+
+    planes = ([[1.0, 0.0, 0.0, 1.5]], None, [[0.0, 1.0, 0.0, 0.5], [0.0, 0.0, 1.0, 1.5]])
+    jobs = [C.Case(f"sweep-{k}", d, (0, 0, 0), C.random_field(d, 70, blocked=0.2) if k == 0 else None,
+                   *A.shell_atoms(n, d, 1.0, 70 + k), planes=planes[k]) for k, (d, n) in enumerate(zip(G.DIMS, G.ATOMS))]
+    pads = [C.Case(f"pad-{k}", (2, 2, 2), (1, 1, 1), C.random_field((2, 2, 2), 80 + k), *A.shell_atoms(2, (2, 2, 2), 1.0, 80 + k),
+                   planes=[[1.0, 1.0, 0.0, 5.0]]) for k in range(3)]
+    order, at = G.interleaved(pads, jobs)
+    packed = list(C.pack(order, hole=1))
+    rec = packed[0] = np.ascontiguousarray(packed[0][at])
+    assert (rec["n"] == G.ATOMS).all() and (rec["atom_first"][1:] > 0).all() and (rec["coef_first"][1:] > 0).all()
+    assert rec["plane_first"][0] > 0 and rec["plane_first"][2] > 0 and rec["field_first"][0] > 0 and (rec["field_first"][1:] == -1).all()
+    assert (np.diff(rec["out_first"]) < 0).all()
+    G.budget_sweep(C, hip_ctx, host, tuple(packed), [d[0] * d[1] * d[2] for d in G.DIMS])

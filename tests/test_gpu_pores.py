@@ -123,3 +123,36 @@ def test_the_public_layer_on_jittered_cc3_frames(hip_ctx):
     assert np.array_equal(dev.cumulative[:, 0], dev.domain_volume) and (dev.raw["n_none"] == 0).all()
     cav = pw.cavity_grid_batch(frames, radii, recs["pore_opt_c"], 1.5, 0.5, recs["maxd"] / 2.0, planes, device=0)
     assert np.array_equal(dev.reach_volume[:, 6], cav.volume) and np.array_equal(dev.series("reach_volume", 6)[1], cav.closed)
+
+
+def test_every_budget_with_padded_inputs_and_outputs_in_reverse(hip_ctx, host):
+    """Three jobs of tiny grids with 0, 1 and 5 atoms and ladders of 2, 1 and 3 probes -- the first with ready-made open
+    words, the second without a mask -- at every budget of a launch from one word to all their words and eight more
+    (tests/_grid_sweep.py): every place where the planner can close a launch group.  Nothing of the inputs starts at 0
+    and the outputs go to the jobs from the back to the front."""
+    import _grid_sweep as G
+
+    rng = np.random.default_rng(70)
+    ladder = ([0.0, 0.3], [0.2], [0.0, 0.3, 0.6])
+    planes = (None, [[1.0, 0.0, 0.0, 2.5]], [[0.0, 1.0, 0.0, 1.5], [0.0, 0.0, 1.0, 9.0]])
+    jobs = []
+    for k, (d, n) in enumerate(zip(G.DIMS, G.ATOMS)):
+        xyz, radii = C.random_atoms(n, d, 70 + k, 1.0, radius=(0.2, 0.6))
+        given = rng.integers(0, 1 << d[0], (len(ladder[k]), d[1] * d[2]), dtype=np.uint64) if k == 0 else None
+        jobs.append(P.Case(f"sweep-{k}", d, (0, 0, 0), ladder[k], 1.0, xyz=xyz, radii=radii, planes=planes[k], words=given))
+    pads = []
+    for k in range(3):
+        xyz, radii = C.random_atoms(2, (2, 2, 2), 80 + k, 1.0)
+        pads.append(P.Case(f"pad-{k}", (2, 2, 2), (1, 1, 1), [0.0, 0.1], 1.0, xyz=xyz, radii=radii, planes=[[1.0, 1.0, 0.0, 5.0]],
+                           words=np.full((2, 4), 3, dtype=np.uint64)))
+    order, at = G.interleaved(pads, jobs)
+    packed = P.Packed(order, hole=1, masks=[c.name != "sweep-1" for c in order])
+    rec = packed.rec = np.ascontiguousarray(packed.rec[at])
+    packed.open_first = np.ascontiguousarray(packed.open_first[at])
+    packed.jobs, packed.with_mask = jobs, [True, False, True]
+    assert (rec["n"] == G.ATOMS).all() and (rec["atom_first"][1:] > 0).all() and (rec["radius_first"][1:] > 0).all()
+    assert (rec["plane_first"][1:] > 0).all() and (rec["probe_first"] > 0).all()
+    assert packed.open_first[0] > 0 and (packed.open_first[1:] == -1).all() and rec["mask_first"][1] == -1
+    assert all((np.diff(rec[name]) < 0).all() for name in ("out", "level_first")) and rec["mask_first"][0] > rec["mask_first"][2] > 0
+    words = [c.L * c.dims[1] * c.dims[2] * (int(c.words is not None) + int(k != 1)) + 1 for k, c in enumerate(jobs)]
+    G.budget_sweep(P, hip_ctx, host, packed, words)

@@ -132,3 +132,29 @@ def test_molecule_and_dlpoly_on_jittered_cc3_frames(hip_ctx, tmp_path):
         ref = traj.rigid_affinity("N2", [298.0, 195.0], directions=dirs, charges=charges, device=-1)
         assert dev.raw.shape == (8,) and dev.raw.tobytes() == ref.raw.tobytes() and dev.levels.tobytes() == ref.levels.tobytes()
         assert dev.closed.all() and len(set(dev.n_voxels.tolist())) > 3 and dev.series("heat")[1].all()
+
+
+def test_every_budget_with_padded_inputs_and_outputs_in_reverse(hip_ctx, host):
+    """Three jobs of tiny grids with 0, 1 and 5 atoms -- one, two and three sites, the second with a mask and charged,
+    the first two with maps -- at every budget of a launch from one word to all their words and eight more
+    (tests/_grid_sweep.py): every place where the planner can close a launch group.  Nothing of the inputs starts at 0
+    and the outputs go to the jobs from the back to the front."""
+    import _grid_sweep as G
+
+    sites, n_dirs, betas, level = (1, 2, 3), (1, 3, 2), ((0.4,), (0.2, 0.9), (0.3,)), (0, 1, -1)
+    jobs = [C.Case(f"sweep-{k}", d, *C.guest_atoms(n, sites[k], d, 1.0, 70 + k), offsets=C.line(sites[k], 0.3),
+                   dirs=C.unit_dirs(n_dirs[k], 70 + k), words=A.words_with(d, 7, 70) if k == 1 else None, betas=betas[k],
+                   charged=int(k == 1), map_level=level[k]) for k, (d, n) in enumerate(zip(G.DIMS, G.ATOMS))]
+    pads = [C.Case(f"pad-{k}", (2, 2, 2), *C.guest_atoms(2, 2, (2, 2, 2), 1.0, 80 + k), offsets=C.line(2, 0.3),
+                   dirs=C.unit_dirs(2, 80 + k), words=A.words_with((2, 2, 2), 3, 80 + k), betas=(0.1, 0.2), map_level=0)
+            for k in range(3)]
+    order, at = G.interleaved(pads, jobs)
+    packed = list(C.pack(order, hole=1))
+    rec = packed[0] = np.ascontiguousarray(packed[0][at])
+    assert (rec["n"] == G.ATOMS).all() and (rec["atom_first"][1:] > 0).all() and (rec["coef_first"][1:] > 0).all()
+    assert rec["word_first"][1] > 0 and all((rec[name] > 0).all() for name in ("beta_first", "site_first", "dir_first"))
+    assert all((np.diff(rec[name]) < 0).all() for name in ("out", "level_first")) and rec["map_first"][0] > rec["map_first"][1] > 0
+    V = [packed[10][q] for q in at]
+    words = [((c.dims[1] * c.dims[2] + 2) // 2 if c.words is not None else 0) + -(-v // 64) * (2 * len(c.betas) + 6)
+             + (2 * v if c.map_level >= 0 else 0) + 1 for c, v in zip(jobs, V)]
+    G.budget_sweep(C, hip_ctx, host, tuple(packed), words)

@@ -129,3 +129,28 @@ def test_the_public_layer_on_jittered_cc3_frames(hip_ctx):
     assert dev.closed.all() and (0 < dev.internal_area).all() and (dev.internal_area < dev.area).all()
     assert len(set(dev.internal_area.tolist())) > 5 and (dev.raw["flags"] == 1).all()
     assert np.array_equal(dev.series("internal_area")[1], cav.closed)
+
+
+def test_padded_inputs_and_outputs_in_reverse(hip_ctx, host):
+    """A call whose jobs have unused atoms, radii and words before the first of them and between them -- every first is
+    positive and every uploaded span starts past 0 (tests/_grid_sweep.py) -- and own their outputs from the back to the
+    front: the host context's integers, on the default path and with the alternative paths forced, under poison."""
+    import _grid_sweep as G
+
+    jobs = next(g for g in C.by_directions(C.cases()) if sum(bool(c.dims) for c in g) > 1 and sum(not c.dims for c in g) > 1)
+    u = jobs[0].directions
+    pads = [C.Case(f"pad-{k}", *C.random_atoms(2, 3.0, 80 + k), u, dims=(3, 2, 2), h=0.5, words=np.full(4, 5, dtype=np.uint64))
+            for k in range(len(jobs))]
+    order, at = G.interleaved(pads, jobs)
+    packed = list(C.pack(order, hole=1))
+    rec = packed[0] = np.ascontiguousarray(packed[0][at])
+    atoms, grid = rec["n"] > 0, rec["word_first"] >= 0
+    assert atoms.sum() > 2 and grid.sum() > 1 and (~grid).sum() > 1
+    assert (rec["atom_first"][atoms] > 0).all() and (rec["radius_first"][atoms] > 0).all() and (rec["word_first"][grid] > 0).all()
+    assert (np.diff(rec["out"]) < 0).all() and (np.diff(rec["count_first"][atoms]) < 0).all()
+    rc, want = C.raw(host, tuple(packed))
+    assert rc == 0
+    S.set_poison(True)
+    for hook in (None, dict(list_capacity=-1, lds_words=-1, block_atoms=2), dict(lds_words=4096)):
+        rc, got = C.raw(hip_ctx, tuple(packed), hook=hook)
+        assert rc == 0 and C.same(got, want), (hook, C.first_difference(got, want))

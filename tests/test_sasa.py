@@ -171,6 +171,82 @@ def test_bad_arguments_are_refused_and_nothing_is_written(host):
         host.sasa(packed[0], packed[1], packed[2], packed[3], packed[4])
 
 
+def sweep_of_rows(outs):
+    """The job named for a shared row of out, or -1: the sweep of sasa_check restated -- rows sorted by (row, job), of
+    equal neighbours the lowest later one."""
+    rows, bad = sorted((o, k) for k, o in enumerate(outs)), -1
+    for i in range(1, len(rows)):
+        if rows[i][0] == rows[i - 1][0] and (bad < 0 or rows[i][1] < bad):
+            bad = rows[i][1]
+    return bad
+
+
+def sweep_of_counts(jobs):
+    """The job named for shared entries of exposed and inside, or -1: the sweep of sasa_check restated -- the jobs
+    (count_first, n) with atoms sorted by (count_first, job), each against the furthest end so far and its owner."""
+    bad = end = owner = -1
+    for first, k in sorted((first, k) for k, (first, n) in enumerate(jobs) if n > 0):
+        if first < end and (bad < 0 or max(k, owner) < bad):
+            bad = max(k, owner)
+        if first + jobs[k][1] > end:
+            end, owner = first + jobs[k][1], k
+    return bad
+
+
+def test_the_job_named_for_shared_outputs_is_the_sweeps():
+    """Which job a refusal for shared outputs names -- or that there is none -- for every sequence of up to four jobs
+    with count_first in 0 .. 3 and n in 0 .. 3 atoms, and for every assignment of rows of out in 0 .. 2.  The rows are
+    swept first and the counts only when no row is shared, so the two are not crossed in full (5.7 million calls):
+    every sequence of jobs has a row of its own each (69904 calls, the counts' sweep alone); every assignment of rows
+    goes with counts that are apart and with counts that all overlap (240 calls: the rows' sweep, and that it comes
+    first); and up to two jobs are crossed in full (2352 calls).  The sweeps above are sasa_check's own, restated."""
+    import itertools
+
+    L = _lib.load()
+    ctx = _lib.Context(-1, host_threads=1)
+    xyz, radii, u = np.array([[0.0, 0.0, 0.0], [9.0, 0.0, 0.0], [0.0, 9.0, 0.0]]), np.ones(3), np.array([[0.0, 0.0, 1.0]])
+    exposed, inside = np.zeros(8, dtype=np.int32), np.zeros(8, dtype=np.int32)
+    out = np.zeros(4, dtype=_lib.SASA_OUT_DTYPE)
+    recs = {N: np.zeros(N, dtype=_lib.SASA_JOB_DTYPE) for N in range(1, 5)}
+    for rec in recs.values():
+        rec["word_first"] = -1
+
+    def named(jobs, outs):
+        rec = recs[len(jobs)]
+        rec["count_first"], rec["n"] = [j[0] for j in jobs], [j[1] for j in jobs]
+        rec["out"] = outs
+        rc = L.pw_sasa(ctx._h, rec.ctypes.data, len(rec), xyz.ctypes.data, 3, radii.ctypes.data, 3, u.ctypes.data, 1, None, 0,
+                       exposed.ctypes.data, inside.ctypes.data, 8, out.ctypes.data, 4)
+        return "" if rc == 0 else L.pw_last_error().decode()
+
+    def want(jobs, outs):
+        bad = sweep_of_rows(outs)
+        if bad >= 0:
+            return f"pw_sasa: job {bad}: shares its row of out with an earlier job"
+        bad = sweep_of_counts(jobs)
+        return f"pw_sasa: job {bad}: shares entries of exposed and inside with an earlier job" if bad >= 0 else ""
+
+    shapes = list(itertools.product(range(4), range(4)))             # (count_first, n)
+    calls = 0
+    for N in range(1, 5):
+        for jobs in itertools.product(shapes, repeat=N):
+            outs = list(range(N))
+            assert named(jobs, outs) == want(jobs, outs), (jobs, outs)
+            calls += 1
+        for outs in itertools.product(range(3), repeat=N):
+            for jobs in ([(k, 1) for k in range(N)], [(0, 2)] * N):
+                assert named(jobs, list(outs)) == want(jobs, list(outs)), (jobs, outs)
+                calls += 1
+    for N in (1, 2):
+        for jobs in itertools.product(shapes, repeat=N):
+            for outs in itertools.product(range(3), repeat=N):
+                assert named(jobs, list(outs)) == want(jobs, list(outs)), (jobs, outs)
+                calls += 1
+    assert calls == 69904 + 240 + 2352
+    # (a case that decides between the orders: sorted by length, job 2 would be named)
+    assert want([(0, 1), (0, 3), (0, 2)], [0, 1, 2]).startswith("pw_sasa: job 1: shares entries")
+
+
 def test_the_wrapper(host):
     c = by_name("random-directions-and-words")
     rec, xyz, radii, directions, words, *_ = C.pack([c])
