@@ -1189,6 +1189,57 @@ int pw_rigid_affinity(pw_context *ctx, const pw_rigid_job *jobs, int64_t n_jobs,
                       int64_t n_dirs, const uint64_t *words, int64_t n_words, const double *betas, int64_t n_betas,
                       double *maps, int64_t n_maps, pw_affinity_level *levels, int64_t n_levels, pw_rigid_out *out,
                       int64_t n_out);
+/* ---- partial charges of an isolated molecule: charge equilibration ---------------------------------------------
+ * The framework charges that the charged jobs of pw_rigid_affinity need, frame by frame, so that a breathing cage
+ * gets the charges of each of its shapes: QEq (Rappe and Goddard 1991) with Ohno-Klopman shielding instead of Slater
+ * overlap integrals.  The reference has no counterpart.  Job k has the n atoms xyz[xyz_first .. +n) (rows of three
+ * doubles, Angstrom) with the parameters params[param_first .. +n) (rows (chi, J) in eV; jobs may share rows, the
+ * frames of a trajectory share one set).  The charges minimise sum chi_i q_i + 1/2 q^T A q at sum q = total_charge,
+ * with A_ii = J_i and A_ij = coulomb / sqrt(r_ij^2 + a^2), a = 2 coulomb / (J_i + J_j): one symmetric positive-definite
+ * n x n problem, solved as A s = -chi and A t = 1 by Jacobi-preconditioned conjugate gradients that stop at a relative
+ * residual of tol or after max_iter steps, then q = s + mu t with mu = (total_charge - sum s) / sum t.  The charges go
+ * to charges[charge_first .. +n); row `out` of the result holds mu (the equalised electronegativity, eV), the two
+ * sums, energy = (chi.q + mu total_charge) / 2 (eV), the dipole sum q_i x_i (e Angstrom), the extreme charges, the
+ * steps of the two systems and flags: PW_CHG_NOT_CONVERGED (max_iter reached; the charges of the last step are
+ * written), PW_CHG_BREAKDOWN (a direction of no positive curvature: the matrix is not positive definite to working
+ * precision) and PW_CHG_NO_SUM (sum t is not positive).  With one of the last two the charges, mu, energy, dipole,
+ * q_min and q_max are NaN: a result, not an error.
+ * The result is DEFINED (pywindow_amd/csrc/pw_charges.hpp: the sums of pw_superpose, every step of the solver written
+ * out): the same bits on every device, launch geometry and run and on a device == -1 context (host threads),
+ * whatever else shares the call, wherever a job's vectors live (LDS up to 512 atoms, a workspace beyond) and however
+ * the jobs are cut into launches to bound that workspace.  A NaN always leaves as 0x7ff8000000000000.
+ * All pointers are host memory; n_points is the number of rows of xyz, of rows of params and of entries of charges.
+ * Jobs may share neither rows of `out` nor entries of `charges`; what no job owns is never touched.  n < 1, a range
+ * outside the arrays, a coordinate, chi, J, total_charge or coulomb that is not finite, J <= 0, coulomb <= 0, tol
+ * outside [1e-14, 1e-2] or max_iter outside [1, 100000]: PW_E_BAD_ARG (pw_last_error names the job and the reason),
+ * and nothing is launched or written.  Device work is queued on the context's stream, its memory allocated and freed
+ * in stream order; the call returns when the results are in place. */
+#define PW_CHG_NOT_CONVERGED 1
+#define PW_CHG_BREAKDOWN 2
+#define PW_CHG_NO_SUM 4
+typedef struct pw_charges_job {
+    int64_t xyz_first;       /* first row of xyz */
+    int64_t param_first;     /* first row of params */
+    int64_t n;               /* atoms, >= 1 */
+    double  total_charge;    /* Q, e */
+    double  coulomb;         /* K, eV Angstrom: 14.399645... for charges in e */
+    double  tol;             /* relative residual at which a system stops, in [1e-14, 1e-2] */
+    int64_t max_iter;        /* in [1, 100000] */
+    int64_t charge_first;    /* first entry of charges */
+    int64_t out;             /* the job's row of the result */
+} pw_charges_job;
+typedef struct pw_charges_out {
+    double  mu;
+    double  sum_s, sum_t;
+    double  energy;
+    double  dipole[3];
+    double  q_min, q_max;
+    int32_t iterations[2];   /* of A s = -chi and of A t = 1 */
+    int32_t flags;           /* PW_CHG_* */
+    int32_t reserved;        /* padding to a multiple of 8 bytes; written as 0 */
+} pw_charges_out;
+int pw_charges(pw_context *ctx, const pw_charges_job *jobs, int64_t n_jobs, const double *xyz, const double *params,
+               int64_t n_points, double *charges, pw_charges_out *out);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

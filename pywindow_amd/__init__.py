@@ -43,6 +43,7 @@ from .rigid import (  # noqa: E402
     rigid_guest_affinity,
     rigid_guest_affinity_batch,
 )
+from .charges import QEQ_PARAMETERS, Charges, equilibrate_charges, equilibrate_charges_batch  # noqa: E402
 from .passage import Passage, guest_passage, guest_passage_batch, passage_field  # noqa: E402
 from .hopping import Hopping, guest_hopping, guest_hopping_batch, window_frame  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
@@ -120,6 +121,10 @@ __all__ = [
     "rigid_coefficients",
     "rigid_guest_affinity",
     "rigid_guest_affinity_batch",
+    "QEQ_PARAMETERS",
+    "Charges",
+    "equilibrate_charges",
+    "equilibrate_charges_batch",
     "Passage",
     "guest_passage",
     "guest_passage_batch",

@@ -352,6 +352,21 @@ assert RIGID_JOB_DTYPE.itemsize == 176 and RIGID_OUT_DTYPE.itemsize == 56
 RIGID_MAX_SITES = 8
 RIGID_MAX_DIRS = 1024
 
+#: numpy mirrors of ``pw_charges_job`` and ``pw_charges_out``
+CHARGES_JOB_DTYPE = np.dtype(
+    [("xyz_first", np.int64), ("param_first", np.int64), ("n", np.int64), ("total_charge", np.float64),
+     ("coulomb", np.float64), ("tol", np.float64), ("max_iter", np.int64), ("charge_first", np.int64), ("out", np.int64)]
+)
+CHARGES_OUT_DTYPE = np.dtype(
+    [("mu", np.float64), ("sum_s", np.float64), ("sum_t", np.float64), ("energy", np.float64), ("dipole", np.float64, (3,)),
+     ("q_min", np.float64), ("q_max", np.float64), ("iterations", np.int32, (2,)), ("flags", np.int32), ("reserved", np.int32)]
+)
+assert CHARGES_JOB_DTYPE.itemsize == 72 and CHARGES_OUT_DTYPE.itemsize == 88
+#: ``PW_CHG_NOT_CONVERGED``, ``PW_CHG_BREAKDOWN``, ``PW_CHG_NO_SUM``
+CHG_NOT_CONVERGED = 1
+CHG_BREAKDOWN = 2
+CHG_NO_SUM = 4
+
 #: numpy mirror of ``pw_passage_job``
 PASSAGE_JOB_DTYPE = np.dtype(
     [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
@@ -482,6 +497,7 @@ EXPORTED_SYMBOLS = [
     "pw_passage",
     "pw_hop",
     "pw_rigid_affinity",
+    "pw_charges",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -629,6 +645,8 @@ def load():
     L.pw_internal_hop.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9
     L.pw_internal_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
+    L.pw_internal_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1357,6 +1375,42 @@ class Context:
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
         return out, levels, maps
+
+    def charges(self, jobs, xyz, params, out=None, workspace_bytes=None, kernel_ms=None):
+        """``pw_charges``: charge equilibration of a batch of jobs (``CHARGES_JOB_DTYPE`` records indexing the rows of
+        ``xyz`` (rows of three), the rows of ``params`` (rows ``(chi, J)`` in eV), the entries of the charges and the
+        rows of the result): ``(charges, out)`` -- ``charges`` float64, zeros up to the furthest entry of a job with the
+        ``n`` entries from ``charge_first`` of every job filled in, and ``out`` a ``CHARGES_OUT_DTYPE`` array with row
+        ``out`` of every job (given: filled in place, rows no job owns stay as they are).  The library takes one length
+        for ``xyz``, ``params`` and the charges: the shorter ones are extended here (parameter rows of zeros, which no
+        job may read).  Whatever the entry refuses: ``ValueError`` with the library's message.  ``workspace_bytes`` /
+        ``kernel_ms`` (a list that receives the time of the kernels by HIP events) go through the library's
+        measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=CHARGES_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 2)
+        some = len(jobs) > 0
+        rows = max(int(jobs["out"].max()) + 1, 0) if some else 0
+        if out is None:
+            out = np.zeros(rows, dtype=CHARGES_OUT_DTYPE)
+        elif out.dtype != CHARGES_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1 or len(out) < rows:
+            raise ValueError("out: a contiguous CHARGES_OUT_DTYPE array with a row for every job")
+        size = max(int((jobs["charge_first"] + jobs["n"]).max()), 0) if some else 0
+        n_points = max(len(x), len(p), size)
+        if len(x) < n_points:
+            x = np.concatenate([x, np.zeros((n_points - len(x), 3))])
+        if len(p) < n_points:
+            p = np.concatenate([p, np.zeros((n_points - len(p), 2))])
+        q = np.zeros(n_points)
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, p.ctypes.data, n_points, q.ctypes.data, out.ctypes.data]
+        if workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_charges", *args)
+        else:
+            ms = ctypes.c_float(0.0)
+            _stat_call("pw_internal_charges", *args, int(workspace_bytes or 0), ctypes.byref(ms))
+            if kernel_ms is not None:
+                kernel_ms.append(float(ms.value))
+        return q[:size], out
 
     def passage(self, jobs, xyz=None, coef=None, planes=None, field=None, out=None, workspace_bytes=None, kernel_ms=None,
                 fills=None, grids=None):

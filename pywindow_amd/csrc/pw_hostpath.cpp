@@ -26,6 +26,7 @@
 #include "pw_pores.hpp"
 #include "pw_passage.hpp"
 #include "pw_hop.hpp"
+#include "pw_charges.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -1730,6 +1731,148 @@ extern "C" int pw_hostpath_hop(const pw_hop_job* jobs, long n_jobs, const double
             out[(long)J.out] = o;
         }
         first = last;
+    }
+    return PW_OK;
+}
+
+// pw_charges on the host (pw_charges.hip checks the arguments and sends device == -1 contexts here): the solver of
+// pw_charges.hpp step by step, the 64 accumulators of a sum as an array, term i going to accumulator i % 64, folded by
+// sup_fold.  Every element of the matrix is recomputed where it is needed, so nothing but the job's ten vectors is held.
+// The threads share out the jobs; a job's row and charges are its own.
+extern "C" int pw_hostpath_charges(const pw_charges_job* jobs, long n_jobs, const double* xyz, const double* params,
+                                   double* charges, pw_charges_out* out, int threads) {
+    std::atomic<long> next{0};
+    auto one = [&](const pw_charges_job& J) {
+        const long n = (long)J.n;
+        const double* X = xyz + 3 * (long)J.xyz_first;
+        const double* P = params + 2 * (long)J.param_first;
+        const double K = J.coulomb, Q = J.total_charge, tol2 = J.tol * J.tol;
+        std::vector<double> state((size_t)(10 * n));
+        double* v[2][5];                                             // x, r, z, p, Ap of the two systems
+        for (int s = 0; s < 2; ++s)
+            for (int f = 0; f < 5; ++f) v[s][f] = state.data() + (5 * s + f) * n;
+        double lanes[SUP_ACC];
+        auto dot = [&](const double* a, const double* b) {
+            for (int l = 0; l < SUP_ACC; ++l) lanes[l] = 0.0;
+            for (long i = 0; i < n; ++i) lanes[i % SUP_ACC] = pw_fma(a[i], b[i], lanes[i % SUP_ACC]);
+            return sup_fold(lanes);
+        };
+        auto sum = [&](const double* a) {
+            for (int l = 0; l < SUP_ACC; ++l) lanes[l] = 0.0;
+            for (long i = 0; i < n; ++i) lanes[i % SUP_ACC] = lanes[i % SUP_ACC] + a[i];
+            return sup_fold(lanes);
+        };
+        ChgSystem sys[2];
+        for (int s = 0; s < 2; ++s) {
+            double *x = v[s][0], *r = v[s][1], *z = v[s][2], *p = v[s][3];
+            for (long i = 0; i < n; ++i) {
+                x[i] = 0.0;
+                r[i] = s == 0 ? -P[2 * i] : 1.0;
+                p[i] = z[i] = r[i] / P[2 * i + 1];
+            }
+            sys[s].rz = dot(r, z);
+            sys[s].rr = sys[s].bb = dot(r, r);
+            sys[s].iterations = 0;
+            sys[s].frozen = sys[s].broke = false;
+        }
+        bool ran_out = false;
+        for (int k = 0;; ++k) {
+            chg_freeze_check(sys[0], tol2, k);
+            chg_freeze_check(sys[1], tol2, k);
+            if (sys[0].frozen && sys[1].frozen) break;
+            if (k == J.max_iter) {
+                ran_out = true;
+                for (int s = 0; s < 2; ++s)
+                    if (!sys[s].frozen) sys[s].iterations = k;
+                break;
+            }
+            const bool on0 = !sys[0].frozen, on1 = !sys[1].frozen;
+            double acc0[SUP_ACC], acc1[SUP_ACC];
+            for (long i = 0; i < n; ++i) {
+                for (int l = 0; l < SUP_ACC; ++l) acc0[l] = acc1[l] = 0.0;
+                const double xi = X[3 * i], yi = X[3 * i + 1], zi = X[3 * i + 2], Ji = P[2 * i + 1];
+                for (long j = 0; j < n; ++j) {
+                    const double a = j == i ? Ji : chg_pair(xi, yi, zi, Ji, X[3 * j], X[3 * j + 1], X[3 * j + 2], P[2 * j + 1], K);
+                    if (on0) acc0[j % SUP_ACC] = pw_fma(a, v[0][3][j], acc0[j % SUP_ACC]);
+                    if (on1) acc1[j % SUP_ACC] = pw_fma(a, v[1][3][j], acc1[j % SUP_ACC]);
+                }
+                if (on0) v[0][4][i] = sup_fold(acc0);
+                if (on1) v[1][4][i] = sup_fold(acc1);
+            }
+            for (int s = 0; s < 2; ++s) {
+                ChgSystem& S = sys[s];
+                if (S.frozen) continue;
+                double *x = v[s][0], *r = v[s][1], *z = v[s][2], *p = v[s][3], *Ap = v[s][4];
+                const double pAp = dot(p, Ap);
+                if (!chg_curvature_ok(S, pAp, k)) continue;
+                const double alpha = S.rz / pAp;
+                for (long i = 0; i < n; ++i) {
+                    x[i] = pw_fma(alpha, p[i], x[i]);
+                    r[i] = pw_fma(-alpha, Ap[i], r[i]);
+                    z[i] = r[i] / P[2 * i + 1];
+                }
+                const double rz_new = dot(r, z);
+                S.rr = dot(r, r);
+                const double beta = rz_new / S.rz;
+                for (long i = 0; i < n; ++i) p[i] = pw_fma(beta, p[i], z[i]);
+                S.rz = rz_new;
+            }
+        }
+        const double *s_vec = v[0][0], *t_vec = v[1][0];
+        const double S = sum(s_vec), T = sum(t_vec);
+        const int flags = chg_flags(sys[0], sys[1], ran_out, T);
+        const bool lost = (flags & (CHG_BREAKDOWN | CHG_NO_SUM)) != 0;
+        const double mu = (Q - S) / T;
+        double* q = charges + (long)J.charge_first;
+        double e[SUP_ACC], d[3][SUP_ACC], lo[SUP_ACC], hi[SUP_ACC];
+        for (int l = 0; l < SUP_ACC; ++l) {
+            e[l] = d[0][l] = d[1][l] = d[2][l] = 0.0;
+            lo[l] = PW_INF;
+            hi[l] = -PW_INF;
+        }
+        for (long i = 0; i < n; ++i) {
+            const int l = (int)(i % SUP_ACC);
+            const double qi = pw_fma(mu, t_vec[i], s_vec[i]);
+            e[l] = pw_fma(P[2 * i], qi, e[l]);
+            for (int a = 0; a < 3; ++a) d[a][l] = pw_fma(qi, X[3 * i + a], d[a][l]);
+            lo[l] = qi < lo[l] ? qi : lo[l];
+            hi[l] = qi > hi[l] ? qi : hi[l];
+            q[i] = lost ? chg_nan() : chg_canon(qi);
+        }
+        for (int s = SUP_ACC / 2; s >= 1; s >>= 1)
+            for (int l = 0; l < s; ++l) {
+                lo[l] = lo[l + s] < lo[l] ? lo[l + s] : lo[l];
+                hi[l] = hi[l + s] > hi[l] ? hi[l + s] : hi[l];
+            }
+        pw_charges_out* o = out + (long)J.out;
+        const double nan = chg_nan();
+        o->mu = lost ? nan : chg_canon(mu);
+        o->sum_s = chg_canon(S);
+        o->sum_t = chg_canon(T);
+        o->energy = lost ? nan : chg_canon(0.5 * (sup_fold(e) + mu * Q));
+        for (int a = 0; a < 3; ++a) o->dipole[a] = lost ? nan : chg_canon(sup_fold(d[a]));
+        o->q_min = lost ? nan : chg_canon(lo[0]);
+        o->q_max = lost ? nan : chg_canon(hi[0]);
+        o->iterations[0] = sys[0].iterations;
+        o->iterations[1] = sys[1].iterations;
+        o->flags = flags;
+        o->reserved = 0;
+    };
+    auto worker = [&]() {
+        for (;;) {
+            const long k = next.fetch_add(1);
+            if (k >= n_jobs) break;
+            one(jobs[k]);
+        }
+    };
+    if (threads < 1) threads = 1;
+    const int count = (long)threads > n_jobs ? (int)std::max(1l, n_jobs) : threads;
+    if (count == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < count; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
     }
     return PW_OK;
 }

@@ -295,8 +295,8 @@ class Molecule:
         one of ``directions`` (``None``: ``pywindow_amd.sphere_directions`` of ``pywindow_amd.rigid.M_DEFAULT``), a
         pose with a site within 0.5 Angstrom of an atom left out (``core2 = 0.25``).  ``guest``: a name of
         ``pywindow_amd.rigid.RIGID_GUESTS`` or a :class:`pywindow_amd.RigidGuest`.  ``charges``: the framework's
-        partial charges in e, one per atom; ``None``: no electrostatics at all (the bundled cage model carries no
-        charges, and the guest's then do nothing).  The reference has no counterpart.  Sets
+        partial charges in e, one per atom, or ``"qeq"``: the library's own (:meth:`calculate_charges`); ``None``: no
+        electrostatics at all (the bundled cage model carries no charges, and the guest's then do nothing).  The reference has no counterpart.  Sets
         ``properties["rigid_guest_affinity"]``: ``guest``, ``temperature``, ``boltzmann_volume``, ``henry``,
         ``mean_energy``, ``heat``, ``min_energy``, ``min_position``, ``min_direction``, ``closed``, ``spacing``;
         ``self.rigid_affinity`` keeps the :class:`pywindow_amd.RigidAffinity`, which is returned.  ``full_analysis``
@@ -313,6 +313,20 @@ class Molecule:
             "min_energy": float(af.min_energy), "min_position": af.min_position, "min_direction": af.min_direction,
             "closed": bool(af.closed), "spacing": float(spacing)}
         return af
+
+    def calculate_charges(self, total_charge: float = 0.0, device=None):
+        """The partial charges of the molecule by charge equilibration (``pywindow_amd.equilibrate_charges``, on the
+        GPU; ``QEQ_PARAMETERS`` of :mod:`pywindow_amd.charges`, which also says what the model leaves out).  The
+        reference has no counterpart.  Sets ``properties["charges"]`` and ``self.charges`` to the ``(n,)`` charges in e
+        and ``self.charge_equilibration`` to the :class:`pywindow_amd.Charges`; returns the charges.  They are what
+        ``calculate_rigid_guest_affinity(charges="qeq")`` uses.  ``full_analysis`` does not call it."""
+        from . import charges as CH
+
+        result = CH.equilibrate_charges(self.coordinates, self.elements, total_charge, device=device)
+        self.charge_equilibration = result
+        self.charges = result.charges
+        self.properties["charges"] = result.charges
+        return result.charges
 
     def calculate_guest_passage(self, guest="Xe", spacing: float = 0.5, close="windows", device=None):
         """What it costs a one-site Lennard-Jones guest to leave the cage through each window

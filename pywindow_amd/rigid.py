@@ -11,9 +11,10 @@ the device and the explicit host path (``device=-1``) return the same bytes.  Fr
 ``boltzmann_volume``, ``henry``, ``mean_energy``, ``heat``, ``min_energy`` with its position and direction, and
 ``selectivity`` -- "CO2 over N2?".
 
-What is left out.  Linear guests only (all sites on one axis).  No guest-guest term: infinite dilution.  The framework's
-partial charges are the caller's: the bundled cage model (UFF) carries none, so without ``charges`` the job is
-uncharged and the guest's own charges do nothing.  Passage and hopping of a rigid guest go through
+What is left out.  Linear guests only (all sites on one axis).  No guest-guest term: infinite dilution.  The bundled
+cage model (UFF) carries no partial charges, so without ``charges`` the job is uncharged and the guest's own charges do
+nothing; ``charges`` are the caller's, one set for all frames or one a frame, or ``"qeq"``: the library equilibrates them
+itself, frame by frame (:mod:`pywindow_amd.charges`).  Passage and hopping of a rigid guest go through
 :meth:`RigidAffinity.free_energy_field`, which :func:`pywindow_amd.passage_field` accepts.
 
 Parameters.  The framework atoms are UFF as in :mod:`pywindow_amd.affinity`, Lorentz-Berthelot mixed with each site.
@@ -78,10 +79,15 @@ def rigid_coefficients(elements, guest, charges=None) -> np.ndarray:
     """Rows ``(A, B, C)`` ``(S, n, 3)`` between every site of ``guest`` (a name of ``RIGID_GUESTS`` or a
     :class:`RigidGuest`) and every framework atom: ``A = 4 eps sigma^12`` and ``B = 4 eps sigma^6`` from UFF,
     Lorentz-Berthelot mixed as :func:`pywindow_amd.lj_coefficients` does (a site with ``eps = 0`` gets ``A = B = 0``; it
-    still blocks within the core), and ``C = COULOMB q_a q_s`` with ``charges`` the caller's ``(n,)`` framework charges
-    in e.  With ``charges=None`` the column is zero and a job made from the rows is uncharged: the guest's charges do
-    nothing, because the bundled cage model carries no charges.  An element without UFF parameters raises
+    still blocks within the core), and ``C = COULOMB q_a q_s`` with ``charges`` the ``(n,)`` framework charges in e.
+    With ``charges=None`` the column is zero and a job made from the rows is uncharged: the guest's charges do
+    nothing, because the bundled cage model carries no charges.  ``charges`` ``(F, n)``, one row a frame, gives
+    ``(F, S, n, 3)``: frame ``f``'s rows are those of ``charges[f]``.  An element without UFF parameters raises
     ``KeyError``."""
+    if charges is not None and np.ndim(charges) == 2:
+        per_frame = np.asarray(charges, dtype=np.float64)
+        return np.stack([rigid_coefficients(elements, guest, row) for row in per_frame]) if len(per_frame) else \
+            np.zeros((0, len(_guest(guest).offsets), len(list(elements)), 3))
     g = _guest(guest)
     rows = np.array([UFF[str(e).upper()] for e in elements], dtype=np.float64).reshape(-1, 2)
     n = len(rows)
@@ -120,6 +126,7 @@ class RigidAffinity:
     map_level: int = -1
     charged: bool = False
     frames: np.ndarray | None = None
+    charges_converged: object = None      # with charges="qeq": whether the frame's charge equilibration converged
 
     @property
     def n_voxels(self):
@@ -191,7 +198,7 @@ class RigidAffinity:
     def series(self, name: str = "boltzmann_volume", level: int = 0):
         """``(values, valid)`` of a quantity over the frames at temperature ``level``, with the validity rule of
         :meth:`pywindow_amd.Affinity.series`: the cavity is closed (always, for a plain grid), the frame was not
-        clamped and the value is finite."""
+        clamped and the value is finite -- and, with ``charges="qeq"``, the frame's charges converged."""
         if name not in _SERIES:
             raise KeyError(f"series: one of {_SERIES}")
         v = np.asarray(getattr(self, name), dtype=np.float64)
@@ -201,6 +208,8 @@ class RigidAffinity:
         valid = np.isfinite(values) & ~np.atleast_1d(self.clamped)
         if self.closed is not None:
             valid &= np.atleast_1d(np.asarray(self.closed, dtype=bool))
+        if self.charges_converged is not None:
+            valid &= np.atleast_1d(np.asarray(self.charges_converged, dtype=bool))
         return values, valid
 
     def free_energy_field(self, t=None):
@@ -224,22 +233,38 @@ def rigid_guest_affinity_batch(xyz, elements_or_coef, guest, temperatures, cavit
     """:func:`rigid_guest_affinity` for ``T`` frames of the same ``n`` atoms in ONE ``pw_rigid_affinity`` call: ``xyz``
     ``(T, n, 3)``; ``cavity`` the :class:`pywindow_amd.Cavity` of the same ``T`` frames made with ``mask=True``, or
     ``grid = (origin (3,) or (T, 3), spacing, (nx, ny, nz))``.  The frames share the coefficients, the directions and
-    the temperatures.  ``kernel_ms``: a list that receives the time of the device work by HIP events."""
+    the temperatures; ``charges`` may be ``(n,)`` for all frames or ``(T, n)``, one row a frame (the coefficient rows are
+    then per frame), or ``"qeq"``: ONE ``pw_charges`` call over the same frames makes them
+    (:func:`pywindow_amd.equilibrate_charges_batch`, total charge 0), and a frame whose charges did not converge is not
+    valid in :meth:`RigidAffinity.series`.  ``kernel_ms``: a list that receives the time of the device work by HIP
+    events."""
     x = np.ascontiguousarray(xyz, dtype=np.float64)
     if x.ndim != 3 or x.shape[2] != 3:
         raise ValueError("xyz: (T, n, 3)")
     T, n = x.shape[:2]
     g = _guest(guest)
     S = len(g.offsets)
+    charges_converged = None
     coef = np.asarray(elements_or_coef)
     if coef.dtype.kind in "fiu" and coef.ndim == 3 and coef.shape[2] == 3:
+        if isinstance(charges, str):
+            raise ValueError('charges="qeq" needs the elements, not ready rows')
         coef = np.ascontiguousarray(coef, dtype=np.float64)
         charged = bool((coef[:, :, 2] != 0.0).any())
     else:
+        if isinstance(charges, str):
+            if charges != "qeq":
+                raise ValueError('charges: None, one per atom, one row a frame or "qeq"')
+            from .charges import equilibrate_charges_batch
+
+            made = equilibrate_charges_batch(x, list(elements_or_coef), device=device)
+            charges_converged = np.atleast_1d(made.converged).copy()
+            charges = np.where(np.isfinite(made.charges), made.charges, 0.0)   # (NaN: a frame that is not valid anyway)
         coef = rigid_coefficients(list(elements_or_coef), g, charges)
         charged = charges is not None
-    if coef.shape[:2] != (S, n):
-        raise ValueError("elements_or_coef: one element per atom, or rows (A, B, C) (S, n, 3)")
+    per_frame_coef = coef.ndim == 4
+    if coef.shape != ((T, S, n, 3) if per_frame_coef else (S, n, 3)):
+        raise ValueError("elements_or_coef: one element per atom, or rows (A, B, C) (S, n, 3); charges: (n,) or (T, n)")
     temps = np.atleast_1d(np.asarray(temperatures, dtype=np.float64))
     if temps.ndim != 1 or not 1 <= len(temps) <= _lib.AFF_MAX_LEVELS or not (np.isfinite(temps) & (temps > 0.0)).all():
         raise ValueError(f"temperatures: 1 .. {_lib.AFF_MAX_LEVELS} positive numbers")
@@ -252,6 +277,8 @@ def rigid_guest_affinity_batch(xyz, elements_or_coef, guest, temperatures, cavit
         raise ValueError("one of cavity and grid")
     jobs = np.zeros(T, dtype=_lib.RIGID_JOB_DTYPE)
     jobs["atom_first"] = np.arange(T) * n
+    if per_frame_coef:
+        jobs["coef_first"] = np.arange(T) * (S * n)
     jobs["n"] = n
     jobs["n_betas"] = len(temps)
     jobs["n_sites"] = S
@@ -295,7 +322,7 @@ def rigid_guest_affinity_batch(xyz, elements_or_coef, guest, temperatures, cavit
         per_frame = [buf[int(f):int(f) + 2 * int(v)].reshape(-1, 2) for f, v in zip(jobs["map_first"], voxels)]
     return RigidAffinity(out, levels.reshape(T, len(temps)), temps, jobs["origin"].copy(), np.array(shape, dtype=np.int64),
                          spacing, d, g, closed, per_frame, int(level) if maps else -1, charged,
-                         None if frames is None else np.array(frames, dtype=np.int64).reshape(-1))
+                         None if frames is None else np.array(frames, dtype=np.int64).reshape(-1), charges_converged)
 
 
 def rigid_guest_affinity(xyz, elements_or_coef, guest, temperatures, cavity=None, grid=None, directions=None, charges=None,
@@ -304,7 +331,8 @@ def rigid_guest_affinity(xyz, elements_or_coef, guest, temperatures, cavity=None
     """The orientation-averaged affinity of the cage ``xyz`` ``(n, 3)`` for a rigid linear guest at the
     ``temperatures`` (K, at most 8): see :class:`RigidAffinity`.  ``guest``: a name of ``RIGID_GUESTS`` or a
     :class:`RigidGuest`.  ``elements_or_coef``: the atoms' element symbols (:func:`rigid_coefficients`, with
-    ``charges`` the framework's partial charges in e), or ready rows ``(A, B, C)`` ``(S, n, 3)`` (charged when some
+    ``charges`` the framework's partial charges in e, or ``"qeq"``: made by
+    :func:`pywindow_amd.equilibrate_charges`), or ready rows ``(A, B, C)`` ``(S, n, 3)`` (charged when some
     ``C`` is not zero).  With elements and ``charges=None`` the job is uncharged and the guest's charges do nothing: the
     bundled cage model carries no charges.  The region is the mask of ``cavity`` (made with ``mask=True``) or every
     voxel of ``grid = (origin, spacing, (nx, ny, nz))``.  ``directions``: ``(M, 3)`` unit vectors, at most 1024
@@ -321,4 +349,5 @@ def rigid_guest_affinity(xyz, elements_or_coef, guest, temperatures, cavity=None
                                       charges, maps, level, core2, cutoff2, device)
     return RigidAffinity(many.raw[0], many.levels[0], many.temperatures, many.origin[0], many.shape[0], many.spacing,
                          many.directions, many.guest, None if many.closed is None else many.closed[0],
-                         None if many.maps is None else many.maps[0], many.map_level, many.charged, None)
+                         None if many.maps is None else many.maps[0], many.map_level, many.charged, None,
+                         None if many.charges_converged is None else many.charges_converged[0])

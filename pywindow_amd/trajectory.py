@@ -533,7 +533,7 @@ class DLPOLY:
         so far (``frames``: a selection of them): one ``pw_cavity`` call for the probe-0 cavities, seeded, boxed and
         closed exactly as :meth:`cavity`, then ALL frames in ONE ``pw_rigid_affinity`` call on the GPU
         (``pywindow_amd.rigid_guest_affinity_batch``, UFF atoms, ``core2 = 0.25``; ``charges``: the framework's partial
-        charges, ``None``: no electrostatics) -- a :class:`pywindow_amd.RigidAffinity` whose fields are arrays over the
+        charges, one set or one row a frame, ``"qeq"``: :meth:`charges` of the same frames, ``None``: no electrostatics) -- a :class:`pywindow_amd.RigidAffinity` whose fields are arrays over the
         frames and whose ``frames`` are the trajectory's frame numbers.  Non-modular, non-periodic analyses only."""
         from . import cavity as CV
         from . import rigid as RG
@@ -542,6 +542,27 @@ class DLPOLY:
         cav = CV.cavity_grid_batch(coords, radii, seeds, 0.0, spacing, half_widths, planes, True, device, frames=sel)
         return RG.rigid_guest_affinity_batch(coords, self.elements(swap_atoms, forcefield), guest, temperatures, cavity=cav,
                                              directions=directions, charges=charges, core2=0.25, device=device, frames=sel)
+
+    def charges(self, frames=None, total_charge: float = 0.0, tol: float = 1e-10, max_iter: int = 1000, device=None,
+                swap_atoms=None, forcefield=None):
+        """The partial charges of the cage in every frame analysed so far (``frames``: any selection of the
+        trajectory's frames) by charge equilibration, ALL frames in ONE ``pw_charges`` call on the GPU
+        (``pywindow_amd.equilibrate_charges_batch``) -- a :class:`pywindow_amd.Charges` whose ``charges`` are
+        ``(frames, atoms)`` and whose ``frames`` are the trajectory's frame numbers.  ``charges().series("dipole_norm")``
+        goes into ``pywindow_amd.time_correlation``, ``lomb_scargle``, ``gaussian_kde_1d``, ``gate_statistics`` and
+        ``transition_counts``.  Non-modular, non-periodic trajectories only."""
+        from . import charges as CH
+
+        if frames is None:
+            if self.analysis_store.modular:
+                raise ValueError("charges: a periodic or modular trajectory is not supported yet (the atom order of a "
+                                 "rebuilt molecule is not fixed across frames)")
+            frames = [int(f) for f in self.analysis_store.unit_frame]
+            if not frames:
+                raise ValueError("charges: no frame has been analysed yet")
+        sel, coords = self._rigid_frames(frames, "charges")
+        return CH.equilibrate_charges_batch(coords, self.elements(swap_atoms, forcefield), total_charge, tol, max_iter,
+                                            device, frames=sel)
 
     def passage(self, guest="Xe", spacing: float = 0.5, frames=None, device=None, close="windows", swap_atoms=None,
                 forcefield=None):
