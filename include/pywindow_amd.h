@@ -1240,6 +1240,71 @@ typedef struct pw_charges_out {
 } pw_charges_out;
 int pw_charges(pw_context *ctx, const pw_charges_job *jobs, int64_t n_jobs, const double *xyz, const double *params,
                int64_t n_points, double *charges, pw_charges_out *out);
+/* ---- the pore network of a crystal cell: periodic void components and in how many dimensions each percolates ----
+ * Every grid entry above looks at one cage cut out of its surroundings.  This one takes a whole periodic cell: are
+ * its voids connected, in how many dimensions, for a guest of which size, and how much of the void is accessible
+ * through that network rather than locked in pockets.  The reference has no counterpart.  The text of record, with the
+ * proofs, is pywindow_amd/csrc/pw_channels.hpp; in short, job k (one cell at one probe) has
+ *     atoms   n >= 0 atoms xyz[atom_first .. +n) with radii[radius_first .. +n) and a probe >= 0.  The job lists every
+ *             periodic image that matters as an atom of its own: only the fill wraps, not the classification;
+ *     a grid  nx x ny x nz voxels, each 1 .. PW_CAVITY_MAX_G, an origin o and step = (ax, bx, by, cx, cy, cz): the cell's
+ *             first vector along x, its second in the xy plane; ax, by, cz > 0.  Voxel (i, j, l) has the centre
+ *             z = oz + (double)l*cz, y = (oy + (double)j*by) + (double)l*cy,
+ *             x = ((ox + (double)i*ax) + (double)j*bx) + (double)l*cx  (products rounded, sums left to right, no fma).
+ * A voxel is OPEN iff it is free by pw_cavity's test (equality is free); there are no planes.  Voxel v has the six
+ * neighbours v +- e_k with indices mod n_k; a step +e_k from index n_k - 1 or -e_k from index 0 CROSSES face k.  The
+ * COMPONENTS are the connected components of the open voxels, numbered by their first voxel in rank
+ * (l * ny + j) * nx + i ascending.  For phi in 1 .. 7 (bit 0 = a, 1 = b, 2 = c), on the nodes (voxel, parity) where a
+ * step changes parity iff it crosses a face of phi, bit phi - 1 of a component's `wraps` is set iff (first voxel, 1)
+ * is reachable from (first voxel, 0): iff the component holds a closed path whose winding vector w has phi . w odd.
+ * rank = 3 - log2(1 + number of clear bits) is the rank mod 2 of the winding lattice: 0 a pocket, 1 a channel, 2 a
+ * layer, 3 a network.  LIMIT: a component all of whose winding vectors are even (a double helix of pitch two cells)
+ * reads as a pocket.
+ * Row `out` of the result: n_open, n_components (all of them), n_recorded = min(n_components, c_max), the voxels and
+ * the components by rank over ALL components (sum n_voxels_by_rank == n_open), flags (PW_CHAN_TRUNCATED iff
+ * n_components > c_max).  Rows comps[comp_first .. + c_max): the first n_recorded components -- first (the rank of the
+ * first voxel), n_voxels, n_cross[k] (its voxels at index n_k - 1 whose +e_k neighbour is in it), wraps, rank -- and
+ * the rest of the c_max rows written as first = -1 and zeros.  mask_first >= 0: the ACCESSIBLE words, the OR of every
+ * component of rank >= 1, to mask[mask_first .. + ny*nz) in the layout of pw_cavity's mask (so they serve as `words`
+ * of pw_affinity and pw_sasa).  label_first >= 0: one byte a voxel in rank order to labels[label_first .. + nx*ny*nz):
+ * the component's row index, 254 for a component beyond c_max, 255 for a voxel that is not open.
+ * Every output is an integer, so the bytes are this definition on every device, launch geometry and run and on a
+ * device == -1 context.  Jobs may share atoms and radii but no output; entries no job owns are never touched.  A value
+ * a job reads that is not finite, ax, by or cz <= 0, a negative radius or probe, a dimension outside
+ * 1 .. PW_CAVITY_MAX_G, c_max outside 0 .. PW_CHAN_MAX_COMPONENTS, a range outside an array or jobs that share
+ * outputs (the later of the two is named): PW_E_BAD_ARG, and nothing is launched or written. */
+#define PW_CHAN_MAX_COMPONENTS 254
+#define PW_CHAN_TRUNCATED 1      /* more components than c_max: the table holds the first c_max, the totals all */
+typedef struct pw_channels_job {
+    int64_t atom_first, n;      /* atoms = xyz[atom_first .. +n), n >= 0 */
+    int64_t radius_first;       /* their radii = radii[radius_first .. +n) */
+    int64_t comp_first;         /* comps[comp_first .. + c_max) is written */
+    int64_t mask_first;         /* mask[mask_first .. + ny*nz) is written, or -1: no mask */
+    int64_t label_first;        /* labels[label_first .. + nx*ny*nz) is written, or -1: no labels */
+    int64_t out;                /* the job's row of the result */
+    double  origin[3];          /* the centre of voxel (0, 0, 0) */
+    double  step[6];            /* ax, bx, by, cx, cy, cz */
+    double  probe;              /* >= 0 */
+    int32_t nx, ny, nz;         /* 1 .. PW_CAVITY_MAX_G */
+    int32_t c_max;              /* 0 .. PW_CHAN_MAX_COMPONENTS */
+} pw_channels_job;
+typedef struct pw_channels_comp {
+    int64_t first;              /* the rank of the component's first voxel; -1 in a row beyond n_recorded */
+    int64_t n_voxels;
+    int64_t n_cross[3];
+    int32_t wraps;              /* bit phi - 1, phi in 1 .. 7 */
+    int32_t rank;               /* 0 .. 3 */
+} pw_channels_comp;
+typedef struct pw_channels_out {
+    int64_t n_open, n_components, n_recorded;
+    int64_t n_voxels_by_rank[4];
+    int64_t n_components_by_rank[4];
+    int32_t flags;              /* PW_CHAN_* */
+    int32_t reserved;           /* padding to a multiple of 8 bytes; written as 0 */
+} pw_channels_out;
+int pw_channels(pw_context *ctx, const pw_channels_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+                const double *radii, int64_t n_radii, pw_channels_out *out, int64_t n_out, pw_channels_comp *comps,
+                int64_t n_comps, uint64_t *mask, int64_t n_mask, uint8_t *labels, int64_t n_labels);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

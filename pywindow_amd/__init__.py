@@ -44,6 +44,7 @@ from .rigid import (  # noqa: E402
     rigid_guest_affinity_batch,
 )
 from .charges import QEQ_PARAMETERS, Charges, equilibrate_charges, equilibrate_charges_batch  # noqa: E402
+from .channels import Channels, channel_network, channel_network_batch  # noqa: E402
 from .passage import Passage, guest_passage, guest_passage_batch, passage_field  # noqa: E402
 from .hopping import Hopping, guest_hopping, guest_hopping_batch, window_frame  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
@@ -125,6 +126,9 @@ __all__ = [
     "Charges",
     "equilibrate_charges",
     "equilibrate_charges_batch",
+    "Channels",
+    "channel_network",
+    "channel_network_batch",
     "Passage",
     "guest_passage",
     "guest_passage_batch",

@@ -367,6 +367,27 @@ CHG_NOT_CONVERGED = 1
 CHG_BREAKDOWN = 2
 CHG_NO_SUM = 4
 
+#: numpy mirrors of ``pw_channels_job``, ``pw_channels_comp`` and ``pw_channels_out``
+CHANNELS_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("radius_first", np.int64), ("comp_first", np.int64),
+     ("mask_first", np.int64), ("label_first", np.int64), ("out", np.int64), ("origin", np.float64, (3,)),
+     ("step", np.float64, (6,)), ("probe", np.float64), ("nx", np.int32), ("ny", np.int32), ("nz", np.int32),
+     ("c_max", np.int32)]
+)
+CHANNELS_COMP_DTYPE = np.dtype(
+    [("first", np.int64), ("n_voxels", np.int64), ("n_cross", np.int64, (3,)), ("wraps", np.int32), ("rank", np.int32)]
+)
+CHANNELS_OUT_DTYPE = np.dtype(
+    [("n_open", np.int64), ("n_components", np.int64), ("n_recorded", np.int64), ("n_voxels_by_rank", np.int64, (4,)),
+     ("n_components_by_rank", np.int64, (4,)), ("flags", np.int32), ("reserved", np.int32)]
+)
+assert CHANNELS_JOB_DTYPE.itemsize == 152 and CHANNELS_COMP_DTYPE.itemsize == 48 and CHANNELS_OUT_DTYPE.itemsize == 96
+#: ``PW_CHAN_MAX_COMPONENTS``, ``PW_CHAN_TRUNCATED``; the labels of a component beyond the cap and of a closed voxel
+CHAN_MAX_COMPONENTS = 254
+CHAN_TRUNCATED = 1
+CHAN_LABEL_BEYOND = 254
+CHAN_LABEL_CLOSED = 255
+
 #: numpy mirror of ``pw_passage_job``
 PASSAGE_JOB_DTYPE = np.dtype(
     [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
@@ -498,6 +519,7 @@ EXPORTED_SYMBOLS = [
     "pw_hop",
     "pw_rigid_affinity",
     "pw_charges",
+    "pw_channels",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -647,6 +669,8 @@ def load():
     L.pw_internal_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
     L.pw_internal_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6
+    L.pw_internal_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6 + [vp, vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1411,6 +1435,58 @@ class Context:
             if kernel_ms is not None:
                 kernel_ms.append(float(ms.value))
         return q[:size], out
+
+    def channels(self, jobs, xyz, radii, out=None, comps=None, mask=None, labels=None, open_words=None, open_first=None,
+                 workspace_bytes=None, kernel_ms=None):
+        """``pw_channels``: the periodic void components of a batch of jobs and how each winds through the cell
+        (``CHANNELS_JOB_DTYPE`` records indexing the rows of ``xyz`` (rows of three), the entries of ``radii``, the rows
+        of the result and of the component table, the words of ``mask`` and the bytes of ``labels``):
+        ``(out, comps, mask, labels)`` -- ``out`` a ``CHANNELS_OUT_DTYPE`` array, ``comps`` a ``CHANNELS_COMP_DTYPE`` array
+        with ``c_max`` rows a job from its ``comp_first``, ``mask`` the uint64 accessible words of the jobs with
+        ``mask_first >= 0`` and ``labels`` the uint8 labels of the jobs with ``label_first >= 0`` (``None`` when no job
+        has one).  An array that is given is filled in place, and entries no job owns stay as they are.  Whatever the
+        entry refuses -- a value that is not finite, ``ax``, ``by`` or ``cz <= 0``, a negative radius or probe, a
+        dimension outside ``1 .. CAVITY_MAX_G``, ``c_max`` outside ``0 .. CHAN_MAX_COMPONENTS``, a range outside an
+        array, jobs that share outputs --: ``ValueError`` with the library's message.  ``open_words`` / ``open_first``
+        / ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the device work by HIP events) go
+        through the library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=CHANNELS_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
+        some = len(jobs) > 0
+        rows = np.int64(1) * jobs["ny"] * jobs["nz"]
+
+        def made(given, dtype, what, first, count):
+            """`given`, checked, or zeros up to the furthest entry of the jobs that write some"""
+            if given is not None:
+                if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+                    raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+                return given
+            has = (jobs[first] >= 0) & (count > 0) if some else np.zeros(0, dtype=bool)
+            return np.zeros(int((jobs[first][has] + count[has]).max()), dtype=dtype) if has.any() else None
+
+        out = made(out, CHANNELS_OUT_DTYPE, "out", "out", np.ones(len(jobs), dtype=np.int64))
+        if out is None:
+            out = np.zeros(0, dtype=CHANNELS_OUT_DTYPE)
+        comps = made(comps, CHANNELS_COMP_DTYPE, "comps", "comp_first", jobs["c_max"].astype(np.int64))
+        mask = made(mask, np.uint64, "mask", "mask_first", rows)
+        labels = made(labels, np.uint8, "labels", "label_first", rows * jobs["nx"])
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), r.ctypes.data, len(r), out.ctypes.data, len(out)]
+        for a in (comps, mask, labels):
+            args += [None if a is None else a.ctypes.data, 0 if a is None else len(a)]
+        if open_words is None and workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_channels", *args)
+            return out, comps, mask, labels
+        w = None if open_words is None else np.ascontiguousarray(open_words, dtype=np.uint64).reshape(-1)
+        f = None if open_first is None else np.ascontiguousarray(open_first, dtype=np.int64).reshape(-1)
+        if (w is None) != (f is None) or (f is not None and len(f) != len(jobs)):
+            raise ValueError("open_words and open_first: both, with one entry of open_first per job")
+        ms = ctypes.c_float(0.0)
+        _stat_call("pw_internal_channels", *args, None if w is None else w.ctypes.data, None if f is None else f.ctypes.data,
+                   0 if w is None else len(w), int(workspace_bytes or 0), ctypes.byref(ms))
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        return out, comps, mask, labels
 
     def passage(self, jobs, xyz=None, coef=None, planes=None, field=None, out=None, workspace_bytes=None, kernel_ms=None,
                 fills=None, grids=None):

@@ -27,6 +27,7 @@
 #include "pw_passage.hpp"
 #include "pw_hop.hpp"
 #include "pw_charges.hpp"
+#include "pw_channels.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -1874,6 +1875,134 @@ extern "C" int pw_hostpath_charges(const pw_charges_job* jobs, long n_jobs, cons
         for (int t = 0; t < count; ++t) pool.emplace_back(worker);
         for (auto& t : pool) t.join();
     }
+    return PW_OK;
+}
+
+// pw_channels on the host (pw_channels.hip checks the arguments and sends device == -1 contexts here): the centres,
+// the gathering of the neighbour rows, the spread inside a word, the fills that are not run and the rank of
+// pw_channels.hpp.  The threads share out the jobs; a job is a plain loop: classify, then component after component
+// from the first set bit of todo, each fill as sweeps forwards and backwards over the words until one changes nothing
+// (at most 2 * nx * ny * nz + 1 of them).  A job's outputs are its own.
+extern "C" int pw_hostpath_channels(const pw_channels_job* jobs, long n_jobs, const double* xyz, const double* radii,
+                                    pw_channels_out* out, pw_channels_comp* comps, unsigned long long* mask,
+                                    unsigned char* labels, const unsigned long long* open_words, const long* open_first,
+                                    int threads) {
+    typedef cavity_word u64;
+    cov_share(n_jobs, threads, [&](long k) {
+        const pw_channels_job& J = jobs[k];
+        const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
+        std::vector<u64> todo((size_t)rows), p0((size_t)rows), p1((size_t)rows), acc((size_t)rows, 0);
+        if (open_first && open_first[k] >= 0) {
+            for (int r = 0; r < rows; ++r) todo[r] = open_words[open_first[k] + r] & cavity_row_mask(nx);
+        } else {
+            const double* atoms = xyz + 3 * (long)J.atom_first;
+            const double* reach = radii + (long)J.radius_first;
+            for (int r = 0; r < rows; ++r) {
+                const int j = r % ny, l = r / ny;
+                const double y = channels_y(J.origin[1], j, J.step[2], l, J.step[4]), z = channels_z(J.origin[2], l, J.step[5]);
+                u64 word = cavity_row_mask(nx);
+                for (long a = 0; a < (long)J.n && word; ++a) {
+                    const double r2 = cavity_reach2(reach[a], J.probe);
+                    const double dy = y - atoms[3 * a + 1], dz = z - atoms[3 * a + 2];
+                    if (cavity_row_clear(dy, dz, r2)) continue;
+                    for (int i = 0; i < nx; ++i)
+                        if (!cavity_free(channels_x(J.origin[0], i, J.step[0], j, J.step[1], l, J.step[3]) - atoms[3 * a], dy, dz, r2))
+                            word &= ~(1ull << i);
+                }
+                todo[r] = word;
+            }
+        }
+        pw_channels_out o{};
+        unsigned char* label = J.label_first >= 0 ? labels + (long)J.label_first : nullptr;
+        for (int r = 0; r < rows; ++r) {
+            o.n_open += cavity_popcount(todo[r]);
+            if (label)
+                for (int i = 0; i < nx; ++i)
+                    if (!((todo[r] >> i) & 1ull)) label[(long)r * nx + i] = (unsigned char)CHAN_LABEL_CLOSED;
+        }
+        pw_channels_comp* table = comps + (long)J.comp_first;
+        const long max_sweeps = 2 * (long)nx * ny * nz + 1;
+        auto load = [&](int q, int row) { return q ? p1[row] : p0[row]; };
+        long count = 0;
+        for (int seed_row = 0; seed_row < rows;) {
+            if (!todo[seed_row]) {
+                ++seed_row;
+                continue;
+            }
+            const int seed_i = __builtin_ctzll(todo[seed_row]);
+            const u64 seed_bit = 1ull << seed_i;
+            int known = 0, wraps = 0, cross = 0, phi = 7;
+            bool measured = false;
+            pw_channels_comp C{};
+            for (int fill = 0; fill < 7 && phi; ++fill) {
+                std::fill(p0.begin(), p0.end(), 0);
+                std::fill(p1.begin(), p1.end(), 0);
+                p0[seed_row] = seed_bit;
+                auto visit = [&](int r) {
+                    if (!todo[r]) return false;
+                    u64 from0 = p0[r], from1 = p1[r], g0, g1;
+                    channels_gather(load, r % ny, r / ny, ny, nz, phi, from0, from1);
+                    channels_fill_words(from0, from1, todo[r], nx, (phi & 1) != 0, g0, g1);
+                    const bool changed = g0 != p0[r] || g1 != p1[r];
+                    p0[r] = g0;
+                    p1[r] = g1;
+                    return changed;
+                };
+                for (long sweep = 0; sweep < max_sweeps; ++sweep) {
+                    bool changed = false;
+                    for (int r = 0; r < rows; ++r) changed = visit(r) || changed;
+                    for (int r = rows - 1; r >= 0; --r) changed = visit(r) || changed;
+                    if (!changed) break;
+                }
+                const bool reached = (p1[seed_row] & seed_bit) != 0;
+                channels_learn(phi, reached, known, wraps);
+                if (!measured) {
+                    for (int r = 0; r < rows; ++r) {
+                        const u64 f = p0[r] | p1[r];
+                        if (!f) continue;
+                        const int j = r % ny, l = r / ny;
+                        long c[3];
+                        channels_row_cross(f, p0[l * ny] | p1[l * ny], p0[j] | p1[j], nx, ny, nz, j, l, c);
+                        C.n_voxels += cavity_popcount(f);
+                        for (int a = 0; a < 3; ++a) C.n_cross[a] += c[a];
+                    }
+                    for (int a = 0; a < 3; ++a) cross |= (C.n_cross[a] > 0) << a;
+                    if (cross) channels_learn(cross, reached, known, wraps);
+                    measured = true;
+                }
+                phi = channels_next(cross, known, wraps);
+            }
+            C.first = (long)seed_row * nx + seed_i;
+            C.wraps = wraps;
+            C.rank = channels_rank(wraps);
+            const unsigned char name = (unsigned char)(count < J.c_max ? count : CHAN_LABEL_BEYOND);
+            for (int r = 0; r < rows; ++r) {
+                const u64 f = p0[r] | p1[r];
+                if (!f) continue;
+                todo[r] &= ~f;
+                if (C.rank >= 1) acc[r] |= f;
+                if (label)
+                    for (int i = 0; i < nx; ++i)
+                        if ((f >> i) & 1ull) label[(long)r * nx + i] = name;
+            }
+            if (count < J.c_max) table[count] = C;
+            o.n_voxels_by_rank[C.rank] += C.n_voxels;
+            o.n_components_by_rank[C.rank] += 1;
+            ++count;
+        }
+        for (long c = count; c < J.c_max; ++c) {
+            pw_channels_comp none{};
+            none.first = -1;
+            table[c] = none;
+        }
+        if (J.mask_first >= 0)
+            for (int r = 0; r < rows; ++r) mask[(long)J.mask_first + r] = acc[r];
+        o.n_components = count;
+        o.n_recorded = count < J.c_max ? count : J.c_max;
+        o.flags = count > J.c_max ? CHAN_TRUNCATED : 0;
+        o.reserved = 0;
+        out[(long)J.out] = o;
+    });
     return PW_OK;
 }
 

@@ -564,6 +564,28 @@ class DLPOLY:
         return CH.equilibrate_charges_batch(coords, self.elements(swap_atoms, forcefield), total_charge, tol, max_iter,
                                             device, frames=sel)
 
+    def channels(self, probe=0.0, spacing: float = 0.5, frames=None, c_max: int = 64, mask: bool = False,
+                 labels: bool = False, device=None, swap_atoms=None, forcefield=None):
+        """The pore network of the periodic cell in every selected frame (``frames``: any selection of the trajectory's
+        frames, ``None``: all of them) for a probe of radius ``probe`` (a sequence: a ladder), ALL frames and probes in
+        ONE ``pw_channels`` call on the GPU (``pywindow_amd.channel_network_batch``) -- a :class:`pywindow_amd.Channels`
+        whose fields are ``(frames, probes)`` arrays and whose ``frames`` are the trajectory's frame numbers.  The
+        frames are read with their lattices as they are in the file: no analysis and no rebuild is needed, since the
+        fill wraps through the cell faces itself.  ``channels().series("accessible_volume")`` goes into
+        ``pywindow_amd.time_correlation``, ``lomb_scargle``, ``gaussian_kde_1d``, ``gate_statistics`` and
+        ``transition_counts``.  Periodic trajectories only: without a cell there is no network to speak of."""
+        from . import channels as CN
+
+        if not self.periodic:
+            raise ValueError("channels: the trajectory is not periodic (imcon 0): there is no cell whose voids could connect; "
+                             "cavity() and pore_sizes() look at a single cage")
+        sel = self._select("all" if frames is None else frames)
+        if not sel:
+            raise ValueError("channels: no frames selected")
+        coords, lattice = self._read_selected(sel, True)
+        return CN.channel_network_batch(coords, self.elements(swap_atoms, forcefield), lattice, probe, spacing, c_max, mask,
+                                        labels, device, frames=sel)
+
     def passage(self, guest="Xe", spacing: float = 0.5, frames=None, device=None, close="windows", swap_atoms=None,
                 forcefield=None):
         """The barrier a one-site Lennard-Jones guest crosses at every window in every frame analysed so far
