@@ -1305,6 +1305,70 @@ typedef struct pw_channels_out {
 int pw_channels(pw_context *ctx, const pw_channels_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
                 const double *radii, int64_t n_radii, pw_channels_out *out, int64_t n_out, pw_channels_comp *comps,
                 int64_t n_comps, uint64_t *mask, int64_t n_mask, uint8_t *labels, int64_t n_labels);
+/* ---- guest percolation: the energy levels at which the voids of a crystal cell connect ---------------------------
+ * pw_channels answers the hard-sphere question; what lets a guest through a soft wall is the energy barrier.  For one
+ * guest in one periodic cell this entry finds, for each of six connection criteria, the lowest energy level at which
+ * the sub-level set of the guest's energy landscape holds a component that meets the criterion: the minimax
+ * (bottleneck) barrier of diffusion.  The reference has no counterpart.  The text of record, with the proofs, is
+ * pywindow_amd/csrc/pw_percolate.hpp; in short, job k has
+ *     the grid of pw_channels (nx, ny, nz, origin, step; the same centres, neighbours and face crossings);
+ *     a field U over every voxel in rank (l*ny + j)*nx + i: with field_first == -1 the Lennard-Jones energy of the
+ *             atoms xyz[atom_first .. +n) with rows (A, B) = coef[coef_first .. +n), core2 and cutoff2, exactly as
+ *             pw_passage computes it (+inf at a blocked voxel; the job lists every periodic image that matters as an
+ *             atom of its own); with field_first >= 0 the caller's field[field_first .. + nx*ny*nz), every value finite
+ *             or +inf.  map_first >= 0: the field is also written to map[map_first .. + nx*ny*nz).
+ * allowed_t(v): U_v is not +inf and U_v <= t.  Criterion c = 0, 1, 2: some periodic component of allowed_t has
+ * rank >= 1, 2, 3 (pw_channels' rank); c = 3, 4, 5: some component has the bit of phi = 1, 2, 4 of its wraps set (a
+ * closed path that winds an odd number of times along a, b, c).  Each is monotone in t and changes only at voxel values.
+ * Row `out` of the result: n_blocked, u_min with u_min_voxel (the lowest rank on a tie; +inf and -1 without a finite
+ * voxel) and flags (PW_PERC_NEVER iff criterion 0 never holds).  Rows levels[level_first .. + 6), one a criterion:
+ * level = B_c, the smallest voxel value at which the criterion holds (+inf with PW_PERC_NEVER when it does not hold at
+ * the largest finite value); first, n_voxels, wraps, rank of the component C of allowed_{B_c} that meets the criterion
+ * and has the lowest first voxel; saddle, the voxel of C with U == B_c of the lowest rank (level carries the bits of U
+ * there); well and well_voxel, the smallest U over C with ties to the lowest rank; n_allowed = |allowed_{B_c}|.  With
+ * PW_PERC_NEVER: voxels and first -1, counts, wraps and rank 0, well +inf.
+ * Every output is a comparison of doubles or an integer count over the defined field: the same bytes on every device,
+ * launch geometry and run and on a device == -1 context.  LIMITS: pw_channels' (windings that are all even read as
+ * none); one guest, no guest-guest term, no charges; the bottleneck of the grid's 6-connectivity at its spacing.
+ * Jobs may share atoms, rows of coef and fields but no output; entries no job owns are never touched.  What pw_channels
+ * refuses of a grid and pw_passage of atoms, coefficients, core2, cutoff2 and a field, a range outside an array or jobs
+ * that share outputs (the later of the two is named): PW_E_BAD_ARG, and nothing is launched or written. */
+#define PW_PERC_CRITERIA 6
+#define PW_PERC_NEVER 1          /* the criterion holds at no finite level */
+typedef struct pw_percolation_job {
+    int64_t atom_first, n;      /* atoms = xyz[atom_first .. +n), n >= 0 (read when field_first == -1) */
+    int64_t coef_first;         /* their rows (A, B) = coef[coef_first .. +n) */
+    int64_t field_first;        /* -1: Lennard-Jones from the atoms; >= 0: field[field_first .. + nx*ny*nz) */
+    int64_t map_first;          /* map[map_first .. + nx*ny*nz) is written, or -1: no map */
+    int64_t level_first;        /* levels[level_first .. + 6) is written */
+    int64_t out;                /* the job's row of the result */
+    double  origin[3];          /* the centre of voxel (0, 0, 0) */
+    double  step[6];            /* ax, bx, by, cx, cy, cz */
+    double  core2;              /* >= 1e-6 */
+    double  cutoff2;            /* 0.0: none; otherwise > core2 */
+    int32_t nx, ny, nz;         /* 1 .. PW_CAVITY_MAX_G */
+    int32_t reserved;           /* padding to a multiple of 8 bytes; not read */
+} pw_percolation_job;
+typedef struct pw_percolation_level {
+    double  level;              /* B_c: the bits of U at the saddle, or +inf */
+    double  well;
+    int64_t first, n_voxels;    /* of the component C */
+    int64_t n_allowed;
+    int32_t saddle[3];          /* (i, j, l), or -1 */
+    int32_t well_voxel[3];
+    int32_t wraps, rank;        /* of C */
+    int32_t flags;              /* PW_PERC_* */
+    int32_t reserved;           /* padding to a multiple of 8 bytes; written as 0 */
+} pw_percolation_level;
+typedef struct pw_percolation_out {
+    int64_t n_blocked;
+    double  u_min;
+    int32_t u_min_voxel[3];     /* (i, j, l), or -1 */
+    int32_t flags;              /* PW_PERC_NEVER iff criterion 0 never holds */
+} pw_percolation_out;
+int pw_percolation(pw_context *ctx, const pw_percolation_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+                   const double *coef, int64_t n_coef, const double *field, int64_t n_field, double *map, int64_t n_map,
+                   pw_percolation_level *levels, int64_t n_levels, pw_percolation_out *out, int64_t n_out);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

@@ -46,6 +46,7 @@ from .rigid import (  # noqa: E402
 from .charges import QEQ_PARAMETERS, Charges, equilibrate_charges, equilibrate_charges_batch  # noqa: E402
 from .channels import Channels, channel_network, channel_network_batch  # noqa: E402
 from .passage import Passage, guest_passage, guest_passage_batch, passage_field  # noqa: E402
+from .percolation import Percolation, guest_percolation, guest_percolation_batch, percolation_field  # noqa: E402
 from .hopping import Hopping, guest_hopping, guest_hopping_batch, window_frame  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
@@ -133,6 +134,10 @@ __all__ = [
     "guest_passage",
     "guest_passage_batch",
     "passage_field",
+    "Percolation",
+    "guest_percolation",
+    "guest_percolation_batch",
+    "percolation_field",
     "Hopping",
     "guest_hopping",
     "guest_hopping_batch",

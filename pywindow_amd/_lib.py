@@ -388,6 +388,25 @@ CHAN_TRUNCATED = 1
 CHAN_LABEL_BEYOND = 254
 CHAN_LABEL_CLOSED = 255
 
+#: numpy mirrors of ``pw_percolation_job``, ``pw_percolation_level`` and ``pw_percolation_out``
+PERCOLATION_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("field_first", np.int64), ("map_first", np.int64),
+     ("level_first", np.int64), ("out", np.int64), ("origin", np.float64, (3,)), ("step", np.float64, (6,)),
+     ("core2", np.float64), ("cutoff2", np.float64), ("nx", np.int32), ("ny", np.int32), ("nz", np.int32), ("reserved", np.int32)]
+)
+PERCOLATION_LEVEL_DTYPE = np.dtype(
+    [("level", np.float64), ("well", np.float64), ("first", np.int64), ("n_voxels", np.int64), ("n_allowed", np.int64),
+     ("saddle", np.int32, (3,)), ("well_voxel", np.int32, (3,)), ("wraps", np.int32), ("rank", np.int32), ("flags", np.int32),
+     ("reserved", np.int32)]
+)
+PERCOLATION_OUT_DTYPE = np.dtype(
+    [("n_blocked", np.int64), ("u_min", np.float64), ("u_min_voxel", np.int32, (3,)), ("flags", np.int32)]
+)
+assert PERCOLATION_JOB_DTYPE.itemsize == 160 and PERCOLATION_LEVEL_DTYPE.itemsize == 80 and PERCOLATION_OUT_DTYPE.itemsize == 32
+#: ``PW_PERC_CRITERIA``, ``PW_PERC_NEVER``
+PERC_CRITERIA = 6
+PERC_NEVER = 1
+
 #: numpy mirror of ``pw_passage_job``
 PASSAGE_JOB_DTYPE = np.dtype(
     [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
@@ -520,6 +539,7 @@ EXPORTED_SYMBOLS = [
     "pw_rigid_affinity",
     "pw_charges",
     "pw_channels",
+    "pw_percolation",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -671,6 +691,8 @@ def load():
     L.pw_internal_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6
     L.pw_internal_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6 + [vp, vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_percolation.argtypes = [vp, vp, i64] + [vp, i64] * 6
+    L.pw_internal_percolation.argtypes = [vp, vp, i64] + [vp, i64] * 6 + [i64, ctypes.POINTER(ctypes.c_float), vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1487,6 +1509,55 @@ class Context:
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
         return out, comps, mask, labels
+
+    def percolation(self, jobs, xyz=None, coef=None, field=None, levels=None, out=None, maps=None, workspace_bytes=None,
+                    kernel_ms=None, diagnostics=None):
+        """``pw_percolation``: for every job of a batch (one periodic cell, one guest) the six energy levels at which the
+        sub-level sets of the guest's landscape connect (``PERCOLATION_JOB_DTYPE`` records indexing the rows of ``xyz``
+        (rows of three) and of ``coef`` (rows ``(A, B)``), the entries of ``field`` and of the maps and the rows of the
+        results): ``(levels, out, maps)`` -- ``levels`` a ``PERCOLATION_LEVEL_DTYPE`` array with six rows a job from its
+        ``level_first``, ``out`` a ``PERCOLATION_OUT_DTYPE`` array and ``maps`` the float64 fields of the jobs with
+        ``map_first >= 0`` (``None`` when no job has one); given: filled in place, entries no job owns stay as they
+        are.  Whatever the entry refuses -- what ``pw_channels`` refuses of a grid and ``pw_passage`` of atoms,
+        coefficients and a field, a range outside an array, jobs that share outputs --: ``ValueError`` with the
+        library's message.  ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the device work by
+        HIP events) / ``diagnostics`` (a list that receives ``(n_evaluations, n_fills)``, two int32 arrays over the
+        jobs; they are no part of the defined result and differ between device and host) go through the library's
+        measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=PERCOLATION_JOB_DTYPE).reshape(-1)
+        x = np.zeros((0, 3)) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        c = np.zeros((0, 2)) if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
+        f = np.zeros(0) if field is None else np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
+        some = len(jobs) > 0
+        voxels = np.int64(1) * jobs["nx"] * jobs["ny"] * jobs["nz"]
+
+        def made(given, dtype, what, size):
+            if given is None:
+                return np.zeros(max(int(size), 0), dtype=dtype)
+            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+            return given
+
+        levels = made(levels, PERCOLATION_LEVEL_DTYPE, "levels", (jobs["level_first"] + PERC_CRITERIA).max() if some else 0)
+        out = made(out, PERCOLATION_OUT_DTYPE, "out", (jobs["out"] + 1).max() if some else 0)
+        has = jobs["map_first"] >= 0
+        if maps is not None or has.any():
+            maps = made(maps, np.float64, "maps", (jobs["map_first"][has] + voxels[has]).max() if has.any() else 0)
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), f.ctypes.data, len(f),
+                None if maps is None else maps.ctypes.data, 0 if maps is None else len(maps), levels.ctypes.data, len(levels),
+                out.ctypes.data, len(out)]
+        if workspace_bytes is None and kernel_ms is None and diagnostics is None:
+            _stat_call("pw_percolation", *args)
+            return levels, out, maps
+        ms = ctypes.c_float(0.0)
+        n_eval, n_fill = np.zeros(len(jobs), dtype=np.int32), np.zeros(len(jobs), dtype=np.int32)
+        _stat_call("pw_internal_percolation", *args, int(workspace_bytes or 0), ctypes.byref(ms), n_eval.ctypes.data,
+                   n_fill.ctypes.data)
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        if diagnostics is not None:
+            diagnostics.append((n_eval, n_fill))
+        return levels, out, maps
 
     def passage(self, jobs, xyz=None, coef=None, planes=None, field=None, out=None, workspace_bytes=None, kernel_ms=None,
                 fills=None, grids=None):

@@ -75,10 +75,11 @@ def cell_grid(R, spacing: float):
     return tuple(int(v) for v in n), 0.5 * S.sum(axis=1), step
 
 
-def cell_images_many(xyz, radii, cells, probe: float, cull: bool = True, chunk: int = 32):
+def cell_images_many(xyz, radii, cells, probe: float, cull: bool = True, chunk: int = 32, sources: bool = False):
     """:func:`cell_images` for ``T`` frames ``xyz`` ``(T, n, 3)`` in their cells ``cells`` ``(T, 3, 3)``:
     ``(xyz, radii, counts)``, the images of frame after frame and how many each frame has.  The same expression for
-    every frame, evaluated ``chunk`` frames at a time."""
+    every frame, evaluated ``chunk`` frames at a time.  ``sources=True``: a fourth array, for every image the index
+    ``0 .. n - 1`` of the atom it is an image of (what an entry with other per-atom rows than radii repeats them by)."""
     x = np.asarray(xyz, dtype=np.float64)
     r = np.asarray(radii, dtype=np.float64).reshape(-1)
     R = np.asarray(cells, dtype=np.float64)
@@ -89,7 +90,7 @@ def cell_images_many(xyz, radii, cells, probe: float, cull: bool = True, chunk: 
         raise ValueError(f"channel_network: a reach of {float(reach.max()):.6g} (radius + probe) is above the cell's smallest "
                          f"perpendicular width {float(width.min()):.6g}: a thin cell, more than 27 images would matter")
     steps = np.array([-1.0, 0.0, 1.0])
-    atoms, kept, counts = [], [], []
+    atoms, kept, counts, source = [], [], [], []
     for lo in range(0, len(x), chunk):
         hi = min(lo + chunk, len(x))
         frac = np.matmul(x[lo:hi], inv[lo:hi].transpose(0, 2, 1))
@@ -106,10 +107,13 @@ def cell_images_many(xyz, radii, cells, probe: float, cull: bool = True, chunk: 
         cells_t = R[lo:hi].transpose(0, 2, 1)
         atoms.append(np.matmul(frac, cells_t)[t, n] + np.matmul(SHIFTS[None], cells_t)[t, shift])
         kept.append(r[n])
+        source.append(n)
         counts.append(keep.sum(axis=(1, 2)))
     if not atoms:
-        return np.zeros((0, 3)), np.zeros(0), np.zeros(0, dtype=np.int64)
-    return np.ascontiguousarray(np.concatenate(atoms)), np.ascontiguousarray(np.concatenate(kept)), np.concatenate(counts)
+        none = (np.zeros((0, 3)), np.zeros(0), np.zeros(0, dtype=np.int64))
+        return none + (np.zeros(0, dtype=np.int64),) if sources else none
+    made = (np.ascontiguousarray(np.concatenate(atoms)), np.ascontiguousarray(np.concatenate(kept)), np.concatenate(counts))
+    return made + (np.concatenate(source).astype(np.int64),) if sources else made
 
 
 def cell_images(xyz, radii, R, probe: float, cull: bool = True):

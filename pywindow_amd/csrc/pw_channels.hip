@@ -11,7 +11,7 @@
 //             component as p0 | p1; the component's n_voxels and n_cross by integer LDS atomics; then only the fills
 //             that channels_next asks for; the row of the table, the labels, acc and the totals; the component leaves
 //             todo.  Until todo is empty: at most n_open turns.
-//   fill      thread t owns rows t, t + 256, ...; a sweep gives a row the words of its four periodic neighbour rows, of
+//   fill      (chan_fill, pw_channels_dev.hpp, shared with pw_percolate.hip) thread t owns rows t, t + 256, ...; a sweep gives a row the words of its four periodic neighbour rows, of
 //             the other parity where the step crosses a face of phi (channels_gather), and takes the x direction to its
 //             fixed point inside the word (channels_fill_words); neighbours are read while their owners may be storing
 //             them (relaxed atomics: either value is a subset of the fixed point), and the sweeps repeat while
@@ -28,6 +28,7 @@
 #include "../../include/pywindow_amd.h"
 #include "pw_cavity_dev.hpp"
 #include "pw_channels.hpp"
+#include "pw_channels_dev.hpp"
 #include "pw_grid_host.hpp"
 
 using namespace pw;
@@ -85,29 +86,6 @@ __device__ inline void chan_classify(const double* __restrict__ atoms, const dou
         }
         const u64 word = __ballot(open);
         if (lane == 0) s_todo[r] = word;
-    }
-}
-
-// the fill for phi of p0, p1 inside `open`: see the head of the file
-__device__ inline void chan_fill(const u64* s_open, u64* s_p0, u64* s_p1, int nx, int ny, int nz, int phi) {
-    const int rows = ny * nz;
-    const long max_sweeps = 2 * (long)nx * ny * nz + 1;
-    auto load = [&](int q, int row) { return __hip_atomic_load((q ? s_p1 : s_p0) + row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); };
-    for (long sweep = 0; sweep < max_sweeps; ++sweep) {
-        int changed = 0;
-        for (int r = threadIdx.x; r < rows; r += CAV_THREADS) {
-            const u64 o = s_open[r];
-            if (!o) continue;
-            const u64 f0 = s_p0[r], f1 = s_p1[r];                    // (only this thread stores them)
-            u64 from0 = f0, from1 = f1, g0, g1;
-            channels_gather(load, r % ny, r / ny, ny, nz, phi, from0, from1);
-            if (!((from0 | from1) & o)) continue;
-            channels_fill_words(from0, from1, o, nx, (phi & 1) != 0, g0, g1);
-            if (g0 != f0) __hip_atomic_store(s_p0 + r, g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (g1 != f1) __hip_atomic_store(s_p1 + r, g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            changed |= g0 != f0 || g1 != f1;
-        }
-        if (!__syncthreads_or(changed)) break;                       // (the same answer in every thread)
     }
 }
 

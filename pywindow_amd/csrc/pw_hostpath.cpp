@@ -28,6 +28,7 @@
 #include "pw_hop.hpp"
 #include "pw_charges.hpp"
 #include "pw_channels.hpp"
+#include "pw_percolate.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -2003,6 +2004,267 @@ extern "C" int pw_hostpath_channels(const pw_channels_job* jobs, long n_jobs, co
         o.reserved = 0;
         out[(long)J.out] = o;
     });
+    return PW_OK;
+}
+
+// pw_percolation on the host (pw_percolate.hip checks the arguments and sends device == -1 contexts here): the centres
+// and the fill of pw_channels.hpp, the pair terms of pw_affinity.hpp, the keys of pw_passage.hpp, the candidates and the
+// search of pw_percolate.hpp.  Jobs go in order in batches whose maps fit PERC_WORKSPACE_BYTES; within a batch the
+// threads first share out slabs of PERC_HOST_SLAB voxels of the maps of the jobs without a field of their own, then the
+// jobs.  A job is a plain loop: the scan of its map, the search -- an evaluation is the allowed words from the map, the
+// candidates, then component after component from the first candidate as pw_hostpath_channels fills them --, and one
+// evaluation at each distinct level for the rows.  n_evaluations, n_fills (may be null): per job, diagnostic.
+extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jobs, const double* xyz, const double* coef,
+                                       const double* field, double* map, pw_percolation_level* levels, pw_percolation_out* out,
+                                       int* n_evaluations, int* n_fills, int threads) {
+    typedef cavity_word u64;
+    constexpr long PERC_HOST_SLAB = 4096, NO_RANK = 0x7fffffffffffffffl;
+    struct Slab { long job, a, b; };
+    std::vector<double> maps;
+    std::vector<long> map_first((size_t)n_jobs);
+    for (long first = 0; first < n_jobs;) {
+        long last = first, words = 0;
+        std::vector<Slab> slabs;
+        for (; last < n_jobs; ++last) {
+            const pw_percolation_job& J = jobs[last];
+            const long V = (long)J.nx * J.ny * J.nz;
+            if (last > first && J.field_first == -1 && words + V > PERC_WORKSPACE_BYTES / 8) break;
+            map_first[last] = words;
+            if (J.field_first == -1) {                               // (a caller's field is read in place)
+                words += V;
+                for (long a = 0; a < V; a += PERC_HOST_SLAB) slabs.push_back({last, a, std::min(a + PERC_HOST_SLAB, V)});
+            }
+        }
+        maps.resize((size_t)words);
+        cov_share((long)slabs.size(), threads, [&](long s) {
+            const Slab& piece = slabs[s];
+            const pw_percolation_job& J = jobs[piece.job];
+            const double* atoms = xyz + 3 * (long)J.atom_first;
+            const double* ab = coef + 2 * (long)J.coef_first;
+            double* U = maps.data() + map_first[piece.job];
+            for (long rank = piece.a; rank < piece.b; ++rank) {
+                const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx), j = row % J.ny, l = row / J.ny;
+                const double x = channels_x(J.origin[0], i, J.step[0], j, J.step[1], l, J.step[3]),
+                             y = channels_y(J.origin[1], j, J.step[2], l, J.step[4]), z = channels_z(J.origin[2], l, J.step[5]);
+                double u_sum = 0.0;
+                bool blocked = false;
+                for (long a = 0; a < (long)J.n && !blocked; ++a) {
+                    const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
+                    blocked = aff_blocked(r2, J.core2);
+                    if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
+                }
+                U[rank] = blocked ? aff_inf() : u_sum;
+            }
+        });
+        cov_share(last - first, threads, [&](long q) {
+            const long k = first + q;
+            const pw_percolation_job& J = jobs[k];
+            const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
+            const long V = (long)nx * rows;
+            const double* U = J.field_first == -1 ? maps.data() + map_first[k] : field + (long)J.field_first;
+            if (J.map_first >= 0)
+                for (long v = 0; v < V; ++v) map[(long)J.map_first + v] = U[v];
+            pw_percolation_level* R = levels + (long)J.level_first;
+            auto voxel = [&](long rank, int* v) {
+                const long row = rank / nx;
+                v[0] = rank >= 0 ? (int)(rank - row * nx) : -1;
+                v[1] = rank >= 0 ? (int)(row % ny) : -1;
+                v[2] = rank >= 0 ? (int)(row / ny) : -1;
+            };
+            // the scan
+            u64 kmin = PAS_KEY_NONE, kmax = 0;
+            long min_rank = NO_RANK, n_blocked = 0;
+            for (long v = 0; v < V; ++v) {
+                const u64 key = pas_key(U[v]);
+                if (key == PAS_KEY_INF) {
+                    ++n_blocked;
+                    continue;
+                }
+                if (pas_before(key, v, kmin, min_rank)) {
+                    kmin = key;
+                    min_rank = v;
+                }
+                kmax = key > kmax ? key : kmax;
+            }
+            const bool some = min_rank != NO_RANK;
+            std::vector<u64> allowed((size_t)rows), todo((size_t)rows), p0((size_t)rows), p1((size_t)rows);
+            long best[PERC_CRITERIA];
+            int evaluations = 0, fills = 0;
+            const long max_sweeps = 2 * V + 1;
+            auto load = [&](int q2, int row) { return q2 ? p1[row] : p0[row]; };
+            // an evaluation (pw_percolate.hip: perc_evaluate)
+            auto evaluate = [&](u64 level, int asked, bool final, bool& complete, u64& below, u64& above) {
+                ++evaluations;
+                below = 0;
+                above = PAS_KEY_NONE;
+                long n_allowed = 0;
+                for (int r = 0; r < rows; ++r) {
+                    u64 word = 0;
+                    for (int i = 0; i < nx; ++i) {
+                        const u64 key = pas_key(U[(long)r * nx + i]);
+                        if (key <= level) {
+                            word |= 1ull << i;
+                            below = key > below ? key : below;
+                        } else if (key < PAS_KEY_INF) {
+                            above = key < above ? key : above;
+                        }
+                    }
+                    allowed[r] = word;
+                    n_allowed += cavity_popcount(word);
+                }
+                for (int r = 0; r < rows; ++r) {
+                    const int j = r % ny, l = r / ny;
+                    todo[r] = perc_candidates(allowed[r], allowed[l * ny], allowed[j], nx, ny, nz, j, l);
+                }
+                int met = 0;
+                complete = true;
+                for (int seed_row = 0; seed_row < rows;) {               // (a turn strikes a candidate off, or moves on)
+                    if (!todo[seed_row]) {
+                        ++seed_row;
+                        continue;
+                    }
+                    const u64 seed_bit = 1ull << __builtin_ctzll(todo[seed_row]);
+                    int known = 0, wraps = 0, cross = 0, phi = 7;
+                    bool measured = false;
+                    long n_voxels = 0;
+                    for (int fill = 0; fill < 7 && phi; ++fill) {
+                        std::fill(p0.begin(), p0.end(), 0);
+                        std::fill(p1.begin(), p1.end(), 0);
+                        p0[seed_row] = seed_bit;
+                        ++fills;
+                        auto visit = [&](int r) {
+                            if (!allowed[r]) return false;
+                            u64 from0 = p0[r], from1 = p1[r], g0, g1;
+                            channels_gather(load, r % ny, r / ny, ny, nz, phi, from0, from1);
+                            if (!((from0 | from1) & allowed[r])) return false;
+                            channels_fill_words(from0, from1, allowed[r], nx, (phi & 1) != 0, g0, g1);
+                            const bool changed = g0 != p0[r] || g1 != p1[r];
+                            p0[r] = g0;
+                            p1[r] = g1;
+                            return changed;
+                        };
+                        for (long sweep = 0; sweep < max_sweeps; ++sweep) {
+                            bool changed = false;
+                            for (int r = 0; r < rows; ++r) changed = visit(r) || changed;
+                            for (int r = rows - 1; r >= 0; --r) changed = visit(r) || changed;
+                            if (!changed) break;
+                        }
+                        const bool reached = (p1[seed_row] & seed_bit) != 0;
+                        channels_learn(phi, reached, known, wraps);
+                        if (!measured) {
+                            long n_cross[3] = {0, 0, 0};
+                            for (int r = 0; r < rows; ++r) {
+                                const u64 f = p0[r] | p1[r];
+                                if (!f) continue;
+                                const int j = r % ny, l = r / ny;
+                                long c[3];
+                                channels_row_cross(f, p0[l * ny] | p1[l * ny], p0[j] | p1[j], nx, ny, nz, j, l, c);
+                                n_voxels += cavity_popcount(f);
+                                for (int a = 0; a < 3; ++a) n_cross[a] += c[a];
+                            }
+                            for (int a = 0; a < 3; ++a) cross |= (n_cross[a] > 0) << a;
+                            if (cross) channels_learn(cross, reached, known, wraps);
+                            measured = true;
+                        }
+                        phi = channels_next(cross, known, wraps);
+                    }
+                    const int crit = perc_criteria(wraps);
+                    met |= crit;
+                    long comp_first = -1;
+                    for (int r = 0; r < rows; ++r) {
+                        const u64 f = p0[r] | p1[r];
+                        if (!f) continue;
+                        if (comp_first < 0) comp_first = (long)r * nx + __builtin_ctzll(f);
+                        todo[r] &= ~f;
+                    }
+                    if (!final) {
+                        if ((met & asked) == asked) {
+                            complete = false;
+                            break;
+                        }
+                        continue;
+                    }
+                    int lead = 0;
+                    for (int c = 0; c < PERC_CRITERIA; ++c)
+                        if (((crit & asked) >> c) & 1) lead |= (comp_first < best[c]) << c;
+                    if (!lead) continue;
+                    u64 well_key = PAS_KEY_NONE;
+                    long well_rank = NO_RANK, saddle_rank = -1;
+                    for (int r = 0; r < rows; ++r) {
+                        const u64 f = p0[r] | p1[r];
+                        for (int i = 0; f && i < nx; ++i) {
+                            if (!((f >> i) & 1ull)) continue;
+                            const long rank = (long)r * nx + i;
+                            const u64 key = pas_key(U[rank]);
+                            if (pas_before(key, rank, well_key, well_rank)) {
+                                well_key = key;
+                                well_rank = rank;
+                            }
+                            if (key == level && saddle_rank < 0) saddle_rank = rank;
+                        }
+                    }
+                    for (int c = 0; c < PERC_CRITERIA; ++c) {
+                        if (!((lead >> c) & 1)) continue;
+                        best[c] = comp_first;
+                        pw_percolation_level& O = R[c];
+                        O.level = saddle_rank >= 0 ? U[saddle_rank] : aff_inf();
+                        O.well = U[well_rank];
+                        O.first = comp_first;
+                        O.n_voxels = n_voxels;
+                        voxel(saddle_rank, O.saddle);
+                        voxel(well_rank, O.well_voxel);
+                        O.wraps = wraps;
+                        O.rank = channels_rank(wraps);
+                        O.flags = 0;
+                        O.reserved = 0;
+                    }
+                }
+                if (final)
+                    for (int c = 0; c < PERC_CRITERIA; ++c)
+                        if ((asked >> c) & 1) R[c].n_allowed = n_allowed;
+                return met;
+            };
+            bool complete;
+            u64 below, above, lo[PERC_CRITERIA], hi[PERC_CRITERIA];
+            const int met_at_top = some ? evaluate(kmax, 63, false, complete, below, above) : 0;
+            pw_percolation_out& O = out[(long)J.out];
+            O.n_blocked = n_blocked;
+            O.u_min = some ? U[min_rank] : aff_inf();
+            voxel(some ? min_rank : -1, O.u_min_voxel);
+            O.flags = (met_at_top & 1) ? 0 : PERC_NEVER;
+            for (int c = 0; c < PERC_CRITERIA; ++c) {
+                pw_percolation_level none{};
+                none.level = none.well = aff_inf();
+                none.first = -1;
+                for (int a = 0; a < 3; ++a) none.saddle[a] = none.well_voxel[a] = -1;
+                none.flags = PERC_NEVER;
+                R[c] = none;
+                best[c] = NO_RANK;
+            }
+            perc_search_begin(lo, hi, kmin, kmax, met_at_top);
+            for (int step = 0; some && step < PERC_MAX_STEPS; ++step) {
+                u64 mid = 0;
+                int needed = 0;
+                if (!perc_search_next(lo, hi, mid, needed)) break;
+                const int met = evaluate(mid, needed, false, complete, below, above);
+                perc_search_learn(lo, hi, met, complete, below, above);
+            }
+            for (int c = 0; some && c < PERC_CRITERIA; ++c) {
+                int asked = 0;
+                bool seen = false;
+                for (int d = 0; d < PERC_CRITERIA; ++d) {
+                    if (hi[d] != hi[c]) continue;
+                    asked |= 1 << d;
+                    seen = seen || d < c;
+                }
+                if (hi[c] == PAS_KEY_INF || seen) continue;
+                evaluate(hi[c], asked, true, complete, below, above);
+            }
+            if (n_evaluations) n_evaluations[k] = evaluations;
+            if (n_fills) n_fills[k] = fills;
+        });
+        first = last;
+    }
     return PW_OK;
 }
 

@@ -525,6 +525,25 @@ class MolecularSystem:
                                            c_max, mask, labels, device)
         return self.channels
 
+    def calculate_guest_percolation(self, guest="Xe", spacing: float = 0.5, cutoff: float = 12.0, core2: float = 0.25,
+                                    maps: bool = False, device=None):
+        """The energy levels at which the voids of the loaded cell connect for a one-site Lennard-Jones guest
+        (``pywindow_amd.guest_percolation``, ``pw_percolation`` on the GPU, UFF atoms): the minimax barrier of
+        diffusion in at least 1, 2, 3 dimensions and along each cell vector, with the well below it.  Needs ``elements``
+        and a ``lattice`` or ``unit_cell``; the result, a :class:`pywindow_amd.Percolation`, is also kept in
+        ``self.percolation``."""
+        from . import percolation as PC
+        from .rebuild import system_lattice
+
+        if "elements" not in self.system:
+            raise KeyError("elements")
+        lattice, periodic = system_lattice(self.system)
+        if not periodic:
+            raise ValueError("calculate_guest_percolation: the system has no unit cell (a 'lattice' or a 'unit_cell' is needed)")
+        self.percolation = PC.guest_percolation(self.system["coordinates"], self.system["elements"], lattice, guest, spacing,
+                                                cutoff, core2, maps, device)
+        return self.percolation
+
     def swap_atom_keys(self, swap_dict: dict, dict_key: str = "atom_ids") -> None:
         """Reference molecular.py:710-749."""
         if "atom_ids" not in self.system:

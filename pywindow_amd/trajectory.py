@@ -586,6 +586,28 @@ class DLPOLY:
         return CN.channel_network_batch(coords, self.elements(swap_atoms, forcefield), lattice, probe, spacing, c_max, mask,
                                         labels, device, frames=sel)
 
+    def percolation(self, guest="Xe", spacing: float = 0.5, cutoff: float = 12.0, frames=None, device=None, swap_atoms=None,
+                    forcefield=None):
+        """The energy levels at which the voids of the periodic cell connect for a one-site Lennard-Jones guest in every
+        selected frame (``frames``: any selection of the trajectory's frames, ``None``: all of them), ALL frames in ONE
+        ``pw_percolation`` call on the GPU (``pywindow_amd.guest_percolation_batch``, UFF atoms, ``core2 = 0.25``) -- a
+        :class:`pywindow_amd.Percolation` whose fields are arrays over the frames and whose ``frames`` are the
+        trajectory's frame numbers.  The frames are read with their lattices as they are in the file, as
+        :meth:`channels` reads them.  ``percolation().series("activation", dim=3)`` goes into
+        ``pywindow_amd.time_correlation``, ``lomb_scargle``, ``gaussian_kde_1d``, ``gate_statistics`` and
+        ``transition_counts``.  Periodic trajectories only."""
+        from . import percolation as PC
+
+        if not self.periodic:
+            raise ValueError("percolation: the trajectory is not periodic (imcon 0): there is no cell whose voids could "
+                             "connect; passage() gives the barrier at the windows of a single cage")
+        sel = self._select("all" if frames is None else frames)
+        if not sel:
+            raise ValueError("percolation: no frames selected")
+        coords, lattice = self._read_selected(sel, True)
+        return PC.guest_percolation_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, spacing, cutoff,
+                                          core2=0.25, device=device, frames=sel)
+
     def passage(self, guest="Xe", spacing: float = 0.5, frames=None, device=None, close="windows", swap_atoms=None,
                 forcefield=None):
         """The barrier a one-site Lennard-Jones guest crosses at every window in every frame analysed so far
