@@ -1369,6 +1369,86 @@ typedef struct pw_percolation_out {
 int pw_percolation(pw_context *ctx, const pw_percolation_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
                    const double *coef, int64_t n_coef, const double *field, int64_t n_field, double *map, int64_t n_map,
                    pw_percolation_level *levels, int64_t n_levels, pw_percolation_out *out, int64_t n_out);
+/* ---- crystal diffusion: the energy basins of a cell, the dividing surfaces between them and their Boltzmann sums -----
+ * pw_percolation gives the level at which the landscape connects; a rate needs how roomy the wells and how wide the
+ * saddles are.  This entry cuts the landscape of one guest in one periodic cell into the basins of steepest descent on
+ * the grid, with the integer cell offset of every voxel to its basin's root, and sums Boltzmann weights over every
+ * basin and over every dividing surface between two basins (or a basin and its own periodic image); the hop network
+ * and the diffusion tensor follow from the rows by plain linear algebra (pywindow_amd/diffusion.py).  The reference has
+ * no counterpart.  The text of record, with the proofs, is pywindow_amd/csrc/pw_basins.hpp; in short, job k has
+ *     pw_percolation's grid and field (atoms or field_first, map_first), n_betas = 1 .. 8 inverse temperatures
+ *     betas[0 .. n_betas), each finite and > 0, and an energy cap (finite or +inf).
+ * A voxel is allowed when U is not +inf and U <= cap.  Its parent is the first in (key(U), rank, position) of itself and
+ * its allowed neighbours in the order -a, +a, -b, +b, -c, +c; roots are their own parents and are numbered 0 .. B-1 by
+ * rank; o(v) is the sum of the face crossings along the parents from v to its root.  Row `out`: n_basins = B and
+ * n_edges = E (the true counts), what was written of each, n_blocked (voxels at +inf), n_allowed, u_min with its voxel
+ * over the allowed voxels (+inf and -1 without one) and flags.  basins[basin_first .. + min(B, b_cap)): root, n_voxels,
+ * u_min (the root's bits), z[b] = sum of w = pw_exp(-(beta_b * U)) (the exponent clamped at 700 with PW_BAS_CLAMPED)
+ * and e[b] = sum of w * U over the basin's voxels.  A face between allowed v and v' = v + e_k whose voxels differ in
+ * basin, or in o beyond the face's own crossing, belongs to the edge (a, b, d) in canonical form (a <= b; a == b: the
+ * first non-zero component of d positive); edges[edge_first .. + E), ascending in (a, b, d): n_faces, saddle (the
+ * smallest face term max(U_v, U_v') by key) with saddle_voxel (v's rank) and saddle_k, and s[b][k] = the sum of
+ * w(term) over the faces across e_k.  Every sum is taken in a written association (row chunks of 64 slots in
+ * pw_affinity's tree, then rows in order), everything else is a comparison or an integer count: the same bytes on every
+ * device, launch geometry, workspace budget and run and on a device == -1 context.  PW_BAS_OVERFLOW (B > b_cap or
+ * E > e_cap): the first b_cap basins and no edge are written.  PW_BAS_RANGE (a component of an o(v) or a d beyond
+ * +-PW_BAS_MAX_OFFSET): no edge is written, n_edges is 0, the o of the labels are 0.  labels[label_first .. + nx*ny*nz)
+ * when label_first >= 0: basin (-1: not allowed) and o per voxel.  Rows beyond what was written are not touched.
+ * Refusals as pw_percolation's, and b_cap or e_cap < 0, n_betas outside 1 .. 8, a beta that is not finite or not
+ * positive, a cap that is not a number or -inf: PW_E_BAD_ARG, nothing launched or written. */
+#define PW_BAS_MAX_BETAS 8
+#define PW_BAS_MAX_OFFSET 255
+#define PW_BAS_OVERFLOW 1        /* more basins than b_cap or more edges than e_cap */
+#define PW_BAS_CLAMPED 2         /* an exponent was clamped at 700 */
+#define PW_BAS_RANGE 4           /* a cell offset left +-PW_BAS_MAX_OFFSET */
+typedef struct pw_basins_job {
+    int64_t atom_first, n;      /* atoms = xyz[atom_first .. +n), n >= 0 (read when field_first == -1) */
+    int64_t coef_first;         /* their rows (A, B) = coef[coef_first .. +n) */
+    int64_t field_first;        /* -1: Lennard-Jones from the atoms; >= 0: field[field_first .. + nx*ny*nz) */
+    int64_t map_first;          /* map[map_first .. + nx*ny*nz) is written, or -1: no map */
+    int64_t basin_first;        /* basins[basin_first .. + b_cap) may be written */
+    int64_t edge_first;         /* edges[edge_first .. + e_cap) may be written */
+    int64_t label_first;        /* labels[label_first .. + nx*ny*nz) is written, or -1: no labels */
+    int64_t out;                /* the job's row of the result */
+    int64_t b_cap, e_cap;       /* >= 0 */
+    double  origin[3];          /* the centre of voxel (0, 0, 0) */
+    double  step[6];            /* ax, bx, by, cx, cy, cz */
+    double  core2;              /* >= 1e-6 */
+    double  cutoff2;            /* 0.0: none; otherwise > core2 */
+    double  cap;                /* finite or +inf */
+    double  betas[PW_BAS_MAX_BETAS];
+    int32_t nx, ny, nz;         /* 1 .. PW_CAVITY_MAX_G */
+    int32_t n_betas;            /* 1 .. PW_BAS_MAX_BETAS */
+} pw_basins_job;
+typedef struct pw_basins_basin {
+    int64_t root, n_voxels;
+    double  u_min;              /* the bits of U at the root */
+    double  z[PW_BAS_MAX_BETAS], e[PW_BAS_MAX_BETAS];
+} pw_basins_basin;
+typedef struct pw_basins_edge {
+    int32_t a, b, d[3];
+    int32_t saddle_k;
+    int64_t n_faces;
+    int64_t saddle_voxel;       /* the rank of v of the saddle's face (v, saddle_k) */
+    double  saddle;
+    double  s[PW_BAS_MAX_BETAS][3];
+} pw_basins_edge;
+typedef struct pw_basins_label {
+    int32_t basin;              /* -1: not allowed */
+    int32_t o[3];
+} pw_basins_label;
+typedef struct pw_basins_out {
+    int64_t n_basins, n_edges;  /* B and E */
+    int64_t n_basins_written, n_edges_written;
+    int64_t n_blocked, n_allowed;
+    double  u_min;
+    int32_t u_min_voxel[3];     /* (i, j, l), or -1 */
+    int32_t flags;              /* PW_BAS_* */
+} pw_basins_out;
+int pw_basins(pw_context *ctx, const pw_basins_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+              const double *coef, int64_t n_coef, const double *field, int64_t n_field, double *map, int64_t n_map,
+              pw_basins_basin *basins, int64_t n_basins, pw_basins_edge *edges, int64_t n_edges, pw_basins_label *labels,
+              int64_t n_labels, pw_basins_out *out, int64_t n_out);
 
 /* Native DL_POLY HISTORY ingest (trajectory.py:647-766): see pw_history_* in
  * pywindow_amd/csrc/pw_history.cpp */

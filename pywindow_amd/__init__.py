@@ -48,6 +48,7 @@ from .channels import Channels, channel_network, channel_network_batch  # noqa: 
 from .passage import Passage, guest_passage, guest_passage_batch, passage_field  # noqa: E402
 from .percolation import Percolation, guest_percolation, guest_percolation_batch, percolation_field  # noqa: E402
 from .hopping import Hopping, guest_hopping, guest_hopping_batch, window_frame  # noqa: E402
+from .diffusion import Diffusion, diffusion_field, guest_diffusion, guest_diffusion_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -138,6 +139,10 @@ __all__ = [
     "guest_percolation",
     "guest_percolation_batch",
     "percolation_field",
+    "Diffusion",
+    "guest_diffusion",
+    "guest_diffusion_batch",
+    "diffusion_field",
     "Hopping",
     "guest_hopping",
     "guest_hopping_batch",

@@ -407,6 +407,35 @@ assert PERCOLATION_JOB_DTYPE.itemsize == 160 and PERCOLATION_LEVEL_DTYPE.itemsiz
 PERC_CRITERIA = 6
 PERC_NEVER = 1
 
+#: numpy mirrors of ``pw_basins_job``, ``pw_basins_basin``, ``pw_basins_edge``, ``pw_basins_label`` and ``pw_basins_out``
+BASINS_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("field_first", np.int64), ("map_first", np.int64),
+     ("basin_first", np.int64), ("edge_first", np.int64), ("label_first", np.int64), ("out", np.int64), ("b_cap", np.int64),
+     ("e_cap", np.int64), ("origin", np.float64, (3,)), ("step", np.float64, (6,)), ("core2", np.float64),
+     ("cutoff2", np.float64), ("cap", np.float64), ("betas", np.float64, (8,)), ("nx", np.int32), ("ny", np.int32),
+     ("nz", np.int32), ("n_betas", np.int32)]
+)
+BASINS_BASIN_DTYPE = np.dtype(
+    [("root", np.int64), ("n_voxels", np.int64), ("u_min", np.float64), ("z", np.float64, (8,)), ("e", np.float64, (8,))]
+)
+BASINS_EDGE_DTYPE = np.dtype(
+    [("a", np.int32), ("b", np.int32), ("d", np.int32, (3,)), ("saddle_k", np.int32), ("n_faces", np.int64),
+     ("saddle_voxel", np.int64), ("saddle", np.float64), ("s", np.float64, (8, 3))]
+)
+BASINS_LABEL_DTYPE = np.dtype([("basin", np.int32), ("o", np.int32, (3,))])
+BASINS_OUT_DTYPE = np.dtype(
+    [("n_basins", np.int64), ("n_edges", np.int64), ("n_basins_written", np.int64), ("n_edges_written", np.int64),
+     ("n_blocked", np.int64), ("n_allowed", np.int64), ("u_min", np.float64), ("u_min_voxel", np.int32, (3,)), ("flags", np.int32)]
+)
+assert (BASINS_JOB_DTYPE.itemsize == 264 and BASINS_BASIN_DTYPE.itemsize == 152 and BASINS_EDGE_DTYPE.itemsize == 240
+        and BASINS_LABEL_DTYPE.itemsize == 16 and BASINS_OUT_DTYPE.itemsize == 72)
+#: ``PW_BAS_MAX_BETAS``, ``PW_BAS_MAX_OFFSET``, ``PW_BAS_OVERFLOW``, ``PW_BAS_CLAMPED``, ``PW_BAS_RANGE``
+BAS_MAX_BETAS = 8
+BAS_MAX_OFFSET = 255
+BAS_OVERFLOW = 1
+BAS_CLAMPED = 2
+BAS_RANGE = 4
+
 #: numpy mirror of ``pw_passage_job``
 PASSAGE_JOB_DTYPE = np.dtype(
     [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("plane_first", np.int64), ("m", np.int64),
@@ -540,6 +569,7 @@ EXPORTED_SYMBOLS = [
     "pw_charges",
     "pw_channels",
     "pw_percolation",
+    "pw_basins",
     "pw_history_open",
     "pw_history_frames",
     "pw_history_atoms",
@@ -693,6 +723,8 @@ def load():
     L.pw_internal_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6 + [vp, vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_percolation.argtypes = [vp, vp, i64] + [vp, i64] * 6
     L.pw_internal_percolation.argtypes = [vp, vp, i64] + [vp, i64] * 6 + [i64, ctypes.POINTER(ctypes.c_float), vp, vp]
+    L.pw_basins.argtypes = [vp, vp, i64] + [vp, i64] * 8
+    L.pw_internal_basins.argtypes = [vp, vp, i64] + [vp, i64] * 8 + [i64, ctypes.POINTER(ctypes.c_float), vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -1558,6 +1590,62 @@ class Context:
         if diagnostics is not None:
             diagnostics.append((n_eval, n_fill))
         return levels, out, maps
+
+    def basins(self, jobs, xyz=None, coef=None, field=None, out=None, basins=None, edges=None, maps=None, labels=None,
+               workspace_bytes=None, kernel_ms=None, diagnostics=None):
+        """``pw_basins``: for every job of a batch (one periodic cell, one guest, up to eight inverse temperatures and an
+        energy cap) the basins of steepest descent of the guest's landscape, the dividing surfaces between them with
+        their integer cell offsets, and the Boltzmann sums over both (``BASINS_JOB_DTYPE`` records indexing the rows of
+        ``xyz`` (rows of three) and of ``coef`` (rows ``(A, B)``), the entries of ``field``, of the maps and of the
+        labels and the rows of the results): ``(out, basins, edges, maps, labels)`` -- ``out`` a ``BASINS_OUT_DTYPE``
+        array, ``basins`` a ``BASINS_BASIN_DTYPE`` array with ``n_basins_written`` rows a job from its ``basin_first``,
+        ``edges`` a ``BASINS_EDGE_DTYPE`` array with ``n_edges_written`` rows a job from its ``edge_first``, ``maps``
+        the float64 fields of the jobs with ``map_first >= 0`` and ``labels`` the ``BASINS_LABEL_DTYPE`` entries of the
+        jobs with ``label_first >= 0`` (``None`` when no job has one); given: filled in place, entries no job writes
+        stay as they are.  Whatever the entry refuses -- what ``pw_percolation`` refuses, a negative capacity,
+        ``n_betas`` outside 1 .. 8, a beta that is not positive, a cap that is no number --: ``ValueError`` with the
+        library's message.  ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the device work by HIP
+        events) / ``diagnostics`` (a list that receives ``(n_rounds, n_faces)``, two int32 arrays over the jobs; they
+        are no part of the defined result) go through the library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=BASINS_JOB_DTYPE).reshape(-1)
+        x = np.zeros((0, 3)) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        c = np.zeros((0, 2)) if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
+        f = np.zeros(0) if field is None else np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
+        some = len(jobs) > 0
+        voxels = np.int64(1) * jobs["nx"] * jobs["ny"] * jobs["nz"]
+
+        def made(given, dtype, what, size):
+            if given is None:
+                return np.zeros(max(int(size), 0), dtype=dtype)
+            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+            return given
+
+        out = made(out, BASINS_OUT_DTYPE, "out", (jobs["out"] + 1).max() if some else 0)
+        basins = made(basins, BASINS_BASIN_DTYPE, "basins", (jobs["basin_first"] + jobs["b_cap"]).max() if some else 0)
+        edges = made(edges, BASINS_EDGE_DTYPE, "edges", (jobs["edge_first"] + jobs["e_cap"]).max() if some else 0)
+        has = jobs["map_first"] >= 0
+        if maps is not None or has.any():
+            maps = made(maps, np.float64, "maps", (jobs["map_first"][has] + voxels[has]).max() if has.any() else 0)
+        lab = jobs["label_first"] >= 0
+        if labels is not None or lab.any():
+            labels = made(labels, BASINS_LABEL_DTYPE, "labels", (jobs["label_first"][lab] + voxels[lab]).max() if lab.any() else 0)
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), f.ctypes.data, len(f),
+                None if maps is None else maps.ctypes.data, 0 if maps is None else len(maps), basins.ctypes.data, len(basins),
+                edges.ctypes.data, len(edges), None if labels is None else labels.ctypes.data, 0 if labels is None else len(labels),
+                out.ctypes.data, len(out)]
+        if workspace_bytes is None and kernel_ms is None and diagnostics is None:
+            _stat_call("pw_basins", *args)
+            return out, basins, edges, maps, labels
+        ms = ctypes.c_float(0.0)
+        n_rounds, n_faces = np.zeros(len(jobs), dtype=np.int32), np.zeros(len(jobs), dtype=np.int32)
+        _stat_call("pw_internal_basins", *args, int(workspace_bytes or 0), ctypes.byref(ms), n_rounds.ctypes.data,
+                   n_faces.ctypes.data)
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        if diagnostics is not None:
+            diagnostics.append((n_rounds, n_faces))
+        return out, basins, edges, maps, labels
 
     def passage(self, jobs, xyz=None, coef=None, planes=None, field=None, out=None, workspace_bytes=None, kernel_ms=None,
                 fills=None, grids=None):

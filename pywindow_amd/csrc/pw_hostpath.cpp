@@ -29,6 +29,7 @@
 #include "pw_charges.hpp"
 #include "pw_channels.hpp"
 #include "pw_percolate.hpp"
+#include "pw_basins.hpp"
 
 #include <stdlib.h>
 #include <string.h>
@@ -2007,6 +2008,23 @@ extern "C" int pw_hostpath_channels(const pw_channels_job* jobs, long n_jobs, co
     return PW_OK;
 }
 
+// the Lennard-Jones energy of the voxel `rank` of the grid of a periodic cell (pw_percolation_job, pw_basins_job):
+// pw_field_cell_dev.hpp's terms in its order; the atoms after one that blocks the voxel add nothing to +inf
+template <class Job>
+inline double cell_field_value(const Job& J, const double* atoms, const double* ab, long rank) {
+    const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx), j = row % J.ny, l = row / J.ny;
+    const double x = channels_x(J.origin[0], i, J.step[0], j, J.step[1], l, J.step[3]),
+                 y = channels_y(J.origin[1], j, J.step[2], l, J.step[4]), z = channels_z(J.origin[2], l, J.step[5]);
+    double u_sum = 0.0;
+    bool blocked = false;
+    for (long a = 0; a < (long)J.n && !blocked; ++a) {
+        const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
+        blocked = aff_blocked(r2, J.core2);
+        if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
+    }
+    return blocked ? aff_inf() : u_sum;
+}
+
 // pw_percolation on the host (pw_percolate.hip checks the arguments and sends device == -1 contexts here): the centres
 // and the fill of pw_channels.hpp, the pair terms of pw_affinity.hpp, the keys of pw_passage.hpp, the candidates and the
 // search of pw_percolate.hpp.  Jobs go in order in batches whose maps fit PERC_WORKSPACE_BYTES; within a batch the
@@ -2043,17 +2061,7 @@ extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jo
             const double* ab = coef + 2 * (long)J.coef_first;
             double* U = maps.data() + map_first[piece.job];
             for (long rank = piece.a; rank < piece.b; ++rank) {
-                const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx), j = row % J.ny, l = row / J.ny;
-                const double x = channels_x(J.origin[0], i, J.step[0], j, J.step[1], l, J.step[3]),
-                             y = channels_y(J.origin[1], j, J.step[2], l, J.step[4]), z = channels_z(J.origin[2], l, J.step[5]);
-                double u_sum = 0.0;
-                bool blocked = false;
-                for (long a = 0; a < (long)J.n && !blocked; ++a) {
-                    const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
-                    blocked = aff_blocked(r2, J.core2);
-                    if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
-                }
-                U[rank] = blocked ? aff_inf() : u_sum;
+                U[rank] = cell_field_value(J, atoms, ab, rank);
             }
         });
         cov_share(last - first, threads, [&](long q) {
@@ -2265,6 +2273,216 @@ extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jo
         });
         first = last;
     }
+    return PW_OK;
+}
+
+// pw_basins on the host (pw_basins.hip checks the arguments and sends device == -1 contexts here): the definition of
+// pw_basins.hpp as plain loops, a job a piece of work.  The parents by bas_parent; the roots numbered in rank order; a
+// voxel's basin and offset by walking its chain down to a voxel that has them already; the faces by their packed keys,
+// sorted; every sum by aff_tree over the 64 slots of a row, the rows in order.  n_rounds, n_faces (may be null): per
+// job, diagnostic.
+extern "C" int pw_hostpath_basins(const pw_basins_job* jobs, long n_jobs, const double* xyz, const double* coef, const double* field,
+                                  double* map, pw_basins_basin* basins, pw_basins_edge* edges, pw_basins_label* labels,
+                                  pw_basins_out* out, int* n_rounds, int* n_faces, int threads) {
+    typedef cavity_word u64;
+    cov_share(n_jobs, threads, [&](long job) {
+        const pw_basins_job& J = jobs[job];
+        const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz, L = J.n_betas;
+        const long V = (long)nx * rows;
+        std::vector<double> own;
+        const double* U = field + (long)J.field_first;
+        if (J.field_first == -1) {
+            own.resize((size_t)V);
+            for (long v = 0; v < V; ++v) own[v] = cell_field_value(J, xyz + 3 * (long)J.atom_first, coef + 2 * (long)J.coef_first, v);
+            U = own.data();
+        }
+        if (J.map_first >= 0)
+            for (long v = 0; v < V; ++v) map[(long)J.map_first + v] = U[v];
+        const u64 cap_key = pas_key(J.cap);
+        pw_basins_out O{};
+        // the scan and the parents
+        u64 kmin = PAS_KEY_NONE;
+        long min_rank = -1;
+        std::vector<long> parent((size_t)V, -1);
+        std::vector<int> step((size_t)(3 * V), 0), o((size_t)(3 * V), 0), id((size_t)V, -1);
+        for (long v = 0; v < V; ++v) {
+            const u64 key = pas_key(U[v]);
+            O.n_blocked += key == PAS_KEY_INF;
+            if (!bas_allowed(U[v], cap_key)) continue;
+            ++O.n_allowed;
+            if (min_rank < 0 || pas_before(key, v, kmin, min_rank)) {
+                kmin = key;
+                min_rank = v;
+            }
+            const long row = v / nx;
+            parent[v] = bas_parent((int)(v - row * nx), (int)(row % ny), (int)(row / ny), v, nx, ny, nz, cap_key,
+                                   [&](long r) { return U[r]; }, &step[3 * v]);
+        }
+        long B = 0;
+        for (long v = 0; v < V; ++v)
+            if (parent[v] == v) id[v] = (int)B++;
+        bool range = false;
+        std::vector<long> chain;
+        for (long v = 0; v < V; ++v) {
+            if (parent[v] < 0 || id[v] >= 0) continue;
+            chain.clear();
+            long u = v;
+            for (; id[u] < 0; u = parent[u]) chain.push_back(u);         // (fewer than V steps: proof (1))
+            for (long q = (long)chain.size() - 1; q >= 0; --q) {
+                const long c = chain[q], p = parent[c];
+                id[c] = id[p];
+                for (int a = 0; a < 3; ++a) {
+                    o[3 * c + a] = step[3 * c + a] + o[3 * p + a];
+                    range = range || o[3 * c + a] > BAS_MAX_OFFSET || o[3 * c + a] < -BAS_MAX_OFFSET;
+                }
+            }
+        }
+        // the faces
+        struct Face { u64 key; long vk; double term; };
+        std::vector<Face> faces;
+        std::vector<u64> keys;
+        for (long v = 0; v < V && !range; ++v) {
+            if (id[v] < 0) continue;
+            const long row = v / nx;
+            const int i = (int)(v - row * nx), j = (int)(row % ny), l = (int)(row / ny);
+            for (int k = 0; k < 3; ++k) {
+                long r = v;
+                int c[3];
+                if (!bas_step(2 * k + 1, i, j, l, nx, ny, nz, r, c)) {
+                    r = v;
+                    c[k] = 1;
+                }
+                if (id[r] < 0) continue;
+                int a = id[v], b = id[r], d[3];
+                for (int q = 0; q < 3; ++q) d[q] = c[q] + o[3 * r + q] - o[3 * v + q];
+                if (a == b && !d[0] && !d[1] && !d[2]) continue;
+                bas_canonical(a, b, d);
+                if (!bas_in_range(d)) {
+                    range = true;
+                    continue;
+                }
+                faces.push_back({bas_edge_key(a, b, d), 4 * v + k, bas_term(U[v], U[r])});
+                keys.push_back(faces.back().key);
+            }
+        }
+        const long n_boundary = (long)faces.size();
+        if (range) {
+            faces.clear();
+            keys.clear();
+        }
+        std::sort(keys.begin(), keys.end());
+        keys.erase(std::unique(keys.begin(), keys.end()), keys.end());
+        const long E = (long)keys.size();
+        const bool overflow = B > (long)J.b_cap || E > (long)J.e_cap;
+        const long b_written = std::min(B, (long)J.b_cap), e_written = overflow ? 0 : E;
+        // the basins' rows and sums
+        pw_basins_basin* R = basins + (long)J.basin_first;
+        for (long v = 0; v < V; ++v) {
+            if (id[v] < 0 || id[v] >= b_written) continue;
+            pw_basins_basin& Q = R[id[v]];
+            if (parent[v] == v) {
+                Q.root = v;
+                Q.n_voxels = 0;
+                Q.u_min = U[v];
+                for (int b = 0; b < BAS_MAX_BETAS; ++b) Q.z[b] = Q.e[b] = 0.0;
+            }
+        }
+        for (long v = 0; v < V; ++v)
+            if (id[v] >= 0 && id[v] < b_written) ++R[id[v]].n_voxels;
+        bool clamped = false;
+        double wt[AFF_CHUNK], slot[AFF_CHUNK];
+        std::vector<int> seen;
+        for (int r = 0; r < rows; ++r) {
+            const long v0 = (long)r * nx;
+            seen.clear();
+            for (int t = 0; t < nx; ++t) {
+                const int a = id[v0 + t];
+                if (a >= 0 && std::find(seen.begin(), seen.end(), a) == seen.end()) seen.push_back(a);
+            }
+            if (seen.empty()) continue;
+            for (int b = 0; b < L; ++b) {
+                for (int t = 0; t < nx; ++t)
+                    wt[t] = id[v0 + t] >= 0 ? aff_weight(J.betas[b], U[v0 + t], POW_EXP_TAB, clamped) : 0.0;
+                for (int a : seen) {
+                    if (a >= b_written) continue;
+                    for (int kind = 0; kind < 2; ++kind) {
+                        for (int t = 0; t < AFF_CHUNK; ++t)
+                            slot[t] = t < nx && id[v0 + t] == a ? (kind ? wt[t] * U[v0 + t] : wt[t]) : 0.0;
+                        double& total = kind ? R[a].e[b] : R[a].z[b];
+                        total = total + aff_tree(slot);
+                    }
+                }
+            }
+        }
+        // the edges' rows and sums
+        if (e_written) {
+            pw_basins_edge* G = edges + (long)J.edge_first;
+            std::vector<u64> saddle_key((size_t)E, PAS_KEY_NONE);
+            std::vector<int> face_edge((size_t)(3 * V), -1);
+            for (long e = 0; e < E; ++e) {
+                pw_basins_edge& Q = G[e];
+                bas_edge_unkey(keys[e], Q.a, Q.b, Q.d);
+                Q.saddle_k = 0;
+                Q.n_faces = 0;
+                Q.saddle_voxel = -1;
+                Q.saddle = 0.0;
+                for (int b = 0; b < BAS_MAX_BETAS; ++b) Q.s[b][0] = Q.s[b][1] = Q.s[b][2] = 0.0;
+            }
+            for (const Face& F : faces) {                                // (ascending in (v, k): the first of a tie stays)
+                const long e = std::lower_bound(keys.begin(), keys.end(), F.key) - keys.begin();
+                pw_basins_edge& Q = G[e];
+                ++Q.n_faces;
+                face_edge[(F.vk & 3) * V + (F.vk >> 2)] = (int)e;
+                if (pas_key(F.term) < saddle_key[e]) {
+                    saddle_key[e] = pas_key(F.term);
+                    Q.saddle = F.term;
+                    Q.saddle_voxel = F.vk >> 2;
+                    Q.saddle_k = (int)(F.vk & 3);
+                }
+            }
+            bool unused = false;
+            for (int b = 0; b < L; ++b)
+                for (int k = 0; k < 3; ++k)
+                    for (int r = 0; r < rows; ++r) {
+                        const long v0 = (long)r * nx;
+                        seen.clear();
+                        for (int t = 0; t < nx; ++t) {
+                            const int e = face_edge[k * V + v0 + t];
+                            wt[t] = 0.0;
+                            if (e < 0) continue;
+                            if (std::find(seen.begin(), seen.end(), e) == seen.end()) seen.push_back(e);
+                            long rr = v0 + t;
+                            int c[3];
+                            const long row = rr / nx;
+                            if (!bas_step(2 * k + 1, t, (int)(row % ny), (int)(row / ny), nx, ny, nz, rr, c)) rr = v0 + t;
+                            wt[t] = aff_weight(J.betas[b], bas_term(U[v0 + t], U[rr]), POW_EXP_TAB, unused);
+                        }
+                        for (int e : seen) {
+                            for (int t = 0; t < AFF_CHUNK; ++t) slot[t] = t < nx && face_edge[k * V + v0 + t] == e ? wt[t] : 0.0;
+                            G[e].s[b][k] = G[e].s[b][k] + aff_tree(slot);
+                        }
+                    }
+        }
+        if (J.label_first >= 0)
+            for (long v = 0; v < V; ++v) {
+                pw_basins_label& Q = labels[(long)J.label_first + v];
+                Q.basin = id[v];
+                for (int a = 0; a < 3; ++a) Q.o[a] = id[v] < 0 || range ? 0 : o[3 * v + a];
+            }
+        O.n_basins = B;
+        O.n_edges = E;
+        O.n_basins_written = b_written;
+        O.n_edges_written = e_written;
+        O.u_min = min_rank >= 0 ? U[min_rank] : aff_inf();
+        const long row = min_rank >= 0 ? min_rank / nx : 0;
+        O.u_min_voxel[0] = min_rank >= 0 ? (int)(min_rank - row * nx) : -1;
+        O.u_min_voxel[1] = min_rank >= 0 ? (int)(row % ny) : -1;
+        O.u_min_voxel[2] = min_rank >= 0 ? (int)(row / ny) : -1;
+        O.flags = (overflow ? BAS_OVERFLOW : 0) | (clamped ? BAS_CLAMPED : 0) | (range ? BAS_RANGE : 0);
+        out[(long)J.out] = O;
+        if (n_rounds) n_rounds[job] = 0;
+        if (n_faces) n_faces[job] = (int)n_boundary;
+    });
     return PW_OK;
 }
 

@@ -544,6 +544,25 @@ class MolecularSystem:
                                                 cutoff, core2, maps, device)
         return self.percolation
 
+    def calculate_guest_diffusion(self, guest="Xe", temperatures=298.0, spacing: float = 0.5, cutoff: float = 12.0,
+                                  core2: float = 0.25, cap: float = 100.0, merge=None, mass=None, maps: bool = False,
+                                  labels: bool = False, device=None):
+        """The self-diffusion tensor of a one-site Lennard-Jones guest through the loaded cell
+        (``pywindow_amd.guest_diffusion``, ``pw_basins`` on the GPU, UFF atoms): the hop network between the energy basins
+        of the guest's landscape and its tensor at every temperature.  Needs ``elements`` and a ``lattice`` or
+        ``unit_cell``; the result, a :class:`pywindow_amd.Diffusion`, is also kept in ``self.diffusion``."""
+        from . import diffusion as DF
+        from .rebuild import system_lattice
+
+        if "elements" not in self.system:
+            raise KeyError("elements")
+        lattice, periodic = system_lattice(self.system)
+        if not periodic:
+            raise ValueError("calculate_guest_diffusion: the system has no unit cell (a 'lattice' or a 'unit_cell' is needed)")
+        self.diffusion = DF.guest_diffusion(self.system["coordinates"], self.system["elements"], lattice, guest, temperatures,
+                                            spacing, cutoff, core2, cap, merge, mass, maps, labels, device)
+        return self.diffusion
+
     def swap_atom_keys(self, swap_dict: dict, dict_key: str = "atom_ids") -> None:
         """Reference molecular.py:710-749."""
         if "atom_ids" not in self.system:

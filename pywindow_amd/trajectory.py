@@ -608,6 +608,27 @@ class DLPOLY:
         return PC.guest_percolation_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, spacing, cutoff,
                                           core2=0.25, device=device, frames=sel)
 
+    def diffusion(self, guest="Xe", temperatures=298.0, frames=None, spacing: float = 0.5, cutoff: float = 12.0,
+                  cap: float = 100.0, merge=None, mass=None, device=None, swap_atoms=None, forcefield=None):
+        """The self-diffusion tensor of a one-site Lennard-Jones guest through the periodic cell of every selected frame
+        (``frames``: any selection of the trajectory's frames, ``None``: all of them), ALL frames in ONE ``pw_basins``
+        call on the GPU (``pywindow_amd.guest_diffusion_batch``, UFF atoms, ``core2 = 0.25``) -- a
+        :class:`pywindow_amd.Diffusion` whose fields are arrays over the frames and whose ``frames`` are the trajectory's
+        frame numbers.  ``diffusion().series("coefficient")`` goes into ``pywindow_amd.time_correlation``,
+        ``lomb_scargle``, ``gaussian_kde_1d``, ``gate_statistics`` and ``transition_counts``.  Periodic trajectories
+        only."""
+        from . import diffusion as DF
+
+        if not self.periodic:
+            raise ValueError("diffusion: the trajectory is not periodic (imcon 0): there is no crystal to diffuse through; "
+                             "hopping() gives the rate out of the windows of a single cage")
+        sel = self._select("all" if frames is None else frames)
+        if not sel:
+            raise ValueError("diffusion: no frames selected")
+        coords, lattice = self._read_selected(sel, True)
+        return DF.guest_diffusion_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, temperatures, spacing,
+                                        cutoff, 0.25, cap, merge, mass, device=device, frames=sel)
+
     def passage(self, guest="Xe", spacing: float = 0.5, frames=None, device=None, close="windows", swap_atoms=None,
                 forcefield=None):
         """The barrier a one-site Lennard-Jones guest crosses at every window in every frame analysed so far
