@@ -1189,6 +1189,51 @@ int pw_rigid_affinity(pw_context *ctx, const pw_rigid_job *jobs, int64_t n_jobs,
                       int64_t n_dirs, const uint64_t *words, int64_t n_words, const double *betas, int64_t n_betas,
                       double *maps, int64_t n_maps, pw_affinity_level *levels, int64_t n_levels, pw_rigid_out *out,
                       int64_t n_out);
+/* ---- rigid linear guests in a crystal: the orientation-averaged Boltzmann factor over a periodic cell --------------
+ * pw_rigid_affinity's pose, weight and fold at every voxel of the skewed grid of a periodic cell, so that the free energy
+ * -ln(zbar) / beta of a rigid guest's centre can feed pw_percolation and pw_basins as a caller's field.  The reference
+ * has no counterpart.  The text of record, with the proof of the atom skip, is pywindow_amd/csrc/pw_rigid_cell.hpp; in
+ * short, job k has
+ *     the grid of a pw_percolation job (origin, step, nx, ny, nz; the same voxel centres and ranks (l*ny + j)*nx + i);
+ *     n >= 0 atoms xyz[atom_first .. +n), every periodic image that matters listed as an atom of its own;
+ *     core2 >= 1e-6 and cutoff2 > core2; cutoff2 == 0 is refused: a cell has no "no cutoff";
+ *     L = n_betas betas, S = n_sites offsets and M = n_dirs directions exactly as a pw_rigid_affinity job;
+ *     rows (A, B) per (site, atom), coef[coef_first + s*n + a], TWO doubles a row: uncharged only.
+ * POSE, WEIGHT, VOXEL and SUMS are pw_rigid_affinity's with charged = 0, the voxel centre being the cell grid's and
+ * every voxel of the grid a rank.  Written: row `out` (pw_rigid_out: n_voxels = nx*ny*nz, n_blocked_poses, n_dead, u_min
+ * with min_voxel and min_dir, ties to the lowest rank and then the lowest o; the flags); rows levels[level_first + b] =
+ * (Z_b, E_b); and, when map_first >= 0, L + 1 planes of nx*ny*nz doubles from maps[map_first]: zbar at beta 0 .. L-1,
+ * then umin_v (+inf at a dead voxel).  With S = 1, t_0 = 0, M = 1 the umin_v plane is pw_percolation's map byte for
+ * byte; with step = (h, 0, h, 0, 0, h) every output shared with pw_rigid_affinity over the whole grid with the same
+ * cutoff2 is that entry's bytes.  An atom that no pose of a block of 4 x 4 x 4 voxels can have within the cutoff is
+ * left out for that block by a test that is proved conservative in floating point: the same bytes on every device,
+ * launch geometry and run and on a device == -1 context, which may or may not skip.
+ * All pointers are host memory; the counts are the rows of xyz, of coef (two doubles) and the entries of offsets, the
+ * rows of dirs, the entries of betas and maps (doubles), the rows of levels and of out.  Jobs may share every input but
+ * no row of out or of levels and no entry of maps; entries no job owns are never touched.  Refused (PW_E_BAD_ARG,
+ * pw_last_error reads "pw_rigid_cell: job k: ..." and names the later of two jobs that share; nothing is launched or
+ * written): what pw_percolation refuses of a grid, pw_rigid_affinity of sites, directions, betas and rows, cutoff2 == 0
+ * or <= core2, more than 2^31 - 1 atoms, a range outside an array, shared outputs. */
+typedef struct pw_rigid_cell_job {
+    int64_t atom_first, n;          /* atoms = xyz[atom_first .. +n), n >= 0 */
+    int64_t coef_first;             /* rows (A, B) = coef[coef_first .. + n_sites*n), row s*n + a */
+    int64_t beta_first, n_betas;    /* betas[beta_first .. +n_betas) */
+    int64_t site_first, n_sites;    /* offsets[site_first .. +n_sites) */
+    int64_t dir_first, n_dirs;      /* dirs[dir_first .. +n_dirs), rows of three */
+    int64_t level_first;            /* levels[level_first .. +n_betas) is written */
+    int64_t map_first;              /* maps[map_first .. + (n_betas + 1)*nx*ny*nz) is written, or -1: no maps */
+    int64_t out;                    /* the job's row of out */
+    double  origin[3];              /* the centre of voxel (0, 0, 0) */
+    double  step[6];                /* ax, bx, by, cx, cy, cz */
+    double  core2;                  /* >= 1e-6 */
+    double  cutoff2;                /* > core2 */
+    int32_t nx, ny, nz;             /* 1 .. PW_CAVITY_MAX_G */
+    int32_t reserved;               /* padding to a multiple of 8 bytes; not read */
+} pw_rigid_cell_job;
+int pw_rigid_cell(pw_context *ctx, const pw_rigid_cell_job *jobs, int64_t n_jobs, const double *xyz, int64_t n_points,
+                  const double *coef, int64_t n_coef, const double *offsets, int64_t n_offsets, const double *dirs,
+                  int64_t n_dirs, const double *betas, int64_t n_betas, double *maps, int64_t n_maps,
+                  pw_affinity_level *levels, int64_t n_levels, pw_rigid_out *out, int64_t n_out);
 /* ---- partial charges of an isolated molecule: charge equilibration ---------------------------------------------
  * The framework charges that the charged jobs of pw_rigid_affinity need, frame by frame, so that a breathing cage
  * gets the charges of each of its shapes: QEq (Rappe and Goddard 1991) with Ohno-Klopman shielding instead of Slater

@@ -49,6 +49,16 @@ from .passage import Passage, guest_passage, guest_passage_batch, passage_field 
 from .percolation import Percolation, guest_percolation, guest_percolation_batch, percolation_field  # noqa: E402
 from .hopping import Hopping, guest_hopping, guest_hopping_batch, window_frame  # noqa: E402
 from .diffusion import Diffusion, diffusion_field, guest_diffusion, guest_diffusion_batch  # noqa: E402
+from .rigid_cell import (  # noqa: E402
+    RIGID_GUEST_MASSES,
+    RigidField,
+    rigid_guest_diffusion,
+    rigid_guest_diffusion_batch,
+    rigid_guest_field,
+    rigid_guest_field_batch,
+    rigid_guest_percolation,
+    rigid_guest_percolation_batch,
+)
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -143,6 +153,14 @@ __all__ = [
     "guest_diffusion",
     "guest_diffusion_batch",
     "diffusion_field",
+    "RIGID_GUEST_MASSES",
+    "RigidField",
+    "rigid_guest_field",
+    "rigid_guest_field_batch",
+    "rigid_guest_percolation",
+    "rigid_guest_percolation_batch",
+    "rigid_guest_diffusion",
+    "rigid_guest_diffusion_batch",
     "Hopping",
     "guest_hopping",
     "guest_hopping_batch",

@@ -352,6 +352,15 @@ assert RIGID_JOB_DTYPE.itemsize == 176 and RIGID_OUT_DTYPE.itemsize == 56
 RIGID_MAX_SITES = 8
 RIGID_MAX_DIRS = 1024
 
+#: numpy mirror of ``pw_rigid_cell_job``; the result rows are ``RIGID_OUT_DTYPE`` and ``AFFINITY_LEVEL_DTYPE``
+RIGID_CELL_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("beta_first", np.int64), ("n_betas", np.int64),
+     ("site_first", np.int64), ("n_sites", np.int64), ("dir_first", np.int64), ("n_dirs", np.int64), ("level_first", np.int64),
+     ("map_first", np.int64), ("out", np.int64), ("origin", np.float64, (3,)), ("step", np.float64, (6,)),
+     ("core2", np.float64), ("cutoff2", np.float64), ("nx", np.int32), ("ny", np.int32), ("nz", np.int32), ("reserved", np.int32)]
+)
+assert RIGID_CELL_JOB_DTYPE.itemsize == 200
+
 #: numpy mirrors of ``pw_charges_job`` and ``pw_charges_out``
 CHARGES_JOB_DTYPE = np.dtype(
     [("xyz_first", np.int64), ("param_first", np.int64), ("n", np.int64), ("total_charge", np.float64),
@@ -566,6 +575,7 @@ EXPORTED_SYMBOLS = [
     "pw_passage",
     "pw_hop",
     "pw_rigid_affinity",
+    "pw_rigid_cell",
     "pw_charges",
     "pw_channels",
     "pw_percolation",
@@ -717,6 +727,8 @@ def load():
     L.pw_internal_hop.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9
     L.pw_internal_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_rigid_cell.argtypes = [vp, vp, i64] + [vp, i64] * 8
+    L.pw_internal_rigid_cell.argtypes = [vp, vp, i64] + [vp, i64] * 8 + [i64, ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int, vp]
     L.pw_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
     L.pw_internal_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6
@@ -1452,6 +1464,58 @@ class Context:
         _stat_call("pw_internal_rigid_affinity", *args, int(workspace_bytes or 0), ctypes.byref(ms))
         if kernel_ms is not None:
             kernel_ms.append(float(ms.value))
+        return out, levels, maps
+
+    def rigid_cell(self, jobs, xyz, coef, offsets, dirs, betas, out=None, levels=None, maps=None, workspace_bytes=None,
+                   kernel_ms=None, diagnostics=None, skip=True):
+        """``pw_rigid_cell``: the orientation-averaged Boltzmann factor of a rigid linear guest at every voxel of the
+        periodic cells of a batch of jobs (``RIGID_CELL_JOB_DTYPE`` records indexing the rows of ``xyz`` (rows of three),
+        of ``coef`` (rows ``(A, B)``, row ``s * n + a`` of a job) and of ``dirs`` (rows of three), the entries of
+        ``offsets`` and of ``betas``, and the rows and entries of the results): ``(out, levels, maps)`` -- ``out`` a
+        ``RIGID_OUT_DTYPE`` array, ``levels`` an ``AFFINITY_LEVEL_DTYPE`` array with ``n_betas`` rows a job from its
+        ``level_first`` and ``maps`` float64, ``n_betas + 1`` planes of ``nx * ny * nz`` entries -- ``zbar`` at every
+        beta, then the lowest pose energy -- from ``map_first`` of a job that has one (``None`` when no job has one);
+        given: filled in place, entries no job owns stay as they are.  Whatever the entry refuses: ``ValueError`` with
+        the library's message.  ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the device work by
+        HIP events) / ``diagnostics`` (a list that receives ``(n_pairs, instances)``: the pair terms evaluated per job
+        and a bit per instance of the main kernel that was launched; no part of the defined result) / ``skip=False`` (no
+        atom is left out: the same bytes) go through the library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=RIGID_CELL_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
+        t = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        some = len(jobs) > 0
+        voxels = np.int64(1) * jobs["nx"] * jobs["ny"] * jobs["nz"]
+
+        def made(given, dtype, what, size):
+            if given is None:
+                return np.zeros(max(int(size), 0), dtype=dtype)
+            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+            return given
+
+        out = made(out, RIGID_OUT_DTYPE, "out", (jobs["out"] + 1).max() if some else 0)
+        levels = made(levels, AFFINITY_LEVEL_DTYPE, "levels", (jobs["level_first"] + jobs["n_betas"]).max() if some else 0)
+        has = jobs["map_first"] >= 0
+        if maps is not None or has.any():
+            maps = made(maps, np.float64, "maps",
+                        (jobs["map_first"][has] + (jobs["n_betas"][has] + 1) * voxels[has]).max() if has.any() else 0)
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), t.ctypes.data, len(t),
+                d.ctypes.data, len(d), b.ctypes.data, len(b), None if maps is None else maps.ctypes.data,
+                0 if maps is None else len(maps), levels.ctypes.data, len(levels), out.ctypes.data, len(out)]
+        if workspace_bytes is None and kernel_ms is None and diagnostics is None and skip:
+            _stat_call("pw_rigid_cell", *args)
+            return out, levels, maps
+        ms = ctypes.c_float(0.0)
+        n_pairs, instances = np.zeros(len(jobs), dtype=np.int64), np.zeros(1, dtype=np.int32)
+        _stat_call("pw_internal_rigid_cell", *args, int(workspace_bytes or 0), ctypes.byref(ms), n_pairs.ctypes.data,
+                   1 if skip else 0, instances.ctypes.data)
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        if diagnostics is not None:
+            diagnostics.append((n_pairs, int(instances[0])))
         return out, levels, maps
 
     def charges(self, jobs, xyz, params, out=None, workspace_bytes=None, kernel_ms=None):

@@ -1,5 +1,5 @@
 // pw_grid_host.hpp -- what the translation units of the grid entries (pw_cavity.hip, pw_sasa.hip, pw_pores.hip,
-// pw_affinity.hip, pw_rigid.hip, pw_passage.hip, pw_hop.hip), pw_charges.hip, pw_channels.hip, pw_percolate.hip and pw_basins.hip share on the host side of a call beyond pw_stat_host.hpp:
+// pw_affinity.hip, pw_rigid.hip, pw_rigid_cell.hip, pw_passage.hip, pw_hop.hip), pw_charges.hip, pw_channels.hip, pw_percolate.hip and pw_basins.hip share on the host side of a call beyond pw_stat_host.hpp:
 // the one range predicate, the span of an array that the jobs of a call read, the launch groups of a plan and the
 // refusals that several entries word alike.  The checks that are an entry's own, the plan loop that fills its job
 // records, its launches and its copy-back stay in its file.  Everything but Span::upload is plain C++ (tests/tools/

@@ -21,6 +21,7 @@
 #include "pw_cov.hpp"
 #include "pw_affinity.hpp"
 #include "pw_rigid.hpp"
+#include "pw_rigid_cell.hpp"
 #include "pw_cavity.hpp"
 #include "pw_sasa.hpp"
 #include "pw_pores.hpp"
@@ -1432,6 +1433,188 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
             o.min_voxel[2] = row / J.ny;
         }
         out[(long)J.out] = o;
+    });
+    return PW_OK;
+}
+
+// pw_rigid_cell on the host (pw_rigid_cell.hip checks the arguments and sends device == -1 contexts here): the pose, the
+// weight and the fold of pw_rigid.hpp on the grid of pw_channels.hpp, with the near list of pw_rigid_cell.hpp -- the same
+// test against the same group centre, so n_pairs is the device's unless `skip` is 0.  The threads share out (job, group)
+// pieces, each of which leaves the records of its voxels; then (job, chunk) pieces leave the partials of pw_rigid.hpp;
+// then one ordered reduce a job.  n_pairs (may be null): per job, diagnostic.
+extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs, const double* xyz, const double* coef,
+                                      const double* offsets, const double* dirs, const double* betas, double* maps,
+                                      pw_affinity_level* levels, pw_rigid_out* out, long long* n_pairs, int skip, int threads) {
+    typedef cavity_word u64;
+    struct Plan { long group_first, chunk_first, rec_first, part_first; };
+    std::vector<Plan> plan((size_t)n_jobs + 1);
+    std::vector<double> reach2((size_t)n_jobs);
+    long n_groups = 0, n_chunks = 0, rec_words = 0, part_words = 0;
+    for (long k = 0; k < n_jobs; ++k) {
+        const pw_rigid_cell_job& J = jobs[k];
+        plan[k] = Plan{n_groups, n_chunks, rec_words, part_words};
+        const long V = (long)J.nx * J.ny * J.nz, chunks = (V + AFF_CHUNK - 1) / AFF_CHUNK;
+        n_groups += rcell_groups(J.nx) * rcell_groups(J.ny) * rcell_groups(J.nz);
+        n_chunks += chunks;
+        rec_words += rcell_record_words(V, (int)J.n_betas);
+        part_words += chunks * rigid_part_words((int)J.n_betas);
+        reach2[k] = rcell_reach2(J.origin, J.step, J.cutoff2, offsets + (long)J.site_first, (int)J.n_sites,
+                                 dirs + 3 * (long)J.dir_first, (int)J.n_dirs, skip != 0);
+    }
+    plan[n_jobs] = Plan{n_groups, n_chunks, rec_words, part_words};
+    std::vector<u64> rec((size_t)rec_words), part((size_t)part_words);
+    std::vector<std::atomic<long long>> pairs((size_t)n_jobs);
+    for (auto& p : pairs) p.store(0, std::memory_order_relaxed);
+    cov_share(n_groups, threads, [&](long piece) {
+        long k = 0, hi = n_jobs;                                     // the last job with group_first <= piece
+        while (hi - k > 1) {
+            const long mid = (k + hi) / 2;
+            if (plan[mid].group_first <= piece) k = mid; else hi = mid;
+        }
+        const pw_rigid_cell_job& J = jobs[k];
+        const int L = (int)J.n_betas, S = (int)J.n_sites, M = (int)J.n_dirs, nx = J.nx, ny = J.ny, nz = J.nz;
+        const long n = (long)J.n, V = (long)nx * ny * nz, g = piece - plan[k].group_first;
+        const long gx = rcell_groups(nx), gy = rcell_groups(ny), grow = g / gx;
+        const int i0 = RCELL_G * (int)(g - grow * gx), j0 = RCELL_G * (int)(grow % gy), l0 = RCELL_G * (int)(grow / gy);
+        const double* atoms = xyz + 3 * (long)J.atom_first;
+        const double* ab = coef + 2 * (long)J.coef_first;
+        const double* ts = offsets + (long)J.site_first;
+        const double* dd = dirs + 3 * (long)J.dir_first;
+        const double inv_M = rigid_inv(M);
+        const double gcx = rcell_centre_x(J.origin, J.step, i0, j0, l0), gcy = rcell_centre_y(J.origin, J.step, j0, l0),
+                     gcz = rcell_centre_z(J.origin, J.step, l0);
+        std::vector<long> near_list;
+        for (long a = 0; a < n; ++a)
+            if (!rcell_far(gcx, gcy, gcz, atoms[3 * a], atoms[3 * a + 1], atoms[3 * a + 2], reach2[k])) near_list.push_back(a);
+        u64* R = rec.data() + plan[k].rec_first;
+        long n_valid = 0;
+        for (int l = l0; l < l0 + RCELL_G && l < nz; ++l)
+            for (int j = j0; j < j0 + RCELL_G && j < ny; ++j)
+                for (int i = i0; i < i0 + RCELL_G && i < nx; ++i) {
+                    ++n_valid;
+                    const long rank = ((long)l * ny + j) * nx + i;
+                    const double x = channels_x(J.origin[0], i, J.step[0], j, J.step[1], l, J.step[3]),
+                                 y = channels_y(J.origin[1], j, J.step[2], l, J.step[4]), z = channels_z(J.origin[2], l, J.step[5]);
+                    RigidFold fold[AFF_MAX_LEVELS];
+                    double umin_v = aff_inf();
+                    int umin_o = -1, n_blocked = 0;
+                    bool clamped = false;
+                    for (int o = 0; o < M; ++o) {
+                        bool blocked = false;
+                        double U = 0.0;
+                        for (int s = 0; s < S && !blocked; ++s) {
+                            const double px = rigid_site(x, ts[s], dd[3 * o]), py = rigid_site(y, ts[s], dd[3 * o + 1]),
+                                         pz = rigid_site(z, ts[s], dd[3 * o + 2]);
+                            const double* rows = ab + 2 * (long)s * n;
+                            double Us = 0.0;
+                            for (size_t q = 0; q < near_list.size() && !blocked; ++q) {
+                                const long a = near_list[q];
+                                const double r2 = aff_r2(px - atoms[3 * a], py - atoms[3 * a + 1], pz - atoms[3 * a + 2]);
+                                blocked = aff_blocked(r2, J.core2);
+                                if (blocked || !aff_counts(r2, J.cutoff2)) continue;
+                                Us = Us + aff_pair(r2, rows[2 * a], rows[2 * a + 1]);
+                            }
+                            U = s ? U + Us : Us;
+                        }
+                        if (blocked) {
+                            ++n_blocked;
+                            continue;
+                        }
+                        if (U < umin_v) {
+                            umin_v = U;
+                            umin_o = o;
+                        }
+                        for (int b = 0; b < L; ++b) fold[b].add(aff_weight(betas[(long)J.beta_first + b], U, POW_EXP_TAB, clamped), U);
+                    }
+                    for (int b = 0; b < L; ++b) {
+                        R[(long)b * V + rank] = pw_d2bits(fold[b].zbar(inv_M));
+                        R[(long)(L + 1 + b) * V + rank] = pw_d2bits(fold[b].ebar(inv_M));
+                    }
+                    R[(long)L * V + rank] = pw_d2bits(umin_v);
+                    R[(long)(2 * L + 1) * V + rank] = rcell_info(n_blocked, clamped, umin_o);
+                }
+        pairs[(size_t)k].fetch_add((long long)near_list.size() * M * S * n_valid, std::memory_order_relaxed);
+    });
+    cov_share(n_chunks, threads, [&](long piece) {
+        long k = 0, hi = n_jobs;                                     // the last job with chunk_first <= piece
+        while (hi - k > 1) {
+            const long mid = (k + hi) / 2;
+            if (plan[mid].chunk_first <= piece) k = mid; else hi = mid;
+        }
+        const pw_rigid_cell_job& J = jobs[k];
+        const int L = (int)J.n_betas, stride = rigid_part_words(L);
+        const long V = (long)J.nx * J.ny * J.nz, chunk = piece - plan[k].chunk_first;
+        const u64* R = rec.data() + plan[k].rec_first;
+        u64* P = part.data() + plan[k].part_first + chunk * stride;
+        double slot_z[AFF_CHUNK], slot_e[AFF_CHUNK];
+        for (int b = 0; b < L; ++b) {
+            for (int t = 0; t < AFF_CHUNK; ++t) {
+                const long rank = chunk * AFF_CHUNK + t;
+                slot_z[t] = rank < V ? pw_bits2d(R[(long)b * V + rank]) : 0.0;
+                slot_e[t] = rank < V ? pw_bits2d(R[(long)(L + 1 + b) * V + rank]) : 0.0;
+            }
+            P[2 * b] = pw_d2bits(aff_tree(slot_z));
+            P[2 * b + 1] = pw_d2bits(aff_tree(slot_e));
+        }
+        double m = aff_inf();
+        long m_rank = chunk * AFF_CHUNK, m_dir = -1, n_blocked = 0, n_dead = 0;
+        bool clamped = false;
+        for (int t = 0; t < AFF_CHUNK; ++t) {
+            const long rank = chunk * AFF_CHUNK + t;
+            if (rank >= V) break;
+            const u64 info = R[(long)(2 * L + 1) * V + rank];
+            const double v = pw_bits2d(R[(long)L * V + rank]);
+            n_blocked += rcell_info_blocked(info);
+            n_dead += rcell_info_dir(info) < 0;
+            clamped = clamped || rcell_info_clamped(info);
+            if (v < m) {
+                m = v;
+                m_rank = rank;
+                m_dir = rcell_info_dir(info);
+            }
+        }
+        P[2 * L] = pw_d2bits(m);
+        P[2 * L + 1] = (u64)m_rank;
+        P[2 * L + 2] = (u64)m_dir;
+        P[2 * L + 3] = (u64)n_blocked;
+        P[2 * L + 4] = (u64)n_dead;
+        P[2 * L + 5] = clamped ? (u64)AFF_CLAMPED : 0ull;
+    });
+    cov_share(n_jobs, threads, [&](long k) {
+        const pw_rigid_cell_job& J = jobs[k];
+        const int L = (int)J.n_betas, stride = rigid_part_words(L);
+        const long V = (long)J.nx * J.ny * J.nz, chunks = plan[k + 1].chunk_first - plan[k].chunk_first;
+        const u64* P = part.data() + plan[k].part_first;
+        for (int b = 0; b < L; ++b) {
+            double sz = 0.0, se = 0.0;
+            for (long c = 0; c < chunks; ++c) {
+                sz = sz + pw_bits2d(P[c * stride + 2 * b]);
+                se = se + pw_bits2d(P[c * stride + 2 * b + 1]);
+            }
+            levels[(long)J.level_first + b] = pw_affinity_level{sz, se};
+        }
+        pw_rigid_out o{V, 0, 0, aff_inf(), {-1, -1, -1}, -1, 0, 0};
+        long rank = -1;
+        for (long c = 0; c < chunks; ++c) {
+            const double v = pw_bits2d(P[c * stride + 2 * L]);
+            if (v < o.u_min) {
+                o.u_min = v;
+                rank = (long)P[c * stride + 2 * L + 1];
+                o.min_dir = (int)P[c * stride + 2 * L + 2];
+            }
+            o.n_blocked_poses += (long)P[c * stride + 2 * L + 3];
+            o.n_dead += (long)P[c * stride + 2 * L + 4];
+            o.flags |= (int)P[c * stride + 2 * L + 5];
+        }
+        if (rank >= 0) {
+            const long row = rank / J.nx;
+            o.min_voxel[0] = (int)(rank - row * J.nx);
+            o.min_voxel[1] = (int)(row % J.ny);
+            o.min_voxel[2] = (int)(row / J.ny);
+        }
+        out[(long)J.out] = o;
+        if (J.map_first >= 0) memcpy(maps + (long)J.map_first, rec.data() + plan[k].rec_first, sizeof(double) * (size_t)((L + 1) * V));
+        if (n_pairs) n_pairs[k] = pairs[(size_t)k].load(std::memory_order_relaxed);
     });
     return PW_OK;
 }

@@ -629,6 +629,55 @@ class DLPOLY:
         return DF.guest_diffusion_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, temperatures, spacing,
                                         cutoff, 0.25, cap, merge, mass, device=device, frames=sel)
 
+    def _rigid_cell_frames(self, what, frames):
+        if not self.periodic:
+            raise ValueError(f"{what}: the trajectory is not periodic (imcon 0): there is no cell; rigid_affinity() gives the "
+                             "affinity of a single cage for a rigid guest")
+        sel = self._select("all" if frames is None else frames)
+        if not sel:
+            raise ValueError(f"{what}: no frames selected")
+        return (sel,) + tuple(self._read_selected(sel, True))
+
+    def rigid_field(self, guest="CO2", temperatures=298.0, frames=None, spacing: float = 0.5, cutoff: float = 12.0,
+                    directions=None, device=None, swap_atoms=None, forcefield=None):
+        """The orientation-averaged Boltzmann factor of a rigid linear guest (N2, CO2, O2 or a
+        :class:`pywindow_amd.RigidGuest`) at every voxel of the periodic cell of every selected frame (``frames``: any
+        selection of the trajectory's frames, ``None``: all of them), ALL frames in ONE ``pw_rigid_cell`` call on the GPU
+        (``pywindow_amd.rigid_guest_field_batch``, UFF atoms, ``core2 = 0.25``) -- a :class:`pywindow_amd.RigidField`
+        whose fields are arrays, or lists, over the frames and whose ``frames`` are the trajectory's frame numbers.
+        Periodic trajectories only."""
+        from . import rigid_cell as RC
+
+        sel, coords, lattice = self._rigid_cell_frames("rigid_field", frames)
+        return RC.rigid_guest_field_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, temperatures, spacing,
+                                          cutoff, 0.25, directions, device, frames=sel)
+
+    def rigid_percolation(self, guest="CO2", temperatures=298.0, frames=None, spacing: float = 0.5, cutoff: float = 12.0,
+                          directions=None, device=None, swap_atoms=None, forcefield=None):
+        """The levels at which the free-energy landscape of a rigid linear guest's centre connects through the periodic
+        cell of every selected frame (``pywindow_amd.rigid_guest_percolation_batch``: one ``pw_rigid_cell`` and one
+        ``pw_percolation`` call on the GPU) -- a list, one :class:`pywindow_amd.Percolation` over the frames per
+        temperature.  Periodic trajectories only."""
+        from . import rigid_cell as RC
+
+        sel, coords, lattice = self._rigid_cell_frames("rigid_percolation", frames)
+        return RC.rigid_guest_percolation_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, temperatures,
+                                                spacing, cutoff, 0.25, directions, device, frames=sel)
+
+    def rigid_diffusion(self, guest="CO2", temperatures=298.0, frames=None, spacing: float = 0.5, cutoff: float = 12.0,
+                        directions=None, cap: float = 100.0, merge=None, mass=None, device=None, swap_atoms=None,
+                        forcefield=None):
+        """The self-diffusion tensor of a rigid linear guest through the periodic cell of every selected frame
+        (``pywindow_amd.rigid_guest_diffusion_batch``: one ``pw_rigid_cell`` and one ``pw_basins`` call on the GPU) -- a
+        :class:`pywindow_amd.Diffusion` with ``tensor`` ``(frames, L, 3, 3)`` whose ``frames`` are the trajectory's frame
+        numbers.  ``rigid_diffusion().series("coefficient")`` goes into ``pywindow_amd.time_correlation`` and the other
+        statistical entries.  Periodic trajectories only."""
+        from . import rigid_cell as RC
+
+        sel, coords, lattice = self._rigid_cell_frames("rigid_diffusion", frames)
+        return RC.rigid_guest_diffusion_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, temperatures,
+                                              spacing, cutoff, 0.25, directions, cap, merge, mass, device=device, frames=sel)
+
     def passage(self, guest="Xe", spacing: float = 0.5, frames=None, device=None, close="windows", swap_atoms=None,
                 forcefield=None):
         """The barrier a one-site Lennard-Jones guest crosses at every window in every frame analysed so far
