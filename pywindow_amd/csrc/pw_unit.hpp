@@ -1729,6 +1729,109 @@ PW_NOINLINE PW_HD inline bool path_scan_thread(const Frame& F, int n, double vx,
     return true;
 }
 
+// ---- a path's smallest gap from the two points that bracket each atom -----------------------
+// The sampling stage wants two things of a path: whether every point's gap is > 0, and twice the smallest gap over its
+// points.  Per radius group g the value of point k is sqrt(max(fl(min_i m2_i(k) + pp_k), 0)) - r_g; rounding, the root
+// and the subtraction are monotone, so the smallest value over the points is sqrt(max(V_g, 0)) - r_g with
+// V_g = min over the group's atoms i and the points k = 1 .. chunks of v_ik = fl(pw_m2add(gg_i(k), xx_i) + pp_k) -- the
+// numbers path_scan_thread forms, the same bits.  With c the step and a an atom, v_ik is a rounded
+//     T_k = xx - 2 k (a . c) + k^2 |c|^2,
+// a parabola in k with its vertex at t* = (a . c) / |c|^2.  For the two integers lo = floor(t*), lo + 1, clamped to
+// [1, chunks] (one point where t* lies outside), every other k of the path has T_k - T_kb >= |c|^2 for a bracket point kb:
+// T_k' - T_lo = |c|^2 (lo - k')(2 t* - k' - lo) >= |c|^2 for k' < lo, likewise above lo + 1 and beyond a clamped end.
+// The computed t is off t* by at most 9 u |a| / |c| (u = 2^-53: the three products of the dot, the five roundings of
+// 1 / sq3(c), the last product); a floor misjudged by eps in t swaps the bracket for its neighbour at an integer t*, where
+// the margin is still |c|^2 (1 - 2 eps).  A v_ik differs from T_k by at most
+//     e = 12 u (xx + |q_k|^2):  8 u |a||q| <= 4 u (|a|^2 + |q|^2) for the rounded point in the dot (2 x (3 u |a||q| of the
+//     fma chain + u |a||q| of q = fl(c k))), 5 u |q|^2 for pp (two from q, three from sq3), u (xx + 2 |a||q|) for
+//     pw_m2add and u (xx + 2 |a||q| + |q|^2) for the last sum
+// (xx is the stored number in both forms: whatever it differs from |a|^2 by shifts every T_k of the atom alike).  So where
+//     |c|^2 (1 - 1e-6)  >  64 u (xx_max + sq3 of the end point)                       [more than 2 e, second-order terms and all]
+// no point outside the bracket undercuts the better bracket point, ties included, and the minimum over the bracket is the
+// minimum over the path.  The same inequality bounds |a| / |c| by 1 / (8 sqrt(u)), hence eps by 1.2e-8: the 1e-6 holds.
+// xx_max is the largest xx of ANY atom of the frame (>= the largest listed one: the caller finds it once per unit).
+// NaN coordinates make every v_ik of their atom NaN in both forms, and fmin drops them in both.
+struct PathSteps {
+    double cx, cy, cz, cd, rinv;      // the step, the number of steps (as a double), 1 / |step|^2
+    int chunks;
+    bool bracket;                     // the guard holds: path_bracket_thread may be used
+};
+// One path's steps by the statements of path_scan_thread, and the guard: false where the margin is not proven, a quantity is
+// not finite, the path has no second point or the radii are not grouped -- the caller scans the path point by point then.
+PW_HD inline PathSteps path_steps(const Frame& F, double vx, double vy, double vz, double inc, double xx_max) {
+    PathSteps s;
+    const double nrm = norm3(vx, vy, vz);
+    const double fd = np_floordiv(nrm, inc);
+    s.bracket = F.cls->k > 0 && fd >= 1.0 && fd <= PW_PATH_POINTS_MAX && nrm < PW_INF;
+    s.chunks = s.bracket ? (int)fd : 0;
+    s.cd = (double)s.chunks;
+    s.cx = vx / s.cd; s.cy = vy / s.cd; s.cz = vz / s.cd;
+    const double cc = sq3(s.cx, s.cy, s.cz);
+    s.rinv = 1.0 / cc;
+    const double bound = (64.0 * 0x1p-53) * (xx_max + sq3(vx, vy, vz));
+    s.bracket = s.bracket && cc > 0.0 && cc < PW_INF && s.rinv < PW_INF && bound < PW_INF && cc * (1.0 - 1e-6) > bound;
+    return s;
+}
+// ok and 2 * best of path_scan_thread for a path whose guard holds (s.bracket), from two points per atom; *n_terms (optional)
+// += the (atom, point) evaluations made.  cand / coff as in points_gap_values.
+// (the steps go in one by one: a structure handed to an out-of-line function by reference would live in scratch)
+PW_NOINLINE PW_HD inline bool path_bracket_thread(const Frame& F, int n, double cx, double cy, double cz, int chunks,
+                                                  double rinv, double m0, double* out_2gap, int* n_eval,
+                                                  const lint* cand = nullptr, const lint* coff = nullptr,
+                                                  long* n_terms = nullptr) {
+    (void)n;
+    const auto& C = *F.cls;
+    const double cd = (double)chunks;
+    double best = PW_INF;
+    long terms = 0;
+    for (int g = 0; g < C.k; ++g) {
+        double m2 = PW_INF;
+        auto atom = [&](double x, double y, double z, double xx) __attribute__((always_inline)) {
+            const double t = pw_fma(z, cz, pw_fma(x, cx, y * cy)) * rinv;
+            // (fmax / fmin drop a NaN: such an atom is evaluated at points 1 and 2, NaN both)
+            const double lo = __builtin_fmin(__builtin_fmax(__builtin_floor(t), 1.0), cd);
+            const double hi = __builtin_fmin(lo + 1.0, cd);
+            // (lo and hi hold integers: c * lo is path_scan_thread's c * (double)k)
+            const double ax = cx * lo, ay = cy * lo, az = cz * lo;
+            const double bx = cx * hi, by = cy * hi, bz = cz * hi;
+            const double ga = pw_fma(z, az, pw_fma(x, ax, y * ay));
+            const double gb = pw_fma(z, bz, pw_fma(x, bx, y * by));
+            const double va = pw_m2add(ga, xx) + sq3(ax, ay, az);
+            const double vb = pw_m2add(gb, xx) + sq3(bx, by, bz);
+            m2 = __builtin_fmin(m2, __builtin_fmin(va, vb));
+        };
+        // blocks of four atoms: all LDS reads of a block are issued before its arithmetic (point_gap_value), and the
+        // four independent chains are in flight together
+        auto span = [&](int c, const int chi, auto at) __attribute__((always_inline)) {
+            terms += 2 * (chi - c);
+            for (; c + 4 <= chi; c += 4) {
+                int i[4];
+                double x[4], y[4], z[4], xx[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) i[j] = at(c + j);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { x[j] = F.x[i[j]]; y[j] = F.y[i[j]]; z[j] = F.z[i[j]]; xx[j] = F.xx[i[j]]; }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) atom(x[j], y[j], z[j], xx[j]);
+            }
+            for (; c < chi; ++c) {
+                const int i = at(c);
+                atom(F.x[i], F.y[i], F.z[i], F.xx[i]);
+            }
+        };
+        if (cand) span(coff[g], coff[g + 1], [&](int c) __attribute__((always_inline)) { return (int)cand[c]; });
+        else span(C.off[g], C.off[g + 1], [](int c) __attribute__((always_inline)) { return c; });
+        const double d = pw_sqrt(m2 > 0.0 ? m2 : 0.0);
+        best = __builtin_fmin(best, d - C.vdw[g]);
+    }
+    if (n_eval) *n_eval += chunks + 1;
+    if (n_terms) *n_terms += terms;
+    // (path_scan_thread: false at the first point whose gap is not > 0, the origin's m0 included; best starts at m0)
+    if (!(m0 > 0.0) || !(best > 0.0)) return false;
+    *out_2gap = (best < m0 ? best : m0) * 2.0;
+    return true;
+}
+
 // The atoms that can matter to the paths of ONE wave (a path each in the lanes that `have` one; vx, vy, vz its end point).
 // A path's result is the smallest gap over its points and where it is first reached, and it starts at m0, the gap at
 // the origin (path_scan_thread): an atom whose gap is PROVABLY above m0 at every point but the origin of every path of
@@ -4174,6 +4277,14 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
             }
 #endif
         }
+#ifndef PW_NO_PATH_BRACKETS      // (tests/test_path_brackets.py builds the host probe with and without: the same records)
+        // (the largest |atom|^2 of the frame, for the guard of path_steps: every wave finds it for itself)
+        double xx_max = 0.0;
+        if (whole > 0) {
+            for (int i = T::lane(); i < n; i += T::WSIZE) xx_max = __builtin_fmax(xx_max, sh.S.xx[i]);
+            xx_max = -T::wave_min(-xx_max);
+        }
+#endif
         for (int j0 = 0; j0 < whole; j0 += T::SIZE) {
             const int j = j0 + T::tid();
             const bool have = j < whole;
@@ -4181,6 +4292,21 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
             const double vx = pts[PT(k, 0)], vy = pts[PT(k, 1)], vz = pts[PT(k, 2)];
             const bool listed = cand_w != nullptr &&
                                 wave_path_candidates<T>(sh.S, n, have, vx, vy, vz, prm.increment, m_origin, cand_w, coff_w);
+#ifndef PW_NO_PATH_BRACKETS
+            // (only the smallest gap is wanted here: two points per atom give it wherever the guard holds -- for every
+            // path of the wave, so that a wave runs one form)
+            const PathSteps steps = path_steps(sh.S, vx, vy, vz, prm.increment, xx_max);
+            if (!T::wave_any(have && !steps.bracket)) {
+                if (have) {
+                    double g2 = 0.0;
+                    bool ok = path_bracket_thread(sh.S, n, steps.cx, steps.cy, steps.cz, steps.chunks, steps.rinv, m_origin,
+                                                  &g2, &evals, listed ? cand_w : nullptr, listed ? coff_w : nullptr);
+                    flag[j] = ok ? 1 : 0;
+                    tmpv[j] = g2;
+                }
+                continue;
+            }
+#endif
             if (have) {
                 double g2, chunk[3];
                 int pos;
