@@ -51,6 +51,14 @@ PW_HD inline bool cavity_inside(const double* plane, double x, double y, double 
 // the bits of the voxels of a row: the low nx
 PW_HD inline cavity_word cavity_row_mask(int nx) { return nx >= 64 ? ~0ull : (1ull << nx) - 1ull; }
 
+// the voxel (i, j, l) of a rank = (l * ny + j) * nx + i into v[3]; (-1, -1, -1) for a negative rank: no such voxel
+PW_HD inline void grid_voxel(long rank, int nx, int ny, int* v) {
+    const long row = rank / nx;
+    v[0] = rank >= 0 ? (int)(rank - row * nx) : -1;
+    v[1] = rank >= 0 ? (int)(row % ny) : -1;
+    v[2] = rank >= 0 ? (int)(row / ny) : -1;
+}
+
 PW_HD inline int cavity_popcount(cavity_word v) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __popcll(v);

@@ -6,16 +6,10 @@
 // `todo` (the open voxels not yet given to a component), `p0` and `p1` (the two parities of a fill) and `acc` (the
 // accessible words) -- and a few integers, as dynamic LDS sized by the largest job of the launch (128 KiB at 64 x 64 rows).
 //   classify  the wave-a-row scheme of cav_classify (pw_cavity_dev.hpp) on the skewed centres, with its row cull.
-//   loop      the first set bit of todo in rank order by an integer workgroup minimum (every thread scans its own rows
-//             from where it stopped the last time: todo only loses bits); the fill for phi = 7 from it, which is the
-//             component as p0 | p1; the component's n_voxels and n_cross by integer LDS atomics; then only the fills
-//             that channels_next asks for; the row of the table, the labels, acc and the totals; the component leaves
+//   loop      the first set bit of todo in rank order (chan_first); its component as p0 | p1, the component's n_voxels,
+//             n_cross and winding bits (chan_walk, which runs chan_fill) -- all three in pw_channels_dev.hpp, shared with
+//             pw_percolate.hip --; then, here, the row of the table, the labels, acc and the totals; the component leaves
 //             todo.  Until todo is empty: at most n_open turns.
-//   fill      (chan_fill, pw_channels_dev.hpp, shared with pw_percolate.hip) thread t owns rows t, t + 256, ...; a sweep gives a row the words of its four periodic neighbour rows, of
-//             the other parity where the step crosses a face of phi (channels_gather), and takes the x direction to its
-//             fixed point inside the word (channels_fill_words); neighbours are read while their owners may be storing
-//             them (relaxed atomics: either value is a subset of the fixed point), and the sweeps repeat while
-//             __syncthreads_or(changed), at most 2 * nx * ny * nz + 1 times.
 // Every branch that leads to a barrier depends on values read from LDS after a barrier, the same in every thread.  No
 // floating-point atomics, no loop without a bound derived from the grid, no workgroup waits for another.
 // Launches follow one another on the context's stream; memory is allocated and released in stream order.
@@ -45,7 +39,6 @@ namespace {
 
 typedef cavity_word u64;
 
-constexpr unsigned CHAN_NONE = 0xFFFFFFFFu;                      // no set bit of todo
 constexpr size_t CHAN_SCRATCH_BYTES = 64;                        // n_voxels, n_cross[3], n_open; the first voxel
 constexpr size_t chan_lds_bytes(long rows) { return 32 * (size_t)rows + CHAN_SCRATCH_BYTES; }
 
@@ -129,58 +122,14 @@ pw_channels_kernel(const ChanJobDev* __restrict__ jobs, const double* __restrict
     // ---- the components, in the order of their first voxels
     long voxels_by_rank[4] = {0, 0, 0, 0}, comps_by_rank[4] = {0, 0, 0, 0}, count = 0;
     const long n_voxels_grid = (long)nx * rows;
-    int cursor = tid;                                                // no row of this thread before it has a bit of todo
+    int cursor = tid;                                                // (chan_first's, pw_channels_dev.hpp)
     for (long turn = 0; turn <= n_voxels_grid; ++turn) {             // (a turn takes a voxel or more out of todo, or ends)
-        if (tid == 0) *s_first = CHAN_NONE;
-        __syncthreads();
-        while (cursor < rows && !s_todo[cursor]) cursor += CAV_THREADS;
-        if (cursor < rows) atomicMin(s_first, (unsigned)cursor * 64u + (unsigned)(__ffsll((long long)s_todo[cursor]) - 1));
-        __syncthreads();
-        const unsigned first = *s_first;
+        const unsigned first = chan_first(s_todo, rows, cursor, s_first);
         if (first == CHAN_NONE) break;
         const int seed_row = (int)(first >> 6);
-        const u64 seed_bit = 1ull << (first & 63u);
-
-        int known = 0, wraps = 0, cross = 0, phi = 7;
-        bool measured = false;
-        long n_voxels = 0, n_cross[3] = {0, 0, 0};
-        for (int fill = 0; fill < 7 && phi; ++fill) {
-            __syncthreads();                                         // (everybody has read what the last fill left)
-            for (int r = tid; r < rows; r += CAV_THREADS) {
-                s_p0[r] = r == seed_row ? seed_bit : 0;
-                s_p1[r] = 0;
-            }
-            if (!measured && tid < 4) s_sum[tid] = 0;
-            __syncthreads();
-            chan_fill(s_todo, s_p0, s_p1, nx, ny, nz, phi);
-            const bool reached = (s_p1[seed_row] & seed_bit) != 0;
-            channels_learn(phi, reached, known, wraps);
-            if (!measured) {
-                for (int r = tid; r < rows; r += CAV_THREADS) {
-                    const u64 f = s_p0[r] | s_p1[r];
-                    if (!f) continue;
-                    const int j = r % ny, l = r / ny;
-                    const int rj = l * ny, rl = j;                   // the rows (0, l) and (j, 0)
-                    long c[3];
-                    channels_row_cross(f, s_p0[rj] | s_p1[rj], s_p0[rl] | s_p1[rl], nx, ny, nz, j, l, c);
-                    atomicAdd(s_sum + 0, (unsigned long long)cavity_popcount(f));
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-                        if (c[k]) atomicAdd(s_sum + 1 + k, (unsigned long long)c[k]);
-                }
-                __syncthreads();
-                n_voxels = (long)s_sum[0];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) {
-                    n_cross[k] = (long)s_sum[1 + k];
-                    cross |= (n_cross[k] > 0) << k;
-                }
-                if (cross) channels_learn(cross, reached, known, wraps);   // ((1): phi = 7 and phi = cross are one graph)
-                measured = true;
-            }
-            phi = channels_next(cross, known, wraps);
-        }
-        const int rank = channels_rank(wraps);
+        const ChannelsWalk W = chan_walk(s_todo, s_p0, s_p1, s_sum, seed_row, 1ull << (first & 63u), nx, ny, nz);
+        const long n_voxels = W.n_voxels;
+        const int wraps = W.wraps, rank = channels_rank(wraps);
 
         // the component leaves todo; p0 | p1 is still the component, and nobody stores to it before the next barrier
         for (int r = tid; r < rows; r += CAV_THREADS) {
@@ -198,7 +147,7 @@ pw_channels_kernel(const ChanJobDev* __restrict__ jobs, const double* __restrict
             pw_channels_comp& C = table[count];
             C.first = (long)seed_row * nx + (long)(first & 63u);
             C.n_voxels = n_voxels;
-            for (int k = 0; k < 3; ++k) C.n_cross[k] = n_cross[k];
+            for (int k = 0; k < 3; ++k) C.n_cross[k] = W.n_cross[k];
             C.wraps = wraps;
             C.rank = rank;
         }

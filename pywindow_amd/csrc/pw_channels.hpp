@@ -147,6 +147,13 @@ PW_HD inline void channels_learn(int phi, bool reached, int& known, int& wraps) 
     if (reached) wraps |= 1 << (phi - 1);
 }
 
+// what the walk of a component returns, on the host (pw_hostpath.cpp: channels_host_walk) and on the device
+// (pw_channels_dev.hpp: chan_walk)
+struct ChannelsWalk {
+    int wraps, fills;                  // the winding bits; the fills that were run (1 .. 7)
+    long n_voxels, n_cross[3];         // of the component, from the first fill
+};
+
 PW_HD inline int channels_rank(int wraps) {
     const int clear = 7 - cavity_popcount((cavity_word)(wraps & 127));
     return clear == 7 ? 0 : clear == 3 ? 1 : clear == 1 ? 2 : 3;     // (clear + 1 is 8, 4, 2 or 1)

@@ -94,6 +94,45 @@ HostTables g_tables;
 unsigned g_rsq[65536];
 std::once_flag g_rsq_once;
 
+// How every entry below pw_hostpath_run shares its work: f(piece) for piece = 0 .. pieces - 1, by at most `threads`
+// threads, each taking the next piece that nobody has; one thread is the calling thread.  Which thread runs a piece and
+// in which order the pieces finish is not defined, so a piece writes only what is its own and keeps its scratch to itself.
+template <class F>
+void host_share(long pieces, int threads, F f) {
+    std::atomic<long> next{0};
+    auto worker = [&]() {
+        for (;;) {
+            const long p = next.fetch_add(1);
+            if (p >= pieces) break;
+            f(p);
+        }
+    };
+    const int count = (long)threads > pieces ? (int)std::max(1l, pieces) : std::max(1, threads);
+    if (count == 1) {
+        worker();
+    } else {
+        std::vector<std::thread> pool;
+        for (int t = 0; t < count; ++t) pool.emplace_back(worker);
+        for (auto& t : pool) t.join();
+    }
+}
+
+// The (job, block) pieces of the statistical entries: job k has blocks_of_job(k) blocks (0: the job has no work), and
+// f(k, block) runs once for every block of every job, shared out by host_share.  A piece finds its job by bisection in
+// the table of first pieces, so it does not matter which pieces the thread had before.
+template <class B, class F>
+void host_share_blocks(long n_jobs, int threads, B blocks_of_job, F f) {
+    std::vector<long> first((size_t)n_jobs + 1, 0);
+    for (long k = 0; k < n_jobs; ++k) first[k + 1] = first[k] + blocks_of_job(k);
+    host_share(first[n_jobs], threads, [&](long w) {
+        const long k = (std::upper_bound(first.begin(), first.end(), w) - first.begin()) - 1;   // the last job with first[k] <= w
+        f(k, w - first[k]);
+    });
+}
+
+// the blocks of `block` that `count` outputs make
+inline long host_blocks(long count, long block) { return (count + block - 1) / block; }
+
 }  // namespace
 
 // One batch on the host.  Returns 0 or PW_E_NOMEM.  extra: windows beyond PW_W_MAX, appended unsorted.
@@ -173,40 +212,21 @@ extern "C" int pw_hostpath_default_threads(void) {
 extern "C" int pw_hostpath_kde(const pw_kde_job* jobs, long n_jobs, const double* samples, const double* points,
                                double* sums, int threads) {
     constexpr long BLOCK = 8;                      // grid points of one piece of work
-    std::vector<long> first((size_t)n_jobs + 1, 0);
-    for (long k = 0; k < n_jobs; ++k) first[k + 1] = first[k] + ((long)jobs[k].n_points + BLOCK - 1) / BLOCK;
-    const long total = first[n_jobs];
-    std::atomic<long> next{0};
-    auto worker = [&]() {
-        long k = 0;
-        for (;;) {
-            const long w = next.fetch_add(1);
-            if (w >= total) break;
-            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
-            const pw_kde_job& J = jobs[k];
-            const long j0 = (w - first[k]) * BLOCK, j1 = std::min(j0 + BLOCK, (long)J.n_points);
-            const double* x = samples + J.sample_first;
-            for (long j = j0; j < j1; ++j) {
-                const double g = points[J.point_first + j];
-                double s = 0.0;
-                for (long i0 = 0; i0 < (long)J.n_samples; i0 += KDE_CHUNK) {
-                    const int len = (int)std::min((long)KDE_CHUNK, (long)J.n_samples - i0);
-                    const double p = kde_chunk_sum(g, x + i0, len, J.inv_bandwidth, POW_EXP_TAB);
-                    s = i0 == 0 ? p : s + p;
-                }
-                sums[J.point_first + j] = s;
+    host_share_blocks(n_jobs, threads, [&](long k) { return host_blocks((long)jobs[k].n_points, BLOCK); }, [&](long k, long block) {
+        const pw_kde_job& J = jobs[k];
+        const long j0 = block * BLOCK, j1 = std::min(j0 + BLOCK, (long)J.n_points);
+        const double* x = samples + J.sample_first;
+        for (long j = j0; j < j1; ++j) {
+            const double g = points[J.point_first + j];
+            double s = 0.0;
+            for (long i0 = 0; i0 < (long)J.n_samples; i0 += KDE_CHUNK) {
+                const int len = (int)std::min((long)KDE_CHUNK, (long)J.n_samples - i0);
+                const double p = kde_chunk_sum(g, x + i0, len, J.inv_bandwidth, POW_EXP_TAB);
+                s = i0 == 0 ? p : s + p;
             }
+            sums[J.point_first + j] = s;
         }
-    };
-    if (threads < 1) threads = 1;
-    if ((long)threads > total) threads = (int)std::max(1l, total);
-    if (threads == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
+    });
     return PW_OK;
 }
 
@@ -214,40 +234,21 @@ extern "C" int pw_hostpath_kde(const pw_kde_job* jobs, long n_jobs, const double
 extern "C" int pw_hostpath_kde2(const pw_kde2_job* jobs, long n_jobs, const double* samples, const double* points,
                                 double* sums, int threads) {
     constexpr long BLOCK = 8;                      // points of one piece of work
-    std::vector<long> first((size_t)n_jobs + 1, 0);
-    for (long k = 0; k < n_jobs; ++k) first[k + 1] = first[k] + ((long)jobs[k].n_points + BLOCK - 1) / BLOCK;
-    const long total = first[n_jobs];
-    std::atomic<long> next{0};
-    auto worker = [&]() {
-        long k = 0;
-        for (;;) {
-            const long w = next.fetch_add(1);
-            if (w >= total) break;
-            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
-            const pw_kde2_job& J = jobs[k];
-            const long j0 = (w - first[k]) * BLOCK, j1 = std::min(j0 + BLOCK, (long)J.n_points);
-            const double* xy = samples + 2 * J.sample_first;
-            for (long j = j0; j < j1; ++j) {
-                const double g0 = points[2 * (J.point_first + j)], g1 = points[2 * (J.point_first + j) + 1];
-                double s = 0.0;
-                for (long i0 = 0; i0 < (long)J.n_samples; i0 += KDE_CHUNK) {
-                    const int len = (int)std::min((long)KDE_CHUNK, (long)J.n_samples - i0);
-                    const double p = kde2_chunk_sum(g0, g1, xy + 2 * i0, len, J.w00, J.w10, J.w11, POW_EXP_TAB);
-                    s = i0 == 0 ? p : s + p;
-                }
-                sums[J.point_first + j] = s;
+    host_share_blocks(n_jobs, threads, [&](long k) { return host_blocks((long)jobs[k].n_points, BLOCK); }, [&](long k, long block) {
+        const pw_kde2_job& J = jobs[k];
+        const long j0 = block * BLOCK, j1 = std::min(j0 + BLOCK, (long)J.n_points);
+        const double* xy = samples + 2 * J.sample_first;
+        for (long j = j0; j < j1; ++j) {
+            const double g0 = points[2 * (J.point_first + j)], g1 = points[2 * (J.point_first + j) + 1];
+            double s = 0.0;
+            for (long i0 = 0; i0 < (long)J.n_samples; i0 += KDE_CHUNK) {
+                const int len = (int)std::min((long)KDE_CHUNK, (long)J.n_samples - i0);
+                const double p = kde2_chunk_sum(g0, g1, xy + 2 * i0, len, J.w00, J.w10, J.w11, POW_EXP_TAB);
+                s = i0 == 0 ? p : s + p;
             }
+            sums[J.point_first + j] = s;
         }
-    };
-    if (threads < 1) threads = 1;
-    if ((long)threads > total) threads = (int)std::max(1l, total);
-    if (threads == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
+    });
     return PW_OK;
 }
 
@@ -256,45 +257,24 @@ extern "C" int pw_hostpath_kde2(const pw_kde2_job* jobs, long n_jobs, const doub
 extern "C" int pw_hostpath_kdew(const pw_kdew_job* jobs, long n_jobs, const double* samples, const double* points,
                                 const double* weights, double* sums, int threads) {
     constexpr long BLOCK = 8;                      // grid points of one piece of work
-    std::vector<long> first((size_t)n_jobs + 1, 0);
-    for (long k = 0; k < n_jobs; ++k) first[k + 1] = first[k] + ((long)jobs[k].n_points + BLOCK - 1) / BLOCK;
-    const long total = first[n_jobs];
-    std::atomic<long> next{0};
-    auto worker = [&]() {
-        long k = 0;
-        std::vector<double> s, p;
-        for (;;) {
-            const long w = next.fetch_add(1);
-            if (w >= total) break;
-            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
-            const pw_kdew_job& J = jobs[k];
-            const long n = (long)J.n_samples, m = (long)J.n_points, nb = (long)J.n_replicas;
-            const long j0 = (w - first[k]) * BLOCK, j1 = std::min(j0 + BLOCK, m);
-            const double* x = samples + J.sample_first;
-            const double* wt = weights + J.weight_first;
-            s.assign((size_t)nb, 0.0);
-            p.assign((size_t)nb, 0.0);
-            for (long j = j0; j < j1; ++j) {
-                const double g = points[J.point_first + j];
-                for (long b = 0; b < nb; ++b) s[b] = 0.0;
-                for (long i0 = 0; i0 < n; i0 += KDE_CHUNK) {
-                    const int len = (int)std::min((long)KDE_CHUNK, n - i0);
-                    kdew_chunk_sums(g, x + i0, wt + i0 * nb, nb, len, nb, J.inv_bandwidth, POW_EXP_TAB, p.data());
-                    for (long b = 0; b < nb; ++b) s[b] = i0 == 0 ? p[b] : s[b] + p[b];
-                }
-                for (long b = 0; b < nb; ++b) sums[J.out_first + b * m + j] = s[b];
+    host_share_blocks(n_jobs, threads, [&](long k) { return host_blocks((long)jobs[k].n_points, BLOCK); }, [&](long k, long block) {
+        const pw_kdew_job& J = jobs[k];
+        const long n = (long)J.n_samples, m = (long)J.n_points, nb = (long)J.n_replicas;
+        const long j0 = block * BLOCK, j1 = std::min(j0 + BLOCK, m);
+        const double* x = samples + J.sample_first;
+        const double* wt = weights + J.weight_first;
+        std::vector<double> s((size_t)nb, 0.0), p((size_t)nb, 0.0);   // (the piece's own: a pair a block of points)
+        for (long j = j0; j < j1; ++j) {
+            const double g = points[J.point_first + j];
+            for (long b = 0; b < nb; ++b) s[b] = 0.0;
+            for (long i0 = 0; i0 < n; i0 += KDE_CHUNK) {
+                const int len = (int)std::min((long)KDE_CHUNK, n - i0);
+                kdew_chunk_sums(g, x + i0, wt + i0 * nb, nb, len, nb, J.inv_bandwidth, POW_EXP_TAB, p.data());
+                for (long b = 0; b < nb; ++b) s[b] = i0 == 0 ? p[b] : s[b] + p[b];
             }
+            for (long b = 0; b < nb; ++b) sums[J.out_first + b * m + j] = s[b];
         }
-    };
-    if (threads < 1) threads = 1;
-    if ((long)threads > total) threads = (int)std::max(1l, total);
-    if (threads == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
+    });
     return PW_OK;
 }
 
@@ -304,55 +284,36 @@ extern "C" int pw_hostpath_kdew(const pw_kdew_job* jobs, long n_jobs, const doub
 // its own t order) as far as the shortest of them reaches, and finish one by one.
 extern "C" int pw_hostpath_corr(const pw_corr_job* jobs, long n_jobs, const double* series, double* sums, int threads) {
     constexpr long BLOCK = 16;                     // lags of one piece of work
-    std::vector<long> first((size_t)n_jobs + 1, 0);
-    for (long k = 0; k < n_jobs; ++k)
-        first[k + 1] = first[k] + (jobs[k].n ? ((long)jobs[k].n_lags + BLOCK - 1) / BLOCK : 0);
-    const long total = first[n_jobs];
-    std::atomic<long> next{0};
-    auto worker = [&]() {
-        long k = 0;
-        for (;;) {
-            const long w = next.fetch_add(1);
-            if (w >= total) break;
-            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
-            const pw_corr_job& J = jobs[k];
-            const long n = (long)J.n, l0 = (w - first[k]) * BLOCK, l1 = std::min(l0 + BLOCK, (long)J.n_lags);
-            const double* a = series + J.a_first;
-            const double* b = series + J.b_first;
-            double s[BLOCK];
-            for (long c = 0; c * CORR_CHUNK < n - l0; ++c) {
-                const long t0 = c * CORR_CHUNK;
-                double p[BLOCK];
-                for (long j = 0; j < BLOCK; ++j) p[j] = 0.0;
-                long t = 0;
-                if (l1 - l0 == BLOCK) {
-                    const long all = std::max(0l, corr_chunk_len(n, l1 - 1, c));   // terms every lag of the block has
-                    const double* bb = b + t0 + l0;
-                    for (; t < all; ++t) {
-                        const double av = a[t0 + t];
-                        for (long j = 0; j < BLOCK; ++j) p[j] = pw_fma(av, bb[t + j], p[j]);
-                    }
-                }
-                for (long j = 0; j < l1 - l0; ++j) {
-                    const long len = corr_chunk_len(n, l0 + j, c);
-                    if (len <= 0) continue;        // the chunk does not exist for this lag
-                    double q = p[j];
-                    for (long u = t; u < len; ++u) q = pw_fma(a[t0 + u], b[t0 + u + l0 + j], q);
-                    s[j] = c == 0 ? q : s[j] + q;
+    auto blocks = [&](long k) { return jobs[k].n ? host_blocks((long)jobs[k].n_lags, BLOCK) : 0; };
+    host_share_blocks(n_jobs, threads, blocks, [&](long k, long block) {
+        const pw_corr_job& J = jobs[k];
+        const long n = (long)J.n, l0 = block * BLOCK, l1 = std::min(l0 + BLOCK, (long)J.n_lags);
+        const double* a = series + J.a_first;
+        const double* b = series + J.b_first;
+        double s[BLOCK];
+        for (long c = 0; c * CORR_CHUNK < n - l0; ++c) {
+            const long t0 = c * CORR_CHUNK;
+            double p[BLOCK];
+            for (long j = 0; j < BLOCK; ++j) p[j] = 0.0;
+            long t = 0;
+            if (l1 - l0 == BLOCK) {
+                const long all = std::max(0l, corr_chunk_len(n, l1 - 1, c));   // terms every lag of the block has
+                const double* bb = b + t0 + l0;
+                for (; t < all; ++t) {
+                    const double av = a[t0 + t];
+                    for (long j = 0; j < BLOCK; ++j) p[j] = pw_fma(av, bb[t + j], p[j]);
                 }
             }
-            for (long j = 0; j < l1 - l0; ++j) sums[J.out_first + l0 + j] = s[j];
+            for (long j = 0; j < l1 - l0; ++j) {
+                const long len = corr_chunk_len(n, l0 + j, c);
+                if (len <= 0) continue;            // the chunk does not exist for this lag
+                double q = p[j];
+                for (long u = t; u < len; ++u) q = pw_fma(a[t0 + u], b[t0 + u + l0 + j], q);
+                s[j] = c == 0 ? q : s[j] + q;
+            }
         }
-    };
-    if (threads < 1) threads = 1;
-    if ((long)threads > total) threads = (int)std::max(1l, total);
-    if (threads == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
+        for (long j = 0; j < l1 - l0; ++j) sums[J.out_first + l0 + j] = s[j];
+    });
     return PW_OK;
 }
 
@@ -363,65 +324,46 @@ extern "C" int pw_hostpath_corr(const pw_corr_job* jobs, long n_jobs, const doub
 extern "C" int pw_hostpath_dft(const pw_dft_job* jobs, long n_jobs, const double* series, double* re, double* im,
                                int threads) {
     constexpr long BLOCK = 8;                      // frequencies of one piece of work
-    std::vector<long> first((size_t)n_jobs + 1, 0);
-    for (long k = 0; k < n_jobs; ++k)
-        first[k + 1] = first[k] + (jobs[k].n && jobs[k].n_freq ? ((long)jobs[k].n_freq + BLOCK - 1) / BLOCK : 0);
-    const long total = first[n_jobs];
-    std::atomic<long> next{0};
-    auto worker = [&]() {
-        long k = 0;
-        std::vector<double> cA((size_t)DFT_CHUNK * BLOCK), sA((size_t)DFT_CHUNK * BLOCK);
-        for (;;) {
-            const long w = next.fetch_add(1);
-            if (w >= total) break;
-            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
-            const pw_dft_job& J = jobs[k];
-            const long n = (long)J.n, M = (long)J.period;
-            const long q0 = (w - first[k]) * BLOCK, count = std::min(BLOCK, (long)J.n_freq - q0);
-            const long steps = std::min(n, (long)DFT_CHUNK);
-            long j[BLOCK];
-            for (long f = 0; f < BLOCK; ++f) j[f] = (long)J.j_first + (q0 + std::min(f, count - 1)) * (long)J.j_step;
-            for (long r = 0; r < steps; ++r)
-                for (long f = 0; f < BLOCK; ++f) dft_phase(j[f], r, M, &cA[r * BLOCK + f], &sA[r * BLOCK + f]);
-            const double* a = series + J.a_first;
-            double sr[BLOCK], si[BLOCK];
-            for (long f = 0; f < BLOCK; ++f) sr[f] = si[f] = 0.0;
-            for (long t0 = 0; t0 < n; t0 += DFT_CHUNK) {
-                const long len = std::min((long)DFT_CHUNK, n - t0);
-                double pc[BLOCK], ps[BLOCK];
-                for (long f = 0; f < BLOCK; ++f) pc[f] = ps[f] = 0.0;
-                for (long r = 0; r < len; ++r) {
-                    const double av = a[t0 + r];
-                    const double* c = &cA[r * BLOCK];
-                    const double* s = &sA[r * BLOCK];
-                    for (long f = 0; f < BLOCK; ++f) {
-                        pc[f] = pw_fma(av, c[f], pc[f]);
-                        ps[f] = pw_fma(av, s[f], ps[f]);
-                    }
-                }
-                for (long f = 0; f < count; ++f) {
-                    double cB, sB, x, y;
-                    dft_phase(j[f], t0, M, &cB, &sB);
-                    dft_rotate(cB, sB, pc[f], ps[f], &x, &y);
-                    sr[f] = sr[f] + x;
-                    si[f] = si[f] + y;
+    auto blocks = [&](long k) { return jobs[k].n && jobs[k].n_freq ? host_blocks((long)jobs[k].n_freq, BLOCK) : 0; };
+    host_share_blocks(n_jobs, threads, blocks, [&](long k, long block) {
+        const pw_dft_job& J = jobs[k];
+        const long n = (long)J.n, M = (long)J.period;
+        const long q0 = block * BLOCK, count = std::min(BLOCK, (long)J.n_freq - q0);
+        const long steps = std::min(n, (long)DFT_CHUNK);
+        double cA[DFT_CHUNK * BLOCK], sA[DFT_CHUNK * BLOCK];         // (the piece's own twiddles, 32 KiB each: no allocation)
+        long j[BLOCK];
+        for (long f = 0; f < BLOCK; ++f) j[f] = (long)J.j_first + (q0 + std::min(f, count - 1)) * (long)J.j_step;
+        for (long r = 0; r < steps; ++r)
+            for (long f = 0; f < BLOCK; ++f) dft_phase(j[f], r, M, &cA[r * BLOCK + f], &sA[r * BLOCK + f]);
+        const double* a = series + J.a_first;
+        double sr[BLOCK], si[BLOCK];
+        for (long f = 0; f < BLOCK; ++f) sr[f] = si[f] = 0.0;
+        for (long t0 = 0; t0 < n; t0 += DFT_CHUNK) {
+            const long len = std::min((long)DFT_CHUNK, n - t0);
+            double pc[BLOCK], ps[BLOCK];
+            for (long f = 0; f < BLOCK; ++f) pc[f] = ps[f] = 0.0;
+            for (long r = 0; r < len; ++r) {
+                const double av = a[t0 + r];
+                const double* c = &cA[r * BLOCK];
+                const double* s = &sA[r * BLOCK];
+                for (long f = 0; f < BLOCK; ++f) {
+                    pc[f] = pw_fma(av, c[f], pc[f]);
+                    ps[f] = pw_fma(av, s[f], ps[f]);
                 }
             }
             for (long f = 0; f < count; ++f) {
-                re[J.out_first + q0 + f] = sr[f];
-                im[J.out_first + q0 + f] = si[f];
+                double cB, sB, x, y;
+                dft_phase(j[f], t0, M, &cB, &sB);
+                dft_rotate(cB, sB, pc[f], ps[f], &x, &y);
+                sr[f] = sr[f] + x;
+                si[f] = si[f] + y;
             }
         }
-    };
-    if (threads < 1) threads = 1;
-    if ((long)threads > total) threads = (int)std::max(1l, total);
-    if (threads == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
+        for (long f = 0; f < count; ++f) {
+            re[J.out_first + q0 + f] = sr[f];
+            im[J.out_first + q0 + f] = si[f];
+        }
+    });
     return PW_OK;
 }
 
@@ -431,50 +373,31 @@ extern "C" int pw_hostpath_dft(const pw_dft_job* jobs, long n_jobs, const double
 extern "C" int pw_hostpath_gate(const pw_gate_job* jobs, long n_jobs, const double* series, const double* thresholds,
                                 long n_bins, long* counts, long* hist, int threads) {
     constexpr long BLOCK = 16;                     // thresholds of one piece of work
-    std::vector<long> first((size_t)n_jobs + 1, 0);
-    for (long k = 0; k < n_jobs; ++k)
-        first[k + 1] = first[k] + (jobs[k].n && jobs[k].n_thr ? ((long)jobs[k].n_thr + BLOCK - 1) / BLOCK : 0);
-    const long total = first[n_jobs];
-    std::atomic<long> next{0};
-    auto worker = [&]() {
-        long k = 0;
-        for (;;) {
-            const long w = next.fetch_add(1);
-            if (w >= total) break;
-            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
-            const pw_gate_job& J = jobs[k];
-            const long n = (long)J.n, q0 = (w - first[k]) * BLOCK, q1 = std::min(q0 + BLOCK, (long)J.n_thr);
-            const double* a = series + J.a_first;
-            for (long q = q0; q < q1; ++q) {
-                const double d = thresholds[J.d_first + q];
-                const long row = (long)J.out_first + q;
-                long* h = n_bins > 0 ? hist + row * 2 * n_bins : nullptr;
-                for (long i = 0; i < 2 * n_bins; ++i) h[i] = 0;
-                auto bin = [&](int s, long len) {
-                    if (n_bins > 0) h[s * n_bins + std::min(len, n_bins) - 1] += 1;
-                };
-                GateWalk W;
-                GateTally<long> T;
-                for (long t0 = 0; t0 < n; t0 += GATE_CHUNK)
-                    gate_merge(W, gate_chunk(a + t0, (int)std::min((long)GATE_CHUNK, n - t0), d, T, bin), T, bin);
-                gate_finish(W, T, bin);
-                long* c = counts + row * GATE_FIELDS;
-                c[0] = T.n_open; c[1] = T.n_closed; c[2] = T.open_runs; c[3] = T.closed_runs;
-                c[4] = T.longest_open; c[5] = T.longest_closed; c[6] = T.openings; c[7] = T.closings;
-                c[8] = T.complete_open_runs; c[9] = T.complete_closed_runs;
-                c[10] = T.complete_open_frames; c[11] = T.complete_closed_frames;
-            }
+    auto blocks = [&](long k) { return jobs[k].n && jobs[k].n_thr ? host_blocks((long)jobs[k].n_thr, BLOCK) : 0; };
+    host_share_blocks(n_jobs, threads, blocks, [&](long k, long block) {
+        const pw_gate_job& J = jobs[k];
+        const long n = (long)J.n, q0 = block * BLOCK, q1 = std::min(q0 + BLOCK, (long)J.n_thr);
+        const double* a = series + J.a_first;
+        for (long q = q0; q < q1; ++q) {
+            const double d = thresholds[J.d_first + q];
+            const long row = (long)J.out_first + q;
+            long* h = n_bins > 0 ? hist + row * 2 * n_bins : nullptr;
+            for (long i = 0; i < 2 * n_bins; ++i) h[i] = 0;
+            auto bin = [&](int s, long len) {
+                if (n_bins > 0) h[s * n_bins + std::min(len, n_bins) - 1] += 1;
+            };
+            GateWalk W;
+            GateTally<long> T;
+            for (long t0 = 0; t0 < n; t0 += GATE_CHUNK)
+                gate_merge(W, gate_chunk(a + t0, (int)std::min((long)GATE_CHUNK, n - t0), d, T, bin), T, bin);
+            gate_finish(W, T, bin);
+            long* c = counts + row * GATE_FIELDS;
+            c[0] = T.n_open; c[1] = T.n_closed; c[2] = T.open_runs; c[3] = T.closed_runs;
+            c[4] = T.longest_open; c[5] = T.longest_closed; c[6] = T.openings; c[7] = T.closings;
+            c[8] = T.complete_open_runs; c[9] = T.complete_closed_runs;
+            c[10] = T.complete_open_frames; c[11] = T.complete_closed_frames;
         }
-    };
-    if (threads < 1) threads = 1;
-    if ((long)threads > total) threads = (int)std::max(1l, total);
-    if (threads == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < threads; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
+    });
     return PW_OK;
 }
 
@@ -487,72 +410,45 @@ extern "C" int pw_hostpath_trans(const pw_trans_job* jobs, long n_jobs, const do
     typedef unsigned long long u64;
     constexpr long BLOCK = 16;                     // lags of one piece of work
     const long S = n_states;
-    std::vector<long> first((size_t)n_jobs + 1, 0), m_first((size_t)n_jobs + 1, 0);
-    for (long k = 0; k < n_jobs; ++k) {
-        const bool live = jobs[k].n && jobs[k].n_lags;
-        first[k + 1] = first[k] + (live ? ((long)jobs[k].n_lags + BLOCK - 1) / BLOCK : 0);
-        m_first[k + 1] = m_first[k] + (live ? ((long)jobs[k].n_edges + 1) * (((long)jobs[k].n + 63) / 64 + 1) : 0);
-    }
-    const long total = first[n_jobs];
+    auto live = [&](long k) { return jobs[k].n && jobs[k].n_lags; };
+    std::vector<long> m_first((size_t)n_jobs + 1, 0);
+    for (long k = 0; k < n_jobs; ++k)
+        m_first[k + 1] = m_first[k] + (live(k) ? ((long)jobs[k].n_edges + 1) * (((long)jobs[k].n + 63) / 64 + 1) : 0);
     std::vector<u64> masks((size_t)m_first[n_jobs], 0);
-    std::atomic<long> next_job{0}, next{0};
-    auto packer = [&]() {
-        for (;;) {
-            const long k = next_job.fetch_add(1);
-            if (k >= n_jobs) break;
-            const pw_trans_job& J = jobs[k];
-            if (!J.n || !J.n_lags) continue;
-            const long n = (long)J.n, stride = (n + 63) / 64 + 1;
-            const double* a = series + J.a_first;
-            u64* M = masks.data() + m_first[k];
-            for (long t = 0; t < n; ++t) {
-                const int s = trans_state(a[t], J.n_edges ? edges + J.e_first : nullptr, (int)J.n_edges);
-                if (s != TRANS_GAP) M[s * stride + t / 64] |= 1ull << (t % 64);
-            }
+    host_share(n_jobs, threads, [&](long k) {                        // the masks, a job a piece
+        const pw_trans_job& J = jobs[k];
+        if (!live(k)) return;
+        const long n = (long)J.n, stride = (n + 63) / 64 + 1;
+        const double* a = series + J.a_first;
+        u64* M = masks.data() + m_first[k];
+        for (long t = 0; t < n; ++t) {
+            const int s = trans_state(a[t], J.n_edges ? edges + J.e_first : nullptr, (int)J.n_edges);
+            if (s != TRANS_GAP) M[s * stride + t / 64] |= 1ull << (t % 64);
         }
-    };
-    auto worker = [&]() {
-        long k = 0;
-        for (;;) {
-            const long w = next.fetch_add(1);
-            if (w >= total) break;
-            while (first[k + 1] <= w) ++k;         // (pieces are handed out in rising order)
-            const pw_trans_job& J = jobs[k];
-            const long n = (long)J.n, nw = (n + 63) / 64, stride = nw + 1, ns = (long)J.n_edges + 1;
-            const long q0 = (w - first[k]) * BLOCK, q1 = std::min(q0 + BLOCK, (long)J.n_lags);
-            const u64* M = masks.data() + m_first[k];
-            for (long q = q0; q < q1; ++q) {
-                const long lag = (long)J.lag_first + q * (long)J.lag_step;
-                long c[TRANS_MAX_STATES][TRANS_MAX_STATES] = {};
-                if (lag < n) {
-                    const long ko = lag / 64;
-                    const unsigned r = (unsigned)(lag % 64);
-                    for (long x = 0; x + ko < nw; ++x)
-                        for (long j = 0; j < ns; ++j) {
-                            const u64 partner = trans_funnel(M[j * stride + x + ko + 1], M[j * stride + x + ko], r);
-                            for (long i = 0; i < ns; ++i) trans_count(c[i][j], M[i * stride + x] & partner);
-                        }
-                }
-                long* row = counts + ((long)J.out_first + q) * S * S;
-                for (long i = 0; i < S; ++i)
-                    for (long j = 0; j < S; ++j) row[i * S + j] = c[i][j];
+    });
+    auto blocks = [&](long k) { return live(k) ? host_blocks((long)jobs[k].n_lags, BLOCK) : 0; };
+    host_share_blocks(n_jobs, threads, blocks, [&](long k, long block) {   // the lags
+        const pw_trans_job& J = jobs[k];
+        const long n = (long)J.n, nw = (n + 63) / 64, stride = nw + 1, ns = (long)J.n_edges + 1;
+        const long q0 = block * BLOCK, q1 = std::min(q0 + BLOCK, (long)J.n_lags);
+        const u64* M = masks.data() + m_first[k];
+        for (long q = q0; q < q1; ++q) {
+            const long lag = (long)J.lag_first + q * (long)J.lag_step;
+            long c[TRANS_MAX_STATES][TRANS_MAX_STATES] = {};
+            if (lag < n) {
+                const long ko = lag / 64;
+                const unsigned r = (unsigned)(lag % 64);
+                for (long x = 0; x + ko < nw; ++x)
+                    for (long j = 0; j < ns; ++j) {
+                        const u64 partner = trans_funnel(M[j * stride + x + ko + 1], M[j * stride + x + ko], r);
+                        for (long i = 0; i < ns; ++i) trans_count(c[i][j], M[i * stride + x] & partner);
+                    }
             }
+            long* row = counts + ((long)J.out_first + q) * S * S;
+            for (long i = 0; i < S; ++i)
+                for (long j = 0; j < S; ++j) row[i * S + j] = c[i][j];
         }
-    };
-    if (threads < 1) threads = 1;
-    for (int phase = 0; phase < 2; ++phase) {
-        const long pieces = phase == 0 ? n_jobs : total;
-        const int count = (long)threads > pieces ? (int)std::max(1l, pieces) : threads;
-        if (count == 1) {
-            if (phase == 0) packer(); else worker();
-        } else {
-            std::vector<std::thread> pool;
-            for (int t = 0; t < count; ++t) {
-                if (phase == 0) pool.emplace_back(packer); else pool.emplace_back(worker);
-            }
-            for (auto& t : pool) t.join();
-        }
-    }
+    });
     return PW_OK;
 }
 
@@ -562,8 +458,6 @@ extern "C" int pw_hostpath_trans(const pw_trans_job* jobs, long n_jobs, const do
 extern "C" int pw_hostpath_superpose(const pw_superpose_job* jobs, long n_jobs, const double* xyz, const double* weights,
                                      pw_superpose_out* out, int threads) {
     constexpr long BLOCK = 16;
-    const long pieces = (n_jobs + BLOCK - 1) / BLOCK;
-    std::atomic<long> next{0};
     auto one = [&](const pw_superpose_job& J) {
         const long n = (long)J.n;
         const double* x = xyz + 3 * (long)J.mobile_first;
@@ -605,22 +499,9 @@ extern "C" int pw_hostpath_superpose(const pw_superpose_job* jobs, long n_jobs, 
         o->sweeps = sweeps;
         o->reserved = 0;
     };
-    auto worker = [&]() {
-        for (;;) {
-            const long p = next.fetch_add(1);
-            if (p >= pieces) break;
-            for (long k = p * BLOCK; k < std::min((p + 1) * BLOCK, n_jobs); ++k) one(jobs[k]);
-        }
-    };
-    if (threads < 1) threads = 1;
-    const int count = (long)threads > pieces ? (int)std::max(1l, pieces) : threads;
-    if (count == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < count; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
+    host_share(host_blocks(n_jobs, BLOCK), threads, [&](long p) {
+        for (long k = p * BLOCK; k < std::min((p + 1) * BLOCK, n_jobs); ++k) one(jobs[k]);
+    });
     return PW_OK;
 }
 
@@ -780,31 +661,10 @@ extern "C" int pw_hostpath_cluster(const pw_cluster_job* jobs, long n_jobs, cons
 namespace {
 constexpr long COV_HOST_BLOCK = 32;
 
-// f(piece) for piece = 0 .. pieces - 1, shared out among at most `threads` threads
-template <class F>
-void cov_share(long pieces, int threads, F f) {
-    std::atomic<long> next{0};
-    auto worker = [&]() {
-        for (;;) {
-            const long p = next.fetch_add(1);
-            if (p >= pieces) break;
-            f(p);
-        }
-    };
-    const int count = (long)threads > pieces ? (int)std::max(1l, pieces) : std::max(1, threads);
-    if (count == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < count; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
-}
-
 // y[t][a] of the job's rows, or z = y - mean when mean is not null
 void cov_host_values(const double* x, const double* tr, long T, long D, const double* mean, int threads, double* y) {
     constexpr long ROWS = 64;
-    cov_share((T + ROWS - 1) / ROWS, threads, [&](long p) {
+    host_share((T + ROWS - 1) / ROWS, threads, [&](long p) {
         for (long t = p * ROWS; t < std::min((p + 1) * ROWS, T); ++t) {
             const double* trow = tr ? tr + t * COV_TRANSFORM_DOUBLES : nullptr;
             for (long a = 0; a < D; ++a) {
@@ -828,7 +688,7 @@ extern "C" int pw_hostpath_covariance(const pw_cov_job* jobs, long n_jobs, const
         y.resize((size_t)(T * D));
         cov_host_values(x, tr, T, D, nullptr, threads, y.data());
         const long col_blocks = (D + COV_HOST_BLOCK - 1) / COV_HOST_BLOCK;
-        cov_share(col_blocks, threads, [&](long p) {
+        host_share(col_blocks, threads, [&](long p) {
             const long a0 = p * COV_HOST_BLOCK, w = std::min(COV_HOST_BLOCK, D - a0);
             double total[COV_HOST_BLOCK];
             for (long c = 0; c < chunks; ++c) {
@@ -841,12 +701,12 @@ extern "C" int pw_hostpath_covariance(const pw_cov_job* jobs, long n_jobs, const
             for (long i = 0; i < w; ++i) m[a0 + i] = total[i] / (double)T;
         });
         if (J.s_first < 0) continue;
-        cov_share((T + 63) / 64, threads, [&](long p) {
+        host_share((T + 63) / 64, threads, [&](long p) {
             for (long t = p * 64; t < std::min((p + 1) * 64, T); ++t)
                 for (long a = 0; a < D; ++a) y[t * D + a] = y[t * D + a] - m[a];
         });
         double* S = scatter + (long)J.s_first;
-        cov_share(col_blocks * (col_blocks + 1) / 2, threads, [&](long p) {
+        host_share(col_blocks * (col_blocks + 1) / 2, threads, [&](long p) {
             int ba, bb;
             cov_tile_of(p, (int)col_blocks, ba, bb);
             const long a0 = ba * COV_HOST_BLOCK, b0 = bb * COV_HOST_BLOCK;
@@ -888,7 +748,7 @@ extern "C" int pw_hostpath_project(const pw_project_job* jobs, long n_jobs, cons
         const double* V = vectors + (long)J.v_first;
         double* P = proj + (long)J.p_first;
         constexpr long ROWS = 16;
-        cov_share((T + ROWS - 1) / ROWS, threads, [&](long p) {
+        host_share((T + ROWS - 1) / ROWS, threads, [&](long p) {
             std::vector<double> z((size_t)D);
             for (long t = p * ROWS; t < std::min((p + 1) * ROWS, T); ++t) {
                 const double* trow = tr ? tr + t * COV_TRANSFORM_DOUBLES : nullptr;
@@ -974,7 +834,7 @@ extern "C" int pw_hostpath_cavity(const pw_cavity_job* jobs, long n_jobs, const 
                                   const double* planes, pw_cavity_out* out, unsigned long long* mask,
                                   const unsigned long long* open_words, const long* open_first, int threads) {
     typedef cavity_word u64;
-    cov_share(n_jobs, threads, [&](long k) {
+    host_share(n_jobs, threads, [&](long k) {
         const pw_cavity_job& J = jobs[k];
         const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
         const CavityHostGrid G{xyz + 3 * (long)J.atom_first, radii + (long)J.radius_first, planes + 4 * (long)J.plane_first,
@@ -1026,7 +886,7 @@ extern "C" int pw_hostpath_pore_sizes(const pw_pores_job* jobs, long n_jobs, con
                                       pw_pores_out* out, unsigned long long* mask, const unsigned long long* open_words,
                                       const long* open_first, int threads) {
     typedef cavity_word u64;
-    cov_share(n_jobs, threads, [&](long k) {
+    host_share(n_jobs, threads, [&](long k) {
         const pw_pores_job& J = jobs[k];
         const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz, L = (int)J.n_levels;
         const u64 xmask = cavity_row_mask(nx);
@@ -1091,7 +951,7 @@ extern "C" int pw_hostpath_sasa(const pw_sasa_job* jobs, long n_jobs, const doub
         slack[k] = J.n ? sasa_slack(sasa_magnitude(xyz + 3 * (long)J.atom_first, radii + (long)J.radius_first, (long)J.n, J.probe)) : -1.0;
         for (long a = 0; a < (long)J.n; a += SASA_HOST_ATOMS) pieces.push_back({k, a, std::min(a + SASA_HOST_ATOMS, (long)J.n)});
     }
-    cov_share((long)pieces.size(), threads, [&](long p) {
+    host_share((long)pieces.size(), threads, [&](long p) {
         const Piece& piece = pieces[p];
         const pw_sasa_job& J = jobs[piece.job];
         const double* atoms = xyz + 3 * (long)J.atom_first;
@@ -1173,7 +1033,7 @@ extern "C" int pw_hostpath_affinity(const pw_affinity_job* jobs, long n_jobs, co
         const int* p = prefix.data() + plan[k].prefix_first;
         aff_voxel(rank, J.word_first >= 0, J.nx, J.ny * J.nz, [&](int r) { return w[r]; }, [&](int r) { return p[r]; }, i, row);
     };
-    cov_share(pieces, threads, [&](long piece) {
+    host_share(pieces, threads, [&](long piece) {
         long k = 0, hi = n_jobs;                                     // the last job with piece_first <= piece
         while (hi - k > 1) {
             const long mid = (k + hi) / 2;
@@ -1238,7 +1098,7 @@ extern "C" int pw_hostpath_affinity(const pw_affinity_job* jobs, long n_jobs, co
             P[2 * L + AFF_PART_FIXED + e] = (u64)below;
         }
     });
-    cov_share(n_jobs, threads, [&](long k) {
+    host_share(n_jobs, threads, [&](long k) {
         const pw_affinity_job& J = jobs[k];
         const int L = (int)J.n_betas, E = (int)J.n_edges, stride = aff_part_words(L, E);
         const long chunks = plan[k + 1].piece_first - plan[k].piece_first;
@@ -1317,7 +1177,7 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
         const int* p = prefix.data() + plan[k].prefix_first;
         aff_voxel(rank, J.word_first >= 0, J.nx, J.ny * J.nz, [&](int r) { return w[r]; }, [&](int r) { return p[r]; }, i, row);
     };
-    cov_share(pieces, threads, [&](long piece) {
+    host_share(pieces, threads, [&](long piece) {
         long k = 0, hi = n_jobs;                                     // the last job with piece_first <= piece
         while (hi - k > 1) {
             const long mid = (k + hi) / 2;
@@ -1399,7 +1259,7 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
         P[2 * L + 4] = (u64)n_dead;
         P[2 * L + 5] = clamped ? (u64)AFF_CLAMPED : 0ull;
     });
-    cov_share(n_jobs, threads, [&](long k) {
+    host_share(n_jobs, threads, [&](long k) {
         const pw_rigid_job& J = jobs[k];
         const int L = (int)J.n_betas, stride = rigid_part_words(L);
         const long chunks = plan[k + 1].piece_first - plan[k].piece_first;
@@ -1465,7 +1325,7 @@ extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs
     std::vector<u64> rec((size_t)rec_words), part((size_t)part_words);
     std::vector<std::atomic<long long>> pairs((size_t)n_jobs);
     for (auto& p : pairs) p.store(0, std::memory_order_relaxed);
-    cov_share(n_groups, threads, [&](long piece) {
+    host_share(n_groups, threads, [&](long piece) {
         long k = 0, hi = n_jobs;                                     // the last job with group_first <= piece
         while (hi - k > 1) {
             const long mid = (k + hi) / 2;
@@ -1535,7 +1395,7 @@ extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs
                 }
         pairs[(size_t)k].fetch_add((long long)near_list.size() * M * S * n_valid, std::memory_order_relaxed);
     });
-    cov_share(n_chunks, threads, [&](long piece) {
+    host_share(n_chunks, threads, [&](long piece) {
         long k = 0, hi = n_jobs;                                     // the last job with chunk_first <= piece
         while (hi - k > 1) {
             const long mid = (k + hi) / 2;
@@ -1580,7 +1440,7 @@ extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs
         P[2 * L + 4] = (u64)n_dead;
         P[2 * L + 5] = clamped ? (u64)AFF_CLAMPED : 0ull;
     });
-    cov_share(n_jobs, threads, [&](long k) {
+    host_share(n_jobs, threads, [&](long k) {
         const pw_rigid_cell_job& J = jobs[k];
         const int L = (int)J.n_betas, stride = rigid_part_words(L);
         const long V = (long)J.nx * J.ny * J.nz, chunks = plan[k + 1].chunk_first - plan[k].chunk_first;
@@ -1619,59 +1479,104 @@ extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs
     return PW_OK;
 }
 
-// pw_passage on the host (pw_passage.hip checks the arguments and sends device == -1 contexts here): the pair terms of
-// pw_affinity.hpp, the plane test and the fill of pw_cavity.hpp, the keys and the bisection of pw_passage.hpp.  Jobs go
-// in order in batches whose maps fit PAS_WORKSPACE_BYTES; within a batch the threads first share out slabs of
-// PAS_HOST_SLAB voxels of the maps of the jobs without a field of their own, then the (job, row) pieces.  A piece builds
-// its held words, then runs level after level: the allowed words from the map, the fill, the face test.
-extern "C" int pw_hostpath_passage(const pw_passage_job* jobs, long n_jobs, const double* xyz, const double* coef,
-                                   const double* planes, const double* field, pw_passage_out* out, int* fills,
-                                   int threads) {
-    typedef cavity_word u64;
-    constexpr long PAS_HOST_SLAB = 4096;
-    struct Piece { long job, a, b; };                                // a slab [a, b) of a map, or row a of a job
+// The Lennard-Jones energy maps of pw_passage, pw_hop and pw_percolation on the host: one pair loop, the two kinds of
+// voxel centres, and the batches the maps are computed in.
+namespace {
+constexpr long FIELD_HOST_SLAB = 4096;                               // voxels of a map in one piece of work
+
+// the energy of a guest at (x, y, z) among the job's atoms: pw_affinity.hpp's pair terms in atom order (pw_field_dev.hpp's
+// and pw_field_cell_dev.hpp's order); the atoms after one that blocks the point add nothing to +inf
+template <class Job>
+inline double field_value_at(const Job& J, const double* atoms, const double* ab, double x, double y, double z) {
+    double u_sum = 0.0;
+    bool blocked = false;
+    for (long a = 0; a < (long)J.n && !blocked; ++a) {
+        const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
+        blocked = aff_blocked(r2, J.core2);
+        if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
+    }
+    return blocked ? aff_inf() : u_sum;
+}
+
+// ... at the voxel `rank` of the grid around a molecule (pw_passage_job, pw_hop_job): pw_cavity.hpp's centres.  (This and
+// the next are objects without state, not functions, so that host_field_batches is compiled with the loop inside it.)
+struct GridFieldValue {
+    template <class Job>
+    double operator()(const Job& J, const double* atoms, const double* ab, long rank) const {
+        const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx);
+        return field_value_at(J, atoms, ab, cavity_coord(J.origin[0], i, J.spacing), cavity_coord(J.origin[1], row % J.ny, J.spacing),
+                              cavity_coord(J.origin[2], row / J.ny, J.spacing));
+    }
+};
+
+// ... at the voxel `rank` of the grid of a periodic cell (pw_percolation_job, pw_basins_job): pw_channels.hpp's centres
+struct CellFieldValue {
+    template <class Job>
+    double operator()(const Job& J, const double* atoms, const double* ab, long rank) const {
+        const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx), j = row % J.ny, l = row / J.ny;
+        return field_value_at(J, atoms, ab, channels_x(J.origin[0], i, J.step[0], j, J.step[1], l, J.step[3]),
+                              channels_y(J.origin[1], j, J.step[2], l, J.step[4]), channels_z(J.origin[2], l, J.step[5]));
+    }
+};
+
+// Jobs go in order in batches [first, last): a batch takes jobs while the maps of those without a field of their own
+// (field_first == -1) fit workspace_bytes, and a job that alone does not fit is a batch.  The threads share out slabs of
+// FIELD_HOST_SLAB voxels of the batch's maps, value(J, atoms, ab, rank) a voxel; then phase(first, last, field_of) does
+// the entry's own work on the batch, field_of(k) being job k's map or the caller's field, which is read in place.
+template <class Job, class Value, class Phase>
+void host_field_batches(const Job* jobs, long n_jobs, const double* xyz, const double* coef, const double* field,
+                        long workspace_bytes, int threads, Value value, Phase phase) {
+    struct Slab { long job, a, b; };
     std::vector<double> maps;
     std::vector<long> map_first((size_t)n_jobs);
     for (long first = 0; first < n_jobs;) {
         long last = first, words = 0;
-        std::vector<Piece> slabs, pieces;
+        std::vector<Slab> slabs;
         for (; last < n_jobs; ++last) {
-            const pw_passage_job& J = jobs[last];
+            const Job& J = jobs[last];
             const long V = (long)J.nx * J.ny * J.nz;
-            if (last > first && J.field_first == -1 && words + V > PAS_WORKSPACE_BYTES / 8) break;
+            if (last > first && J.field_first == -1 && words + V > workspace_bytes / 8) break;
             map_first[last] = words;
-            if (J.field_first == -1) {                               // (a caller's field is read in place)
-                words += V;
-                for (long a = 0; a < V; a += PAS_HOST_SLAB) slabs.push_back({last, a, std::min(a + PAS_HOST_SLAB, V)});
-            }
-            for (long k = 0; k < pas_rows_out((long)J.m); ++k) pieces.push_back({last, k, 0});
+            if (J.field_first != -1) continue;
+            words += V;
+            for (long a = 0; a < V; a += FIELD_HOST_SLAB) slabs.push_back({last, a, std::min(a + FIELD_HOST_SLAB, V)});
         }
         maps.resize((size_t)words);
-        cov_share((long)slabs.size(), threads, [&](long s) {
-            const Piece& piece = slabs[s];
-            const pw_passage_job& J = jobs[piece.job];
+        host_share((long)slabs.size(), threads, [&](long s) {
+            const Slab& piece = slabs[s];
+            const Job& J = jobs[piece.job];
             const double* atoms = xyz + 3 * (long)J.atom_first;
             const double* ab = coef + 2 * (long)J.coef_first;
             double* U = maps.data() + map_first[piece.job];
-            for (long rank = piece.a; rank < piece.b; ++rank) {
-                const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx);
-                const double x = cavity_coord(J.origin[0], i, J.spacing), y = cavity_coord(J.origin[1], row % J.ny, J.spacing),
-                             z = cavity_coord(J.origin[2], row / J.ny, J.spacing);
-                double u_sum = 0.0;
-                bool blocked = false;
-                for (long a = 0; a < (long)J.n && !blocked; ++a) {
-                    const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
-                    blocked = aff_blocked(r2, J.core2);
-                    if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
-                }
-                U[rank] = blocked ? aff_inf() : u_sum;
-            }
+            for (long rank = piece.a; rank < piece.b; ++rank) U[rank] = value(J, atoms, ab, rank);
         });
-        cov_share((long)pieces.size(), threads, [&](long p) {
+        phase(first, last, [&](long k) -> const double* {
+            return jobs[k].field_first == -1 ? maps.data() + map_first[k] : field + (long)jobs[k].field_first;
+        });
+        first = last;
+    }
+}
+}  // namespace
+
+// pw_passage on the host (pw_passage.hip checks the arguments and sends device == -1 contexts here): the plane test and
+// the fill of pw_cavity.hpp, the keys and the bisection of pw_passage.hpp, on the maps of host_field_batches within
+// PAS_WORKSPACE_BYTES.  A batch's (job, row) pieces are shared out; a piece builds its held words, then runs level after
+// level: the allowed words from the map, the fill, the face test.
+extern "C" int pw_hostpath_passage(const pw_passage_job* jobs, long n_jobs, const double* xyz, const double* coef,
+                                   const double* planes, const double* field, pw_passage_out* out, int* fills,
+                                   int threads) {
+    typedef cavity_word u64;
+    struct Piece { long job, row; };
+    host_field_batches(jobs, n_jobs, xyz, coef, field, PAS_WORKSPACE_BYTES, threads, GridFieldValue(),
+                       [&](long first, long last, auto field_of) {
+        std::vector<Piece> pieces;
+        for (long job = first; job < last; ++job)
+            for (long k = 0; k < pas_rows_out((long)jobs[job].m); ++k) pieces.push_back({job, k});
+        host_share((long)pieces.size(), threads, [&](long p) {
             const pw_passage_job& J = jobs[pieces[p].job];
-            const long k = pieces[p].a;
+            const long k = pieces[p].row;
             const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
-            const double* U = J.field_first == -1 ? maps.data() + map_first[pieces[p].job] : field + (long)J.field_first;
+            const double* U = field_of(pieces[p].job);
             const double* cuts = planes + 4 * (long)J.plane_first;
             const CavityHostGrid G{nullptr, nullptr, nullptr, 0, 0, J.origin, J.spacing, nx, ny, nz, J.seed};
             std::vector<u64> held((size_t)rows), open((size_t)rows), fill((size_t)rows);
@@ -1763,77 +1668,35 @@ extern "C" int pw_hostpath_passage(const pw_passage_job* jobs, long n_jobs, cons
                     }
                 o.barrier = saddle_rank >= 0 ? U[saddle_rank] : aff_inf();
                 o.well = U[well_rank];
-                const long ranks[2] = {saddle_rank, well_rank};
-                for (int w = 0; w < 2; ++w) {
-                    int* v = w ? o.well_voxel : o.saddle;
-                    const long row = ranks[w] / nx;
-                    v[0] = ranks[w] >= 0 ? (int)(ranks[w] - row * nx) : -1;
-                    v[1] = ranks[w] >= 0 ? (int)(row % ny) : -1;
-                    v[2] = ranks[w] >= 0 ? (int)(row / ny) : -1;
-                }
+                grid_voxel(saddle_rank, nx, ny, o.saddle);
+                grid_voxel(well_rank, nx, ny, o.well_voxel);
             }
             out[(long)J.out_first + k] = o;
             if (fills) fills[(long)J.out_first + k] = n_fills;
         });
-        first = last;
-    }
+    });
     return PW_OK;
 }
 
-// pw_hop on the host (pw_hop.hip checks the arguments and sends device == -1 contexts here): the pair terms of
-// pw_affinity.hpp, the plane test of pw_cavity.hpp, the fill, the minimum and the sums of pw_hop.hpp.  Jobs go in order
-// in batches whose maps fit HOP_WORKSPACE_BYTES; within a batch the threads first share out slabs of HOP_HOST_SLAB voxels
-// of the maps of the jobs without a field of their own, then the (job, slab) pieces; a job's row of out is put together
-// from its pieces' counts and flags afterwards.
+// pw_hop on the host (pw_hop.hip checks the arguments and sends device == -1 contexts here): the plane test of
+// pw_cavity.hpp, the fill, the minimum and the sums of pw_hop.hpp, on the maps of host_field_batches within
+// HOP_WORKSPACE_BYTES.  A batch's (job, slab) pieces are shared out; a job's row of out is put together from its pieces'
+// counts and flags afterwards.
 extern "C" int pw_hostpath_hop(const pw_hop_job* jobs, long n_jobs, const double* xyz, const double* coef,
                                const double* planes, const double* field, const double* betas, pw_hop_slab* slabs,
                                pw_affinity_level* sums, pw_hop_out* out, unsigned long long* words, int threads) {
     typedef cavity_word u64;
-    constexpr long HOP_HOST_SLAB = 4096;
-    struct Piece { long job, a, b; };                                // a slab [a, b) of a map, or slab a of a job
-    std::vector<double> maps;
-    std::vector<long> map_first((size_t)n_jobs);
-    for (long first = 0; first < n_jobs;) {
-        long last = first, map_words = 0;
-        std::vector<Piece> slices, pieces;
-        for (; last < n_jobs; ++last) {
-            const pw_hop_job& J = jobs[last];
-            const long V = (long)J.nx * J.ny * J.nz;
-            if (last > first && J.field_first == -1 && map_words + V > HOP_WORKSPACE_BYTES / 8) break;
-            map_first[last] = map_words;
-            if (J.field_first == -1) {                               // (a caller's field is read in place)
-                map_words += V;
-                for (long a = 0; a < V; a += HOP_HOST_SLAB) slices.push_back({last, a, std::min(a + HOP_HOST_SLAB, V)});
-            }
-            for (long l = 0; l < J.nz; ++l) pieces.push_back({last, l, 0});
-        }
-        maps.resize((size_t)map_words);
+    struct Piece { long job, slab; };
+    host_field_batches(jobs, n_jobs, xyz, coef, field, HOP_WORKSPACE_BYTES, threads, GridFieldValue(),
+                       [&](long first, long last, auto field_of) {
+        std::vector<Piece> pieces;
+        for (long job = first; job < last; ++job)
+            for (long l = 0; l < jobs[job].nz; ++l) pieces.push_back({job, l});
         std::vector<int> piece_flags(pieces.size(), 0);
-        cov_share((long)slices.size(), threads, [&](long s) {
-            const Piece& piece = slices[s];
-            const pw_hop_job& J = jobs[piece.job];
-            const double* atoms = xyz + 3 * (long)J.atom_first;
-            const double* ab = coef + 2 * (long)J.coef_first;
-            double* U = maps.data() + map_first[piece.job];
-            for (long rank = piece.a; rank < piece.b; ++rank) {
-                const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx);
-                const double x = cavity_coord(J.origin[0], i, J.spacing), y = cavity_coord(J.origin[1], row % J.ny, J.spacing),
-                             z = cavity_coord(J.origin[2], row / J.ny, J.spacing);
-                double u_sum = 0.0;
-                bool blocked = false;
-                for (long a = 0; a < (long)J.n && !blocked; ++a) {
-                    const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
-                    blocked = aff_blocked(r2, J.core2);
-                    if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
-                }
-                U[rank] = blocked ? aff_inf() : u_sum;
-            }
-        });
-        cov_share((long)pieces.size(), threads, [&](long p) {
+        host_share((long)pieces.size(), threads, [&](long p) {
             const pw_hop_job& J = jobs[pieces[p].job];
-            const int l = (int)pieces[p].a, nx = J.nx, ny = J.ny, L = (int)J.n_betas;
-            const double* U = (J.field_first == -1 ? maps.data() + map_first[pieces[p].job] : field + (long)J.field_first) +
-                              (long)l * ny * nx;
+            const int l = (int)pieces[p].slab, nx = J.nx, ny = J.ny, L = (int)J.n_betas;
+            const double* U = field_of(pieces[p].job) + (long)l * ny * nx;
             const double* cuts = planes + 4 * (long)J.plane_first;
             const double z = cavity_coord(J.origin[2], l, J.spacing);
             u64 open[CAVITY_MAX_G], fill[CAVITY_MAX_G];
@@ -1916,8 +1779,7 @@ extern "C" int pw_hostpath_hop(const pw_hop_job* jobs, long n_jobs, const double
             }
             out[(long)J.out] = o;
         }
-        first = last;
-    }
+    });
     return PW_OK;
 }
 
@@ -1927,7 +1789,6 @@ extern "C" int pw_hostpath_hop(const pw_hop_job* jobs, long n_jobs, const double
 // The threads share out the jobs; a job's row and charges are its own.
 extern "C" int pw_hostpath_charges(const pw_charges_job* jobs, long n_jobs, const double* xyz, const double* params,
                                    double* charges, pw_charges_out* out, int threads) {
-    std::atomic<long> next{0};
     auto one = [&](const pw_charges_job& J) {
         const long n = (long)J.n;
         const double* X = xyz + 3 * (long)J.xyz_first;
@@ -2044,36 +1905,80 @@ extern "C" int pw_hostpath_charges(const pw_charges_job* jobs, long n_jobs, cons
         o->flags = flags;
         o->reserved = 0;
     };
-    auto worker = [&]() {
-        for (;;) {
-            const long k = next.fetch_add(1);
-            if (k >= n_jobs) break;
-            one(jobs[k]);
-        }
-    };
-    if (threads < 1) threads = 1;
-    const int count = (long)threads > n_jobs ? (int)std::max(1l, n_jobs) : threads;
-    if (count == 1) {
-        worker();
-    } else {
-        std::vector<std::thread> pool;
-        for (int t = 0; t < count; ++t) pool.emplace_back(worker);
-        for (auto& t : pool) t.join();
-    }
+    host_share(n_jobs, threads, [&](long k) { one(jobs[k]); });
     return PW_OK;
 }
 
-// pw_channels on the host (pw_channels.hip checks the arguments and sends device == -1 contexts here): the centres,
-// the gathering of the neighbour rows, the spread inside a word, the fills that are not run and the rank of
-// pw_channels.hpp.  The threads share out the jobs; a job is a plain loop: classify, then component after component
-// from the first set bit of todo, each fill as sweeps forwards and backwards over the words until one changes nothing
-// (at most 2 * nx * ny * nz + 1 of them).  A job's outputs are its own.
+// The component of a seed voxel in the open words of a periodic grid and how it winds (pw_channels.hpp), for
+// pw_hostpath_channels and pw_hostpath_percolation: chan_walk of pw_channels_dev.hpp as a plain loop.
+namespace {
+// From the bit seed_bit of row seed_row, which is open: up to seven fills for the phi that channels_next asks for, phi = 7
+// first, channels_learn after each; the first fill also gives the voxels and the three crossing counts of the component
+// (channels_row_cross) and `cross`.  A fill is sweeps forwards and backwards over the rows until one changes nothing, at
+// most 2 * nx * ny * nz + 1 of them.  On return p0 | p1 is the component.
+// A row is skipped when the words gathered for it miss its open word.  That changes nothing: the row's own p0, p1 are
+// among the gathered words and lie inside its open word (the seed is open, every other store is a result of
+// channels_fill_words), so they are zero then, and the fill of nothing gives g0 = g1 = 0 as well.  chan_fill on the
+// device skips the same rows.
+ChannelsWalk channels_host_walk(const std::vector<cavity_word>& open, std::vector<cavity_word>& p0, std::vector<cavity_word>& p1,
+                                int seed_row, cavity_word seed_bit, int nx, int ny, int nz) {
+    typedef cavity_word u64;
+    const int rows = ny * nz;
+    const long max_sweeps = 2 * (long)nx * ny * nz + 1;
+    auto load = [&](int q, int row) { return q ? p1[row] : p0[row]; };
+    ChannelsWalk W{0, 0, 0, {0, 0, 0}};
+    int known = 0, cross = 0, phi = 7;
+    for (; W.fills < 7 && phi; ++W.fills) {
+        std::fill(p0.begin(), p0.end(), 0);
+        std::fill(p1.begin(), p1.end(), 0);
+        p0[seed_row] = seed_bit;
+        auto visit = [&](int r) {
+            if (!open[r]) return false;
+            u64 from0 = p0[r], from1 = p1[r], g0, g1;
+            channels_gather(load, r % ny, r / ny, ny, nz, phi, from0, from1);
+            if (!((from0 | from1) & open[r])) return false;
+            channels_fill_words(from0, from1, open[r], nx, (phi & 1) != 0, g0, g1);
+            const bool changed = g0 != p0[r] || g1 != p1[r];
+            p0[r] = g0;
+            p1[r] = g1;
+            return changed;
+        };
+        for (long sweep = 0; sweep < max_sweeps; ++sweep) {
+            bool changed = false;
+            for (int r = 0; r < rows; ++r) changed = visit(r) || changed;
+            for (int r = rows - 1; r >= 0; --r) changed = visit(r) || changed;
+            if (!changed) break;
+        }
+        const bool reached = (p1[seed_row] & seed_bit) != 0;
+        channels_learn(phi, reached, known, W.wraps);
+        if (W.fills == 0) {
+            for (int r = 0; r < rows; ++r) {
+                const u64 f = p0[r] | p1[r];
+                if (!f) continue;
+                const int j = r % ny, l = r / ny;
+                long c[3];
+                channels_row_cross(f, p0[l * ny] | p1[l * ny], p0[j] | p1[j], nx, ny, nz, j, l, c);
+                W.n_voxels += cavity_popcount(f);
+                for (int a = 0; a < 3; ++a) W.n_cross[a] += c[a];
+            }
+            for (int a = 0; a < 3; ++a) cross |= (W.n_cross[a] > 0) << a;
+            if (cross) channels_learn(cross, reached, known, W.wraps);
+        }
+        phi = channels_next(cross, known, W.wraps);
+    }
+    return W;
+}
+}  // namespace
+
+// pw_channels on the host (pw_channels.hip checks the arguments and sends device == -1 contexts here): the centres and
+// the rank of pw_channels.hpp, the components by channels_host_walk.  The threads share out the jobs; a job is a plain
+// loop: classify, then component after component from the first set bit of todo.  A job's outputs are its own.
 extern "C" int pw_hostpath_channels(const pw_channels_job* jobs, long n_jobs, const double* xyz, const double* radii,
                                     pw_channels_out* out, pw_channels_comp* comps, unsigned long long* mask,
                                     unsigned char* labels, const unsigned long long* open_words, const long* open_first,
                                     int threads) {
     typedef cavity_word u64;
-    cov_share(n_jobs, threads, [&](long k) {
+    host_share(n_jobs, threads, [&](long k) {
         const pw_channels_job& J = jobs[k];
         const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
         std::vector<u64> todo((size_t)rows), p0((size_t)rows), p1((size_t)rows), acc((size_t)rows, 0);
@@ -2106,8 +2011,6 @@ extern "C" int pw_hostpath_channels(const pw_channels_job* jobs, long n_jobs, co
                     if (!((todo[r] >> i) & 1ull)) label[(long)r * nx + i] = (unsigned char)CHAN_LABEL_CLOSED;
         }
         pw_channels_comp* table = comps + (long)J.comp_first;
-        const long max_sweeps = 2 * (long)nx * ny * nz + 1;
-        auto load = [&](int q, int row) { return q ? p1[row] : p0[row]; };
         long count = 0;
         for (int seed_row = 0; seed_row < rows;) {
             if (!todo[seed_row]) {
@@ -2115,51 +2018,13 @@ extern "C" int pw_hostpath_channels(const pw_channels_job* jobs, long n_jobs, co
                 continue;
             }
             const int seed_i = __builtin_ctzll(todo[seed_row]);
-            const u64 seed_bit = 1ull << seed_i;
-            int known = 0, wraps = 0, cross = 0, phi = 7;
-            bool measured = false;
+            const ChannelsWalk W = channels_host_walk(todo, p0, p1, seed_row, 1ull << seed_i, nx, ny, nz);
             pw_channels_comp C{};
-            for (int fill = 0; fill < 7 && phi; ++fill) {
-                std::fill(p0.begin(), p0.end(), 0);
-                std::fill(p1.begin(), p1.end(), 0);
-                p0[seed_row] = seed_bit;
-                auto visit = [&](int r) {
-                    if (!todo[r]) return false;
-                    u64 from0 = p0[r], from1 = p1[r], g0, g1;
-                    channels_gather(load, r % ny, r / ny, ny, nz, phi, from0, from1);
-                    channels_fill_words(from0, from1, todo[r], nx, (phi & 1) != 0, g0, g1);
-                    const bool changed = g0 != p0[r] || g1 != p1[r];
-                    p0[r] = g0;
-                    p1[r] = g1;
-                    return changed;
-                };
-                for (long sweep = 0; sweep < max_sweeps; ++sweep) {
-                    bool changed = false;
-                    for (int r = 0; r < rows; ++r) changed = visit(r) || changed;
-                    for (int r = rows - 1; r >= 0; --r) changed = visit(r) || changed;
-                    if (!changed) break;
-                }
-                const bool reached = (p1[seed_row] & seed_bit) != 0;
-                channels_learn(phi, reached, known, wraps);
-                if (!measured) {
-                    for (int r = 0; r < rows; ++r) {
-                        const u64 f = p0[r] | p1[r];
-                        if (!f) continue;
-                        const int j = r % ny, l = r / ny;
-                        long c[3];
-                        channels_row_cross(f, p0[l * ny] | p1[l * ny], p0[j] | p1[j], nx, ny, nz, j, l, c);
-                        C.n_voxels += cavity_popcount(f);
-                        for (int a = 0; a < 3; ++a) C.n_cross[a] += c[a];
-                    }
-                    for (int a = 0; a < 3; ++a) cross |= (C.n_cross[a] > 0) << a;
-                    if (cross) channels_learn(cross, reached, known, wraps);
-                    measured = true;
-                }
-                phi = channels_next(cross, known, wraps);
-            }
             C.first = (long)seed_row * nx + seed_i;
-            C.wraps = wraps;
-            C.rank = channels_rank(wraps);
+            C.n_voxels = W.n_voxels;
+            for (int a = 0; a < 3; ++a) C.n_cross[a] = W.n_cross[a];
+            C.wraps = W.wraps;
+            C.rank = channels_rank(W.wraps);
             const unsigned char name = (unsigned char)(count < J.c_max ? count : CHAN_LABEL_BEYOND);
             for (int r = 0; r < rows; ++r) {
                 const u64 f = p0[r] | p1[r];
@@ -2191,77 +2056,28 @@ extern "C" int pw_hostpath_channels(const pw_channels_job* jobs, long n_jobs, co
     return PW_OK;
 }
 
-// the Lennard-Jones energy of the voxel `rank` of the grid of a periodic cell (pw_percolation_job, pw_basins_job):
-// pw_field_cell_dev.hpp's terms in its order; the atoms after one that blocks the voxel add nothing to +inf
-template <class Job>
-inline double cell_field_value(const Job& J, const double* atoms, const double* ab, long rank) {
-    const int row = (int)(rank / J.nx), i = (int)(rank - (long)row * J.nx), j = row % J.ny, l = row / J.ny;
-    const double x = channels_x(J.origin[0], i, J.step[0], j, J.step[1], l, J.step[3]),
-                 y = channels_y(J.origin[1], j, J.step[2], l, J.step[4]), z = channels_z(J.origin[2], l, J.step[5]);
-    double u_sum = 0.0;
-    bool blocked = false;
-    for (long a = 0; a < (long)J.n && !blocked; ++a) {
-        const double r2 = aff_r2(x - atoms[3 * a], y - atoms[3 * a + 1], z - atoms[3 * a + 2]);
-        blocked = aff_blocked(r2, J.core2);
-        if (!blocked && aff_counts(r2, J.cutoff2)) u_sum = u_sum + aff_pair(r2, ab[2 * a], ab[2 * a + 1]);
-    }
-    return blocked ? aff_inf() : u_sum;
-}
-
-// pw_percolation on the host (pw_percolate.hip checks the arguments and sends device == -1 contexts here): the centres
-// and the fill of pw_channels.hpp, the pair terms of pw_affinity.hpp, the keys of pw_passage.hpp, the candidates and the
-// search of pw_percolate.hpp.  Jobs go in order in batches whose maps fit PERC_WORKSPACE_BYTES; within a batch the
-// threads first share out slabs of PERC_HOST_SLAB voxels of the maps of the jobs without a field of their own, then the
-// jobs.  A job is a plain loop: the scan of its map, the search -- an evaluation is the allowed words from the map, the
-// candidates, then component after component from the first candidate as pw_hostpath_channels fills them --, and one
-// evaluation at each distinct level for the rows.  n_evaluations, n_fills (may be null): per job, diagnostic.
+// pw_percolation on the host (pw_percolate.hip checks the arguments and sends device == -1 contexts here): the keys of
+// pw_passage.hpp, the candidates and the search of pw_percolate.hpp, on the maps of host_field_batches within
+// PERC_WORKSPACE_BYTES.  A batch's jobs are shared out.  A job is a plain loop: the scan of its map, the search -- an
+// evaluation is the allowed words from the map, the candidates, then component after component from the first candidate
+// by channels_host_walk --, and one evaluation at each distinct level for the rows.  n_evaluations, n_fills (may be
+// null): per job, diagnostic.
 extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jobs, const double* xyz, const double* coef,
                                        const double* field, double* map, pw_percolation_level* levels, pw_percolation_out* out,
                                        int* n_evaluations, int* n_fills, int threads) {
     typedef cavity_word u64;
-    constexpr long PERC_HOST_SLAB = 4096, NO_RANK = 0x7fffffffffffffffl;
-    struct Slab { long job, a, b; };
-    std::vector<double> maps;
-    std::vector<long> map_first((size_t)n_jobs);
-    for (long first = 0; first < n_jobs;) {
-        long last = first, words = 0;
-        std::vector<Slab> slabs;
-        for (; last < n_jobs; ++last) {
-            const pw_percolation_job& J = jobs[last];
-            const long V = (long)J.nx * J.ny * J.nz;
-            if (last > first && J.field_first == -1 && words + V > PERC_WORKSPACE_BYTES / 8) break;
-            map_first[last] = words;
-            if (J.field_first == -1) {                               // (a caller's field is read in place)
-                words += V;
-                for (long a = 0; a < V; a += PERC_HOST_SLAB) slabs.push_back({last, a, std::min(a + PERC_HOST_SLAB, V)});
-            }
-        }
-        maps.resize((size_t)words);
-        cov_share((long)slabs.size(), threads, [&](long s) {
-            const Slab& piece = slabs[s];
-            const pw_percolation_job& J = jobs[piece.job];
-            const double* atoms = xyz + 3 * (long)J.atom_first;
-            const double* ab = coef + 2 * (long)J.coef_first;
-            double* U = maps.data() + map_first[piece.job];
-            for (long rank = piece.a; rank < piece.b; ++rank) {
-                U[rank] = cell_field_value(J, atoms, ab, rank);
-            }
-        });
-        cov_share(last - first, threads, [&](long q) {
+    constexpr long NO_RANK = 0x7fffffffffffffffl;
+    host_field_batches(jobs, n_jobs, xyz, coef, field, PERC_WORKSPACE_BYTES, threads, CellFieldValue(),
+                       [&](long first, long last, auto field_of) {
+        host_share(last - first, threads, [&](long q) {
             const long k = first + q;
             const pw_percolation_job& J = jobs[k];
             const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz;
             const long V = (long)nx * rows;
-            const double* U = J.field_first == -1 ? maps.data() + map_first[k] : field + (long)J.field_first;
+            const double* U = field_of(k);
             if (J.map_first >= 0)
                 for (long v = 0; v < V; ++v) map[(long)J.map_first + v] = U[v];
             pw_percolation_level* R = levels + (long)J.level_first;
-            auto voxel = [&](long rank, int* v) {
-                const long row = rank / nx;
-                v[0] = rank >= 0 ? (int)(rank - row * nx) : -1;
-                v[1] = rank >= 0 ? (int)(row % ny) : -1;
-                v[2] = rank >= 0 ? (int)(row / ny) : -1;
-            };
             // the scan
             u64 kmin = PAS_KEY_NONE, kmax = 0;
             long min_rank = NO_RANK, n_blocked = 0;
@@ -2281,8 +2097,6 @@ extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jo
             std::vector<u64> allowed((size_t)rows), todo((size_t)rows), p0((size_t)rows), p1((size_t)rows);
             long best[PERC_CRITERIA];
             int evaluations = 0, fills = 0;
-            const long max_sweeps = 2 * V + 1;
-            auto load = [&](int q2, int row) { return q2 ? p1[row] : p0[row]; };
             // an evaluation (pw_percolate.hip: perc_evaluate)
             auto evaluate = [&](u64 level, int asked, bool final, bool& complete, u64& below, u64& above) {
                 ++evaluations;
@@ -2315,50 +2129,10 @@ extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jo
                         continue;
                     }
                     const u64 seed_bit = 1ull << __builtin_ctzll(todo[seed_row]);
-                    int known = 0, wraps = 0, cross = 0, phi = 7;
-                    bool measured = false;
-                    long n_voxels = 0;
-                    for (int fill = 0; fill < 7 && phi; ++fill) {
-                        std::fill(p0.begin(), p0.end(), 0);
-                        std::fill(p1.begin(), p1.end(), 0);
-                        p0[seed_row] = seed_bit;
-                        ++fills;
-                        auto visit = [&](int r) {
-                            if (!allowed[r]) return false;
-                            u64 from0 = p0[r], from1 = p1[r], g0, g1;
-                            channels_gather(load, r % ny, r / ny, ny, nz, phi, from0, from1);
-                            if (!((from0 | from1) & allowed[r])) return false;
-                            channels_fill_words(from0, from1, allowed[r], nx, (phi & 1) != 0, g0, g1);
-                            const bool changed = g0 != p0[r] || g1 != p1[r];
-                            p0[r] = g0;
-                            p1[r] = g1;
-                            return changed;
-                        };
-                        for (long sweep = 0; sweep < max_sweeps; ++sweep) {
-                            bool changed = false;
-                            for (int r = 0; r < rows; ++r) changed = visit(r) || changed;
-                            for (int r = rows - 1; r >= 0; --r) changed = visit(r) || changed;
-                            if (!changed) break;
-                        }
-                        const bool reached = (p1[seed_row] & seed_bit) != 0;
-                        channels_learn(phi, reached, known, wraps);
-                        if (!measured) {
-                            long n_cross[3] = {0, 0, 0};
-                            for (int r = 0; r < rows; ++r) {
-                                const u64 f = p0[r] | p1[r];
-                                if (!f) continue;
-                                const int j = r % ny, l = r / ny;
-                                long c[3];
-                                channels_row_cross(f, p0[l * ny] | p1[l * ny], p0[j] | p1[j], nx, ny, nz, j, l, c);
-                                n_voxels += cavity_popcount(f);
-                                for (int a = 0; a < 3; ++a) n_cross[a] += c[a];
-                            }
-                            for (int a = 0; a < 3; ++a) cross |= (n_cross[a] > 0) << a;
-                            if (cross) channels_learn(cross, reached, known, wraps);
-                            measured = true;
-                        }
-                        phi = channels_next(cross, known, wraps);
-                    }
+                    const ChannelsWalk W = channels_host_walk(allowed, p0, p1, seed_row, seed_bit, nx, ny, nz);
+                    const int wraps = W.wraps;
+                    const long n_voxels = W.n_voxels;
+                    fills += W.fills;
                     const int crit = perc_criteria(wraps);
                     met |= crit;
                     long comp_first = -1;
@@ -2402,8 +2176,8 @@ extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jo
                         O.well = U[well_rank];
                         O.first = comp_first;
                         O.n_voxels = n_voxels;
-                        voxel(saddle_rank, O.saddle);
-                        voxel(well_rank, O.well_voxel);
+                        grid_voxel(saddle_rank, nx, ny, O.saddle);
+                        grid_voxel(well_rank, nx, ny, O.well_voxel);
                         O.wraps = wraps;
                         O.rank = channels_rank(wraps);
                         O.flags = 0;
@@ -2421,7 +2195,7 @@ extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jo
             pw_percolation_out& O = out[(long)J.out];
             O.n_blocked = n_blocked;
             O.u_min = some ? U[min_rank] : aff_inf();
-            voxel(some ? min_rank : -1, O.u_min_voxel);
+            grid_voxel(some ? min_rank : -1, nx, ny, O.u_min_voxel);
             O.flags = (met_at_top & 1) ? 0 : PERC_NEVER;
             for (int c = 0; c < PERC_CRITERIA; ++c) {
                 pw_percolation_level none{};
@@ -2454,8 +2228,7 @@ extern "C" int pw_hostpath_percolation(const pw_percolation_job* jobs, long n_jo
             if (n_evaluations) n_evaluations[k] = evaluations;
             if (n_fills) n_fills[k] = fills;
         });
-        first = last;
-    }
+    });
     return PW_OK;
 }
 
@@ -2468,7 +2241,7 @@ extern "C" int pw_hostpath_basins(const pw_basins_job* jobs, long n_jobs, const 
                                   double* map, pw_basins_basin* basins, pw_basins_edge* edges, pw_basins_label* labels,
                                   pw_basins_out* out, int* n_rounds, int* n_faces, int threads) {
     typedef cavity_word u64;
-    cov_share(n_jobs, threads, [&](long job) {
+    host_share(n_jobs, threads, [&](long job) {
         const pw_basins_job& J = jobs[job];
         const int nx = J.nx, ny = J.ny, nz = J.nz, rows = ny * nz, L = J.n_betas;
         const long V = (long)nx * rows;
@@ -2476,7 +2249,7 @@ extern "C" int pw_hostpath_basins(const pw_basins_job* jobs, long n_jobs, const 
         const double* U = field + (long)J.field_first;
         if (J.field_first == -1) {
             own.resize((size_t)V);
-            for (long v = 0; v < V; ++v) own[v] = cell_field_value(J, xyz + 3 * (long)J.atom_first, coef + 2 * (long)J.coef_first, v);
+            for (long v = 0; v < V; ++v) own[v] = CellFieldValue()(J, xyz + 3 * (long)J.atom_first, coef + 2 * (long)J.coef_first, v);
             U = own.data();
         }
         if (J.map_first >= 0)
@@ -2657,10 +2430,7 @@ extern "C" int pw_hostpath_basins(const pw_basins_job* jobs, long n_jobs, const 
         O.n_basins_written = b_written;
         O.n_edges_written = e_written;
         O.u_min = min_rank >= 0 ? U[min_rank] : aff_inf();
-        const long row = min_rank >= 0 ? min_rank / nx : 0;
-        O.u_min_voxel[0] = min_rank >= 0 ? (int)(min_rank - row * nx) : -1;
-        O.u_min_voxel[1] = min_rank >= 0 ? (int)(row % ny) : -1;
-        O.u_min_voxel[2] = min_rank >= 0 ? (int)(row / ny) : -1;
+        grid_voxel(min_rank, nx, ny, O.u_min_voxel);
         O.flags = (overflow ? BAS_OVERFLOW : 0) | (clamped ? BAS_CLAMPED : 0) | (range ? BAS_RANGE : 0);
         out[(long)J.out] = O;
         if (n_rounds) n_rounds[job] = 0;

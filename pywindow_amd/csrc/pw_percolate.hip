@@ -10,8 +10,8 @@
 //            (128.5 KiB at 64 x 64 rows); the map stays in the workspace.  One scan of the map gives n_blocked, u_min and
 //            the two ends of the keys.  AN EVALUATION of a level (perc_evaluate): a wave a row ballots key <= level into
 //            the row's word, keeping the nearest keys on both sides; todo = perc_candidates; then pw_channels_kernel's
-//            component loop -- the first bit of todo by an integer workgroup minimum, the fill for phi = 7 (the
-//            component, n_voxels, n_cross), the fills channels_next asks for -- and the component leaves todo.  It stops
+//            component loop by the same functions (pw_channels_dev.hpp) -- chan_first, the first bit of todo; chan_walk,
+//            the component, its n_voxels and winding bits -- and the component leaves todo.  It stops
 //            as soon as every criterion it was asked about is met.  The search of pw_percolate.hpp lives in LDS, stepped
 //            by thread 0 between barriers; then one evaluation that goes through every candidate at each distinct B_c
 //            writes the rows: of the components that meet a criterion, the one with the lowest first voxel, measured
@@ -230,13 +230,6 @@ __device__ inline void perc_measure(const u64* __restrict__ map, int nx, int row
     saddle_rank = sr == PERC_NO_RANK ? -1 : sr;
 }
 
-__device__ inline void perc_voxel(long rank, int nx, int ny, int* v) {
-    const long row = rank / nx;
-    v[0] = rank >= 0 ? (int)(rank - row * nx) : -1;
-    v[1] = rank >= 0 ? (int)(row % ny) : -1;
-    v[2] = rank >= 0 ? (int)(row / ny) : -1;
-}
-
 // AN EVALUATION of the level `key` (the head of the file): the criteria met by the components found, bit c for criterion
 // c.  `asked`: with rows == nullptr the criteria after all of which the evaluation stops (complete = false then); with
 // rows the criteria whose rows are written at this level, and every candidate is gone through.  The same in every thread;
@@ -261,55 +254,14 @@ __device__ inline int perc_evaluate(const u64* __restrict__ map, int nx, int ny,
     int met = 0;
     complete = true;
     const long n_voxels_grid = (long)nx * rows;
-    int cursor = tid;                                                // no row of this thread before it has a bit of todo
+    int cursor = tid;                                                // (chan_first's, pw_channels_dev.hpp)
     for (long turn = 0; turn <= n_voxels_grid; ++turn) {             // (a turn takes a candidate or more out of todo, or ends)
-        if (tid == 0) S->first = PERC_NONE;
-        __syncthreads();
-        while (cursor < rows && !s_todo[cursor]) cursor += CAV_THREADS;
-        if (cursor < rows) atomicMin(&S->first, (unsigned)cursor * 64u + (unsigned)(__ffsll((long long)s_todo[cursor]) - 1));
-        __syncthreads();
-        const unsigned first = S->first;
-        if (first == PERC_NONE) break;
-        const int seed_row = (int)(first >> 6);
-        const u64 seed_bit = 1ull << (first & 63u);
-
-        int known = 0, wraps = 0, cross = 0, phi = 7;
-        bool measured = false;
-        long n_voxels = 0;
-        for (int fill = 0; fill < 7 && phi; ++fill) {                    // (seven bits to learn)
-            __syncthreads();                                         // (everybody has read what the last fill left)
-            for (int r = tid; r < rows; r += CAV_THREADS) {
-                s_p0[r] = r == seed_row ? seed_bit : 0;
-                s_p1[r] = 0;
-            }
-            if (!measured && tid < 4) S->sum[tid] = 0;
-            __syncthreads();
-            chan_fill(s_allowed, s_p0, s_p1, nx, ny, nz, phi);
-            ++fills;
-            const bool reached = (s_p1[seed_row] & seed_bit) != 0;
-            channels_learn(phi, reached, known, wraps);
-            if (!measured) {
-                for (int r = tid; r < rows; r += CAV_THREADS) {
-                    const u64 f = s_p0[r] | s_p1[r];
-                    if (!f) continue;
-                    const int j = r % ny, l = r / ny;
-                    const int rj = l * ny, rl = j;                   // the rows (0, l) and (j, 0)
-                    long c[3];
-                    channels_row_cross(f, s_p0[rj] | s_p1[rj], s_p0[rl] | s_p1[rl], nx, ny, nz, j, l, c);
-                    atomicAdd(S->sum + 0, (unsigned long long)cavity_popcount(f));
-#pragma unroll
-                    for (int k = 0; k < 3; ++k)
-                        if (c[k]) atomicAdd(S->sum + 1 + k, (unsigned long long)c[k]);
-                }
-                __syncthreads();
-                n_voxels = (long)S->sum[0];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) cross |= (S->sum[1 + k] > 0) << k;
-                if (cross) channels_learn(cross, reached, known, wraps);   // ((1): phi = 7 and phi = cross are one graph)
-                measured = true;
-            }
-            phi = channels_next(cross, known, wraps);
-        }
+        const unsigned first = chan_first(s_todo, rows, cursor, &S->first);
+        if (first == CHAN_NONE) break;
+        const ChannelsWalk W = chan_walk(s_allowed, s_p0, s_p1, S->sum, (int)(first >> 6), 1ull << (first & 63u), nx, ny, nz);
+        const long n_voxels = W.n_voxels;
+        const int wraps = W.wraps;
+        fills += W.fills;
         const int crit = perc_criteria(wraps);
         met |= crit;
 
@@ -352,8 +304,8 @@ __device__ inline int perc_evaluate(const u64* __restrict__ map, int nx, int ny,
                 R.well = pw_bits2d(map[well_rank]);
                 R.first = comp_first;
                 R.n_voxels = n_voxels;
-                perc_voxel(saddle_rank, nx, ny, R.saddle);
-                perc_voxel(well_rank, nx, ny, R.well_voxel);
+                grid_voxel(saddle_rank, nx, ny, R.saddle);
+                grid_voxel(well_rank, nx, ny, R.well_voxel);
                 R.wraps = wraps;
                 R.rank = channels_rank(wraps);
                 R.flags = 0;
@@ -401,7 +353,7 @@ pw_percolation_kernel(const PercJobDev* __restrict__ jobs, const u64* __restrict
         pw_percolation_out& O = out[blockIdx.x];
         O.n_blocked = n_blocked;
         O.u_min = some ? pw_bits2d(map[min_rank]) : aff_inf();
-        perc_voxel(some ? min_rank : -1, nx, ny, O.u_min_voxel);
+        grid_voxel(some ? min_rank : -1, nx, ny, O.u_min_voxel);
         O.flags = (met & 1) ? 0 : PERC_NEVER;
         for (int c = 0; c < PERC_CRITERIA; ++c) {                    // (the rows of the criteria that never hold stay so)
             pw_percolation_level& N = R[c];
