@@ -2455,3 +2455,24 @@ extern "C" void pw_hostpath_math(int which, const double* x, const double* y, lo
     std::call_once(g_rsq_once, [] { rsqrt14_decode(g_rsq); });
     for (long i = 0; i < n; ++i) out[i] = pw_math_probe(which, x[i], y ? y[i] : 0.0, g_rsq);
 }
+
+// a batch of optimiser cases on a one-lane team (test instrumentation, pw_lb_probe.hip: pw_internal_lb_probe, which
+// has checked that every image is safe to run); the block is a copy, as the device's is
+#include "pw_lb_probe.hpp"
+template <int N>
+static void lb_probe_host(void* cases, long n_cases) {
+    LbProbeCase<N>* cs = (LbProbeCase<N>*)cases;
+    for (long u = 0; u < n_cases; ++u) {
+        LbMem<N> block = cs[u].mem;
+        lb_probe_run<HostTeam, N>(&cs[u], &block);
+#if defined(PW_PROFILE) && defined(PW_LB_FINE)
+        block.prof_fine = nullptr;      // (a diagnostic build's pointer member: pointers never leave the library)
+#endif
+        cs[u].mem = block;
+    }
+}
+extern "C" int pw_hostpath_lb_probe(int n, void* cases, long n_cases) {
+    if (n == 3) lb_probe_host<3>(cases, n_cases);
+    else lb_probe_host<1>(cases, n_cases);
+    return PW_OK;
+}

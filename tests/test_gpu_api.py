@@ -487,3 +487,17 @@ def test_a_path_that_would_never_end_is_flagged_on_the_device(hip_ctx):
         assert np.array_equal(rec[k], ok[k]), k
     again = hip_ctx.analyse(batch, _lib.STAGE_ALL)
     assert again.tobytes() == ok.tobytes()
+
+
+def test_the_optimiser_probe_refuses_a_device_context(hip_ctx):
+    """pw_internal_lb_probe has a host side only (pywindow_amd/csrc/pw_lb_probe.hip): on a device context it is an
+    error, launches nothing and falls back to nothing -- the case comes back as it went in"""
+    import _lb_cases as C
+
+    c = C.setup_image(3).ops("STEP")
+    before = c.raw.copy()
+    rc, out = C.run_rc(hip_ctx, [c])
+    assert rc == -1 and np.array_equal(out[0].raw, before)      # PW_E_NO_DEVICE
+    bad = c.copy()
+    bad["col"] = 11
+    assert C.run_rc(hip_ctx, [bad])[0] == C.PW_E_BAD_ARG

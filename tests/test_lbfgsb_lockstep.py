@@ -44,3 +44,32 @@ def test_window_neck_runs_are_lockstep_identical(LS):
             n += 1
             if n >= 24:
                 return
+
+
+def _table_runs():
+    import _lb_cases
+
+    return _lb_cases.RUNS
+
+
+@pytest.mark.parametrize("k", range(7))
+def test_analytic_objectives_are_lockstep_identical_and_reach_their_edges(LS, k):
+    """Objectives that reach what the cage objectives do not -- ten correction pairs, the shift of WN1 (iupdat > 10),
+    variables entering and leaving the free set, a restart after a failed line search, an abnormal end -- with the
+    tool's forward-difference gradient.  What each run reaches is asserted, so a later change of an objective cannot
+    quietly lose an edge (tests/_lb_cases.py: RUNS; tests/test_lb_probe.py drives the probe's STEP and MINIMIZE on them)."""
+    name, fun, _, x0, l, u, nbd, reach = _table_runs()[k]
+    trace = []
+    res = LS.lockstep(fun, np.array(x0), np.array(l), np.array(u), list(nbd), trace=trace)
+    assert res["first_bad"] is None, (name, res["first_bad"])
+    trace = np.array(trace)
+    assert res["ncall"] == reach["calls"], name
+    if "col" in reach:
+        assert trace[:, 2].max() == reach["col"], name
+    if "iupdat" in reach:
+        assert trace[:, 5].max() == reach["iupdat"], name
+    if "nfree" in reach:
+        assert set(int(v) for v in trace[:, 10]) == reach["nfree"], name
+    if "info" in reach:
+        assert reach["info"] <= set(int(v) for v in trace[:, 9]), name
+    assert res["task"][0] == (8 if reach.get("ending") == "ABNORMAL" else 4), name

@@ -48,7 +48,9 @@ def layout(n):
     for k, s in names: out[k] = (o, o+s); o += s
     return out, o
 
-def lockstep(fun, x0, lb, ub, nbd, verbose=False, maxcalls=5000):
+def lockstep(fun, x0, lb, ub, nbd, verbose=False, maxcalls=5000, trace=None):
+    """trace: a list that receives, per call, pw::Lbfgsb's integers (hs_lbN_dump: task, msg, col, head, iter, iupdat,
+    nfgv, ifun, iback, info, nfree, nskip, updatd)"""
     n = len(x0); lay, tot = layout(n)
     # scipy side
     x = np.array(x0, float); low = np.where(np.isinf(lb), 0.0, lb); up = np.where(np.isinf(ub), 0.0, ub)
@@ -67,6 +69,7 @@ def lockstep(fun, x0, lb, ub, nbd, verbose=False, maxcalls=5000):
         getattr(L, f"hs_lb{n}_step")(h, P(mx), mf, P(mg), mset)
         getattr(L, f"hs_lb{n}_dump")(h, P(mwa), mint.ctypes.data_as(ip), P(mdbl))
         ncall += 1
+        if trace is not None: trace.append(mint.copy())
         # compare
         bad = []
         if not np.array_equal(x, mx): bad.append(("x", x.copy(), mx.copy()))
