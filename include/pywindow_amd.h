@@ -1234,6 +1234,52 @@ int pw_rigid_cell(pw_context *ctx, const pw_rigid_cell_job *jobs, int64_t n_jobs
                   const double *coef, int64_t n_coef, const double *offsets, int64_t n_offsets, const double *dirs,
                   int64_t n_dirs, const double *betas, int64_t n_betas, double *maps, int64_t n_maps,
                   pw_affinity_level *levels, int64_t n_levels, pw_rigid_out *out, int64_t n_out);
+/* ---- charged rigid guests in a crystal: pw_rigid_cell with the Ewald sum of the framework's point charges ----------
+ * The same field for a guest whose sites carry charges, against a framework of point charges: a defined periodic
+ * electrostatic energy, which a cutoff Coulomb sum over images is not.  The reference has no counterpart.  The text of
+ * record is pywindow_amd/csrc/pw_ewald.hpp; in short, job k is a pw_rigid_cell job (`cell`) whose rows of coef are
+ * (A, B, C), THREE doubles a row, C = coulomb * q_site * q_atom in kJ/mol Angstrom, and which has
+ *     charged (0 or 1): with 0 the job is pw_rigid_cell's definition verbatim and returns that entry's bytes; C, alpha,
+ *     the site charges, the cell atoms and the rows are neither read nor evaluated;
+ *     alpha >= 0, finite, the splitting parameter in 1 / Angstrom;
+ *     S = cell.n_sites site charges site_q[charge_first .. +S);
+ *     n_cell >= 0 cell atoms cell[cell_first .. +n_cell), rows (x, y, z, q) of four doubles: the atoms of the primary
+ *     cell only, in the job's triangular frame, with their charges.  They make the structure factors; the listed atoms
+ *     xyz with their images make the real-space part;
+ *     K = n_k rows kvecs[k_first .. +K), 0 <= K <= PW_EWALD_MAX_K, rows (h, k, l, w) of four doubles: integer-valued
+ *     indices of a reciprocal-lattice vector with |h|, |k|, |l| <= PW_EWALD_MAX_INDEX, and its weight w in kJ/mol per
+ *     squared charge.  The rows are data, as the directions are: nothing derives or orders them.
+ * A counting atom of a charged job adds (C * erfc(alpha * r)) / r to pw_rigid_cell's pair term, truncated at cutoff2 as
+ * that term is; a pose's energy is the sum over its sites and then, last, Urec(v, o) = sum_k (P_ok cos(k . x_v) + Q_ok
+ * sin(k . x_v)) in row order, with P and Q from the structure factors of the cell atoms and the form factors of the
+ * guest in that orientation.  erfc is the library's own (pw_math.hpp: pw_erfc), exactly 1.0 at 0: with alpha == 0 and
+ * K == 0 on a cell with step = (h, 0, h, 0, 0, h) every output shared with a charged pw_rigid_affinity job over the whole
+ * grid is that entry's bytes.  Everything written, the skip of far atoms and the equality of the bytes on every device,
+ * launch geometry, grouping and on a device == -1 context are pw_rigid_cell's.  Left out by design: the guest's
+ * interaction with its own images (infinite dilution); any self or background term (none arises between a guest and a
+ * NEUTRAL framework; neutrality is the caller's to ensure); periodic charge equilibration; non-linear guests.
+ * The counts are pw_rigid_cell's (coef: rows of three doubles) and the entries of site_q, the rows of cell and of kvecs.
+ * Refused (PW_E_BAD_ARG, pw_last_error reads "pw_rigid_cell_ewald: job k: ..."; nothing is launched or written): what
+ * pw_rigid_cell refuses; charged neither 0 nor 1; and of a charged job a charge term C, alpha, a site charge, a cell
+ * atom or a weight that is not finite, alpha < 0, n_k outside 0 .. PW_EWALD_MAX_K, an index that is not an integer within
+ * the cap, a range outside its array. */
+#define PW_EWALD_MAX_K 4096
+#define PW_EWALD_MAX_INDEX 64
+typedef struct pw_rigid_cell_ewald_job {
+    pw_rigid_cell_job cell;         /* the pw_rigid_cell job; rows (A, B, C) = coef[coef_first .. + n_sites*n) */
+    int64_t charge_first;           /* site charges = site_q[charge_first .. + cell.n_sites) */
+    int64_t cell_first, n_cell;     /* cell atoms = cell[cell_first .. +n_cell), rows (x, y, z, q) */
+    int64_t k_first, n_k;           /* rows (h, k, l, w) = kvecs[k_first .. +n_k) */
+    double  alpha;                  /* >= 0 */
+    int32_t charged;                /* 0 or 1 */
+    int32_t reserved;               /* padding to a multiple of 8 bytes; not read */
+} pw_rigid_cell_ewald_job;
+int pw_rigid_cell_ewald(pw_context *ctx, const pw_rigid_cell_ewald_job *jobs, int64_t n_jobs, const double *xyz,
+                        int64_t n_points, const double *coef, int64_t n_coef, const double *offsets, int64_t n_offsets,
+                        const double *dirs, int64_t n_dirs, const double *betas, int64_t n_betas, const double *site_q,
+                        int64_t n_site_q, const double *cell, int64_t n_cell, const double *kvecs, int64_t n_kvecs,
+                        double *maps, int64_t n_maps, pw_affinity_level *levels, int64_t n_levels, pw_rigid_out *out,
+                        int64_t n_out);
 /* ---- partial charges of an isolated molecule: charge equilibration ---------------------------------------------
  * The framework charges that the charged jobs of pw_rigid_affinity need, frame by frame, so that a breathing cage
  * gets the charges of each of its shapes: QEq (Rappe and Goddard 1991) with Ohno-Klopman shielding instead of Slater

@@ -59,6 +59,7 @@ from .rigid_cell import (  # noqa: E402
     rigid_guest_percolation,
     rigid_guest_percolation_batch,
 )
+from .ewald import EwaldPotential, ewald_parameters, ewald_potential  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -75,6 +76,9 @@ from .utilities import (  # noqa: E402
 
 __all__ = [
     "DLPOLY",
+    "EwaldPotential",
+    "ewald_parameters",
+    "ewald_potential",
     "Distribution",
     "Distribution2D",
     "DistributionBand",

@@ -361,6 +361,16 @@ RIGID_CELL_JOB_DTYPE = np.dtype(
 )
 assert RIGID_CELL_JOB_DTYPE.itemsize == 200
 
+#: numpy mirror of ``pw_rigid_cell_ewald_job``: ``cell`` is a ``RIGID_CELL_JOB_DTYPE`` record
+RIGID_CELL_EWALD_JOB_DTYPE = np.dtype(
+    [("cell", RIGID_CELL_JOB_DTYPE), ("charge_first", np.int64), ("cell_first", np.int64), ("n_cell", np.int64),
+     ("k_first", np.int64), ("n_k", np.int64), ("alpha", np.float64), ("charged", np.int32), ("reserved", np.int32)]
+)
+assert RIGID_CELL_EWALD_JOB_DTYPE.itemsize == 256
+#: ``PW_EWALD_MAX_K``, ``PW_EWALD_MAX_INDEX``
+EWALD_MAX_K = 4096
+EWALD_MAX_INDEX = 64
+
 #: numpy mirrors of ``pw_charges_job`` and ``pw_charges_out``
 CHARGES_JOB_DTYPE = np.dtype(
     [("xyz_first", np.int64), ("param_first", np.int64), ("n", np.int64), ("total_charge", np.float64),
@@ -576,6 +586,7 @@ EXPORTED_SYMBOLS = [
     "pw_hop",
     "pw_rigid_affinity",
     "pw_rigid_cell",
+    "pw_rigid_cell_ewald",
     "pw_charges",
     "pw_channels",
     "pw_percolation",
@@ -729,6 +740,9 @@ def load():
     L.pw_internal_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_rigid_cell.argtypes = [vp, vp, i64] + [vp, i64] * 8
     L.pw_internal_rigid_cell.argtypes = [vp, vp, i64] + [vp, i64] * 8 + [i64, ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int, vp]
+    L.pw_rigid_cell_ewald.argtypes = [vp, vp, i64] + [vp, i64] * 11
+    L.pw_internal_rigid_cell_ewald.argtypes = [vp, vp, i64] + [vp, i64] * 11 + [i64, ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int, vp]
+    L.pw_internal_erfc.argtypes = [vp, vp, i64, vp]
     L.pw_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
     L.pw_internal_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6
@@ -1517,6 +1531,62 @@ class Context:
         if diagnostics is not None:
             diagnostics.append((n_pairs, int(instances[0])))
         return out, levels, maps
+
+    def rigid_cell_ewald(self, jobs, xyz, coef, offsets, dirs, betas, site_q, cell, kvecs, out=None, levels=None, maps=None,
+                         workspace_bytes=None, kernel_ms=None, diagnostics=None, skip=True):
+        """``pw_rigid_cell_ewald``: :meth:`rigid_cell` for jobs that may be charged (``RIGID_CELL_EWALD_JOB_DTYPE`` records,
+        whose ``cell`` is the ``pw_rigid_cell`` job): the rows of ``coef`` are ``(A, B, C)``; ``site_q`` the site charges,
+        ``cell`` rows ``(x, y, z, q)`` of the primary cell's atoms and ``kvecs`` rows ``(h, k, l, w)`` of the reciprocal
+        sum (:func:`pywindow_amd.ewald_parameters`).  The results and the measurement arguments are :meth:`rigid_cell`'s."""
+        jobs = np.ascontiguousarray(jobs, dtype=RIGID_CELL_EWALD_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 3)
+        t = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
+        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
+        q = np.ascontiguousarray(site_q, dtype=np.float64).reshape(-1)
+        ca = np.ascontiguousarray(cell, dtype=np.float64).reshape(-1, 4)
+        kv = np.ascontiguousarray(kvecs, dtype=np.float64).reshape(-1, 4)
+        inner = jobs["cell"]
+        some = len(jobs) > 0
+        voxels = np.int64(1) * inner["nx"] * inner["ny"] * inner["nz"]
+
+        def made(given, dtype, what, size):
+            if given is None:
+                return np.zeros(max(int(size), 0), dtype=dtype)
+            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+                raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+            return given
+
+        out = made(out, RIGID_OUT_DTYPE, "out", (inner["out"] + 1).max() if some else 0)
+        levels = made(levels, AFFINITY_LEVEL_DTYPE, "levels", (inner["level_first"] + inner["n_betas"]).max() if some else 0)
+        has = inner["map_first"] >= 0
+        if maps is not None or has.any():
+            maps = made(maps, np.float64, "maps",
+                        (inner["map_first"][has] + (inner["n_betas"][has] + 1) * voxels[has]).max() if has.any() else 0)
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), t.ctypes.data, len(t),
+                d.ctypes.data, len(d), b.ctypes.data, len(b), q.ctypes.data, len(q), ca.ctypes.data, len(ca), kv.ctypes.data,
+                len(kv), None if maps is None else maps.ctypes.data, 0 if maps is None else len(maps), levels.ctypes.data,
+                len(levels), out.ctypes.data, len(out)]
+        if workspace_bytes is None and kernel_ms is None and diagnostics is None and skip:
+            _stat_call("pw_rigid_cell_ewald", *args)
+            return out, levels, maps
+        ms = ctypes.c_float(0.0)
+        n_pairs, instances = np.zeros(len(jobs), dtype=np.int64), np.zeros(1, dtype=np.int32)
+        _stat_call("pw_internal_rigid_cell_ewald", *args, int(workspace_bytes or 0), ctypes.byref(ms), n_pairs.ctypes.data,
+                   1 if skip else 0, instances.ctypes.data)
+        if kernel_ms is not None:
+            kernel_ms.append(float(ms.value))
+        if diagnostics is not None:
+            diagnostics.append((n_pairs, int(instances[0])))
+        return out, levels, maps
+
+    def erfc(self, x):
+        """The library's ``pw_erfc`` (pw_math.hpp) element by element on this context (test instrumentation): float64."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        out = np.zeros(len(x), dtype=np.float64)
+        _stat_call("pw_internal_erfc", self._h, x.ctypes.data, len(x), out.ctypes.data)
+        return out
 
     def charges(self, jobs, xyz, params, out=None, workspace_bytes=None, kernel_ms=None):
         """``pw_charges``: charge equilibration of a batch of jobs (``CHARGES_JOB_DTYPE`` records indexing the rows of

@@ -22,6 +22,7 @@
 #include "pw_affinity.hpp"
 #include "pw_rigid.hpp"
 #include "pw_rigid_cell.hpp"
+#include "pw_ewald.hpp"
 #include "pw_cavity.hpp"
 #include "pw_sasa.hpp"
 #include "pw_pores.hpp"
@@ -1301,12 +1302,62 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
 // weight and the fold of pw_rigid.hpp on the grid of pw_channels.hpp, with the near list of pw_rigid_cell.hpp -- the same
 // test against the same group centre, so n_pairs is the device's unless `skip` is 0.  The threads share out (job, group)
 // pieces, each of which leaves the records of its voxels; then (job, chunk) pieces leave the partials of pw_rigid.hpp;
-// then one ordered reduce a job.  n_pairs (may be null): per job, diagnostic.
+// then one ordered reduce a job.  n_pairs (may be null): per job, diagnostic.  With `ew` (pw_rigid_cell_ewald; null for
+// pw_rigid_cell) the rows of coef are (A, B, C) and a charged job takes pw_ewald.hpp's pair term and reciprocal sum.
 extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs, const double* xyz, const double* coef,
                                       const double* offsets, const double* dirs, const double* betas, double* maps,
-                                      pw_affinity_level* levels, pw_rigid_out* out, long long* n_pairs, int skip, int threads) {
+                                      pw_affinity_level* levels, pw_rigid_out* out, long long* n_pairs, int skip, int threads,
+                                      const EwaldHost* ew) {
     typedef cavity_word u64;
     struct Plan { long group_first, chunk_first, rec_first, part_first; };
+    // pw_rigid_cell_ewald (pw_ewald.hpp): rows of three and, per charged job with rows of the reciprocal sum, the tables
+    // (c0, s0) a row and (P, Q) per (orientation, row), made before the groups that read them
+    const int W = ew ? 3 : 2;
+    struct Rec { long first, krow_first; };
+    std::vector<Rec> recp((size_t)n_jobs + 1);
+    long table_words = 0, krows = 0;
+    for (long k = 0; k < n_jobs; ++k) {
+        recp[k] = Rec{table_words, krows};
+        if (ew && ew->jobs[k].charged && ew->jobs[k].n_k > 0) {
+            table_words += ewald_table_words(ew->jobs[k].n_k, (long)jobs[k].n_dirs);
+            krows += ew->jobs[k].n_k;
+        }
+    }
+    recp[n_jobs] = Rec{table_words, krows};
+    std::vector<double> tables((size_t)table_words);
+    host_share(krows, threads, [&](long piece) {
+        long k = 0, hi = n_jobs;                                     // the last job with krow_first <= piece
+        while (hi - k > 1) {
+            const long mid = (k + hi) / 2;
+            if (recp[mid].krow_first <= piece) k = mid; else hi = mid;
+        }
+        const pw_rigid_cell_job& J = jobs[k];
+        const EwaldHostJob& E = ew->jobs[k];
+        const long row = piece - recp[k].krow_first, K = E.n_k, M = (long)J.n_dirs;
+        const double* kv = ew->kvecs + 4 * (E.k_first + row);
+        const EwaldK kk = ewald_kvec(J.step, J.nx, J.ny, J.nz, kv[0], kv[1], kv[2]);
+        double slot_c[AFF_CHUNK], slot_s[AFF_CHUNK];
+        for (int t = 0; t < AFF_CHUNK; ++t) {
+            double sc = 0.0, ss = 0.0;
+            for (long j = t; j < E.n_cell; j += AFF_CHUNK) {
+                const double* a = ew->cell + 4 * (E.cell_first + j);
+                const EwaldCS f = ewald_sincos(ewald_dot(kk, a[0], a[1], a[2]));
+                sc = sc + a[3] * f.c;
+                ss = ss + a[3] * f.s;
+            }
+            slot_c[t] = sc;
+            slot_s[t] = ss;
+        }
+        const double Sc = aff_tree(slot_c), Ss = aff_tree(slot_s);
+        double* T = tables.data() + recp[k].first;
+        const EwaldCS e0 = ewald_sincos(ewald_dot(kk, J.origin[0], J.origin[1], J.origin[2]));
+        T[2 * row] = e0.c;
+        T[2 * row + 1] = e0.s;
+        const double* dd = dirs + 3 * (long)J.dir_first;
+        for (long o = 0; o < M; ++o)
+            ewald_pq(kk, kv[3], Sc, Ss, offsets + (long)J.site_first, ew->site_q + E.charge_first, (int)J.n_sites, dd[3 * o],
+                     dd[3 * o + 1], dd[3 * o + 2], T + 2 * K + 2 * (o * K + row), T + 2 * K + 2 * (o * K + row) + 1);
+    });
     std::vector<Plan> plan((size_t)n_jobs + 1);
     std::vector<double> reach2((size_t)n_jobs);
     long n_groups = 0, n_chunks = 0, rec_words = 0, part_words = 0;
@@ -1337,10 +1388,19 @@ extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs
         const long gx = rcell_groups(nx), gy = rcell_groups(ny), grow = g / gx;
         const int i0 = RCELL_G * (int)(g - grow * gx), j0 = RCELL_G * (int)(grow % gy), l0 = RCELL_G * (int)(grow / gy);
         const double* atoms = xyz + 3 * (long)J.atom_first;
-        const double* ab = coef + 2 * (long)J.coef_first;
+        const double* ab = coef + W * (long)J.coef_first;
         const double* ts = offsets + (long)J.site_first;
         const double* dd = dirs + 3 * (long)J.dir_first;
         const double inv_M = rigid_inv(M);
+        const bool charged = ew && ew->jobs[k].charged;
+        const double alpha = charged ? ew->jobs[k].alpha : 0.0;
+        const long K = charged ? ew->jobs[k].n_k : 0;
+        const double* kv = K ? ew->kvecs + 4 * ew->jobs[k].k_first : nullptr;
+        const double* T = K ? tables.data() + recp[k].first : nullptr;
+        std::vector<EwaldCS> wave((size_t)K), axis_x((size_t)(K ? nx : 0)), axis_y((size_t)(K ? ny : 0)), axis_z((size_t)(K ? nz : 0));
+        for (int q = 0; K && q < nx; ++q) axis_x[q] = ewald_axis(nx, q);
+        for (int q = 0; K && q < ny; ++q) axis_y[q] = ewald_axis(ny, q);
+        for (int q = 0; K && q < nz; ++q) axis_z[q] = ewald_axis(nz, q);
         const double gcx = rcell_centre_x(J.origin, J.step, i0, j0, l0), gcy = rcell_centre_y(J.origin, J.step, j0, l0),
                      gcz = rcell_centre_z(J.origin, J.step, l0);
         std::vector<long> near_list;
@@ -1359,26 +1419,39 @@ extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs
                     double umin_v = aff_inf();
                     int umin_o = -1, n_blocked = 0;
                     bool clamped = false;
+                    for (long r = 0; r < K; ++r) {                   // (c_kv, s_kv) of the voxel, row by row
+                        const EwaldCS e0{T[2 * r], T[2 * r + 1]};
+                        wave[r] = ewald_add(ewald_add(ewald_add(e0, axis_x[ewald_residue((int)kv[4 * r], i, nx)]),
+                                                      axis_y[ewald_residue((int)kv[4 * r + 1], j, ny)]),
+                                            axis_z[ewald_residue((int)kv[4 * r + 2], l, nz)]);
+                    }
                     for (int o = 0; o < M; ++o) {
                         bool blocked = false;
                         double U = 0.0;
                         for (int s = 0; s < S && !blocked; ++s) {
                             const double px = rigid_site(x, ts[s], dd[3 * o]), py = rigid_site(y, ts[s], dd[3 * o + 1]),
                                          pz = rigid_site(z, ts[s], dd[3 * o + 2]);
-                            const double* rows = ab + 2 * (long)s * n;
+                            const double* rows = ab + W * (long)s * n;
                             double Us = 0.0;
                             for (size_t q = 0; q < near_list.size() && !blocked; ++q) {
                                 const long a = near_list[q];
                                 const double r2 = aff_r2(px - atoms[3 * a], py - atoms[3 * a + 1], pz - atoms[3 * a + 2]);
                                 blocked = aff_blocked(r2, J.core2);
                                 if (blocked || !aff_counts(r2, J.cutoff2)) continue;
-                                Us = Us + aff_pair(r2, rows[2 * a], rows[2 * a + 1]);
+                                const double u = aff_pair(r2, rows[W * a], rows[W * a + 1]);
+                                Us = Us + (charged ? ewald_pair(u, r2, rows[W * a + 2], alpha, POW_EXP_TAB) : u);
                             }
                             U = s ? U + Us : Us;
                         }
                         if (blocked) {
                             ++n_blocked;
                             continue;
+                        }
+                        if (K) {
+                            const double* PQ = T + 2 * K + 2 * (long)o * K;
+                            double urec = 0.0;
+                            for (long r = 0; r < K; ++r) urec = urec + ewald_term(PQ[2 * r], PQ[2 * r + 1], wave[r]);
+                            U = U + urec;
                         }
                         if (U < umin_v) {
                             umin_v = U;
@@ -2454,6 +2527,11 @@ extern "C" void pw_hostpath_exp(const double* x, long n, double* y) {
 extern "C" void pw_hostpath_math(int which, const double* x, const double* y, long n, double* out) {
     std::call_once(g_rsq_once, [] { rsqrt14_decode(g_rsq); });
     for (long i = 0; i < n; ++i) out[i] = pw_math_probe(which, x[i], y ? y[i] : 0.0, g_rsq);
+}
+
+// pw_erfc element by element (test instrumentation, pw_ewald.hip: pw_internal_erfc)
+extern "C" void pw_hostpath_erfc(const double* x, long n, double* out) {
+    for (long i = 0; i < n; ++i) out[i] = pw_erfc(x[i]);
 }
 
 // a batch of optimiser cases on a one-lane team (test instrumentation, pw_lb_probe.hip: pw_internal_lb_probe, which

@@ -276,6 +276,84 @@ PW_HD inline double pw_exp_tab(double x, Tab tab) {
 }
 PW_HD inline double pw_exp(double x) { return pw_exp_tab(x, POW_EXP_TAB); }
 
+// ---- erfc(x) for x >= 0 --------------------------------------------------------------------------
+// The real-space Ewald term of pw_ewald.hpp is the one caller.  Like pw_exp this is the project's own definition: what
+// matters is that the gfx950 build and the -ffp-contract=off host build return the SAME BITS and that the value is
+// accurate.  Every operation is written out and none is fused.
+// Method: the classical piecewise rational form (W. J. Cody, "Rational Chebyshev approximations for the error function",
+// Math. Comp. 23 (1969), in the arrangement and with the coefficients published with Sun's freely distributable
+// math library, 1993):
+//     x < 2^-56              1 - x                                    (exactly 1.0 at 0)
+//     x < 0.84375            erf(x) = x + x * P(x^2) / Q(x^2); 1 - erf(x), or 0.5 - ((x - 0.5) + x * P / Q) from 0.25 on
+//     x < 1.25               1 - erx - P(x - 1) / Q(x - 1), erx = 0.845062911510467529297
+//     x < 1 / 0.35           exp(-z*z - 0.5625) * exp((z - x) * (z + x) + R(1 / x^2) / S(1 / x^2)) / x
+//     x < 28                 the same with a second pair (R, S)
+//     otherwise              +0.0
+// z is x with its low 32 bits cleared, so z * z is exact and the first exponential takes an argument without a
+// rounding error: THE ARGUMENT SPLIT.  The exponentials are pw_exp_tab's, so a first factor below the smallest normal
+// (x above 26.6) is +0.0: the true value is a denormal from x = 26.543 on, and there the result is +0.0 or a denormal.
+// Never NaN for a finite argument; NaN and negative arguments are not the path's (a NaN gives +0.0).
+// Piece boundaries: 2^-56, 0.25, 0.84375, 1.25, 1 / 0.35, 28 (tests/test_ewald_host.py sweeps each with both neighbours).
+// Accuracy: measured maximum 3.0 ulp against the C library's erfc (documented below 1 ulp) over that sweep with 10^5
+// log-spaced arguments, up to the last argument whose value is a normal number; the test allows twice that.  The
+// largest errors are in 0.84375 <= x < 1.25, where 1 - erx and P / Q cancel to a value half their size.
+template <class Tab>
+PW_HD inline double pw_erfc_tab(double x, Tab tab) {
+    const double erx = 8.45062911510467529297e-01;
+    if (x < 1.3877787807814457e-17) return 1.0 - x;                  // 2^-56
+    if (x < 0.84375) {
+        const double pp0 = 1.28379167095512558561e-01, pp1 = -3.25042107247001499370e-01, pp2 = -2.84817495755985104766e-02,
+                     pp3 = -5.77027029648944159157e-03, pp4 = -2.37630166566501626084e-05;
+        const double qq1 = 3.97917223959155352819e-01, qq2 = 6.50222499887672944485e-02, qq3 = 5.08130628187576562776e-03,
+                     qq4 = 1.32494738004321644526e-04, qq5 = -3.96022827877536812320e-06;
+        const double z = x * x;
+        const double r = pp0 + z * (pp1 + z * (pp2 + z * (pp3 + z * pp4)));
+        const double s = 1.0 + z * (qq1 + z * (qq2 + z * (qq3 + z * (qq4 + z * qq5))));
+        const double y = r / s;
+        if (x < 0.25) return 1.0 - (x + x * y);
+        const double t = x * y + (x - 0.5);
+        return 0.5 - t;
+    }
+    if (x < 1.25) {
+        const double pa0 = -2.36211856075265944077e-03, pa1 = 4.14856118683748331666e-01, pa2 = -3.72207876035701323847e-01,
+                     pa3 = 3.18346619901161753674e-01, pa4 = -1.10894694282396677476e-01, pa5 = 3.54783043256182359371e-02,
+                     pa6 = -2.16637559486879084300e-03;
+        const double qa1 = 1.06420880400844228286e-01, qa2 = 5.40397917702171048937e-01, qa3 = 7.18286544141962662868e-02,
+                     qa4 = 1.26171219808761642112e-01, qa5 = 1.36370839120290507362e-02, qa6 = 1.19844998467991074170e-02;
+        const double s = x - 1.0;
+        const double P = pa0 + s * (pa1 + s * (pa2 + s * (pa3 + s * (pa4 + s * (pa5 + s * pa6)))));
+        const double Q = 1.0 + s * (qa1 + s * (qa2 + s * (qa3 + s * (qa4 + s * (qa5 + s * qa6)))));
+        return (1.0 - erx) - P / Q;
+    }
+    if (!(x < 28.0)) return 0.0;
+    const double s = 1.0 / (x * x);
+    double R, S;
+    if (x < 2.857142857142857) {                                     // 1 / 0.35
+        const double ra0 = -9.86494403484714822705e-03, ra1 = -6.93858572707181764372e-01, ra2 = -1.05586262253232909814e+01,
+                     ra3 = -6.23753324503260060396e+01, ra4 = -1.62396669462573470355e+02, ra5 = -1.84605092906711035994e+02,
+                     ra6 = -8.12874355063065934246e+01, ra7 = -9.81432934416914548592e+00;
+        const double sa1 = 1.96512716674392571292e+01, sa2 = 1.37657754143519042600e+02, sa3 = 4.34565877475229228821e+02,
+                     sa4 = 6.45387271733267880336e+02, sa5 = 4.29008140027567833386e+02, sa6 = 1.08635005541779435134e+02,
+                     sa7 = 6.57024977031928170135e+00, sa8 = -6.04244152148580987438e-02;
+        R = ra0 + s * (ra1 + s * (ra2 + s * (ra3 + s * (ra4 + s * (ra5 + s * (ra6 + s * ra7))))));
+        S = 1.0 + s * (sa1 + s * (sa2 + s * (sa3 + s * (sa4 + s * (sa5 + s * (sa6 + s * (sa7 + s * sa8)))))));
+    } else {
+        const double rb0 = -9.86494292470009928597e-03, rb1 = -7.99283237680523006574e-01, rb2 = -1.77579549177547519889e+01,
+                     rb3 = -1.60636384855821916062e+02, rb4 = -6.37566443368389627722e+02, rb5 = -1.02509513161107724954e+03,
+                     rb6 = -4.83519191608651397019e+02;
+        const double sb1 = 3.03380607434824582924e+01, sb2 = 3.25792512996573918826e+02, sb3 = 1.53672958608443695994e+03,
+                     sb4 = 3.19985821950859553908e+03, sb5 = 2.55305040643316442583e+03, sb6 = 4.74528541206955367215e+02,
+                     sb7 = -2.24409524465858183362e+01;
+        R = rb0 + s * (rb1 + s * (rb2 + s * (rb3 + s * (rb4 + s * (rb5 + s * rb6)))));
+        S = 1.0 + s * (sb1 + s * (sb2 + s * (sb3 + s * (sb4 + s * (sb5 + s * (sb6 + s * sb7))))));
+    }
+    const double z = pw_bits2d(pw_d2bits(x) & 0xffffffff00000000ull);
+    const double first = pw_exp_tab(-(z * z) - 0.5625, tab);
+    const double second = pw_exp_tab((z - x) * (z + x) + R / S, tab);
+    return (first * second) / x;
+}
+PW_HD inline double pw_erfc(double x) { return pw_erfc_tab(x, POW_EXP_TAB); }
+
 // x ** 2 and x ** 3 for any finite x (pow's sign handling for integer exponents).  Outside pw_pow_np's domain -- a
 // power below 2^-1020 or beyond 1e300, zero, infinities, NaN -- the plain product, which is within one ulp of pow.
 PW_HD inline double pw_square_np(double x) {

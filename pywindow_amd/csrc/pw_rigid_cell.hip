@@ -1,6 +1,8 @@
 // pw_rigid_cell.hip -- gfx950 kernels and the C ABI entry of the orientation-averaged Boltzmann factor of a rigid linear
 // guest at every voxel of a periodic cell (include/pywindow_amd.h: pw_rigid_cell; definition of the result, the skip and
-// its proof in pw_rigid_cell.hpp).  Three kernels a launch group:
+// its proof in pw_rigid_cell.hpp), and of the same field with the Ewald sum of the framework's point charges
+// (pw_rigid_cell_ewald; definition in pw_ewald.hpp, the two kernels of its reciprocal part in pw_ewald.hip, launched ahead
+// of the main kernel, which is instantiated a second time for rows of three doubles).  Three kernels a launch group:
 //   main     a work item is (job, group of 4 x 4 x 4 voxels), one wavefront an item, a lane a voxel.  Instantiated on the
 //            number of sites as pw_rigid_kernel is (1, 2, 3, and a guarded form unrolled to 8 that serves 4 .. 8), so
 //            that every per-site and per-orientation value has a register of its own: nothing private is indexed at run
@@ -29,7 +31,7 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_affinity_dev.hpp"
-#include "pw_rigid_cell.hpp"
+#include "pw_ewald_dev.hpp"
 #include "pw_grid_host.hpp"
 
 using namespace pw;
@@ -37,9 +39,10 @@ using namespace pw;
 extern "C" int pw_hostpath_rigid_cell(const pw_rigid_cell_job* jobs, long n_jobs, const double* xyz, const double* coef,
                                       const double* offsets, const double* dirs, const double* betas, double* maps,
                                       pw_affinity_level* levels, pw_rigid_out* out, long long* n_pairs, int skip,
-                                      int threads);   // pw_hostpath.cpp
+                                      int threads, const EwaldHost* ew);   // pw_hostpath.cpp
 
-static_assert(sizeof(pw_rigid_cell_job) == 200 && sizeof(pw_rigid_out) == 56, "the layouts of the header");
+static_assert(sizeof(pw_rigid_cell_job) == 200 && sizeof(pw_rigid_out) == 56 && sizeof(pw_rigid_cell_ewald_job) == 256,
+              "the layouts of the header");
 static_assert(RCELL_G * RCELL_G * RCELL_G == AFF_CHUNK && RCELL_NEAR_CAP % AFF_CHUNK == 0, "a group is a wavefront");
 
 namespace {
@@ -49,30 +52,18 @@ typedef cavity_word u64;
 constexpr int RCELL_RB = 2;                          // orientations held in registers at a time, S <= 3
 constexpr int RCELL_CLASSES = 4;                     // 1, 2, 3, guarded 8
 
-// a job as the kernels read it: firsts relative to the spans of the arrays that were uploaded
-struct RCellJobDev {
-    long atom_first, n, coef_first;
-    long rec_first;            // the job's (2L + 2) V record words in the workspace of its launch
-    long part_first;           // the job's [chunks][stride] partials in that workspace
-    long item_first;           // the job's first group among the work items of the main kernel
-    long chunk_first;          // the job's first chunk among the work items of the sums kernel
-    long chunks, V;
-    long beta_first, site_first, dir_first;   // into the uploaded betas, offsets and directions
-    long level_first;          // into the compact result of the call
-    double o[3], s[6], core2, cutoff2, reach2;
-    int nx, ny, nz, gx, gy, L, S, M, cls, reserved;
-};
-
 int rcell_class(int S) { return S <= 3 ? S - 1 : 3; }
 
-// S_T sites unrolled; GUARD: the job has J.S <= S_T of them and every site is behind `s < S`; RB orientations a pass
-template <int S_T, bool GUARD, int RB>
+// S_T sites unrolled; GUARD: the job has J.S <= S_T of them and every site is behind `s < S`; RB orientations a pass; W
+// doubles a row of coef: 2 is pw_rigid_cell, 3 is pw_rigid_cell_ewald, whose charged jobs take pw_ewald.hpp's pair term
+// behind a branch that is the same in every lane and add Urec from the workspace to the pose's energy
+template <int S_T, bool GUARD, int RB, int W>
 __global__ void __launch_bounds__(AFF_CHUNK)
 pw_rigid_cell_kernel(const RCellJobDev* __restrict__ jobs, int n_jobs, long total, int cls, const double* __restrict__ xyz,
                      const double* __restrict__ coef, const double* __restrict__ offsets, const double* __restrict__ dirs,
                      const double* __restrict__ betas, u64* __restrict__ ws, unsigned long long* __restrict__ n_pairs) {
     __shared__ double s_xyz[3 * AFF_TILE];
-    __shared__ double s_coef[2 * S_T * AFF_TILE];                    // row (atom t, site s) at 2 * (t * S_T + s)
+    __shared__ double s_coef[W * S_T * AFF_TILE];                    // row (atom t, site s) at W * (t * S_T + s)
     __shared__ double s_off[RIGID_MAX_SITES];
     __shared__ int s_near[RCELL_NEAR_CAP];                           // the near list: atom indices of the job, ascending
     __shared__ __attribute__((aligned(16))) uint64_t s_tab[256];
@@ -98,7 +89,10 @@ pw_rigid_cell_kernel(const RCellJobDev* __restrict__ jobs, int n_jobs, long tota
         const double core2 = J.core2, cutoff2 = J.cutoff2, reach2 = J.reach2, inv_M = rigid_inv(M);
         const long n = J.n;
         const double* atoms = xyz + 3 * J.atom_first;
-        const double* rows_ab = coef + 2 * J.coef_first;
+        const double* rows_ab = coef + W * J.coef_first;
+        const bool charged = W == 3 && J.charged != 0;               // (the same in every lane)
+        const double alpha = J.alpha;
+        const double* urec = charged && J.urec_first >= 0 ? (const double*)(ws + J.urec_first) : nullptr;
         // the near list of the atoms from `a` on, until they end or the list is full; the first atom it did not look at.
         // The caller puts the barriers around it.  count is the same in every lane
         auto build = [&](long a, int& count) {
@@ -123,9 +117,10 @@ pw_rigid_cell_kernel(const RCellJobDev* __restrict__ jobs, int n_jobs, long tota
 #pragma unroll
                 for (int s = 0; s < S_T; ++s) {
                     if (GUARD && s >= S) continue;
-                    const double* src = rows_ab + 2 * ((long)s * n + idx);
-                    s_coef[2 * (t * S_T + s)] = src[0];
-                    s_coef[2 * (t * S_T + s) + 1] = src[1];
+                    const double* src = rows_ab + W * ((long)s * n + idx);
+                    s_coef[W * (t * S_T + s)] = src[0];
+                    s_coef[W * (t * S_T + s) + 1] = src[1];
+                    if (W == 3 && charged) s_coef[W * (t * S_T + s) + 2] = src[2];
                 }
             }
         };
@@ -186,13 +181,19 @@ pw_rigid_cell_kernel(const RCellJobDev* __restrict__ jobs, int n_jobs, long tota
 #pragma unroll
                         for (int s = 0; s < S_T; ++s) {
                             if (GUARD && s >= S) continue;
-                            const double A = s_coef[2 * (t * S_T + s)], B = s_coef[2 * (t * S_T + s) + 1];
+                            const double A = s_coef[W * (t * S_T + s)], B = s_coef[W * (t * S_T + s) + 1];
+                            const double C = W == 3 && charged ? s_coef[W * (t * S_T + s) + 2] : 0.0;
 #pragma unroll
                             for (int r = 0; r < RB; ++r) {
                                 const double r2 = aff_r2(px[r][s] - X, py[r][s] - Y, pz[r][s] - Z);
                                 blocked[r] = blocked[r] || aff_blocked(r2, core2);
-                                const double u = aff_pair(r2, A, B);
-                                U[r][s] = aff_counts(r2, cutoff2) ? U[r][s] + u : U[r][s];
+                                double u = aff_pair(r2, A, B);
+                                if (W == 3 && charged) {
+                                    // (only a counting atom: alpha * r stays within the cutoff, the branch follows the lanes)
+                                    if (aff_counts(r2, cutoff2)) U[r][s] = U[r][s] + ewald_pair(u, r2, C, alpha, s_tab);
+                                } else {
+                                    U[r][s] = aff_counts(r2, cutoff2) ? U[r][s] + u : U[r][s];
+                                }
                             }
                         }
                     }
@@ -206,6 +207,7 @@ pw_rigid_cell_kernel(const RCellJobDev* __restrict__ jobs, int n_jobs, long tota
 #pragma unroll
                 for (int s = 1; s < S_T; ++s)
                     if (!GUARD || s < S) Ut = Ut + U[r][s];
+                if (W == 3 && urec) Ut = Ut + urec[(long)(o0 + r) * J.V + ((long)(lv * ny + jv) * nx + iv)];
                 const bool live = !blocked[r];
                 n_blocked += blocked[r];
                 if (live && Ut < umin_v) {
@@ -333,12 +335,17 @@ pw_rigid_cell_reduce_kernel(const RCellJobDev* __restrict__ jobs, const u64* __r
 }
 
 // one instance over the items of a launch group; `lds`: the bytes of the directions of the group's largest M
-void rcell_launch(int cls, unsigned blocks, size_t lds, hipStream_t st, const RCellJobDev* jobs, int n_jobs, long total,
-                  const double* xyz, const double* coef, const double* offsets, const double* dirs, const double* betas, u64* ws,
+void rcell_launch(int cls, bool wide, unsigned blocks, size_t lds, hipStream_t st, const RCellJobDev* jobs, int n_jobs,
+                  long total, const double* xyz, const double* coef, const double* offsets, const double* dirs, const double* betas, u64* ws,
                   unsigned long long* n_pairs) {
-#define RCELL_GO(S_T, GUARD, RB)                                                                                       \
-    hipLaunchKernelGGL((pw_rigid_cell_kernel<S_T, GUARD, RB>), dim3(blocks), dim3(AFF_CHUNK), lds, st, jobs, n_jobs, total, \
-                       cls, xyz, coef, offsets, dirs, betas, ws, n_pairs)
+#define RCELL_GO_W(S_T, GUARD, RB, W)                                                                                  \
+    hipLaunchKernelGGL((pw_rigid_cell_kernel<S_T, GUARD, RB, W>), dim3(blocks), dim3(AFF_CHUNK), lds, st, jobs, n_jobs,  \
+                       total, cls, xyz, coef, offsets, dirs, betas, ws, n_pairs)
+#define RCELL_GO(S_T, GUARD, RB)                 \
+    do {                                         \
+        if (wide) RCELL_GO_W(S_T, GUARD, RB, 3); \
+        else RCELL_GO_W(S_T, GUARD, RB, 2);      \
+    } while (0)
     switch (cls) {
         case 0: RCELL_GO(1, false, RCELL_RB); break;
         case 1: RCELL_GO(2, false, RCELL_RB); break;
@@ -346,18 +353,25 @@ void rcell_launch(int cls, unsigned blocks, size_t lds, hipStream_t st, const RC
         default: RCELL_GO(RIGID_MAX_SITES, true, 1); break;
     }
 #undef RCELL_GO
+#undef RCELL_GO_W
 }
 
-const char* const ENTRY = "pw_rigid_cell";
-int rcell_bad(long k, const char* what) { return stat_bad(ENTRY, k, what); }
+// what pw_rigid_cell_ewald hands over beyond pw_rigid_cell's arguments; null for pw_rigid_cell
+struct EwaldArgs {
+    const pw_rigid_cell_ewald_job* jobs;
+    const double *site_q, *cell, *kvecs;
+    long n_site_q, n_cell, n_kvecs;
+};
 
 inline long rcell_voxels(const pw_rigid_cell_job& J) { return (long)J.nx * J.ny * J.nz; }
 inline long rcell_map_words(const pw_rigid_cell_job& J) { return J.map_first >= 0 ? (J.n_betas + 1) * rcell_voxels(J) : 0; }
 
 // Everything is checked before anything is launched or written
-int rcell_check(const pw_rigid_cell_job* jobs, long n_jobs, const double* xyz, long n_points, const double* coef, long n_coef,
-                const double* offsets, long n_offsets, const double* dirs, long n_dirs, const double* betas, long n_betas,
-                const double* maps, long n_maps, const pw_affinity_level* levels, long n_levels, long n_out) {
+int rcell_check(const char* ENTRY, int W, const pw_rigid_cell_job* jobs, long n_jobs, const double* xyz, long n_points,
+                const double* coef, long n_coef, const double* offsets, long n_offsets, const double* dirs, long n_dirs,
+                const double* betas, long n_betas, const double* maps, long n_maps, const pw_affinity_level* levels, long n_levels,
+                long n_out, const EwaldArgs* ew) {
+    auto rcell_bad = [&](long k, const char* what) { return stat_bad(ENTRY, k, what); };
     for (long k = 0; k < n_jobs; ++k) {
         const pw_rigid_cell_job& J = jobs[k];
         GRID_CHECK(grid_dims_check(ENTRY, k, J.nx, J.ny, J.nz));
@@ -395,7 +409,34 @@ int rcell_check(const pw_rigid_cell_job* jobs, long n_jobs, const double* xyz, l
             if (!pw_finite(d) || pw_abs(d) > 1.0) return rcell_bad(k, "a direction's component is not finite or outside -1 .. 1");
         }
         GRID_CHECK(grid_xyz_check(ENTRY, k, xyz, J.atom_first, J.n));   // (every coordinate, then every row)
-        GRID_CHECK(grid_coef_check(ENTRY, k, coef, J.coef_first, S * J.n, 2, false));
+        const bool charged = ew && ew->jobs[k].charged != 0;
+        GRID_CHECK(grid_coef_check(ENTRY, k, coef, J.coef_first, S * J.n, W, charged));
+        if (!ew) continue;
+        const pw_rigid_cell_ewald_job& E = ew->jobs[k];
+        if (E.charged != 0 && E.charged != 1) return rcell_bad(k, "charged is neither 0 nor 1");
+        if (!charged) continue;                                      // (nothing else of the job is read)
+        if (!pw_finite(E.alpha)) return rcell_bad(k, "alpha is not finite");
+        if (E.alpha < 0.0) return rcell_bad(k, "alpha < 0");
+        if (E.n_k < 0 || E.n_k > EWALD_MAX_K) return rcell_bad(k, "n_k outside 0 .. PW_EWALD_MAX_K (4096)");
+        if (E.n_cell < 0 || E.n_cell > 0x7fffffffl) return rcell_bad(k, "n_cell is negative or above 2^31 - 1");
+        if (span_outside(E.charge_first, S, ew->n_site_q)) return rcell_bad(k, "site charges outside site_q");
+        if (span_outside(E.cell_first, E.n_cell, ew->n_cell)) return rcell_bad(k, "cell atoms outside cell");
+        if (span_outside(E.k_first, E.n_k, ew->n_kvecs)) return rcell_bad(k, "rows outside kvecs");
+        if (!ew->site_q || (E.n_cell && !ew->cell) || (E.n_k && !ew->kvecs)) return rcell_bad(k, "null array");
+        for (long s = 0; s < S; ++s) {
+            const double q = ew->site_q[E.charge_first + s];
+            if (!pw_finite(q) || pw_abs(q) > AFF_MAX_COEF) return rcell_bad(k, "a site charge is not finite or beyond 1e100");
+        }
+        for (long c = 4 * E.cell_first; c < 4 * (E.cell_first + E.n_cell); ++c)
+            if (!pw_finite(ew->cell[c]) || pw_abs(ew->cell[c]) > AFF_MAX_COEF)
+                return rcell_bad(k, "a cell atom's coordinate or charge is not finite or beyond 1e100");
+        for (long r = E.k_first; r < E.k_first + E.n_k; ++r) {
+            const double* kv = ew->kvecs + 4 * r;
+            for (int a = 0; a < 3; ++a)
+                if (!pw_finite(kv[a]) || pw_abs(kv[a]) > (double)EWALD_MAX_INDEX || kv[a] != (double)(int)kv[a])
+                    return rcell_bad(k, "an index of a row is not an integer within -PW_EWALD_MAX_INDEX .. PW_EWALD_MAX_INDEX (64)");
+            if (!pw_finite(kv[3])) return rcell_bad(k, "a weight is not finite");
+        }
     }
     GRID_CHECK(shared_output(ENTRY, n_jobs, "shares its row of out with an earlier job",
                              [&](long k) { return OutSpan{(long)jobs[k].out, 1}; }));
@@ -414,7 +455,8 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
                const double* coef, int64_t n_coef, const double* offsets, int64_t n_offsets, const double* dirs, int64_t n_dirs,
                const double* betas, int64_t n_betas, double* maps, int64_t n_maps, pw_affinity_level* levels, int64_t n_levels,
                pw_rigid_out* out, int64_t n_out, int64_t workspace_bytes, float* kernel_ms, int64_t* n_pairs, int skip,
-               int32_t* instances) {
+               int32_t* instances, const char* ENTRY = "pw_rigid_cell", const EwaldArgs* ew = nullptr) {
+    const int W = ew ? 3 : 2;
     if (!ctx || n_jobs < 0 || n_jobs > 0x7ffffff0 || (n_jobs && (!jobs || !out)) || n_points < 0 || n_coef < 0 || n_offsets < 0 ||
         n_dirs < 0 || n_betas < 0 || n_maps < 0 || n_levels < 0 || n_out < 0 || workspace_bytes < 0)
         return PW_E_BAD_ARG;
@@ -423,17 +465,25 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
     if (n_jobs == 0) return PW_OK;
     PW_LOCK_CONTEXT(ctx);
     const long N = (long)n_jobs;
-    const int rc = rcell_check(jobs, N, xyz, (long)n_points, coef, (long)n_coef, offsets, (long)n_offsets, dirs, (long)n_dirs, betas,
-                               (long)n_betas, maps, (long)n_maps, levels, (long)n_levels, (long)n_out);
+    const int rc = rcell_check(ENTRY, W, jobs, N, xyz, (long)n_points, coef, (long)n_coef, offsets, (long)n_offsets, dirs,
+                               (long)n_dirs, betas, (long)n_betas, maps, (long)n_maps, levels, (long)n_levels, (long)n_out, ew);
     if (rc != PW_OK) return rc;
-    if (pw_context_device(ctx) < 0)
+    std::vector<EwaldHostJob> ew_jobs((size_t)(ew ? N : 0));
+    for (long k = 0; ew && k < N; ++k) {
+        const pw_rigid_cell_ewald_job& E = ew->jobs[k];
+        ew_jobs[k] = EwaldHostJob{(long)E.charge_first, (long)E.cell_first, (long)E.n_cell, (long)E.k_first, (long)E.n_k, E.alpha,
+                                  E.charged};
+    }
+    if (pw_context_device(ctx) < 0) {
+        const EwaldHost host{ew_jobs.data(), ew ? ew->site_q : nullptr, ew ? ew->cell : nullptr, ew ? ew->kvecs : nullptr};
         return pw_hostpath_rigid_cell(jobs, N, xyz, coef, offsets, dirs, betas, maps, levels, out, (long long*)n_pairs, skip,
-                                      pw_context_host_threads(ctx, 0));
+                                      pw_context_host_threads(ctx, 0), ew ? &host : nullptr);
+    }
 
     // the spans of the arrays that the jobs read, and the plan: jobs in order, gathered into launches while their
     // records and partials fit the budget
     const long budget_words = (workspace_bytes ? (long)workspace_bytes : RCELL_WORKSPACE_BYTES) / 8;
-    Span atoms, rows_ab, beta_span, site_span, dir_span;
+    Span atoms, rows_ab, beta_span, site_span, dir_span, q_span, cell_span, k_span;
     for (long k = 0; k < N; ++k) {
         const pw_rigid_cell_job& J = jobs[k];
         atoms.widen((long)J.atom_first, (long)J.n);
@@ -441,10 +491,20 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
         beta_span.widen((long)J.beta_first, (long)J.n_betas);
         site_span.widen((long)J.site_first, (long)J.n_sites);
         dir_span.widen((long)J.dir_first, (long)J.n_dirs);
+        if (!ew || !ew_jobs[k].charged) continue;
+        q_span.widen(ew_jobs[k].charge_first, (long)J.n_sites);
+        cell_span.widen(ew_jobs[k].cell_first, ew_jobs[k].n_cell);
+        k_span.widen(ew_jobs[k].k_first, ew_jobs[k].n_k);
     }
-    // betas, offsets and directions travel as one array (every job has some of each: the three spans have a lo)
+    // betas, offsets and directions travel as one array (every job has some of each: the three spans have a lo), and
+    // behind them what the charged jobs read: site charges, cell atoms and rows (h, k, l, w)
     const long n_beta_span = beta_span.count(), n_site_span = site_span.count(), n_dir_span = dir_span.count();
-    std::vector<double> params((size_t)(n_beta_span + n_site_span + 3 * n_dir_span));
+    const long n_q_span = q_span.count(), n_cell_span = cell_span.count(), n_k_span = k_span.count();
+    const long q_at = n_beta_span + n_site_span + 3 * n_dir_span, cell_at = q_at + n_q_span, k_at = cell_at + 4 * n_cell_span;
+    std::vector<double> params((size_t)(k_at + 4 * n_k_span));
+    if (n_q_span) memcpy(params.data() + q_at, ew->site_q + q_span.lo, sizeof(double) * (size_t)n_q_span);
+    if (n_cell_span) memcpy(params.data() + cell_at, ew->cell + 4 * cell_span.lo, sizeof(double) * 4 * (size_t)n_cell_span);
+    if (n_k_span) memcpy(params.data() + k_at, ew->kvecs + 4 * k_span.lo, sizeof(double) * 4 * (size_t)n_k_span);
     memcpy(params.data(), betas + beta_span.lo, sizeof(double) * (size_t)n_beta_span);
     memcpy(params.data() + n_beta_span, offsets + site_span.lo, sizeof(double) * (size_t)n_site_span);
     memcpy(params.data() + n_beta_span + n_site_span, dirs + 3 * dir_span.lo, sizeof(double) * 3 * (size_t)n_dir_span);
@@ -452,19 +512,35 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
     std::vector<RCellJobDev> devs((size_t)N);
     std::vector<LaunchGroup> groups;
     LaunchGroup cur;
-    long n_level_rows = 0;
+    long n_level_rows = 0, tiles = 0;                                // tiles: the items of the Urec kernel in `cur` so far
     for (long k = 0; k < N; ++k) {
         const pw_rigid_cell_job& J = jobs[k];
         const long L = (long)J.n_betas, V = rcell_voxels(J), chunks = (V + AFF_CHUNK - 1) / AFF_CHUNK;
         const long gx = rcell_groups(J.nx), gy = rcell_groups(J.ny), gz = rcell_groups(J.nz);
-        const long rec_words = rcell_record_words(V, (int)L), need = rec_words + chunks * rigid_part_words((int)L);
+        const long rec_words = rcell_record_words(V, (int)L), part_words = chunks * rigid_part_words((int)L);
+        const bool charged = ew && ew_jobs[k].charged;
+        const long K = charged ? ew_jobs[k].n_k : 0, M = (long)J.n_dirs;
+        const long table_words = K ? ewald_table_words(K, M) : 0, urec_words = K ? ewald_urec_words(V, M) : 0;
+        const long need = rec_words + part_words + table_words + urec_words;
         place(groups, cur, budget_words, need);
+        if (cur.last == cur.first) tiles = 0;                        // (a group was opened)
         RCellJobDev& D = devs[k];
         D.atom_first = atoms.rel((long)J.atom_first, (long)J.n);
         D.n = (long)J.n;
         D.coef_first = rows_ab.rel((long)J.coef_first, (long)J.n);
         D.rec_first = cur.words;
         D.part_first = cur.words + rec_words;
+        D.table_first = cur.words + rec_words + part_words;
+        D.urec_first = K ? D.table_first + table_words : -1;
+        D.krow_first = cur.rows;                                     // (LaunchGroup's rows: the rows of the group's tables kernel)
+        D.tile_first = tiles;
+        D.charged = charged ? 1 : 0;
+        D.alpha = charged ? ew_jobs[k].alpha : 0.0;
+        D.q_first = charged ? ew_jobs[k].charge_first - q_span.lo_or_zero() : 0;
+        D.cell_first = charged ? cell_span.rel(ew_jobs[k].cell_first, ew_jobs[k].n_cell) : 0;
+        D.n_cell = charged ? ew_jobs[k].n_cell : 0;
+        D.k_first = charged ? k_span.rel(ew_jobs[k].k_first, K) : 0;
+        D.K = K;
         D.item_first = cur.items;
         D.chunk_first = cur.blocks;
         D.chunks = chunks;
@@ -480,9 +556,10 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
                                 (int)J.n_dirs, skip != 0);
         D.nx = J.nx; D.ny = J.ny; D.nz = J.nz; D.gx = (int)gx; D.gy = (int)gy; D.L = (int)L; D.S = (int)J.n_sites; D.M = (int)J.n_dirs;
         D.cls = rcell_class((int)J.n_sites);
-        D.reserved = 0;
         n_level_rows += L;
         cur.words += need; cur.cost += need; cur.items += gx * gy * gz; cur.blocks += chunks; cur.last += 1;
+        cur.rows += K;
+        tiles += K ? gx * gy * gz * ((M + EWALD_OT - 1) / EWALD_OT) : 0;
     }
     groups.push_back(cur);
 
@@ -509,7 +586,7 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
         STAT_TRY(buf.alloc(&d_jobs, sizeof(RCellJobDev) * (size_t)N));
         STAT_TRY(hipMemcpyAsync(d_jobs, devs.data(), sizeof(RCellJobDev) * (size_t)N, hipMemcpyHostToDevice, st));
         STAT_TRY(atoms.upload(buf, &d_xyz, xyz, 3));
-        STAT_TRY(rows_ab.upload(buf, &d_coef, coef, 2));
+        STAT_TRY(rows_ab.upload(buf, &d_coef, coef, W));
         STAT_TRY(buf.alloc(&d_params, sizeof(double) * params.size()));
         STAT_TRY(hipMemcpyAsync(d_params, params.data(), sizeof(double) * params.size(), hipMemcpyHostToDevice, st));
         STAT_TRY(buf.alloc(&d_ws, ws_bytes));
@@ -534,10 +611,15 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
                 max_M = devs[k].M > max_M ? devs[k].M : max_M;
             }
             const long blocks = G.items < 65536 ? G.items : 65536, sum_blocks = G.blocks < 65536 ? G.blocks : 65536;
+            const RCellJobDev& last = devs[G.last - 1];
+            const long group_tiles = last.tile_first + (last.K ? (long)last.gx * last.gy * rcell_groups(last.nz) *
+                                                                     ((last.M + EWALD_OT - 1) / EWALD_OT) : 0);
+            STAT_TRY(ewald_launch(st, d_jobs + G.first, (int)n_group, G.rows, group_tiles, d_params + cell_at, d_params + k_at,
+                                  d_params + q_at, d_offsets, d_dirs, d_ws));
             for (int cls = 0; cls < RCELL_CLASSES; ++cls) {
                 if (!needed[cls]) continue;
-                rcell_launch(cls, (unsigned)blocks, sizeof(double) * 3 * (size_t)max_M, st, d_jobs + G.first, (int)n_group, G.items,
-                             d_xyz, d_coef, d_offsets, d_dirs, d_betas, d_ws, d_pairs + G.first);
+                rcell_launch(cls, W == 3, (unsigned)blocks, sizeof(double) * 3 * (size_t)max_M, st, d_jobs + G.first, (int)n_group,
+                             G.items, d_xyz, d_coef, d_offsets, d_dirs, d_betas, d_ws, d_pairs + G.first);
                 STAT_TRY(hipGetLastError());
                 ran |= 1 << cls;
             }
@@ -593,4 +675,49 @@ extern "C" int pw_internal_rigid_cell(pw_context* ctx, const pw_rigid_cell_job* 
                                       int32_t* instances) {
     return rigid_cell(ctx, jobs, n_jobs, xyz, n_points, coef, n_coef, offsets, n_offsets, dirs, n_dirs, betas, n_betas, maps, n_maps,
                       levels, n_levels, out, n_out, workspace_bytes, kernel_ms, n_pairs, skip, instances);
+}
+
+namespace {
+
+// pw_rigid_cell_ewald: the embedded pw_rigid_cell jobs as an array of their own, then the one plan with the Ewald arguments
+int rigid_cell_ewald(pw_context* ctx, const pw_rigid_cell_ewald_job* jobs, int64_t n_jobs, const double* xyz, int64_t n_points,
+                     const double* coef, int64_t n_coef, const double* offsets, int64_t n_offsets, const double* dirs,
+                     int64_t n_dirs, const double* betas, int64_t n_betas, const double* site_q, int64_t n_site_q,
+                     const double* cell, int64_t n_cell, const double* kvecs, int64_t n_kvecs, double* maps, int64_t n_maps,
+                     pw_affinity_level* levels, int64_t n_levels, pw_rigid_out* out, int64_t n_out, int64_t workspace_bytes,
+                     float* kernel_ms, int64_t* n_pairs, int skip, int32_t* instances) {
+    if (n_jobs < 0 || n_jobs > 0x7ffffff0 || (n_jobs && !jobs) || n_site_q < 0 || n_cell < 0 || n_kvecs < 0) return PW_E_BAD_ARG;
+    std::vector<pw_rigid_cell_job> cells((size_t)n_jobs);
+    for (int64_t k = 0; k < n_jobs; ++k) cells[(size_t)k] = jobs[k].cell;
+    const EwaldArgs ew{jobs, site_q, cell, kvecs, (long)n_site_q, (long)n_cell, (long)n_kvecs};
+    return rigid_cell(ctx, cells.data(), n_jobs, xyz, n_points, coef, n_coef, offsets, n_offsets, dirs, n_dirs, betas, n_betas, maps,
+                      n_maps, levels, n_levels, out, n_out, workspace_bytes, kernel_ms, n_pairs, skip, instances,
+                      "pw_rigid_cell_ewald", &ew);
+}
+
+}  // namespace
+
+extern "C" int pw_rigid_cell_ewald(pw_context* ctx, const pw_rigid_cell_ewald_job* jobs, int64_t n_jobs, const double* xyz,
+                                   int64_t n_points, const double* coef, int64_t n_coef, const double* offsets, int64_t n_offsets,
+                                   const double* dirs, int64_t n_dirs, const double* betas, int64_t n_betas, const double* site_q,
+                                   int64_t n_site_q, const double* cell, int64_t n_cell, const double* kvecs, int64_t n_kvecs,
+                                   double* maps, int64_t n_maps, pw_affinity_level* levels, int64_t n_levels, pw_rigid_out* out,
+                                   int64_t n_out) {
+    return rigid_cell_ewald(ctx, jobs, n_jobs, xyz, n_points, coef, n_coef, offsets, n_offsets, dirs, n_dirs, betas, n_betas, site_q,
+                            n_site_q, cell, n_cell, kvecs, n_kvecs, maps, n_maps, levels, n_levels, out, n_out, 0, nullptr, nullptr, 1,
+                            nullptr);
+}
+
+// measurement and test hook (not part of the header): pw_rigid_cell_ewald with pw_internal_rigid_cell's knobs
+extern "C" int pw_internal_rigid_cell_ewald(pw_context* ctx, const pw_rigid_cell_ewald_job* jobs, int64_t n_jobs, const double* xyz,
+                                            int64_t n_points, const double* coef, int64_t n_coef, const double* offsets,
+                                            int64_t n_offsets, const double* dirs, int64_t n_dirs, const double* betas,
+                                            int64_t n_betas, const double* site_q, int64_t n_site_q, const double* cell,
+                                            int64_t n_cell, const double* kvecs, int64_t n_kvecs, double* maps, int64_t n_maps,
+                                            pw_affinity_level* levels, int64_t n_levels, pw_rigid_out* out, int64_t n_out,
+                                            int64_t workspace_bytes, float* kernel_ms, int64_t* n_pairs, int skip,
+                                            int32_t* instances) {
+    return rigid_cell_ewald(ctx, jobs, n_jobs, xyz, n_points, coef, n_coef, offsets, n_offsets, dirs, n_dirs, betas, n_betas, site_q,
+                            n_site_q, cell, n_cell, kvecs, n_kvecs, maps, n_maps, levels, n_levels, out, n_out, workspace_bytes,
+                            kernel_ms, n_pairs, skip, instances);
 }

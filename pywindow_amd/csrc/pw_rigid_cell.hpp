@@ -8,7 +8,8 @@
 // voxel centres by channels_x / _y / _z), n atoms X -- every periodic image that matters listed as an atom of its own --,
 // core2 >= 1e-6, cutoff2 > core2 (0 is refused: a cell has no "no cutoff"), L <= 8 betas, and of a pw_rigid job the
 // S <= RIGID_MAX_SITES offsets t_s (|t_s| <= 16), the M <= RIGID_MAX_DIRS directions d_o (data: components within
-// [-1, 1], nothing normalises them) and rows (A, B) per (site, atom), row s * n + a, two doubles a row.  Uncharged only.
+// [-1, 1], nothing normalises them) and rows (A, B) per (site, atom), row s * n + a, two doubles a row.  Uncharged only
+// (pw_ewald.hpp defines the charged entry, pw_rigid_cell_ewald, on top of this one).
 //   POSE, WEIGHT, VOXEL  pw_rigid.hpp's with charged = 0 and the voxel centre by channels_x / _y / _z: the site position
 //            by rigid_site; per site the atoms in index order, aff_r2, aff_blocked, aff_counts, aff_pair, the per-site
 //            accumulators from +0.0; U = U_0 + U_1 + ...; aff_weight with its clamp and AFF_CLAMPED; RigidFold over the

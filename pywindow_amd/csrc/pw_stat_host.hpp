@@ -20,7 +20,7 @@ extern "C" int pw_context_device(pw_context* ctx);
 namespace pw {
 
 // Test hook (pw_kde.hip: pw_internal_poison_scratch): while the flag is set, the statistical entries (pw_kde_sums,
-// pw_kde2_sums, pw_kde_wsums, pw_corr_sums, pw_dft_sums, pw_gate_counts, pw_trans_counts, pw_superpose, pw_cluster_gromos, pw_covariance, pw_project, pw_cavity, pw_sasa, pw_pore_sizes, pw_affinity, pw_rigid_affinity, pw_rigid_cell, pw_passage, pw_hop, pw_charges, pw_channels) fill their workspace and their
+// pw_kde2_sums, pw_kde_wsums, pw_corr_sums, pw_dft_sums, pw_gate_counts, pw_trans_counts, pw_superpose, pw_cluster_gromos, pw_covariance, pw_project, pw_cavity, pw_sasa, pw_pore_sizes, pw_affinity, pw_rigid_affinity, pw_rigid_cell, pw_rigid_cell_ewald, pw_passage, pw_hop, pw_charges, pw_channels) fill their workspace and their
 // compact device result with bytes 0xFF -- a NaN as a double, garbage as a gate summary or a bit mask -- before their first kernel,
 // so that a read of device memory the call never wrote shows in the result.  The periodic pre-processing (pw_rebuild.hip) does
 // the same with its team slabs and its device outputs.  Off at start; an entry reads the flag

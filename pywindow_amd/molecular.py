@@ -574,30 +574,34 @@ class MolecularSystem:
         return self.system["coordinates"], self.system["elements"], lattice
 
     def calculate_rigid_guest_percolation(self, guest="CO2", temperatures=298.0, spacing: float = 0.5, cutoff: float = 12.0,
-                                          core2: float = 0.25, directions=None, device=None):
+                                          core2: float = 0.25, directions=None, device=None, charges=None,
+                                          ewald_tolerance: float = 1e-6):
         """The levels at which the free-energy landscape of a rigid linear guest's centre (N2, CO2, O2 or a
         :class:`pywindow_amd.RigidGuest`) connects through the loaded cell (``pywindow_amd.rigid_guest_percolation``:
         ``pw_rigid_cell``, then ``pw_percolation`` on the GPU, UFF atoms): a list, one
-        :class:`pywindow_amd.Percolation` per temperature, also kept in ``self.rigid_percolation``."""
+        :class:`pywindow_amd.Percolation` per temperature, also kept in ``self.rigid_percolation``.  ``charges`` (the framework's point charges in e, one per atom or one row a frame) and
+        ``ewald_tolerance``: the Ewald sum of ``pywindow_amd.rigid_guest_field``; ``None``: uncharged, ``pw_rigid_cell``."""
         from . import rigid_cell as RC
 
         xyz, elements, lattice = self._rigid_cell_inputs("calculate_rigid_guest_percolation")
         self.rigid_percolation = RC.rigid_guest_percolation(xyz, elements, lattice, guest, temperatures, spacing, cutoff, core2,
-                                                            directions, device)
+                                                            directions, device, charges=charges, ewald_tolerance=ewald_tolerance)
         return self.rigid_percolation
 
     def calculate_rigid_guest_diffusion(self, guest="CO2", temperatures=298.0, spacing: float = 0.5, cutoff: float = 12.0,
                                         core2: float = 0.25, directions=None, cap: float = 100.0, merge=None, mass=None,
-                                        labels: bool = False, device=None):
+                                        labels: bool = False, device=None, charges=None, ewald_tolerance: float = 1e-6):
         """The self-diffusion tensor of a rigid linear guest through the loaded cell
         (``pywindow_amd.rigid_guest_diffusion``: ``pw_rigid_cell``, then ``pw_basins`` on the GPU, UFF atoms), each
         temperature on its own free-energy field: a :class:`pywindow_amd.Diffusion`, also kept in
-        ``self.rigid_diffusion``."""
+        ``self.rigid_diffusion``.  ``charges`` (the framework's point charges in e, one per atom or one row a frame) and
+        ``ewald_tolerance``: the Ewald sum of ``pywindow_amd.rigid_guest_field``; ``None``: uncharged, ``pw_rigid_cell``."""
         from . import rigid_cell as RC
 
         xyz, elements, lattice = self._rigid_cell_inputs("calculate_rigid_guest_diffusion")
         self.rigid_diffusion = RC.rigid_guest_diffusion(xyz, elements, lattice, guest, temperatures, spacing, cutoff, core2,
-                                                        directions, cap, merge, mass, labels, device)
+                                                        directions, cap, merge, mass, labels, device, charges=charges,
+                                                        ewald_tolerance=ewald_tolerance)
         return self.rigid_diffusion
 
     def swap_atom_keys(self, swap_dict: dict, dict_key: str = "atom_ids") -> None:

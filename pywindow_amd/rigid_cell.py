@@ -10,8 +10,14 @@ order of additions, so the device and the explicit host path (``device=-1``) ret
 free energy of the guest's centre at that temperature: a periodic scalar field, which ``pw_percolation`` and ``pw_basins``
 take as a caller's field.  Every temperature has its own field.
 
-What is left out.  Charges: a cutoff Coulomb sum over images is not a defined periodic energy, so the jobs are uncharged
-and ``charges=`` is not accepted (a Wolf or Ewald term and periodic charge equilibration are not built).  Non-linear
+Charges.  A cutoff Coulomb sum over images is not a defined periodic energy; with ``charges=`` (the framework's point
+charges, one per atom or one row a frame) the jobs go through ``pw_rigid_cell_ewald`` and every pose energy carries the
+Ewald sum of the framework's charges on the guest's site charges (:mod:`pywindow_amd.ewald`,
+pywindow_amd/csrc/pw_ewald.hpp): the real-space term in the pair loop, the reciprocal term added last.  Without
+``charges`` the calls are ``pw_rigid_cell``'s exactly as before.
+
+What is left out.  Periodic charge equilibration (``charges="qeq"`` is refused: it is the isolated-molecule model); a
+framework that is not neutral (no background term); the guest's interaction with its own images.  Non-linear
 guests.  Guest-guest terms: infinite dilution.  The fields travel through host memory between the three entries.  The
 reference has no counterpart.
 
@@ -32,8 +38,9 @@ import numpy as np
 from . import _lib, engine
 from .affinity import _PER_BAR, R
 from .diffusion import Diffusion, _basins_jobs, _frame, _one as _one_diffusion, _run
+from .ewald import ewald_parameters, framework_charges
 from .percolation import _one as _one_percolation, _result as _percolation_result, plan_jobs
-from .rigid import M_DEFAULT, _guest, rigid_coefficients
+from .rigid import COULOMB, M_DEFAULT, _guest, rigid_coefficients
 from .surface import sphere_directions
 
 __all__ = ["RIGID_GUEST_MASSES", "RigidField", "rigid_guest_field", "rigid_guest_field_batch", "rigid_guest_percolation",
@@ -184,11 +191,51 @@ def _temperatures(temperatures):
 
 def plan_field(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5, cutoff: float = 12.0,
                core2: float = 0.25, directions=None):
-    """What :func:`rigid_guest_field_batch` hands to ``Context.rigid_cell`` and keeps for the result: ``(jobs, atoms, coef,
-    offsets, dirs, betas, given, temps, Rs, Qs, shapes, g)``.  Job ``t`` is frame ``t``; the grid, the rotation and the
+    """What :func:`rigid_guest_field_batch` hands to ``Context.rigid_cell`` and keeps for the result (:func:`_plan`)."""
+    return _plan(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions)[0]
+
+
+def plan_charged_field(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
+                       cutoff: float = 12.0, core2: float = 0.25, directions=None, charges=None, ewald_tolerance: float = 1e-6):
+    """:func:`plan_field` for a framework with the point charges ``charges`` (``(n,)`` or ``(T, n)``, e): ``(planned, ew)``,
+    ``ew`` what ``Context.rigid_cell_ewald`` takes beyond the plan -- ``jobs`` (``_lib.RIGID_CELL_EWALD_JOB_DTYPE``, every
+    job charged), ``coef`` the rows ``(A, B, C)`` with ``C = COULOMB q_site q_atom`` image by image, ``site_q``, ``cell``
+    the rows ``(x, y, z, q)`` of each frame's own atoms in its triangular frame and ``kvecs`` the rows of
+    :func:`pywindow_amd.ewald_parameters` of each frame's cell at ``cutoff`` and ``ewald_tolerance``."""
+    planned, source, x, lat = _plan(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions)
+    jobs, atoms, coef, offsets = planned[:4]
+    Qs, g = planned[9], planned[11]
+    T, n = x.shape[:2]
+    q = framework_charges(charges, T, n)
+    S = len(offsets)
+    site_q = np.ascontiguousarray(g.charges, dtype=np.float64)
+    ew_jobs = np.zeros(T, dtype=_lib.RIGID_CELL_EWALD_JOB_DTYPE)
+    ew_jobs["cell"] = jobs
+    rows, kvecs = [], []
+    for t in range(T):
+        a, m = int(jobs["atom_first"][t]), int(jobs["n"][t])
+        ab = coef[S * a:S * (a + m)].reshape(S, m, 2)
+        c = COULOMB * site_q[:, None] * q[t, source[a:a + m]][None, :]
+        rows.append(np.concatenate([ab, c[:, :, None]], axis=2).reshape(-1, 3))
+        alpha, kv = ewald_parameters(lat[t], cutoff, ewald_tolerance)
+        ew_jobs["alpha"][t] = alpha
+        ew_jobs["k_first"][t] = sum(len(v) for v in kvecs)
+        ew_jobs["n_k"][t] = len(kv)
+        kvecs.append(kv)
+    ew_jobs["cell_first"] = n * np.arange(T)
+    ew_jobs["n_cell"] = n
+    ew_jobs["charged"] = 1
+    cell = np.concatenate([np.matmul(x, Qs), q[:, :, None]], axis=2).reshape(-1, 4)
+    return planned, {"jobs": ew_jobs, "coef": np.concatenate(rows) if rows else np.zeros((0, 3)), "site_q": site_q,
+                     "cell": np.ascontiguousarray(cell), "kvecs": np.concatenate(kvecs) if kvecs else np.zeros((0, 4))}
+
+
+def _plan(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions):
+    """``(planned, source, xyz, lattices)``: what :func:`rigid_guest_field_batch` hands to ``Context.rigid_cell`` and keeps
+    for the result, ``planned = (jobs, atoms, coef, offsets, dirs, betas, given, temps, Rs, Qs, shapes, g)``.  Job ``t`` is frame ``t``; the grid, the rotation and the
     images are :func:`pywindow_amd.percolation.plan_jobs`'s with the reach ``cutoff + max|t_s| * max|d_o|`` in place of
     the cutoff; the rows ``(A, B)`` of every site are repeated image by image; the directions are rotated into each
-    frame's triangular cell."""
+    frame's triangular cell.  ``source``: for every image the atom it is an image of."""
     x = np.ascontiguousarray(xyz, dtype=np.float64)
     if x.ndim != 3 or x.shape[2] != 3:
         raise ValueError("xyz: (T, n, 3)")
@@ -243,12 +290,16 @@ def plan_field(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, 
     jobs["core2"], jobs["cutoff2"] = core2, cutoff * cutoff
     dirs = np.clip(np.matmul(given[None], Qs), -1.0, 1.0).reshape(-1, 3)         # rows: d_triangular = d @ Q
     coef_rows = np.concatenate(rows) if rows else np.zeros((0, 2))
-    return jobs, atoms, coef_rows, offsets, dirs, 1.0 / (R * temps), given, temps, Rs, Qs, shapes, g
+    return (jobs, atoms, coef_rows, offsets, dirs, 1.0 / (R * temps), given, temps, Rs, Qs, shapes, g), source, x, lat
 
 
-def _field(planned, ctx, spacing, frames, kernel_ms=None, diagnostics=None) -> RigidField:
+def _field(planned, ctx, spacing, frames, kernel_ms=None, diagnostics=None, ew=None) -> RigidField:
     jobs, atoms, coef, offsets, dirs, betas, given, temps, Rs, Qs, shapes, g = planned
-    out, levels, maps = ctx.rigid_cell(jobs, atoms, coef, offsets, dirs, betas, kernel_ms=kernel_ms, diagnostics=diagnostics)
+    if ew is None:
+        out, levels, maps = ctx.rigid_cell(jobs, atoms, coef, offsets, dirs, betas, kernel_ms=kernel_ms, diagnostics=diagnostics)
+    else:
+        out, levels, maps = ctx.rigid_cell_ewald(ew["jobs"], atoms, ew["coef"], offsets, dirs, betas, ew["site_q"], ew["cell"],
+                                                 ew["kvecs"], kernel_ms=kernel_ms, diagnostics=diagnostics)
     T, L = len(jobs), len(temps)
     zbar, low = [], []
     for J in jobs:
@@ -269,16 +320,21 @@ def _one_field(many: RigidField) -> RigidField:
 
 def rigid_guest_field_batch(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
                             cutoff: float = 12.0, core2: float = 0.25, directions=None, device=None, frames=None,
-                            kernel_ms=None, diagnostics=None) -> RigidField:
+                            kernel_ms=None, diagnostics=None, charges=None, ewald_tolerance: float = 1e-6) -> RigidField:
     """:func:`rigid_guest_field` for ``T`` frames of the same ``n`` atoms, all jobs in ONE ``pw_rigid_cell`` call: ``xyz``
     ``(T, n, 3)``, ``lattice`` ``(3, 3)`` or ``(T, 3, 3)``.  ``kernel_ms``: a list that receives the time of the device work
-    by HIP events; ``diagnostics``: a list that receives ``(n_pairs, instances)``."""
-    planned = plan_field(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions)
-    return _field(planned, engine.context(device), spacing, frames, kernel_ms, diagnostics)
+    by HIP events; ``diagnostics``: a list that receives ``(n_pairs, instances)``.  ``charges`` ``(n,)`` or ``(T, n)``: the
+    framework's point charges, one ``pw_rigid_cell_ewald`` call (``None``: ``pw_rigid_cell`` as before)."""
+    if charges is None:
+        planned = plan_field(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions)
+        return _field(planned, engine.context(device), spacing, frames, kernel_ms, diagnostics)
+    planned, ew = plan_charged_field(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions, charges,
+                                     ewald_tolerance)
+    return _field(planned, engine.context(device), spacing, frames, kernel_ms, diagnostics, ew)
 
 
 def rigid_guest_field(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5, cutoff: float = 12.0,
-                      core2: float = 0.25, directions=None, device=None) -> RigidField:
+                      core2: float = 0.25, directions=None, device=None, charges=None, ewald_tolerance: float = 1e-6) -> RigidField:
     """The orientation-averaged Boltzmann factor of the rigid linear guest ``guest`` (a name of ``RIGID_GUESTS`` or a
     :class:`pywindow_amd.RigidGuest`) at every voxel of the cell ``lattice`` (columns as vectors) filled with the atoms
     ``xyz`` ``(n, 3)``, at every temperature of ``temperatures`` (1 to 8, in K): see :class:`RigidField`.
@@ -289,14 +345,18 @@ def rigid_guest_field(xyz, elements_or_coef, lattice, guest="CO2", temperatures=
     the guest's longest arm -- in place of the cutoff: a reach above the cell's smallest perpendicular width raises and
     names the largest cutoff that fits.  ``directions``: ``(M, 3)``, at most 1024 (``None``:
     ``pywindow_amd.sphere_directions(64)``), in the frame of ``xyz``; they are data, neither normalised nor checked for
-    length.  A pose with a site within ``sqrt(core2)`` of an atom is blocked.  The jobs are uncharged.  ``xyz``
-    ``(T, n, 3)`` is :func:`rigid_guest_field_batch`.  ``device``: the HIP ordinal (``None``: the process's); ``-1`` the
-    explicit host path."""
+    length.  A pose with a site within ``sqrt(core2)`` of an atom is blocked.  ``charges``: the framework's point charges in
+    e, one per atom (or one row a frame): every pose energy then carries the Ewald sum of those charges on the guest's site
+    charges, real-space part cut at ``cutoff``, parameters by :func:`pywindow_amd.ewald_parameters` at ``ewald_tolerance``; a
+    framework that is not neutral within ``1e-8 * sum |q|`` and ``"qeq"`` are refused.  ``None``: the jobs are uncharged.
+    ``xyz`` ``(T, n, 3)`` is :func:`rigid_guest_field_batch`.  ``device``: the HIP ordinal (``None``: the process's); ``-1``
+    the explicit host path."""
     x = np.asarray(xyz, dtype=np.float64)
     args = (elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions, device)
+    kw = dict(charges=charges, ewald_tolerance=ewald_tolerance)
     if x.ndim == 3:
-        return rigid_guest_field_batch(x, *args)
-    return _one_field(rigid_guest_field_batch(x.reshape(1, -1, 3), *args))
+        return rigid_guest_field_batch(x, *args, **kw)
+    return _one_field(rigid_guest_field_batch(x.reshape(1, -1, 3), *args, **kw))
 
 
 def _field_jobs(field: RigidField):
@@ -316,12 +376,13 @@ def _field_jobs(field: RigidField):
 
 
 def rigid_guest_percolation_batch(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
-                                  cutoff: float = 12.0, core2: float = 0.25, directions=None, device=None, frames=None):
+                                  cutoff: float = 12.0, core2: float = 0.25, directions=None, device=None, frames=None,
+                                  charges=None, ewald_tolerance: float = 1e-6):
     """:func:`rigid_guest_percolation` for ``T`` frames: one ``pw_rigid_cell`` call, then every (frame, temperature) as a
     job on its free-energy field in ONE ``pw_percolation`` call.  A list, one :class:`pywindow_amd.Percolation` over the
     frames per temperature."""
     field = rigid_guest_field_batch(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions, device,
-                                    frames)
+                                    frames, charges=charges, ewald_tolerance=ewald_tolerance)
     jobs, values = _field_jobs(field)
     levels, out, _ = engine.context(device).percolation(jobs, field=values)
     T, L = len(field.raw), len(field.temperatures)
@@ -331,20 +392,23 @@ def rigid_guest_percolation_batch(xyz, elements_or_coef, lattice, guest="CO2", t
 
 
 def rigid_guest_percolation(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
-                            cutoff: float = 12.0, core2: float = 0.25, directions=None, device=None):
+                            cutoff: float = 12.0, core2: float = 0.25, directions=None, device=None, charges=None,
+                            ewald_tolerance: float = 1e-6):
     """The levels at which the free-energy landscape of a rigid linear guest's centre connects through the crystal: per
     temperature a :class:`pywindow_amd.Percolation` of ``-R T ln zbar`` (:func:`rigid_guest_field`, the same arguments);
     energies are free energies at that temperature, in kJ/mol.  A list over the temperatures."""
     x = np.asarray(xyz, dtype=np.float64)
     args = (elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions, device)
+    kw = dict(charges=charges, ewald_tolerance=ewald_tolerance)
     if x.ndim == 3:
-        return rigid_guest_percolation_batch(x, *args)
-    return [_one_percolation(p) for p in rigid_guest_percolation_batch(x.reshape(1, -1, 3), *args)]
+        return rigid_guest_percolation_batch(x, *args, **kw)
+    return [_one_percolation(p) for p in rigid_guest_percolation_batch(x.reshape(1, -1, 3), *args, **kw)]
 
 
 def rigid_guest_diffusion_batch(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
                                 cutoff: float = 12.0, core2: float = 0.25, directions=None, cap: float = 100.0, merge=None,
-                                mass=None, labels: bool = False, device=None, frames=None) -> Diffusion:
+                                mass=None, labels: bool = False, device=None, frames=None, charges=None,
+                                ewald_tolerance: float = 1e-6) -> Diffusion:
     """:func:`rigid_guest_diffusion` for ``T`` frames: one ``pw_rigid_cell`` call, then every (frame, temperature) as a
     ``pw_basins`` job on that temperature's free-energy field with that one beta, all in ONE ``pw_basins`` call (and one
     more for the jobs that overflowed the first capacities)."""
@@ -359,7 +423,8 @@ def rigid_guest_diffusion_batch(xyz, elements_or_coef, lattice, guest="CO2", tem
     cap = float(cap)
     if math.isnan(cap) or math.isnan(merge) or merge < 0.0 or not mass > 0.0:
         raise ValueError("cap: a number; merge: >= 0; mass: positive")
-    field = rigid_guest_field_batch(xyz, elements_or_coef, lattice, g, temps, spacing, cutoff, core2, directions, device, frames)
+    field = rigid_guest_field_batch(xyz, elements_or_coef, lattice, g, temps, spacing, cutoff, core2, directions, device, frames,
+                                    charges=charges, ewald_tolerance=ewald_tolerance)
     perc, values = _field_jobs(field)
     T, L = len(field.raw), len(temps)
     jobs = _basins_jobs(perc, temps[:1], cap, False, labels)
@@ -394,7 +459,7 @@ def rigid_guest_diffusion_batch(xyz, elements_or_coef, lattice, guest="CO2", tem
 
 def rigid_guest_diffusion(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
                           cutoff: float = 12.0, core2: float = 0.25, directions=None, cap: float = 100.0, merge=None, mass=None,
-                          labels: bool = False, device=None) -> Diffusion:
+                          labels: bool = False, device=None, charges=None, ewald_tolerance: float = 1e-6) -> Diffusion:
     """The self-diffusion tensor of a rigid linear guest through the crystal at every temperature of ``temperatures``: the
     model of :func:`pywindow_amd.guest_diffusion` on the free energy of the guest's centre, ``-R T ln zbar`` of
     :func:`rigid_guest_field` (the same arguments), each temperature on its own field with its own basins and hop network.
@@ -403,9 +468,11 @@ def rigid_guest_diffusion(xyz, elements_or_coef, lattice, guest="CO2", temperatu
     temperatures whose entries have one level; ``valid`` holds when every temperature is valid.  ``merge`` defaults to
     ``R * min(temperatures)`` for every temperature; ``mass`` (g/mol) comes from ``RIGID_GUEST_MASSES`` for N2, CO2 and O2
     and is required for a caller's :class:`pywindow_amd.RigidGuest`.  The orientational part of the transition state is
-    in the field; the mass is the molecule's, so the rotational kinetic prefactor is left out."""
+    in the field; the mass is the molecule's, so the rotational kinetic prefactor is left out.  ``charges`` /
+    ``ewald_tolerance``: :func:`rigid_guest_field`'s."""
     x = np.asarray(xyz, dtype=np.float64)
     args = (elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions, cap, merge, mass, labels, device)
+    kw = dict(charges=charges, ewald_tolerance=ewald_tolerance)
     if x.ndim == 3:
-        return rigid_guest_diffusion_batch(x, *args)
-    return _one_diffusion(rigid_guest_diffusion_batch(x.reshape(1, -1, 3), *args))
+        return rigid_guest_diffusion_batch(x, *args, **kw)
+    return _one_diffusion(rigid_guest_diffusion_batch(x.reshape(1, -1, 3), *args, **kw))

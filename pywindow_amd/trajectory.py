@@ -639,21 +639,24 @@ class DLPOLY:
         return (sel,) + tuple(self._read_selected(sel, True))
 
     def rigid_field(self, guest="CO2", temperatures=298.0, frames=None, spacing: float = 0.5, cutoff: float = 12.0,
-                    directions=None, device=None, swap_atoms=None, forcefield=None):
+                    directions=None, device=None, swap_atoms=None, forcefield=None, charges=None, ewald_tolerance: float = 1e-6):
         """The orientation-averaged Boltzmann factor of a rigid linear guest (N2, CO2, O2 or a
         :class:`pywindow_amd.RigidGuest`) at every voxel of the periodic cell of every selected frame (``frames``: any
         selection of the trajectory's frames, ``None``: all of them), ALL frames in ONE ``pw_rigid_cell`` call on the GPU
         (``pywindow_amd.rigid_guest_field_batch``, UFF atoms, ``core2 = 0.25``) -- a :class:`pywindow_amd.RigidField`
         whose fields are arrays, or lists, over the frames and whose ``frames`` are the trajectory's frame numbers.
-        Periodic trajectories only."""
+        Periodic trajectories only.  ``charges`` (the framework's point charges in e, one per atom or one row a selected frame) and
+        ``ewald_tolerance``: the Ewald sum of ``pywindow_amd.rigid_guest_field``; ``None``: uncharged, ``pw_rigid_cell``."""
         from . import rigid_cell as RC
 
         sel, coords, lattice = self._rigid_cell_frames("rigid_field", frames)
         return RC.rigid_guest_field_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, temperatures, spacing,
-                                          cutoff, 0.25, directions, device, frames=sel)
+                                          cutoff, 0.25, directions, device, frames=sel, charges=charges,
+                                          ewald_tolerance=ewald_tolerance)
 
     def rigid_percolation(self, guest="CO2", temperatures=298.0, frames=None, spacing: float = 0.5, cutoff: float = 12.0,
-                          directions=None, device=None, swap_atoms=None, forcefield=None):
+                          directions=None, device=None, swap_atoms=None, forcefield=None, charges=None,
+                          ewald_tolerance: float = 1e-6):
         """The levels at which the free-energy landscape of a rigid linear guest's centre connects through the periodic
         cell of every selected frame (``pywindow_amd.rigid_guest_percolation_batch``: one ``pw_rigid_cell`` and one
         ``pw_percolation`` call on the GPU) -- a list, one :class:`pywindow_amd.Percolation` over the frames per
@@ -662,11 +665,12 @@ class DLPOLY:
 
         sel, coords, lattice = self._rigid_cell_frames("rigid_percolation", frames)
         return RC.rigid_guest_percolation_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, temperatures,
-                                                spacing, cutoff, 0.25, directions, device, frames=sel)
+                                                spacing, cutoff, 0.25, directions, device, frames=sel, charges=charges,
+                                                ewald_tolerance=ewald_tolerance)
 
     def rigid_diffusion(self, guest="CO2", temperatures=298.0, frames=None, spacing: float = 0.5, cutoff: float = 12.0,
                         directions=None, cap: float = 100.0, merge=None, mass=None, device=None, swap_atoms=None,
-                        forcefield=None):
+                        forcefield=None, charges=None, ewald_tolerance: float = 1e-6):
         """The self-diffusion tensor of a rigid linear guest through the periodic cell of every selected frame
         (``pywindow_amd.rigid_guest_diffusion_batch``: one ``pw_rigid_cell`` and one ``pw_basins`` call on the GPU) -- a
         :class:`pywindow_amd.Diffusion` with ``tensor`` ``(frames, L, 3, 3)`` whose ``frames`` are the trajectory's frame
@@ -676,7 +680,8 @@ class DLPOLY:
 
         sel, coords, lattice = self._rigid_cell_frames("rigid_diffusion", frames)
         return RC.rigid_guest_diffusion_batch(coords, self.elements(swap_atoms, forcefield), lattice, guest, temperatures,
-                                              spacing, cutoff, 0.25, directions, cap, merge, mass, device=device, frames=sel)
+                                              spacing, cutoff, 0.25, directions, cap, merge, mass, device=device, frames=sel,
+                                              charges=charges, ewald_tolerance=ewald_tolerance)
 
     def passage(self, guest="Xe", spacing: float = 0.5, frames=None, device=None, close="windows", swap_atoms=None,
                 forcefield=None):
