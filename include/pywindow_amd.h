@@ -1257,7 +1257,8 @@ int pw_rigid_cell(pw_context *ctx, const pw_rigid_cell_job *jobs, int64_t n_jobs
  * grid is that entry's bytes.  Everything written, the skip of far atoms and the equality of the bytes on every device,
  * launch geometry, grouping and on a device == -1 context are pw_rigid_cell's.  Left out by design: the guest's
  * interaction with its own images (infinite dilution); any self or background term (none arises between a guest and a
- * NEUTRAL framework; neutrality is the caller's to ensure); periodic charge equilibration; non-linear guests.
+ * NEUTRAL framework; neutrality is the caller's to ensure); non-linear guests.  The charges are given: pw_charges_cell
+ * below makes them for a cell.
  * The counts are pw_rigid_cell's (coef: rows of three doubles) and the entries of site_q, the rows of cell and of kvecs.
  * Refused (PW_E_BAD_ARG, pw_last_error reads "pw_rigid_cell_ewald: job k: ..."; nothing is launched or written): what
  * pw_rigid_cell refuses; charged neither 0 nor 1; and of a charged job a charge term C, alpha, a site charge, a cell
@@ -1331,6 +1332,58 @@ typedef struct pw_charges_out {
 } pw_charges_out;
 int pw_charges(pw_context *ctx, const pw_charges_job *jobs, int64_t n_jobs, const double *xyz, const double *params,
                int64_t n_points, double *charges, pw_charges_out *out);
+/* ---- partial charges of a periodic crystal cell: charge equilibration with an Ewald sum ------------------------------
+ * pw_charges treats a cage as if it sat in vacuum; this entry makes the charges that pw_rigid_cell_ewald needs for the
+ * cell itself.  The reference has no counterpart.  The text of record is pywindow_amd/csrc/pw_charges_cell.hpp; in
+ * short, job k has the n >= 1 atoms xyz[xyz_first .. +n) in the triangular frame of the cell's edges (a1, b1, b2, c1, c2,
+ * c3), taken as they are (the caller wraps them into the cell), the parameters params[param_first .. +n) (rows (chi, J)
+ * in eV), coulomb in eV Angstrom, alpha >= 0 in 1 / Angstrom, cutoff2, the switch shield_on2 < shield_off2 <= cutoff2
+ * (Angstrom^2), and n_k rows kvecs[k_first .. +n_k) (h, k, l, w): the rows of pw_rigid_cell_ewald with the weight in eV
+ * per squared charge, data as they are there, under the same caps.  The cell is neutral: there is no total charge.
+ * The charges minimise sum chi_i q_i + 1/2 q^T A q at sum q = 0 with A = D + R + G: D_i = J_i - coulomb 2 alpha / sqrt(pi);
+ * R the sum over the 27 nearest images (an atom's own included, itself not) within cutoff2, equality counting, of
+ * s(r2) (K / sqrt(r2 + a^2) - K / r) + K erfc(alpha r) / r with a = 2 K / (J_i + J_j) and s the quintic switch that is 1
+ * below shield_on2 and 0 above shield_off2 (coincident atoms take the finite limit); G_ij = sum_k w_k cos(k . (x_i -
+ * x_j)), applied through structure factors.  Twenty-seven images suffice for wrapped atoms when the cutoff is at most
+ * the cell's smallest perpendicular width; the entry checks neither.  The solver is projected, Jacobi-preconditioned
+ * conjugate gradients on the neutral subspace; it stops at rz <= tol^2 rz0 or after max_iter steps.  The charges go to
+ * charges[charge_first .. +n); row `out` holds mu (the equalised electronegativity, eV), energy = chi.q / 2 (eV), the
+ * extreme charges, the steps and flags with pw_charges' meanings (PW_CHG_NOT_CONVERGED: the charges of the last step are
+ * written; PW_CHG_BREAKDOWN and PW_CHG_NO_SUM: everything but the steps and flags is NaN).  There is no dipole.
+ * The result is DEFINED: the same bits on every device, launch geometry and run and on a device == -1 context, whatever
+ * else shares the call, wherever a job's vectors live (LDS up to 1536 atoms, a workspace beyond), whether a row of R is
+ * stored or recomputed and however the jobs are cut into launches.  A NaN always leaves as 0x7ff8000000000000.
+ * All pointers are host memory; n_points is the number of rows of xyz, of rows of params and of entries of charges,
+ * n_kvecs the rows of kvecs.  Refused (PW_E_BAD_ARG, pw_last_error reads "pw_charges_cell: job k: ..."; nothing is
+ * launched or written): n < 1, a range outside its array, shared rows of out or entries of charges, a value that is not
+ * finite, J <= 0, coulomb <= 0, alpha < 0, cutoff2 <= 0, shield_on2 < 0, shield_on2 >= shield_off2, shield_off2 >
+ * cutoff2, a1, b2 or c3 not positive, n_k outside 0 .. PW_EWALD_MAX_K, an index that is not an integer within
+ * PW_EWALD_MAX_INDEX, tol outside [1e-14, 1e-2], max_iter outside [1, 100000]. */
+typedef struct pw_charges_cell_job {
+    int64_t xyz_first;       /* first row of xyz */
+    int64_t param_first;     /* first row of params */
+    int64_t n;               /* atoms, >= 1 */
+    int64_t k_first, n_k;    /* rows (h, k, l, w) = kvecs[k_first .. +n_k) */
+    double  edges[6];        /* a1, b1, b2, c1, c2, c3 */
+    double  coulomb;         /* K, eV Angstrom */
+    double  alpha;           /* >= 0 */
+    double  cutoff2;         /* > 0 */
+    double  shield_on2, shield_off2;
+    double  tol;             /* in [1e-14, 1e-2] */
+    int64_t max_iter;        /* in [1, 100000] */
+    int64_t charge_first;    /* first entry of charges */
+    int64_t out;             /* the job's row of the result */
+} pw_charges_cell_job;
+typedef struct pw_charges_cell_out {
+    double  mu;
+    double  energy;
+    double  q_min, q_max;
+    int32_t iterations;
+    int32_t flags;           /* PW_CHG_* */
+} pw_charges_cell_out;
+int pw_charges_cell(pw_context *ctx, const pw_charges_cell_job *jobs, int64_t n_jobs, const double *xyz,
+                    const double *params, int64_t n_points, const double *kvecs, int64_t n_kvecs, double *charges,
+                    pw_charges_cell_out *out);
 /* ---- the pore network of a crystal cell: periodic void components and in how many dimensions each percolates ----
  * Every grid entry above looks at one cage cut out of its surroundings.  This one takes a whole periodic cell: are
  * its voids connected, in how many dimensions, for a guest of which size, and how much of the void is accessible

@@ -60,6 +60,7 @@ from .rigid_cell import (  # noqa: E402
     rigid_guest_percolation_batch,
 )
 from .ewald import EwaldPotential, ewald_parameters, ewald_potential  # noqa: E402
+from .charges_cell import CellCharges, equilibrate_cell_charges, equilibrate_cell_charges_batch  # noqa: E402
 from .molecular import MolecularSystem, Molecule  # noqa: E402
 from .trajectory import DLPOLY  # noqa: E402
 from .utilities import (  # noqa: E402
@@ -142,6 +143,9 @@ __all__ = [
     "Charges",
     "equilibrate_charges",
     "equilibrate_charges_batch",
+    "CellCharges",
+    "equilibrate_cell_charges",
+    "equilibrate_cell_charges_batch",
     "Channels",
     "channel_network",
     "channel_network_batch",

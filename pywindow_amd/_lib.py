@@ -386,6 +386,21 @@ CHG_NOT_CONVERGED = 1
 CHG_BREAKDOWN = 2
 CHG_NO_SUM = 4
 
+#: numpy mirrors of ``pw_charges_cell_job`` and ``pw_charges_cell_out``
+CHARGES_CELL_JOB_DTYPE = np.dtype(
+    [("xyz_first", np.int64), ("param_first", np.int64), ("n", np.int64), ("k_first", np.int64), ("n_k", np.int64),
+     ("edges", np.float64, (6,)), ("coulomb", np.float64), ("alpha", np.float64), ("cutoff2", np.float64),
+     ("shield_on2", np.float64), ("shield_off2", np.float64), ("tol", np.float64), ("max_iter", np.int64),
+     ("charge_first", np.int64), ("out", np.int64)]
+)
+CHARGES_CELL_OUT_DTYPE = np.dtype(
+    [("mu", np.float64), ("energy", np.float64), ("q_min", np.float64), ("q_max", np.float64), ("iterations", np.int32),
+     ("flags", np.int32)]
+)
+assert CHARGES_CELL_JOB_DTYPE.itemsize == 160 and CHARGES_CELL_OUT_DTYPE.itemsize == 40
+#: the solver's vectors of a ``pw_charges_cell`` job stay in LDS up to so many atoms (pw_charges_cell.hpp: CHC_LDS_ATOMS)
+CHARGES_CELL_LDS_ATOMS = 1536
+
 #: numpy mirrors of ``pw_channels_job``, ``pw_channels_comp`` and ``pw_channels_out``
 CHANNELS_JOB_DTYPE = np.dtype(
     [("atom_first", np.int64), ("n", np.int64), ("radius_first", np.int64), ("comp_first", np.int64),
@@ -588,6 +603,7 @@ EXPORTED_SYMBOLS = [
     "pw_rigid_cell",
     "pw_rigid_cell_ewald",
     "pw_charges",
+    "pw_charges_cell",
     "pw_channels",
     "pw_percolation",
     "pw_basins",
@@ -745,6 +761,10 @@ def load():
     L.pw_internal_erfc.argtypes = [vp, vp, i64, vp]
     L.pw_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
     L.pw_internal_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(ctypes.c_float)]
+    L.pw_charges_cell.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp]
+    L.pw_internal_charges_cell.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp]
+    L.pw_internal_sincos.argtypes = [vp, i64, vp, vp]
+    L.pw_internal_sincos.restype = None
     L.pw_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6
     L.pw_internal_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6 + [vp, vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
     L.pw_percolation.argtypes = [vp, vp, i64] + [vp, i64] * 6
@@ -1588,6 +1608,15 @@ class Context:
         _stat_call("pw_internal_erfc", self._h, x.ctypes.data, len(x), out.ctypes.data)
         return out
 
+    @staticmethod
+    def sincos(x):
+        """The library's ``ewald_sincos`` (pw_ewald.hpp: ``pw_sincos``, NaN beyond its range) element by element on the host
+        (test instrumentation): ``(sin, cos)``, float64."""
+        x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+        s, c = np.zeros(len(x)), np.zeros(len(x))
+        load().pw_internal_sincos(x.ctypes.data, len(x), s.ctypes.data, c.ctypes.data)
+        return s, c
+
     def charges(self, jobs, xyz, params, out=None, workspace_bytes=None, kernel_ms=None):
         """``pw_charges``: charge equilibration of a batch of jobs (``CHARGES_JOB_DTYPE`` records indexing the rows of
         ``xyz`` (rows of three), the rows of ``params`` (rows ``(chi, J)`` in eV), the entries of the charges and the
@@ -1622,6 +1651,42 @@ class Context:
             _stat_call("pw_internal_charges", *args, int(workspace_bytes or 0), ctypes.byref(ms))
             if kernel_ms is not None:
                 kernel_ms.append(float(ms.value))
+        return q[:size], out
+
+    def charges_cell(self, jobs, xyz, params, kvecs, out=None, workspace_bytes=None, kernel_ms=None):
+        """``pw_charges_cell``: charge equilibration on a periodic cell of a batch of jobs (``CHARGES_CELL_JOB_DTYPE``
+        records indexing the rows of ``xyz`` (rows of three, in the triangular frame of the job's edges and wrapped by the
+        caller), the rows of ``params`` (rows ``(chi, J)`` in eV), the rows of ``kvecs`` (rows ``(h, k, l, w)``, ``w`` in
+        eV), the entries of the charges and the rows of the result): ``(charges, out)`` as :meth:`charges` returns them,
+        ``out`` a ``CHARGES_CELL_OUT_DTYPE`` array.  Whatever the entry refuses: ``ValueError`` with the library's message.
+        ``workspace_bytes`` / ``kernel_ms`` (a list that receives ``(count, rows, solver)``, the times of the three kinds
+        of kernel in ms by HIP events) go through the library's measurement entry."""
+        jobs = np.ascontiguousarray(jobs, dtype=CHARGES_CELL_JOB_DTYPE).reshape(-1)
+        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 2)
+        kv = np.ascontiguousarray(kvecs, dtype=np.float64).reshape(-1, 4)
+        some = len(jobs) > 0
+        rows = max(int(jobs["out"].max()) + 1, 0) if some else 0
+        if out is None:
+            out = np.zeros(rows, dtype=CHARGES_CELL_OUT_DTYPE)
+        elif out.dtype != CHARGES_CELL_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1 or len(out) < rows:
+            raise ValueError("out: a contiguous CHARGES_CELL_OUT_DTYPE array with a row for every job")
+        size = max(int((jobs["charge_first"] + jobs["n"]).max()), 0) if some else 0
+        n_points = max(len(x), len(p), size)
+        if len(x) < n_points:
+            x = np.concatenate([x, np.zeros((n_points - len(x), 3))])
+        if len(p) < n_points:
+            p = np.concatenate([p, np.zeros((n_points - len(p), 2))])
+        q = np.zeros(n_points)
+        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, p.ctypes.data, n_points, kv.ctypes.data, len(kv),
+                q.ctypes.data, out.ctypes.data]
+        if workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_charges_cell", *args)
+        else:
+            ms = (ctypes.c_float * 3)()
+            _stat_call("pw_internal_charges_cell", *args, int(workspace_bytes or 0), ctypes.addressof(ms))
+            if kernel_ms is not None:
+                kernel_ms.append(tuple(float(v) for v in ms))
         return q[:size], out
 
     def channels(self, jobs, xyz, radii, out=None, comps=None, mask=None, labels=None, open_words=None, open_first=None,

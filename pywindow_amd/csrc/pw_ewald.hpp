@@ -60,7 +60,8 @@
 //
 // LEFT OUT BY DESIGN.  The guest's interaction with its own periodic images: infinite dilution.  Any self or background
 // term: there is none in a framework-guest energy when the framework is neutral, which the Python layer enforces and this
-// entry does not check.  Periodic charge equilibration: the charges are given.  Non-linear guests.
+// entry does not check.  Non-linear guests.  The charges are given: periodic charge equilibration is an entry of its own,
+// pw_charges_cell (pw_charges_cell.hpp), which takes this file's wave vectors and phase arithmetic.
 #pragma once
 #include "pw_rigid_cell.hpp"
 

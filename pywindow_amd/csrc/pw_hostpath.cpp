@@ -29,6 +29,7 @@
 #include "pw_passage.hpp"
 #include "pw_hop.hpp"
 #include "pw_charges.hpp"
+#include "pw_charges_cell.hpp"
 #include "pw_channels.hpp"
 #include "pw_percolate.hpp"
 #include "pw_basins.hpp"
@@ -1977,6 +1978,182 @@ extern "C" int pw_hostpath_charges(const pw_charges_job* jobs, long n_jobs, cons
         o->iterations[1] = sys[1].iterations;
         o->flags = flags;
         o->reserved = 0;
+    };
+    host_share(n_jobs, threads, [&](long k) { one(jobs[k]); });
+    return PW_OK;
+}
+
+// pw_charges_cell on the host (pw_charges_cell.hip checks the arguments and sends device == -1 contexts here): the
+// definition of pw_charges_cell.hpp step by step.  A job's rows of R are built once as lists, its phases once as (n_k, n)
+// arrays -- the definition lets either be kept or recomputed --, and the sums are pw_hostpath_charges'.  The threads share
+// out the jobs.
+extern "C" int pw_hostpath_charges_cell(const pw_charges_cell_job* jobs, long n_jobs, const double* xyz, const double* params,
+                                        const double* kvecs, double* charges, pw_charges_cell_out* out, int threads) {
+    auto one = [&](const pw_charges_cell_job& J) {
+        const long n = (long)J.n, nk = (long)J.n_k;
+        const double* X = xyz + 3 * (long)J.xyz_first;
+        const double* P = params + 2 * (long)J.param_first;
+        const double* KV = kvecs + 4 * (long)J.k_first;
+        const double K = J.coulomb, alpha = J.alpha, tol2 = J.tol * J.tol;
+        // R: the lists
+        double shift[CHC_IMAGES][3];
+        for (int m = 0; m < CHC_IMAGES; ++m) chc_shift(J.edges, m, &shift[m][0], &shift[m][1], &shift[m][2]);
+        std::vector<long> first((size_t)n + 1, 0);
+        std::vector<double> value;
+        std::vector<int> column;
+        for (long i = 0; i < n; ++i) {
+            const double xi = X[3 * i], yi = X[3 * i + 1], zi = X[3 * i + 2], Ji = P[2 * i + 1];
+            for (long j = 0; j < n; ++j)
+                for (int m = 0; m < CHC_IMAGES; ++m) {
+                    if (j == i && m == CHC_SELF_IMAGE) continue;
+                    const double r2 = chc_r2(xi, yi, zi, X[3 * j], X[3 * j + 1], X[3 * j + 2], shift[m][0], shift[m][1], shift[m][2]);
+                    if (!(r2 <= J.cutoff2)) continue;
+                    value.push_back(chc_term(r2, Ji, P[2 * j + 1], K, alpha, J.shield_on2, J.shield_off2));
+                    column.push_back((int)j);
+                }
+            first[(size_t)i + 1] = (long)value.size();
+        }
+        // G: the tables and the phases
+        ChcTables T;
+        T.top[0] = T.top[1] = T.top[2] = 0;
+        for (long k = 0; k < nk; ++k)
+            for (int a = 0; a < 3; ++a) {
+                const int v = (int)KV[4 * k + a];
+                T.top[a] = std::max(T.top[a], v < 0 ? -v : v);
+            }
+        chc_tables_layout(T, n);
+        std::vector<double> tab((size_t)chc_table_words(T.top, n));
+        for (int a = 0; a < 3; ++a)
+            for (int m = 0; m <= T.top[a]; ++m) {
+                const EwaldK kv = chc_axis_kvec(J.edges, a, m);
+                for (long j = 0; j < n; ++j) {
+                    const EwaldCS e = ewald_sincos(ewald_dot(kv, X[3 * j], X[3 * j + 1], X[3 * j + 2]));
+                    tab[(size_t)(T.first[a] + 2l * m * n + j)] = e.c;
+                    tab[(size_t)(T.first[a] + 2l * m * n + n + j)] = e.s;
+                }
+            }
+        std::vector<double> pc((size_t)(nk * n)), ps((size_t)(nk * n)), Sc((size_t)nk), Ss((size_t)nk);
+        for (long k = 0; k < nk; ++k)
+            for (long j = 0; j < n; ++j) {
+                const EwaldCS ph = chc_phase(tab.data(), T, n, j, (int)KV[4 * k], (int)KV[4 * k + 1], (int)KV[4 * k + 2]);
+                pc[(size_t)(k * n + j)] = ph.c;
+                ps[(size_t)(k * n + j)] = ph.s;
+            }
+        std::vector<double> state((size_t)(5 * n));
+        double *q = state.data(), *r = q + n, *z = r + n, *p = z + n, *y = p + n;
+        double lanes[SUP_ACC], lanes2[SUP_ACC];
+        auto dot = [&](const double* a, const double* b, long count) {
+            for (int l = 0; l < SUP_ACC; ++l) lanes[l] = 0.0;
+            for (long i = 0; i < count; ++i) lanes[i % SUP_ACC] = pw_fma(a[i], b[i], lanes[i % SUP_ACC]);
+            return sup_fold(lanes);
+        };
+        for (int l = 0; l < SUP_ACC; ++l) lanes[l] = 0.0;
+        for (long i = 0; i < n; ++i) lanes[i % SUP_ACC] = lanes[i % SUP_ACC] + 1.0 / P[2 * i + 1];
+        const double sJ = sup_fold(lanes);
+        // z and lambda from r
+        auto precondition = [&]() {
+            for (int l = 0; l < SUP_ACC; ++l) lanes[l] = 0.0;
+            for (long i = 0; i < n; ++i) {
+                z[i] = r[i] / P[2 * i + 1];
+                lanes[i % SUP_ACC] = lanes[i % SUP_ACC] + z[i];
+            }
+            const double lambda = sup_fold(lanes) / sJ;
+            for (long i = 0; i < n; ++i) z[i] = z[i] - lambda / P[2 * i + 1];
+            return lambda;
+        };
+        ChcState S;
+        for (long i = 0; i < n; ++i) {
+            q[i] = 0.0;
+            r[i] = -P[2 * i];
+        }
+        S.lambda = precondition();
+        for (long i = 0; i < n; ++i) p[i] = z[i];
+        // r.z with the residual's constant part taken out (pw_charges_cell.hpp, SOLVER)
+        auto projected_dot = [&](double lambda) {
+            for (int l = 0; l < SUP_ACC; ++l) lanes[l] = 0.0;
+            for (long i = 0; i < n; ++i) lanes[i % SUP_ACC] = pw_fma(r[i] - lambda, z[i], lanes[i % SUP_ACC]);
+            return sup_fold(lanes);
+        };
+        S.rz = S.rz0 = projected_dot(S.lambda);
+        S.iterations = 0;
+        S.ran_out = S.broke = false;
+        const double self = chc_self(K, alpha);
+        for (int k = 0;; ++k) {
+            S.iterations = k;
+            if (S.rz <= tol2 * S.rz0) break;
+            if (k == J.max_iter) {
+                S.ran_out = true;
+                break;
+            }
+            for (long kr = 0; kr < nk; ++kr) {
+                for (int l = 0; l < SUP_ACC; ++l) lanes[l] = lanes2[l] = 0.0;
+                const double *c = pc.data() + kr * n, *s = ps.data() + kr * n;
+                for (long j = 0; j < n; ++j) {
+                    lanes[j % SUP_ACC] = pw_fma(p[j], c[j], lanes[j % SUP_ACC]);
+                    lanes2[j % SUP_ACC] = pw_fma(p[j], s[j], lanes2[j % SUP_ACC]);
+                }
+                Sc[(size_t)kr] = sup_fold(lanes);
+                Ss[(size_t)kr] = sup_fold(lanes2);
+            }
+            for (long i = 0; i < n; ++i) {
+                for (int l = 0; l < SUP_ACC; ++l) lanes[l] = lanes2[l] = 0.0;
+                for (long e = first[(size_t)i], t = 0; e < first[(size_t)i + 1]; ++e, ++t)
+                    lanes[t % SUP_ACC] = pw_fma(value[(size_t)e], p[column[(size_t)e]], lanes[t % SUP_ACC]);
+                const double real = sup_fold(lanes);
+                for (long kr = 0; kr < nk; ++kr) {
+                    EwaldCS ph;
+                    ph.c = pc[(size_t)(kr * n + i)];
+                    ph.s = ps[(size_t)(kr * n + i)];
+                    lanes2[kr % SUP_ACC] = pw_fma(KV[4 * kr + 3], chc_rec_term(ph, Sc[(size_t)kr], Ss[(size_t)kr]), lanes2[kr % SUP_ACC]);
+                }
+                const double rec = sup_fold(lanes2);
+                y[i] = ((P[2 * i + 1] - self) * p[i] + real) + rec;
+            }
+            const double pAp = dot(p, y, n);
+            if (!(pAp > 0.0)) {
+                S.broke = true;
+                break;
+            }
+            const double al = S.rz / pAp;
+            for (long i = 0; i < n; ++i) {
+                q[i] = pw_fma(al, p[i], q[i]);
+                r[i] = pw_fma(-al, y[i], r[i]);
+            }
+            S.lambda = precondition();
+            const double rz_new = projected_dot(S.lambda);
+            const double beta = rz_new / S.rz;
+            for (long i = 0; i < n; ++i) p[i] = pw_fma(beta, p[i], z[i]);
+            S.rz = rz_new;
+        }
+        const int flags = chc_flags(S, sJ);
+        const bool lost = (flags & (CHG_BREAKDOWN | CHG_NO_SUM)) != 0;
+        const double nan = chg_nan();
+        double e[SUP_ACC], lo[SUP_ACC], hi[SUP_ACC];
+        for (int l = 0; l < SUP_ACC; ++l) {
+            e[l] = 0.0;
+            lo[l] = PW_INF;
+            hi[l] = -PW_INF;
+        }
+        double* Q = charges + (long)J.charge_first;
+        for (long i = 0; i < n; ++i) {
+            const int l = (int)(i % SUP_ACC);
+            e[l] = pw_fma(P[2 * i], q[i], e[l]);
+            lo[l] = q[i] < lo[l] ? q[i] : lo[l];
+            hi[l] = q[i] > hi[l] ? q[i] : hi[l];
+            Q[i] = lost ? nan : chg_canon(q[i]);
+        }
+        for (int s = SUP_ACC / 2; s >= 1; s >>= 1)
+            for (int l = 0; l < s; ++l) {
+                lo[l] = lo[l + s] < lo[l] ? lo[l + s] : lo[l];
+                hi[l] = hi[l + s] > hi[l] ? hi[l + s] : hi[l];
+            }
+        pw_charges_cell_out* o = out + (long)J.out;
+        o->mu = lost ? nan : chg_canon(-S.lambda);
+        o->energy = lost ? nan : chg_canon(0.5 * sup_fold(e));
+        o->q_min = lost ? nan : chg_canon(lo[0]);
+        o->q_max = lost ? nan : chg_canon(hi[0]);
+        o->iterations = S.iterations;
+        o->flags = flags;
     };
     host_share(n_jobs, threads, [&](long k) { one(jobs[k]); });
     return PW_OK;

@@ -241,6 +241,7 @@ class Diffusion:
     labels: object = None
     frames: np.ndarray | None = None
     voxel_volume: object = None
+    charges_converged: object = None      # of a rigid guest with charges="qeq-cell": whether the frame's charges converged (part of valid)
 
     @property
     def coefficient(self):

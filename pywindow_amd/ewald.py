@@ -8,9 +8,9 @@ of the reciprocal lattice, ``S(k) = sum_j q_j exp(i k.x_j)`` and ``w_k = COULOMB
 The library takes ``alpha`` and the rows ``(h, k, l, w)`` as data; :func:`ewald_parameters` makes them.
 
 What is left out: the guest's interaction with its own images (infinite dilution); any self or background term (none
-arises between a guest and a neutral framework, and a framework that is not neutral is refused); periodic charge
-equilibration (``charges="qeq"`` on a cell is refused: it is the isolated-molecule model); non-linear guests.  The
-reference has no counterpart.
+arises between a guest and a neutral framework, and a framework that is not neutral is refused); non-linear guests.
+Periodic charge equilibration is ``pw_charges_cell`` (:mod:`pywindow_amd.charges_cell`, ``charges="qeq-cell"``);
+``charges="qeq"`` on a cell stays refused: it is the isolated-molecule model.  The reference has no counterpart.
 """
 
 from __future__ import annotations
@@ -85,13 +85,15 @@ def ewald_parameters(lattice, cutoff: float, tolerance: float = 1e-6):
 
 
 def framework_charges(charges, T: int, n: int):
-    """``charges`` as ``(T, n)`` float64: one value per atom, or one row a frame.  ``"qeq"`` is refused -- charge
-    equilibration here is the isolated-molecule model, not a periodic one -- and so is a frame whose charges do not sum to
-    zero within ``1e-8 * sum |q|``: the Ewald sum has no background term."""
+    """``charges`` as ``(T, n)`` float64: one value per atom, or one row a frame.  ``"qeq"`` is refused -- that is the
+    isolated-molecule model; the periodic one is ``"qeq-cell"``, which :mod:`pywindow_amd.rigid_cell` turns into numbers
+    before it comes here -- and so is a frame whose charges do not sum to zero within ``1e-8 * sum |q|``: the Ewald sum has
+    no background term."""
     if isinstance(charges, str):
         if charges == "qeq":
             raise ValueError("charges: \"qeq\" is the isolated-molecule model (pw_charges equilibrates one molecule in vacuum); "
-                             "periodic charge equilibration is not built: give the cell's charges as numbers")
+                             "on a cell use \"qeq-cell\" (pw_charges_cell, periodic charge equilibration) or give the cell's "
+                             "charges as numbers")
         raise ValueError("charges: one value per atom, or one row a frame")
     q = np.asarray(charges, dtype=np.float64)
     if q.ndim == 1:

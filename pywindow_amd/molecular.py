@@ -573,6 +573,20 @@ class MolecularSystem:
             raise ValueError(f"{what}: the system has no unit cell (a 'lattice' or a 'unit_cell' is needed)")
         return self.system["coordinates"], self.system["elements"], lattice
 
+    def calculate_cell_charges(self, cutoff: float = 12.0, tolerance: float = 1e-6, shield=(4.0, 6.0), tol: float = 1e-10,
+                               max_iter: int = 1000, device=None):
+        """The partial charges of every atom of the loaded cell by periodic charge equilibration
+        (``pywindow_amd.equilibrate_cell_charges``, ``pw_charges_cell`` on the GPU; ``QEQ_PARAMETERS`` of
+        :mod:`pywindow_amd.charges`; :mod:`pywindow_amd.charges_cell` says what the model leaves out and why ``shield`` is a
+        model parameter).  Needs ``elements`` and a ``lattice`` or ``unit_cell``.  The result, a
+        :class:`pywindow_amd.CellCharges`, is also kept in ``self.cell_charges``; it is what
+        ``calculate_rigid_guest_percolation(charges="qeq-cell")`` and ``_diffusion`` make for themselves."""
+        from . import charges_cell as CC
+
+        xyz, elements, lattice = self._rigid_cell_inputs("calculate_cell_charges")
+        self.cell_charges = CC.equilibrate_cell_charges(xyz, elements, lattice, cutoff, tolerance, shield, tol, max_iter, device)
+        return self.cell_charges
+
     def calculate_rigid_guest_percolation(self, guest="CO2", temperatures=298.0, spacing: float = 0.5, cutoff: float = 12.0,
                                           core2: float = 0.25, directions=None, device=None, charges=None,
                                           ewald_tolerance: float = 1e-6):
@@ -580,7 +594,8 @@ class MolecularSystem:
         :class:`pywindow_amd.RigidGuest`) connects through the loaded cell (``pywindow_amd.rigid_guest_percolation``:
         ``pw_rigid_cell``, then ``pw_percolation`` on the GPU, UFF atoms): a list, one
         :class:`pywindow_amd.Percolation` per temperature, also kept in ``self.rigid_percolation``.  ``charges`` (the framework's point charges in e, one per atom or one row a frame) and
-        ``ewald_tolerance``: the Ewald sum of ``pywindow_amd.rigid_guest_field``; ``None``: uncharged, ``pw_rigid_cell``."""
+        ``ewald_tolerance``: the Ewald sum of ``pywindow_amd.rigid_guest_field``; ``"qeq-cell"``: the charges of
+        :meth:`calculate_cell_charges` at the same cutoff and tolerance; ``None``: uncharged, ``pw_rigid_cell``."""
         from . import rigid_cell as RC
 
         xyz, elements, lattice = self._rigid_cell_inputs("calculate_rigid_guest_percolation")
@@ -595,7 +610,8 @@ class MolecularSystem:
         (``pywindow_amd.rigid_guest_diffusion``: ``pw_rigid_cell``, then ``pw_basins`` on the GPU, UFF atoms), each
         temperature on its own free-energy field: a :class:`pywindow_amd.Diffusion`, also kept in
         ``self.rigid_diffusion``.  ``charges`` (the framework's point charges in e, one per atom or one row a frame) and
-        ``ewald_tolerance``: the Ewald sum of ``pywindow_amd.rigid_guest_field``; ``None``: uncharged, ``pw_rigid_cell``."""
+        ``ewald_tolerance``: the Ewald sum of ``pywindow_amd.rigid_guest_field``; ``"qeq-cell"``: the charges of
+        :meth:`calculate_cell_charges` at the same cutoff and tolerance; ``None``: uncharged, ``pw_rigid_cell``."""
         from . import rigid_cell as RC
 
         xyz, elements, lattice = self._rigid_cell_inputs("calculate_rigid_guest_diffusion")

@@ -56,6 +56,7 @@ class Percolation:
     guest: object = None
     maps: object = None
     frames: np.ndarray | None = None
+    charges_converged: object = None      # of a rigid guest's field with charges="qeq-cell": whether the frame's charges converged
 
     @property
     def barrier(self):
@@ -143,7 +144,8 @@ class Percolation:
     def series(self, name: str = "activation", dim: int = 3, axis: int | None = None):
         """``(values, valid)`` over the frames: ``"activation"``, ``"barrier"`` or ``"well"`` of the connection in at
         least ``dim`` dimensions, or ``"axis_activation"`` along cell vector ``axis``; ``valid`` is false where the
-        level is ``+inf``.  Ready for :func:`pywindow_amd.time_correlation`, :func:`pywindow_amd.lomb_scargle`,
+        level is ``+inf`` or, with ``charges="qeq-cell"``, the frame's charges did not converge.  Ready for
+        :func:`pywindow_amd.time_correlation`, :func:`pywindow_amd.lomb_scargle`,
         :func:`pywindow_amd.gaussian_kde_1d`, :func:`pywindow_amd.gate_statistics` and
         :func:`pywindow_amd.transition_counts`."""
         if name not in _SERIES:
@@ -157,7 +159,10 @@ class Percolation:
                 raise ValueError("series: dim 1, 2 or 3")
             column, level = int(dim) - 1, self.barrier
         v = np.atleast_2d(np.asarray(getattr(self, name), dtype=np.float64))[:, column].copy()
-        return v, np.isfinite(np.atleast_2d(level)[:, column])
+        valid = np.isfinite(np.atleast_2d(level)[:, column])
+        if self.charges_converged is not None:
+            valid = valid & np.atleast_1d(np.asarray(self.charges_converged, dtype=bool))
+        return v, valid
 
 
 def _coefficients(elements_or_coef, guest, n: int) -> np.ndarray:

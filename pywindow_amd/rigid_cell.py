@@ -16,8 +16,12 @@ Ewald sum of the framework's charges on the guest's site charges (:mod:`pywindow
 pywindow_amd/csrc/pw_ewald.hpp): the real-space term in the pair loop, the reciprocal term added last.  Without
 ``charges`` the calls are ``pw_rigid_cell``'s exactly as before.
 
-What is left out.  Periodic charge equilibration (``charges="qeq"`` is refused: it is the isolated-molecule model); a
-framework that is not neutral (no background term); the guest's interaction with its own images.  Non-linear
+``charges="qeq-cell"`` makes them by periodic charge equilibration first (``pw_charges_cell``,
+:mod:`pywindow_amd.charges_cell`): one call over the same frames with the call's own ``cutoff`` and ``ewald_tolerance``,
+then everything proceeds as with given charges; the result carries ``charges_converged`` and a frame whose charges did not
+converge is not valid.  ``charges="qeq"`` stays refused: it is the isolated-molecule model.
+
+What is left out.  A framework that is not neutral (no background term); the guest's interaction with its own images.  Non-linear
 guests.  Guest-guest terms: infinite dilution.  The fields travel through host memory between the three entries.  The
 reference has no counterpart.
 
@@ -77,6 +81,7 @@ class RigidField:
     directions: np.ndarray
     guest: object = None
     frames: np.ndarray | None = None
+    charges_converged: object = None      # with charges="qeq-cell": whether the frame's charge equilibration converged
 
     @property
     def n_voxels(self):
@@ -167,14 +172,18 @@ class RigidField:
 
     def series(self, name: str = "boltzmann_volume", level: int = 0):
         """``(values, valid)`` of a quantity over the frames at temperature ``level``, with the validity rule of
-        :meth:`pywindow_amd.RigidAffinity.series` for a plain grid: the frame was not clamped and the value is finite."""
+        :meth:`pywindow_amd.RigidAffinity.series` for a plain grid: the frame was not clamped and the value is finite --
+        and, with ``charges="qeq-cell"``, the frame's charges converged."""
         if name not in _SERIES:
             raise KeyError(f"series: one of {_SERIES}")
         v = np.asarray(getattr(self, name), dtype=np.float64)
         if name in ("boltzmann_volume", "henry", "mean_energy", "heat"):
             v = v[..., level]
         values = np.atleast_1d(v).copy()
-        return values, np.isfinite(values) & ~np.atleast_1d(self.clamped)
+        valid = np.isfinite(values) & ~np.atleast_1d(self.clamped)
+        if self.charges_converged is not None:
+            valid &= np.atleast_1d(np.asarray(self.charges_converged, dtype=bool))
+        return values, valid
 
 
 def _free_energy(zbar, temperature):
@@ -315,7 +324,26 @@ def _field(planned, ctx, spacing, frames, kernel_ms=None, diagnostics=None, ew=N
 def _one_field(many: RigidField) -> RigidField:
     return dataclasses.replace(many, raw=many.raw[0], levels=many.levels[0], zbar=many.zbar[0], u_min_map=many.u_min_map[0],
                                shape=many.shape[0], origin=many.origin[0], step=many.step[0], lattice=many.lattice[0],
-                               rotation=many.rotation[0], frames=None)
+                               rotation=many.rotation[0], frames=None, charges_converged=_first(many.charges_converged))
+
+
+def _first(converged):
+    return None if converged is None else converged[0]
+
+
+def _cell_charges(xyz, elements_or_coef, lattice, cutoff, ewald_tolerance, charges, device):
+    """``(charges, converged)``: ``charges`` as they were given and ``None``, or for ``"qeq-cell"`` the ``(T, n)`` charges of ONE
+    ``pw_charges_cell`` call over the frames at the call's own ``cutoff`` and ``ewald_tolerance`` and whether each frame's
+    converged.  (A frame without charges gets zeros: it is not valid anyway.)"""
+    if not (isinstance(charges, str) and charges == "qeq-cell"):
+        return charges, None
+    from .charges_cell import equilibrate_cell_charges_batch
+
+    coef = np.asarray(elements_or_coef)
+    if coef.dtype.kind in "fiu":
+        raise ValueError('charges="qeq-cell" needs the elements, not ready rows')
+    made = equilibrate_cell_charges_batch(xyz, list(elements_or_coef), lattice, cutoff, ewald_tolerance, device=device)
+    return np.where(np.isfinite(made.charges), made.charges, 0.0), np.atleast_1d(made.converged).copy()
 
 
 def rigid_guest_field_batch(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
@@ -324,13 +352,17 @@ def rigid_guest_field_batch(xyz, elements_or_coef, lattice, guest="CO2", tempera
     """:func:`rigid_guest_field` for ``T`` frames of the same ``n`` atoms, all jobs in ONE ``pw_rigid_cell`` call: ``xyz``
     ``(T, n, 3)``, ``lattice`` ``(3, 3)`` or ``(T, 3, 3)``.  ``kernel_ms``: a list that receives the time of the device work
     by HIP events; ``diagnostics``: a list that receives ``(n_pairs, instances)``.  ``charges`` ``(n,)`` or ``(T, n)``: the
-    framework's point charges, one ``pw_rigid_cell_ewald`` call (``None``: ``pw_rigid_cell`` as before)."""
+    framework's point charges, one ``pw_rigid_cell_ewald`` call (``None``: ``pw_rigid_cell`` as before); ``"qeq-cell"``: ONE
+    ``pw_charges_cell`` call over the same frames makes them first (:func:`_cell_charges`)."""
     if charges is None:
         planned = plan_field(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions)
         return _field(planned, engine.context(device), spacing, frames, kernel_ms, diagnostics)
+    charges, converged = _cell_charges(np.asarray(xyz, dtype=np.float64), elements_or_coef, lattice, cutoff, ewald_tolerance, charges,
+                                       device)
     planned, ew = plan_charged_field(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions, charges,
                                      ewald_tolerance)
-    return _field(planned, engine.context(device), spacing, frames, kernel_ms, diagnostics, ew)
+    field = _field(planned, engine.context(device), spacing, frames, kernel_ms, diagnostics, ew)
+    return field if converged is None else dataclasses.replace(field, charges_converged=converged)
 
 
 def rigid_guest_field(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5, cutoff: float = 12.0,
@@ -348,7 +380,10 @@ def rigid_guest_field(xyz, elements_or_coef, lattice, guest="CO2", temperatures=
     length.  A pose with a site within ``sqrt(core2)`` of an atom is blocked.  ``charges``: the framework's point charges in
     e, one per atom (or one row a frame): every pose energy then carries the Ewald sum of those charges on the guest's site
     charges, real-space part cut at ``cutoff``, parameters by :func:`pywindow_amd.ewald_parameters` at ``ewald_tolerance``; a
-    framework that is not neutral within ``1e-8 * sum |q|`` and ``"qeq"`` are refused.  ``None``: the jobs are uncharged.
+    framework that is not neutral within ``1e-8 * sum |q|`` and ``"qeq"`` are refused.  ``"qeq-cell"``: the library makes the
+    charges itself by periodic charge equilibration at the same ``cutoff`` and ``ewald_tolerance``
+    (:func:`pywindow_amd.equilibrate_cell_charges`, its defaults otherwise; needs the elements); ``charges_converged`` says
+    whether that converged, and a frame where it did not is not valid.  ``None``: the jobs are uncharged.
     ``xyz`` ``(T, n, 3)`` is :func:`rigid_guest_field_batch`.  ``device``: the HIP ordinal (``None``: the process's); ``-1``
     the explicit host path."""
     x = np.asarray(xyz, dtype=np.float64)
@@ -387,8 +422,9 @@ def rigid_guest_percolation_batch(xyz, elements_or_coef, lattice, guest="CO2", t
     levels, out, _ = engine.context(device).percolation(jobs, field=values)
     T, L = len(field.raw), len(field.temperatures)
     Rs = np.matmul(np.swapaxes(field.rotation, -1, -2), field.lattice)
-    return [_percolation_result(jobs[l::L], levels.reshape(T * L, 6)[l::L].copy(), out[l::L].copy(), None, Rs, field.rotation,
+    made = [_percolation_result(jobs[l::L], levels.reshape(T * L, 6)[l::L].copy(), out[l::L].copy(), None, Rs, field.rotation,
                                 field.shape, spacing, field.guest, frames) for l in range(L)]
+    return [dataclasses.replace(p, charges_converged=field.charges_converged) for p in made]
 
 
 def rigid_guest_percolation(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
@@ -402,7 +438,8 @@ def rigid_guest_percolation(xyz, elements_or_coef, lattice, guest="CO2", tempera
     kw = dict(charges=charges, ewald_tolerance=ewald_tolerance)
     if x.ndim == 3:
         return rigid_guest_percolation_batch(x, *args, **kw)
-    return [_one_percolation(p) for p in rigid_guest_percolation_batch(x.reshape(1, -1, 3), *args, **kw)]
+    return [dataclasses.replace(_one_percolation(p), charges_converged=_first(p.charges_converged))
+            for p in rigid_guest_percolation_batch(x.reshape(1, -1, 3), *args, **kw)]
 
 
 def rigid_guest_diffusion_batch(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
@@ -449,12 +486,15 @@ def rigid_guest_diffusion_batch(xyz, elements_or_coef, lattice, guest="CO2", tem
     if labels:
         cut = [[labelled[int(J["label_first"]):int(J["label_first"]) + int(J["nx"]) * int(J["ny"]) * int(J["nz"])]
                 .reshape(int(J["nz"]), int(J["ny"]), int(J["nx"])) for J in jobs[t * L:(t + 1) * L]] for t in range(T)]
+    valid = table("valid", bool).all(axis=1)
+    if field.charges_converged is not None:
+        valid = valid & field.charges_converged
     return Diffusion(tensor, temps, out.reshape(T, L), out["n_basins"].reshape(T, L).copy(),
                      table("sites", np.int64, len), table("trapped", np.float64, lambda v: v[0]),
-                     table("barrierless", bool), table("rank", np.int64), table("valid", bool).all(axis=1), per("sites"),
+                     table("barrierless", bool), table("rank", np.int64), valid, per("sites"),
                      per("Z"), per("hops"), per("rates"), field.lattice, Qs, field.shape, float(spacing), merge, mass, g,
                      None, cut, None if frames is None else np.array(frames, dtype=np.int64).reshape(-1),
-                     [made[t * L]["volume"] for t in range(T)])
+                     [made[t * L]["volume"] for t in range(T)], field.charges_converged)
 
 
 def rigid_guest_diffusion(xyz, elements_or_coef, lattice, guest="CO2", temperatures=298.0, spacing: float = 0.5,
@@ -469,10 +509,12 @@ def rigid_guest_diffusion(xyz, elements_or_coef, lattice, guest="CO2", temperatu
     ``R * min(temperatures)`` for every temperature; ``mass`` (g/mol) comes from ``RIGID_GUEST_MASSES`` for N2, CO2 and O2
     and is required for a caller's :class:`pywindow_amd.RigidGuest`.  The orientational part of the transition state is
     in the field; the mass is the molecule's, so the rotational kinetic prefactor is left out.  ``charges`` /
-    ``ewald_tolerance``: :func:`rigid_guest_field`'s."""
+    ``ewald_tolerance``: :func:`rigid_guest_field`'s; with ``"qeq-cell"`` a frame whose charges did not converge is not
+    ``valid``."""
     x = np.asarray(xyz, dtype=np.float64)
     args = (elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions, cap, merge, mass, labels, device)
     kw = dict(charges=charges, ewald_tolerance=ewald_tolerance)
     if x.ndim == 3:
         return rigid_guest_diffusion_batch(x, *args, **kw)
-    return _one_diffusion(rigid_guest_diffusion_batch(x.reshape(1, -1, 3), *args, **kw))
+    many = rigid_guest_diffusion_batch(x.reshape(1, -1, 3), *args, **kw)
+    return dataclasses.replace(_one_diffusion(many), charges_converged=_first(many.charges_converged))

@@ -564,6 +564,28 @@ class DLPOLY:
         return CH.equilibrate_charges_batch(coords, self.elements(swap_atoms, forcefield), total_charge, tol, max_iter,
                                             device, frames=sel)
 
+    def cell_charges(self, frames=None, cutoff: float = 12.0, tolerance: float = 1e-6, shield=(4.0, 6.0), tol: float = 1e-10,
+                     max_iter: int = 1000, device=None, swap_atoms=None, forcefield=None):
+        """The partial charges of every atom of the periodic cell in every selected frame (``frames``: any selection of the
+        trajectory's frames, ``None``: all of them) by periodic charge equilibration, ALL frames in ONE
+        ``pw_charges_cell`` call on the GPU (``pywindow_amd.equilibrate_cell_charges_batch``, which explains ``cutoff``,
+        ``tolerance`` and the model parameter ``shield``) -- a :class:`pywindow_amd.CellCharges` whose ``charges`` are
+        ``(frames, atoms)`` and whose ``frames`` are the trajectory's frame numbers.  The frames are read with their
+        lattices as they are in the file, as :meth:`channels` reads them; ``rigid_field(charges="qeq-cell")`` and its kin
+        make the same charges themselves.  ``cell_charges().series("q_max")`` goes into ``pywindow_amd.time_correlation``
+        and the other statistical entries.  Periodic trajectories only: :meth:`charges` is the isolated cage."""
+        from . import charges_cell as CC
+
+        if not self.periodic:
+            raise ValueError("cell_charges: the trajectory is not periodic (imcon 0): there is no cell; charges() equilibrates "
+                             "a single cage in vacuum")
+        sel = self._select("all" if frames is None else frames)
+        if not sel:
+            raise ValueError("cell_charges: no frames selected")
+        coords, lattice = self._read_selected(sel, True)
+        return CC.equilibrate_cell_charges_batch(coords, self.elements(swap_atoms, forcefield), lattice, cutoff, tolerance,
+                                                 shield, tol, max_iter, device, frames=sel)
+
     def channels(self, probe=0.0, spacing: float = 0.5, frames=None, c_max: int = 64, mask: bool = False,
                  labels: bool = False, device=None, swap_atoms=None, forcefield=None):
         """The pore network of the periodic cell in every selected frame (``frames``: any selection of the trajectory's
@@ -645,8 +667,10 @@ class DLPOLY:
         selection of the trajectory's frames, ``None``: all of them), ALL frames in ONE ``pw_rigid_cell`` call on the GPU
         (``pywindow_amd.rigid_guest_field_batch``, UFF atoms, ``core2 = 0.25``) -- a :class:`pywindow_amd.RigidField`
         whose fields are arrays, or lists, over the frames and whose ``frames`` are the trajectory's frame numbers.
-        Periodic trajectories only.  ``charges`` (the framework's point charges in e, one per atom or one row a selected frame) and
-        ``ewald_tolerance``: the Ewald sum of ``pywindow_amd.rigid_guest_field``; ``None``: uncharged, ``pw_rigid_cell``."""
+        Periodic trajectories only.  ``charges`` (the framework's point charges in e, one per atom or one row a selected frame,
+        or ``"qeq-cell"``: made by ``pw_charges_cell``, as :meth:`cell_charges` makes them) and ``ewald_tolerance``: the Ewald
+        sum of ``pywindow_amd.rigid_guest_field``; ``None``: uncharged, ``pw_rigid_cell``.  :meth:`rigid_percolation` and
+        :meth:`rigid_diffusion` take the same two."""
         from . import rigid_cell as RC
 
         sel, coords, lattice = self._rigid_cell_frames("rigid_field", frames)
