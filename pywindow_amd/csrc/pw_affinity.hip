@@ -376,7 +376,7 @@ int affinity(pw_context* ctx, const pw_affinity_job* jobs, int64_t n_jobs, const
                 STAT_TRY(hipGetLastError());
             }
             if (G.items) {
-                const long blocks = G.items < 65536 ? G.items : 65536;
+                const long blocks = launch_blocks(G.items, 65536);
                 hipLaunchKernelGGL(pw_affinity_kernel, dim3((unsigned)blocks), dim3(AFF_CHUNK), 0, st, d_jobs + G.first,
                                    (int)n_group, G.items, d_xyz, d_coef, d_words, d_params, d_ws);
                 STAT_TRY(hipGetLastError());

@@ -675,7 +675,7 @@ int basins_call(pw_context* ctx, const pw_basins_job* jobs, int64_t n_jobs, cons
                     STAT_TRY(hipMemcpyAsync(d_ws + devs[k].map_first, field + jobs[k].field_first, sizeof(double) * (size_t)devs[k].V,
                                             hipMemcpyHostToDevice, st));
             if (G.items) {
-                const long blocks = G.items < 65536 ? G.items : 65536;
+                const long blocks = launch_blocks(G.items, 65536);
                 hipLaunchKernelGGL(pw_basins_field_kernel, dim3((unsigned)blocks), dim3(AFF_CHUNK), 0, st, d_jobs + G.first,
                                    (int)n_group, G.items, d_xyz, d_coef, d_ws);
                 STAT_TRY(hipGetLastError());

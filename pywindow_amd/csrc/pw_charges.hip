@@ -320,15 +320,14 @@ int charges_call(pw_context* ctx, const pw_charges_job* jobs, int64_t n_jobs, co
                 if (devs[k].state_first < 0) lds_atoms = devs[k].n > lds_atoms ? devs[k].n : lds_atoms;
                 else any_global = true;
             }
-            const unsigned blocks = (unsigned)(n_group < 65536 ? n_group : 65536);
             if (lds_atoms) {
-                hipLaunchKernelGGL(pw_charges_kernel<true>, dim3(blocks), dim3(CHG_THREADS),
+                hipLaunchKernelGGL(pw_charges_kernel<true>, dim3((unsigned)launch_blocks(n_group, 65536)), dim3(CHG_THREADS),
                                    sizeof(double) * CHG_VECTORS * (size_t)lds_atoms, st, d_jobs + G.first, (int)n_group, d_xyz,
                                    d_params, d_ws, d_charges, d_out + G.first);
                 STAT_TRY(hipGetLastError());
             }
             if (any_global) {
-                hipLaunchKernelGGL(pw_charges_kernel<false>, dim3(blocks), dim3(CHG_THREADS), 0, st, d_jobs + G.first,
+                hipLaunchKernelGGL(pw_charges_kernel<false>, dim3((unsigned)launch_blocks(n_group, 65536)), dim3(CHG_THREADS), 0, st, d_jobs + G.first,
                                    (int)n_group, d_xyz, d_params, d_ws, d_charges, d_out + G.first);
                 STAT_TRY(hipGetLastError());
             }

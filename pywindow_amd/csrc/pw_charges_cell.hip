@@ -480,15 +480,14 @@ int charges_cell_call(pw_context* ctx, const pw_charges_cell_job* jobs, int64_t 
                 STAT_TRY(hipEventRecord(ev_rows.b, st));
                 STAT_TRY(hipEventRecord(ev_solve.a, st));
             }
-            const unsigned blocks = (unsigned)(n_group < 65536 ? n_group : 65536);
             if (lds_atoms) {
-                hipLaunchKernelGGL(chc_solve_kernel<true>, dim3(blocks), dim3(CHC_THREADS),
+                hipLaunchKernelGGL(chc_solve_kernel<true>, dim3((unsigned)launch_blocks(n_group, 65536)), dim3(CHC_THREADS),
                                    sizeof(double) * CHC_VECTORS * (size_t)lds_atoms, st, d_jobs + G.first, (int)n_group, d_params,
                                    d_kvecs, d_firsts, d_counts, d_ws, d_charges, d_out + G.first);
                 STAT_TRY(hipGetLastError());
             }
             if (any_global) {
-                hipLaunchKernelGGL(chc_solve_kernel<false>, dim3(blocks), dim3(CHC_THREADS), 0, st, d_jobs + G.first, (int)n_group,
+                hipLaunchKernelGGL(chc_solve_kernel<false>, dim3((unsigned)launch_blocks(n_group, 65536)), dim3(CHC_THREADS), 0, st, d_jobs + G.first, (int)n_group,
                                    d_params, d_kvecs, d_firsts, d_counts, d_ws, d_charges, d_out + G.first);
                 STAT_TRY(hipGetLastError());
             }

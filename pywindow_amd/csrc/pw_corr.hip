@@ -262,12 +262,12 @@ int corr_sums(pw_context* ctx, const pw_corr_job* jobs, int64_t n_jobs, const do
         // stride over their work, so the launch geometry is free)
         for (const CorrLaunch& L : launches) {
             const int count = (int)(L.last - L.first);
-            const long grid1 = L.items < (1l << 20) ? L.items : (1l << 20);
+            const long grid1 = launch_blocks(L.items, 1l << 20);
             hipLaunchKernelGGL(pw_corr_partial_kernel, dim3((unsigned)grid1), dim3(CORR_WAVE), 0, st, d_slabs + L.first, count,
                                L.items, d_x, d_part);
             STAT_TRY(hipGetLastError());
             const long blocks2 = (L.out_hi - L.out_lo + 255) / 256;
-            hipLaunchKernelGGL(pw_corr_reduce_kernel, dim3((unsigned)(blocks2 < 65536 ? blocks2 : 65536)), dim3(256), 0, st,
+            hipLaunchKernelGGL(pw_corr_reduce_kernel, dim3((unsigned)launch_blocks(blocks2, 65536)), dim3(256), 0, st,
                                d_slabs + L.first, count, L.out_lo, L.out_hi - L.out_lo, d_part, d_out);
             STAT_TRY(hipGetLastError());
         }

@@ -155,11 +155,11 @@ hipError_t pw::ewald_launch(hipStream_t st, const RCellJobDev* jobs, int n_jobs,
                             const double* kvecs, const double* site_q, const double* offsets, const double* dirs,
                             unsigned long long* ws) {
     if (rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(pw_ewald_tables_kernel, dim3((unsigned)(rows < 65536 ? rows : 65536)), dim3(AFF_CHUNK), 0, st, jobs, n_jobs,
+    hipLaunchKernelGGL(pw_ewald_tables_kernel, dim3((unsigned)launch_blocks(rows, 65536)), dim3(AFF_CHUNK), 0, st, jobs, n_jobs,
                        rows, cell, kvecs, site_q, offsets, dirs, ws);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(pw_ewald_urec_kernel, dim3((unsigned)(tiles < 65536 ? tiles : 65536)), dim3(AFF_CHUNK), 0, st, jobs, n_jobs,
+    hipLaunchKernelGGL(pw_ewald_urec_kernel, dim3((unsigned)launch_blocks(tiles, 65536)), dim3(AFF_CHUNK), 0, st, jobs, n_jobs,
                        tiles, kvecs, ws);
     return hipGetLastError();
 }
@@ -185,7 +185,7 @@ extern "C" int pw_internal_erfc(pw_context* ctx, const double* x, int64_t n, dou
         STAT_TRY(buf.alloc(&d_out, bytes));
         STAT_TRY(hipMemcpyAsync(d_x, x, bytes, hipMemcpyHostToDevice, st));
         const long blocks = ((long)n + 255) / 256;
-        hipLaunchKernelGGL(pw_erfc_probe_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, (long)n, d_x,
+        hipLaunchKernelGGL(pw_erfc_probe_kernel, dim3((unsigned)launch_blocks(blocks, 65536)), dim3(256), 0, st, (long)n, d_x,
                            d_out);
         STAT_TRY(hipGetLastError());
         STAT_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st));

@@ -393,7 +393,7 @@ int hop(pw_context* ctx, const pw_hop_job* jobs, int64_t n_jobs, const double* x
                                             hipMemcpyHostToDevice, st));
             STAT_TRY(marks.mark(st));
             if (G.items) {
-                const long blocks = G.items < 65536 ? G.items : 65536;
+                const long blocks = launch_blocks(G.items, 65536);
                 hipLaunchKernelGGL(pw_hop_field_kernel, dim3((unsigned)blocks), dim3(AFF_CHUNK), 0, st, d_jobs + G.first,
                                    (int)n_group, G.items, d_xyz, d_coef, d_ws);
                 STAT_TRY(hipGetLastError());

@@ -252,12 +252,12 @@ int kde_sums(pw_context* ctx, const pw_kde_job* jobs, int64_t n_jobs, const doub
         STAT_TRY(ev.start(st));
         // (a job without samples has no pair and its sums are the reduce kernel's zeros; the launch geometry is
         // free: both kernels stride over their work)
-        const long grid1 = items < 1 ? 1 : (items < (1l << 20) ? items : (1l << 20));
+        const long grid1 = items < 1 ? 1 : launch_blocks(items, 1l << 20);
         hipLaunchKernelGGL(pw_kde_partial_kernel, dim3((unsigned)grid1), dim3(KDE_WAVE), 0, st, d_jobs, (int)n_jobs, d_x, d_g,
                            d_part);
         STAT_TRY(hipGetLastError());
         const long blocks2 = (outs + 255) / 256;
-        hipLaunchKernelGGL(pw_kde_reduce_kernel, dim3((unsigned)(blocks2 < 65536 ? blocks2 : 65536)), dim3(256), 0, st, d_jobs,
+        hipLaunchKernelGGL(pw_kde_reduce_kernel, dim3((unsigned)launch_blocks(blocks2, 65536)), dim3(256), 0, st, d_jobs,
                            (int)n_jobs, d_part, d_out);
         STAT_TRY(hipGetLastError());
         STAT_TRY(ev.stop(st));
@@ -388,13 +388,13 @@ int kde2_sums(pw_context* ctx, const pw_kde2_job* jobs, int64_t n_jobs, const do
         for (const Kde2Launch& L : launches) {
             const int count = (int)(L.last - L.first);
             if (L.items) {
-                const long grid1 = L.items < (1l << 20) ? L.items : (1l << 20);
+                const long grid1 = launch_blocks(L.items, 1l << 20);
                 hipLaunchKernelGGL(pw_kde2_partial_kernel, dim3((unsigned)grid1), dim3(KDE_WAVE), 0, st, d_slabs + L.first, count,
                                    L.items, d_x, d_g, d_part);
                 STAT_TRY(hipGetLastError());
             }
             const long blocks2 = (L.out_hi - L.out_lo + 255) / 256;
-            hipLaunchKernelGGL(pw_kde2_reduce_kernel, dim3((unsigned)(blocks2 < 65536 ? blocks2 : 65536)), dim3(256), 0, st,
+            hipLaunchKernelGGL(pw_kde2_reduce_kernel, dim3((unsigned)launch_blocks(blocks2, 65536)), dim3(256), 0, st,
                                d_slabs + L.first, count, L.out_lo, L.out_hi - L.out_lo, d_part, d_out);
             STAT_TRY(hipGetLastError());
         }
@@ -440,6 +440,13 @@ extern "C" int pw_internal_kde2_sums(pw_context* ctx, const pw_kde2_job* jobs, i
 // no result changes, unless a kernel reads what the call never wrote.
 extern "C" void pw_internal_poison_scratch(int on) { g_poison_scratch.store(on != 0, std::memory_order_relaxed); }
 
+// test hook (not part of the header): while blocks > 0, every capped launch of the library -- the kernels whose
+// workgroups stride over their work items; pw_stat_host.hpp: launch_blocks -- gets min(items, blocks) workgroups, so
+// that a small batch sends every workgroup round its item loop again; 0 gives every launch site its own cap back.
+// Process-wide, off at start; no kernel reads it and the host path never does.  Returns how many launches were given
+// fewer workgroups than items since the hook was last called, and clears that count.
+extern "C" long pw_internal_launch_cap(int blocks) { return launch_cap_hook(blocks); }
+
 // test instrumentation (not part of the header): y[i] = pw_exp(x[i]) on the context's device, or on the host
 // for a device == -1 context -- the two must agree to the bit (tests/test_gpu_kde.py)
 extern "C" int pw_internal_exp(pw_context* ctx, const double* x, int64_t n, double* y) {
@@ -460,7 +467,7 @@ extern "C" int pw_internal_exp(pw_context* ctx, const double* x, int64_t n, doub
         STAT_TRY(buf.alloc(&d_y, sizeof(double) * (size_t)n));
         STAT_TRY(hipMemcpyAsync(d_x, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
         const long blocks = ((long)n + 255) / 256;
-        hipLaunchKernelGGL(pw_exp_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, (long)n, d_x, d_y);
+        hipLaunchKernelGGL(pw_exp_kernel, dim3((unsigned)launch_blocks(blocks, 65536)), dim3(256), 0, st, (long)n, d_x, d_y);
         STAT_TRY(hipGetLastError());
         STAT_TRY(hipMemcpyAsync(y, d_y, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
     }

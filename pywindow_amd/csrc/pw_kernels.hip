@@ -24,6 +24,7 @@
 
 #include "../../include/pywindow_amd.h"
 #include "pw_host.hpp"
+#include "pw_stat_host.hpp"
 #include <vector>
 // (the stage functions do not assume where the team state is: the chains keep it in LDS, the window search on its
 // stack -- its out-of-line stage function spills five times as much when its table of pointers is an LDS object: 269
@@ -1233,7 +1234,7 @@ int pw_internal_math(pw_context* c, int which, const double* x, const double* y,
     HIP_TRY(hipMemcpyAsync(buf.p[0], x, bytes, hipMemcpyHostToDevice, st));
     if (y) HIP_TRY(hipMemcpyAsync(buf.p[1], y, bytes, hipMemcpyHostToDevice, st));
     const long blocks = ((long)n + 255) / 256;
-    hipLaunchKernelGGL(pw_math_probe_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, which, (long)n,
+    hipLaunchKernelGGL(pw_math_probe_kernel, dim3((unsigned)pw::launch_blocks(blocks, 65536)), dim3(256), 0, st, which, (long)n,
                        buf.p[0], buf.p[1], c->rsq_tab, buf.p[2]);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out, buf.p[2], bytes, hipMemcpyDeviceToHost, st));

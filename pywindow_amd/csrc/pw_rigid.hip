@@ -496,9 +496,9 @@ int rigid(pw_context* ctx, const pw_rigid_job* jobs, int64_t n_jobs, const doubl
                 STAT_TRY(hipGetLastError());
             }
             if (G.items) {
-                const long blocks = G.items < 65536 ? G.items : 65536;
                 for (int cls = 0; cls < RIGID_CLASSES; ++cls) {
                     if (!needed[cls]) continue;
+                    const long blocks = launch_blocks(G.items, 65536);   // (asked a launch: the test hook counts launches)
                     rigid_launch(cls, (unsigned)blocks, sizeof(double) * 3 * (size_t)max_M, st, d_jobs + G.first, (int)n_group,
                                  G.items, d_xyz, d_coef, d_offsets, d_dirs, d_words, d_betas, d_ws);
                     STAT_TRY(hipGetLastError());

@@ -610,7 +610,6 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
                 needed[devs[k].cls] = true;
                 max_M = devs[k].M > max_M ? devs[k].M : max_M;
             }
-            const long blocks = G.items < 65536 ? G.items : 65536, sum_blocks = G.blocks < 65536 ? G.blocks : 65536;
             const RCellJobDev& last = devs[G.last - 1];
             const long group_tiles = last.tile_first + (last.K ? (long)last.gx * last.gy * rcell_groups(last.nz) *
                                                                      ((last.M + EWALD_OT - 1) / EWALD_OT) : 0);
@@ -618,11 +617,13 @@ int rigid_cell(pw_context* ctx, const pw_rigid_cell_job* jobs, int64_t n_jobs, c
                                   d_params + q_at, d_offsets, d_dirs, d_ws));
             for (int cls = 0; cls < RCELL_CLASSES; ++cls) {
                 if (!needed[cls]) continue;
+                const long blocks = launch_blocks(G.items, 65536);   // (asked a launch: the test hook counts launches)
                 rcell_launch(cls, W == 3, (unsigned)blocks, sizeof(double) * 3 * (size_t)max_M, st, d_jobs + G.first, (int)n_group,
                              G.items, d_xyz, d_coef, d_offsets, d_dirs, d_betas, d_ws, d_pairs + G.first);
                 STAT_TRY(hipGetLastError());
                 ran |= 1 << cls;
             }
+            const long sum_blocks = launch_blocks(G.blocks, 65536);
             hipLaunchKernelGGL(pw_rigid_cell_sums_kernel, dim3((unsigned)sum_blocks), dim3(AFF_CHUNK), 0, st, d_jobs + G.first,
                                (int)n_group, G.blocks, d_ws);
             STAT_TRY(hipGetLastError());

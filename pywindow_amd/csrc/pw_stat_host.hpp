@@ -1,8 +1,9 @@
 // pw_stat_host.hpp -- what the translation units of the statistical entries (pw_kde.hip, pw_kdew.hip, pw_corr.hip,
 // pw_dft.hip, pw_gate.hip, pw_trans.hip, pw_superpose.hip, pw_cluster.hip, pw_cov.hip) and, through pw_grid_host.hpp,
 // those of the grid entries (listed there) share on the host side of a call: device
-// memory and events of one call, the two ways an entry reports a failure, the search of a work item's slab and the
-// poison switch.  Not for pw_hostpath.cpp: this is HIP.
+// memory and events of one call, the two ways an entry reports a failure, the search of a work item's slab, the
+// poison switch and, for every launch whose workgroups stride over its work items (pw_kernels.hip's math probe among
+// them), the grid of a capped launch with its test hook.  Not for pw_hostpath.cpp: this is HIP.
 #pragma once
 #include <stdio.h>
 
@@ -24,11 +25,34 @@ namespace pw {
 // compact device result with bytes 0xFF -- a NaN as a double, garbage as a gate summary or a bit mask -- before their first kernel,
 // so that a read of device memory the call never wrote shows in the result.  The periodic pre-processing (pw_rebuild.hip) does
 // the same with its team slabs and its device outputs.  Off at start; an entry reads the flag
-// once a call, and the host path (device -1) never does.
+// once a call, and the host path (device -1) never does.  Its companion is the launch-cap hook below (pw_kde.hip:
+// pw_internal_launch_cap), which makes the workgroups of a small batch take a second work item: the tests set both.
 inline std::atomic<int> g_poison_scratch{0};
 inline bool scratch_poisoned() { return g_poison_scratch.load(std::memory_order_relaxed) != 0; }
 inline hipError_t poison_scratch(bool on, void* p, size_t bytes, hipStream_t st) {
     return on && bytes ? hipMemsetAsync(p, 0xFF, bytes, st) : hipSuccess;
+}
+
+// The grid of a capped launch: the kernels whose workgroups walk their work items with
+// `for (item = blockIdx.x; item < total; item += gridDim.x)` are launched with min(items, cap) workgroups, `cap` being the
+// launch site's own (65536, or 2^20 for the partial kernels of pw_kde.hip, pw_kdew.hip and pw_corr.hip); the guard for
+// zero items stays with the site.  Plain C++.  Test hook (pw_kde.hip: pw_internal_launch_cap(blocks)): while blocks > 0
+// every site gets min(items, blocks) instead, so that a batch of a few dozen items sends every workgroup round its loop
+// again -- the second item of a workgroup is otherwise met only beyond the cap -- and 0 gives every site its own cap
+// back.  Off at start; read on the host at the launch site only, never by a kernel or by the host path (device -1).
+// g_launch_cut counts the calls that returned fewer workgroups than items; the hook returns and clears it, which is how
+// a test knows that the launches it meant to cut were cut.
+inline std::atomic<long> g_launch_cap{0};
+inline std::atomic<long> g_launch_cut{0};
+inline long launch_blocks(long items, long cap) {
+    const long hook = g_launch_cap.load(std::memory_order_relaxed);
+    const long blocks = hook > 0 ? (items < hook ? items : hook) : (items < cap ? items : cap);
+    if (blocks < items) g_launch_cut.fetch_add(1, std::memory_order_relaxed);
+    return blocks;
+}
+inline long launch_cap_hook(long blocks) {
+    g_launch_cap.store(blocks > 0 ? blocks : 0, std::memory_order_relaxed);
+    return g_launch_cut.exchange(0, std::memory_order_relaxed);
 }
 
 // (what follows has internal linkage, as when every file had a copy of its own: it adds nothing to the library's symbols)

@@ -447,6 +447,16 @@ def set_poison(on: bool) -> None:
     L.pw_internal_poison_scratch(1 if on else 0)
 
 
+def set_launch_cap(blocks: int) -> int:
+    """The library's test hook pw_internal_launch_cap (csrc/pw_kde.hip): while blocks > 0 every capped launch gets
+    min(items, blocks) workgroups, 0 gives each launch site its own cap back.  Returns how many launches were given
+    fewer workgroups than items since the last call, and clears that count."""
+    L = _library()
+    L.pw_internal_launch_cap.argtypes = [ctypes.c_int]
+    L.pw_internal_launch_cap.restype = ctypes.c_long
+    return int(L.pw_internal_launch_cap(int(blocks)))
+
+
 @contextlib.contextmanager
 def poisoned():
     set_poison(True)

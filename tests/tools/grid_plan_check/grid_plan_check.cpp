@@ -15,6 +15,10 @@
 // boundaries are those of the rule as each entry wrote it out before the header (restated below with plain integers);
 // most_words is the largest group.  Span over every mix of up to three members (first 0 .. 3, count 0 .. 2) is the
 // minimum and maximum of the members that have entries, or (0, 0); span_outside is its definition.
+// launch_blocks (pw_stat_host.hpp, the grid of a capped launch) at 0, 1, cap - 1, cap and cap + 1 items for the caps of the
+// launch sites (65536 and 2^20) and a small one: min(items, cap) with the test hook off, min(items, hook) with it at 1 and
+// 3, the site's cap again after 0; the hook returns exactly the number of calls that got fewer workgroups than items
+// since it was last called, and clears it.
 #include <limits.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -143,10 +147,29 @@ static void ranges() {
     CHECK(span_outside(LONG_MAX - 1, 5, LONG_MAX) && !span_outside(LONG_MAX - 5, 5, LONG_MAX));   // (no overflow on the way)
 }
 
+static void launches() {
+    CHECK(launch_cap_hook(0) == 0);                                  // (off at start, nothing counted)
+    for (const long hook : {0l, 1l, 3l, 0l})
+        for (const long cap : {7l, 65536l, 1l << 20}) {
+            CHECK(launch_cap_hook(hook) == 0);
+            long cut = 0;
+            for (const long items : {0l, 1l, cap - 1, cap, cap + 1}) {
+                const long limit = hook > 0 ? hook : cap, want = items < limit ? items : limit;
+                CHECK(launch_blocks(items, cap) == want);
+                cut += want < items;
+            }
+            CHECK(cut == (hook > 0 ? 3 : 1));                        // (cap - 1, cap, cap + 1 under the hook; cap + 1 without)
+            CHECK(launch_cap_hook(hook) == cut);
+            CHECK(launch_cap_hook(hook) == 0);                       // (the count was cleared)
+        }
+    CHECK(launch_cap_hook(-5) == 0 && launch_blocks(10, 4) == 4 && launch_cap_hook(0) == 1);   // (a negative value is 0)
+}
+
 int main() {
     plans();
     spans();
     ranges();
+    launches();
     printf("grid_plan_check: %ld checks hold\n", g_checks);
     return 0;
 }
