@@ -75,6 +75,9 @@ constexpr double ONE_PI = 3.141592653589793;
 // position back to the caller's atom index (used for every reported index and for
 // first-index tie-breaks), `inv` is its inverse.
 constexpr int PW_KCLS = 8;
+#ifndef PW_LEFTOVER_ROUND_DIV
+#define PW_LEFTOVER_ROUND_DIV 16      // left-over paths from a 1/16 of the team on go as a round of their own (stage_windows)
+#endif
 constexpr double PW_PATH_POINTS_MAX = 1048576.0;      // points of one path scan (PW_ST_PATH_TOO_LONG beyond)
 struct ClassInfo {
     int k;                  // number of groups; 0 => more than PW_KCLS radii, no grouping used
@@ -1832,6 +1835,64 @@ PW_NOINLINE PW_HD inline bool path_bracket_thread(const Frame& F, int n, double 
     return true;
 }
 
+// ---- the same for ONE WAVE: lanes over atoms, the smallest gap of a path AND the first point that has it ------
+// The points k_first .. chunks of a path of step c (k_first = 0: the origin is a point like any other, c * 0.0 is what the
+// walk forms) under the guard of path_steps.  Here every atom's own gap is formed at its two bracket points (gap_atom's
+// statements: the per-group form sqrt(min V) - r_g and the per-atom form have the same minimum, see point_gap_value), and
+// the result is the lexicographically smallest (gap, k) over the atoms and their bracket points.  That is the smallest
+// gap m* of the walk and the FIRST point that has it: m* = min_i min_k gap_ik, and a pair (i, k) with gap_ik == m* has k in
+// i's bracket -- for a point k outside it the radicand v_ik exceeds that of the better bracket point kb by more than
+// |c|^2 (1 - 1e-6) - 2 e > |c|^2 / 2 (the comment above PathSteps), and such a difference survives the clamp, the root and
+// the subtraction as a STRICT inequality: v_ikb >= -e, so max(v_ik, 0) - max(v_ikb, 0) > |c|^2 / 2 - e too; the guard
+// bounds every radicand by xx_max + |end|^2 < |c|^2 / (64 u), so the two roots differ by more than
+// (|c|^2 / 4) / (2 sqrt(v)) >= 16 u sqrt(v), sixteen ulps of the larger root, and the subtraction of the same radius from
+// both rounds by at most one ulp of the larger of root and radius each -- where the radius is the larger, the gaps are
+// negative and only their sign is used.  (Both radicands clamped to 0 cannot happen under the guard; if it did, the gap
+// would be <= 0, the path rejected and its position not used.)  So the first point with the smallest value is the smallest
+// k among the bracket pairs with gap == m*, which is what the order (gap, k) and wave_argmin's lowest index on ties find.
+// "Every gap > 0" is "m* > 0".  A NaN atom drops out of both forms (no comparison with a NaN holds); no atom left:
+// gap = inf and k = 0x7fffffff, the walk's initial values.  A one-lane team runs the same loop over all atoms.
+// (out of line with scalar arguments as path_bracket_thread is; the result comes back in registers)
+struct PathMin {
+    double gap;
+    int k;
+};
+template <class T>
+PW_NOINLINE PW_HD inline PathMin wave_path_bracket(const Frame& F, int n, double cx, double cy, double cz, int chunks,
+                                                   double rinv, int k_first, long* n_terms = nullptr) {
+    const double kf = (double)k_first, cd = (double)chunks;
+    double best = PW_INF;
+    int pos = 0x7fffffff;
+    long terms = 0;
+    for (int i = T::lane(); i < n; i += T::WSIZE) {
+        const double x = F.x[i], y = F.y[i], z = F.z[i], xx = F.xx[i], r = F.vdw[i];
+        const double t = pw_fma(z, cz, pw_fma(x, cx, y * cy)) * rinv;
+        // (fmax / fmin drop a NaN: such an atom is evaluated at the first two points, NaN both)
+        const double lo = __builtin_fmin(__builtin_fmax(__builtin_floor(t), kf), cd);
+        const double hi = __builtin_fmin(lo + 1.0, cd);
+        // (lo and hi hold integers: c * lo is the walk's c * (double)k)
+        const double ax = cx * lo, ay = cy * lo, az = cz * lo;
+        const double bx = cx * hi, by = cy * hi, bz = cz * hi;
+        const double ga = pw_fma(z, az, pw_fma(x, ax, y * ay));
+        const double gb = pw_fma(z, bz, pw_fma(x, bx, y * by));
+        const double va = pw_m2add(ga, xx) + sq3(ax, ay, az);
+        const double vb = pw_m2add(gb, xx) + sq3(bx, by, bz);
+        const double da = pw_sqrt(va > 0.0 ? va : 0.0) - r;
+        const double db = pw_sqrt(vb > 0.0 ? vb : 0.0) - r;
+        const int ka = (int)lo, kb = (int)hi;
+        if (da < best || (da == best && ka < pos)) { best = da; pos = ka; }
+        if (db < best || (db == best && kb < pos)) { best = db; pos = kb; }
+        terms += 2;
+    }
+    T::wave_argmin(best, pos);
+    if (!(best < PW_INF)) pos = 0x7fffffff;
+    if (n_terms) *n_terms += terms;
+    PathMin out;
+    out.gap = best;
+    out.k = pos;
+    return out;
+}
+
 // The atoms that can matter to the paths of ONE wave (a path each in the lanes that `have` one; vx, vy, vz its end point).
 // A path's result is the smallest gap over its points and where it is first reached, and it starts at m0, the gap at
 // the origin (path_scan_thread): an atom whose gap is PROVABLY above m0 at every point but the origin of every path of
@@ -3193,136 +3254,6 @@ PW_NOINLINE __device__ inline bool wave_brute_bounded(Frame R, int n, PW_LDS dou
 }
 #endif
 
-// ---- the refined path scan of a window fit over the atoms around the path -------------------------------------
-// window_analysis walks the cluster's vector in steps of increment2 (0.1 A: ~116 points, utilities.py:1226) and needs
-// three things of the walk: that every point has a positive gap, the smallest gap m*, and the FIRST point that has it.
-// All three are decided by the atoms that can come within m* of some point of the path.  m* is at most the gap T0 at any
-// single point (four points of the outer half are evaluated over all atoms), and an atom's gap at a point of the
-// segment is at least its distance to the segment minus its radius: so the atoms with dist(a, segment) - r <= T0 (+ a
-// margin a million times the rounding error) contain every atom that attains m* anywhere -- the walk over those alone
-// has the same minimum at the same points (elsewhere its values are upper bounds, which is all a minimum needs).
-// For a cage that is the rim of one window and the wall around the path, a fifth of the atoms.  `scratch`: the
-// window's optimiser block, not yet in use.  Returns false (nothing done) when the radii are ungrouped, the list does
-// not fit or a value is not finite: the caller walks the path over all atoms.
-#if defined(__HIP_DEVICE_COMPILE__)
-template <class T>
-PW_NOINLINE __device__ inline bool wave_path_tube(Frame F, int n, PW_LDS double* scratch, int cap, double cx, double cy,
-                                                  double cz, int chunks, double* pbest_out, int* ppos_out, bool* ok_out) {
-    const PW_LDS ClassInfo* C = F.cls;
-    const int kk = T::uniform_i(C->k);
-    cap = T::uniform_i(cap);
-    n = T::uniform_i(n);
-    chunks = T::uniform_i(chunks);
-    if (kk == 0 || cap < 16 || n > 256 || chunks < 16) return false;
-    PW_LDS double *sx = scratch, *sy = scratch + cap, *sz = scratch + 2 * cap, *sq = scratch + 3 * cap;
-    const int lane = T::lane();
-    // 1. an upper bound of the smallest gap: four points of the outer half, every atom
-    double T0;
-    {
-        double px[4], py[4], pz[4], gv[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int k = (int)(((long)chunks * (4 + q)) / 8);
-            px[q] = cx * (double)k; py[q] = cy * (double)k; pz[q] = cz * (double)k;
-        }
-        wave_gap4<T>(F, n, px, py, pz, gv);
-        T0 = __builtin_fmin(__builtin_fmin(gv[0], gv[1]), __builtin_fmin(gv[2], gv[3]));
-    }
-    if (!(pw_abs(T0) < 1.0e6)) return false;
-    // 2. the atoms within T0 + radius of the segment from the origin to the last point, copied in stored order
-    const double ex = cx * (double)chunks, ey = cy * (double)chunks, ez = cz * (double)chunks;
-    const double len2 = sq3(ex, ey, ez);
-    if (!(len2 > 0.0) || !(len2 < 1.0e12)) return false;
-    int coff[PW_KCLS + 1];
-#pragma unroll
-    for (int g = 0; g <= PW_KCLS; ++g) coff[g] = 0;
-    int total = 0;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        if (64 * t >= n) continue;
-        const int i = lane + 64 * t;
-        const int ic = i < n ? i : 0;
-        const double ax = F.x[ic], ay = F.y[ic], az = F.z[ic], aq = F.xx[ic];
-        double s = (ax * ex + ay * ey + az * ez) / len2;
-        s = s < 0.0 ? 0.0 : (s > 1.0 ? 1.0 : s);
-        const double dx = ax - s * ex, dy = ay - s * ey, dz = az - s * ez;
-        const double d2 = dx * dx + dy * dy + dz * dz;
-        const double lim = T0 + F.vdw[ic] + 1e-6;
-        const bool in = i < n && lim >= 0.0 && d2 <= lim * lim * (1.0 + 1e-9);
-        const unsigned long long mk = T::ballot(in);
-        const int at = total + (int)__builtin_popcountll(mk & ((1ull << lane) - 1ull));
-        if (in && at < cap) { sx[at] = ax; sy[at] = ay; sz[at] = az; sq[at] = aq; }
-#pragma unroll
-        for (int g = 0; g <= PW_KCLS; ++g) {
-            const int first = g < kk ? T::uniform_i(C->off[g]) : n;
-            const int below = first - 64 * t;
-            const unsigned long long lt = below >= 64 ? ~0ull : (below <= 0 ? 0ull : ((1ull << below) - 1ull));
-            coff[g] += (int)__builtin_popcountll(mk & lt);
-        }
-        total += (int)__builtin_popcountll(mk);
-    }
-    if (total > cap || total == 0) return false;
-    T::wave_sync();
-    // 3. the walk over the list: two points per lane and pass, point_gap_value's operations
-    double pbest = PW_INF;
-    int ppos = 0x7fffffff;
-    bool ok = true;
-    for (int k0 = lane; k0 <= chunks; k0 += 128) {
-        const int k1 = k0 + 64 <= chunks ? k0 + 64 : k0;
-        const double qx[2] = {cx * (double)k0, cx * (double)k1};
-        const double qy[2] = {cy * (double)k0, cy * (double)k1};
-        const double qz[2] = {cz * (double)k0, cz * (double)k1};
-        double best[2] = {PW_INF, PW_INF};
-        const double pp[2] = {sq3(qx[0], qy[0], qz[0]), sq3(qx[1], qy[1], qz[1])};
-#pragma unroll
-        for (int g = 0; g < PW_KCLS; ++g) {
-            if (g >= kk) continue;
-            double m2[2] = {PW_INF, PW_INF};
-            const int jlo = coff[g], jhi = coff[g + 1];
-            int j = jlo;
-            for (; j + 4 <= jhi; j += 4) {
-                double bx[4], by[4], bz[4], bq[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) { bx[t] = sx[j + t]; by[t] = sy[j + t]; bz[t] = sz[j + t]; bq[t] = sq[j + t]; }
-#pragma unroll
-                for (int t = 0; t < 4; ++t)
-#pragma unroll
-                    for (int p = 0; p < 2; ++p) {
-                        const double gg = pw_fma(bz[t], qz[p], pw_fma(bx[t], qx[p], by[t] * qy[p]));
-                        m2[p] = __builtin_fmin(m2[p], pw_m2add(gg, bq[t]));
-                    }
-            }
-            for (; j < jhi; ++j) {
-                const double bx = sx[j], by = sy[j], bz = sz[j], bq = sq[j];
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    const double gg = pw_fma(bz, qz[p], pw_fma(bx, qx[p], by * qy[p]));
-                    m2[p] = __builtin_fmin(m2[p], pw_m2add(gg, bq));
-                }
-            }
-            const double r = C->vdw[g];
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const double m2p = m2[p] + pp[p];
-                const double d = pw_sqrt(m2p > 0.0 ? m2p : 0.0);
-                best[p] = __builtin_fmin(best[p], d - r);
-            }
-        }
-        if (!(best[0] > 0.0)) ok = false;
-        if (best[0] < pbest) { pbest = best[0]; ppos = k0; }
-        if (k1 != k0) {
-            if (!(best[1] > 0.0)) ok = false;
-            if (best[1] < pbest) { pbest = best[1]; ppos = k1; }
-        }
-    }
-    T::wave_sync();
-    *pbest_out = pbest;
-    *ppos_out = ppos;
-    *ok_out = ok;
-    return true;
-}
-#endif
-
 // ---- one window (utilities.py:1191-1361), executed by ONE wave -------------------------------
 // per-cluster arrays of the window fits: in the team's LDS (UnitVars) for up to PW_W_MAX clusters, in the
 // team's global slab beyond -- the number of clusters has no upper limit (utilities.py:1481-1536)
@@ -3351,13 +3282,27 @@ PW_NOINLINE PW_HD inline void wave_window(const Frame& FS, const Frame& R, PW_LD
     double pbest = PW_INF;
     int ppos = 0x7fffffff;
     bool ok = true;
-    bool tubed = false;
-#if defined(__HIP_DEVICE_COMPILE__)
-    if (T::WSIZE == 64)
-        tubed = wave_path_tube<T>(FS, n, (PW_LDS double*)lbmem, (int)(sizeof(LbMem<1>) / 8 / 4), cx, cy, cz, chunks, &pbest, &ppos, &ok);
+    bool bracketed = false;
+#ifndef PW_NO_PATH_BRACKETS      // (tests/test_refined_brackets.py builds the host probe with and without: the same records)
+    {
+        // Lanes over atoms, each atom at the two points that bracket it: the smallest gap and the first point that has
+        // it (wave_path_bracket), wherever the guard of path_steps holds for THIS walk's steps.  Where it does not
+        // (ungrouped radii, coordinates beyond about 1e7 A, no step) the walks below run.
+        double xx_max = 0.0;
+        for (int i = T::lane(); i < n; i += T::WSIZE) xx_max = __builtin_fmax(xx_max, FS.xx[i]);
+        xx_max = -T::wave_min(-xx_max);
+        const PathSteps steps = path_steps(FS, vx, vy, vz, prm.increment2, xx_max);
+        if (steps.bracket && steps.chunks == chunks && steps.cx == cx && steps.cy == cy && steps.cz == cz) {
+            const PathMin pm = wave_path_bracket<T>(FS, n, cx, cy, cz, chunks, steps.rinv, 0);
+            pbest = pm.gap;
+            ppos = pm.k;
+            ok = pm.gap > 0.0;
+            bracketed = true;
+        }
+    }
 #endif
-    if (tubed) {
-        // (done: the walk over the atoms around the path, wave_path_tube)
+    if (bracketed) {
+        // (done: pbest and ppos are the wave's already, the reduction below leaves them as they are)
     } else if (T::WSIZE == 64) {
         // two path points per lane and pass over the atoms
         for (int k0 = T::lane(); k0 <= chunks; k0 += 2 * T::WSIZE) {
@@ -3390,7 +3335,7 @@ PW_NOINLINE PW_HD inline void wave_window(const Frame& FS, const Frame& R, PW_LD
         }
         return;
     }
-    T::wave_argmin(pbest, ppos);
+    if (!bracketed) T::wave_argmin(pbest, ppos);
     PW_T1(ws, 2, t_p);
     PW_T0(t_r);
     double new_z = norm3(cx * (double)ppos, cy * (double)ppos, cz * (double)ppos);
@@ -4260,8 +4205,12 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
         // (the first point of every path: the origin)
         const double m_origin = wave_gap_value<T>(sh.S, n, 0.0, 0.0, 0.0);
         int whole = T::SIZE > 1 ? (ncand / T::SIZE) * T::SIZE : ncand;
-        // (a left-over path costs a wave 10 us, a partial round 40: from sixteen paths on the round is the cheaper)
-        if ((ncand - whole) * 16 >= T::SIZE) whole = ncand;
+        // (From sixteen left-over paths on -- a sixteenth of the team -- they go as a round of their own.  Measured again with
+        // the left-over paths on the bracket scan, at 16, 32, 64 and 128 paths (-DPW_LEFTOVER_ROUND_DIV=16, 8, 4, 2), on 1000
+        // copies of a shell that leaves 272 vectors, sixteen of them left over: 0.787-0.798 ms per launch at 16 against
+        // 0.811-0.818 at the others, medians of three, where two runs of one build differ by 0.01 and single launches by 0.03;
+        // a CC3 frame leaves at most 14 and does not notice: 16 stays.  profiles/r09_refined_brackets.json)
+        if ((ncand - whole) * PW_LEFTOVER_ROUND_DIV >= T::SIZE) whole = ncand;
         // (a wave's 64 paths -- consecutive survivors: a band of latitudes -- go through the atoms that can matter to
         // them, two thirds of the molecule: wave_path_candidates; the list lives behind the path values)
         lint* cand_w = nullptr;
@@ -4280,7 +4229,7 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
 #ifndef PW_NO_PATH_BRACKETS      // (tests/test_path_brackets.py builds the host probe with and without: the same records)
         // (the largest |atom|^2 of the frame, for the guard of path_steps: every wave finds it for itself)
         double xx_max = 0.0;
-        if (whole > 0) {
+        if (ncand > 0) {                   // (whole rounds or left-over paths)
             for (int i = T::lane(); i < n; i += T::WSIZE) xx_max = __builtin_fmax(xx_max, sh.S.xx[i]);
             xx_max = -T::wave_min(-xx_max);
         }
@@ -4319,7 +4268,8 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
         const int left = ncand - whole;
         if (left > 0) {
             // The paths of a last, partial round (fewer than a quarter of the team's threads): ONE WAVE per path, the
-            // atoms spread over its lanes, point after point (wave_gap_value: the same value as the one-thread scan).
+            // atoms spread over its lanes -- each atom at its two bracket points where the guard holds, otherwise point
+            // after point (wave_gap_value): the same value as the one-thread scan either way.
             // (Until round 6 a path's points went one to a thread, every thread through all atoms for its point: nine
             // lanes of a wave busy, 12.7 us for the four paths a CC3 frame usually leaves -- in-kernel timer.)
             for (int j = whole + T::wave(); j < ncand; j += T::NWAVES) {
@@ -4328,44 +4278,23 @@ PW_HD inline __attribute__((always_inline)) int windows_bulk_impl(UnitShared& sh
                 const int chunks = (int)np_floordiv(norm3(vx, vy, vz), prm.increment);
                 double g2 = 0.0;
                 bool ok = true;
-                bool all_at_once = false;
-                if constexpr (T::WSIZE == 64) all_at_once = chunks >= 1 && chunks <= 16 && sh.S.cls->k > 0;
-                if (all_at_once) {
-                    if constexpr (T::WSIZE == 64) {
-                        // All points of the path at once: four lanes to a point, each a quarter of every radius group
-                        // (points_gap_values' arithmetic: the smallest squared distance of a group, then one root), the
-                        // four folded by lane exchanges; then the path's statements over the points in order.
-                        const auto& C = *sh.S.cls;
-                        const Frame& F = sh.S;
-                        const double cx = vx / (double)chunks, cy = vy / (double)chunks, cz = vz / (double)chunks;
-                        const int sub = T::lane() & 3;
-                        const int q = (T::lane() >> 2) + 1 <= chunks ? (T::lane() >> 2) + 1 : chunks;
-                        const double qx = cx * (double)q, qy = cy * (double)q, qz = cz * (double)q;
-                        const double pp = sq3(qx, qy, qz);
-                        double gap = PW_INF;
-                        for (int g = 0; g < C.k; ++g) {
-                            double m2 = PW_INF;
-                            const int hi = C.off[g + 1];
-                            for (int i = C.off[g] + sub; i < hi; i += 4) {
-                                const double x = F.x[i], y = F.y[i], z = F.z[i], xx = F.xx[i];
-                                const double gg = pw_fma(z, qz, pw_fma(x, qx, y * qy));
-                                m2 = __builtin_fmin(m2, pw_m2add(gg, xx));
-                            }
-                            m2 = __builtin_fmin(m2, T::xor_d(m2, 1));
-                            m2 = __builtin_fmin(m2, T::xor_d(m2, 2));
-                            const double m2p = m2 + pp;
-                            const double d = pw_sqrt(m2p > 0.0 ? m2p : 0.0);
-                            gap = __builtin_fmin(gap, d - C.vdw[g]);
-                        }
-                        double best = m_origin;
-                        if (!(m_origin > 0.0)) ok = false;
-                        for (int q2 = 1; q2 <= chunks && ok; ++q2) {
-                            const double m = T::bcast_u(gap, 4 * (q2 - 1));
-                            if (!(m > 0.0)) ok = false;
-                            else if (m < best) best = m;
-                        }
-                        g2 = best * 2.0;
+                bool bracketed = false;
+#ifndef PW_NO_PATH_BRACKETS
+                {
+                    // Lanes over atoms, each atom at the two points that bracket it (wave_path_bracket from point 1 on: the
+                    // origin's gap is m_origin), ending as path_bracket_thread ends; where the guard of path_steps does not
+                    // hold, point after point as below.
+                    const PathSteps steps = path_steps(sh.S, vx, vy, vz, prm.increment, xx_max);
+                    if (steps.bracket) {
+                        const PathMin pm = wave_path_bracket<T>(sh.S, n, steps.cx, steps.cy, steps.cz, steps.chunks, steps.rinv, 1);
+                        ok = m_origin > 0.0 && pm.gap > 0.0;
+                        if (ok) g2 = (pm.gap < m_origin ? pm.gap : m_origin) * 2.0;
+                        bracketed = true;
                     }
+                }
+#endif
+                if (bracketed) {
+                    // (done)
                 } else if (chunks >= 1) {
                     // (path_scan_thread's statements: the first point is the origin, its gap the caller's m_origin)
                     const double cx = vx / (double)chunks, cy = vy / (double)chunks, cz = vz / (double)chunks;
