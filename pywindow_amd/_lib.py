@@ -730,47 +730,26 @@ def load():
     L.pw_trans_counts.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     L.pw_superpose.argtypes = [vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp]
     L.pw_cluster_gromos.argtypes = [vp, vp, ctypes.c_int64, vp, ctypes.c_int64, vp, vp, vp, vp]
-    i64 = ctypes.c_int64
-    L.pw_covariance.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
-    L.pw_project.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
-    L.pw_internal_covariance.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
-    L.pw_internal_project.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, ctypes.POINTER(ctypes.c_float)]
-    L.pw_cavity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
-    L.pw_internal_cavity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, i64,
-                                     ctypes.POINTER(ctypes.c_float)]
-    L.pw_sasa.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64]
-    L.pw_internal_sasa.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64, i64, i64, i64,
-                                   ctypes.POINTER(ctypes.c_float)]
-    L.pw_pore_sizes.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
-    L.pw_internal_pore_sizes.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp,
-                                         i64, i64, ctypes.POINTER(ctypes.c_float)]
-    L.pw_affinity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
-    L.pw_internal_affinity.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64,
-                                       vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
-    L.pw_passage.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64]
-    L.pw_internal_passage.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, i64,
-                                      ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int]
-    L.pw_hop.argtypes = [vp, vp, i64] + [vp, i64] * 9
-    L.pw_internal_hop.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
-    L.pw_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9
-    L.pw_internal_rigid_affinity.argtypes = [vp, vp, i64] + [vp, i64] * 9 + [i64, ctypes.POINTER(ctypes.c_float)]
-    L.pw_rigid_cell.argtypes = [vp, vp, i64] + [vp, i64] * 8
-    L.pw_internal_rigid_cell.argtypes = [vp, vp, i64] + [vp, i64] * 8 + [i64, ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int, vp]
-    L.pw_rigid_cell_ewald.argtypes = [vp, vp, i64] + [vp, i64] * 11
-    L.pw_internal_rigid_cell_ewald.argtypes = [vp, vp, i64] + [vp, i64] * 11 + [i64, ctypes.POINTER(ctypes.c_float), vp, ctypes.c_int, vp]
+    i64, fp = ctypes.c_int64, ctypes.POINTER(ctypes.c_float)
+    # the grid, charge and crystal entries take the context, the jobs and n (pointer, length) pairs; the measurement entry of
+    # each takes the same and a tail
+    open_words, counters, pair_counts = [vp, vp, i64, i64, fp], [i64, fp, vp, vp], [i64, fp, vp, ctypes.c_int, vp]
+    for name, n, tail in (("covariance", 4, [i64, fp]), ("project", 5, [fp]), ("cavity", 5, open_words),
+                          ("pore_sizes", 7, open_words), ("affinity", 9, [i64, fp]), ("passage", 5, [i64, fp, vp, ctypes.c_int]),
+                          ("hop", 9, [i64, fp]), ("rigid_affinity", 9, [i64, fp]), ("rigid_cell", 8, pair_counts),
+                          ("rigid_cell_ewald", 11, pair_counts), ("channels", 6, open_words), ("percolation", 6, counters),
+                          ("basins", 8, counters)):
+        getattr(L, "pw_" + name).argtypes = [vp, vp, i64] + [vp, i64] * n
+        getattr(L, "pw_internal_" + name).argtypes = [vp, vp, i64] + [vp, i64] * n + tail
+    # (no pure pairs: the two counts of pw_sasa share a length, as do xyz, params and the charges of the charges pair)
+    sasa = [vp, vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, vp, i64, vp, i64]
+    L.pw_sasa.argtypes, L.pw_internal_sasa.argtypes = sasa, sasa + [i64, i64, i64, fp]
     L.pw_internal_erfc.argtypes = [vp, vp, i64, vp]
-    L.pw_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp]
-    L.pw_internal_charges.argtypes = [vp, vp, i64, vp, vp, i64, vp, vp, i64, ctypes.POINTER(ctypes.c_float)]
-    L.pw_charges_cell.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp]
-    L.pw_internal_charges_cell.argtypes = [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, i64, vp]
+    charges, charges_cell = [vp, vp, i64, vp, vp, i64, vp, vp], [vp, vp, i64, vp, vp, i64, vp, i64, vp, vp]
+    L.pw_charges.argtypes, L.pw_internal_charges.argtypes = charges, charges + [i64, fp]
+    L.pw_charges_cell.argtypes, L.pw_internal_charges_cell.argtypes = charges_cell, charges_cell + [i64, vp]
     L.pw_internal_sincos.argtypes = [vp, i64, vp, vp]
     L.pw_internal_sincos.restype = None
-    L.pw_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6
-    L.pw_internal_channels.argtypes = [vp, vp, i64] + [vp, i64] * 6 + [vp, vp, i64, i64, ctypes.POINTER(ctypes.c_float)]
-    L.pw_percolation.argtypes = [vp, vp, i64] + [vp, i64] * 6
-    L.pw_internal_percolation.argtypes = [vp, vp, i64] + [vp, i64] * 6 + [i64, ctypes.POINTER(ctypes.c_float), vp, vp]
-    L.pw_basins.argtypes = [vp, vp, i64] + [vp, i64] * 8
-    L.pw_internal_basins.argtypes = [vp, vp, i64] + [vp, i64] * 8 + [i64, ctypes.POINTER(ctypes.c_float), vp, vp]
     L.pw_history_open.argtypes = [ctypes.c_char_p, ctypes.POINTER(vp)]
     L.pw_history_frames.argtypes = [vp]
     L.pw_history_frames.restype = ctypes.c_int64
@@ -839,6 +818,66 @@ def _stat_call(name: str, *args) -> None:
     if rc == -2:
         raise ValueError(load().pw_last_error().decode(errors="replace"))
     _check(rc, name)
+
+
+# ---- what the wrappers of the grid, charge and crystal entries (Context.covariance ... Context.hop) share ------------
+
+def _rows(a, width=None, dtype=np.float64, optional=False):
+    """``a`` as a contiguous array of ``dtype``, flat or in rows of ``width``.  With ``optional``, ``None`` is the array
+    of no rows: the library gets a pointer that is not null, and the length 0."""
+    if a is None and optional:
+        return np.zeros(0 if width is None else (0, width), dtype=dtype)
+    return np.ascontiguousarray(a, dtype=dtype).reshape(-1 if width is None else (-1, width))
+
+
+def _furthest(ends) -> int:
+    """The furthest of the jobs' ends, 0 without jobs."""
+    return int(ends.max()) if len(ends) else 0
+
+
+def _result(given, dtype, what, size):
+    """The result array ``what``: ``given``, checked, or zeros up to ``size`` entries."""
+    if given is None:
+        return np.zeros(max(int(size), 0), dtype=dtype)
+    if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
+        raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
+    return given
+
+
+def _result_if_any(given, dtype, what, first, count):
+    """:func:`_result` for a result that only the jobs with ``first >= 0`` have, ``count`` entries each from there:
+    ``None`` unless it is given or a job has one."""
+    has = first >= 0
+    if given is None and not has.any():
+        return None
+    return _result(given, dtype, what, _furthest((first + count)[has]))
+
+
+def _pl(a):
+    """(pointer, length) of an array; the null pointer and 0 for ``None``."""
+    return (None, 0) if a is None else (a.ctypes.data, len(a))
+
+
+def _pls(*arrays) -> list:
+    return [v for a in arrays for v in _pl(a)]
+
+
+def _open_words(open_words, open_first, n_jobs: int):
+    """Ready-made open words (uint64) and where each job's begin (int64, one a job): both arrays, or ``None`` twice."""
+    w = None if open_words is None else _rows(open_words, dtype=np.uint64)
+    f = None if open_first is None else _rows(open_first, dtype=np.int64)
+    if (w is None) != (f is None) or (f is not None and len(f) != n_jobs):
+        raise ValueError("open_words and open_first: both, with one entry of open_first per job")
+    return w, f
+
+
+def _measured(name: str, args, before, kernel_ms, after=(), n_ms: int = 1) -> None:
+    """The measurement entry ``pw_internal_<name>``: ``args``, ``before``, the ``n_ms`` floats that receive the times of
+    the device work, ``after``.  ``kernel_ms``, a list or ``None``, receives the time: a float, or a tuple of ``n_ms``."""
+    ms = (ctypes.c_float * n_ms)()
+    _stat_call("pw_internal_" + name, *args, *before, ms, *after)
+    if kernel_ms is not None:
+        kernel_ms.append(float(ms[0]) if n_ms == 1 else tuple(float(v) for v in ms))
 
 
 class Batch:
@@ -1225,29 +1264,17 @@ class Context:
         ``s_first = -1``: the mean only.  ``workspace_bytes`` (the budget of the partial sums; the result may not depend
         on it) and ``kernel_ms`` (a list that receives the kernels' time by HIP events) go through the hook
         ``pw_internal_covariance``.  Whatever the library refuses (include/pywindow_amd.h) raises ``ValueError``."""
-        jobs = np.ascontiguousarray(jobs, dtype=COV_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
-        tr = None if transforms is None else np.ascontiguousarray(transforms, dtype=SUPERPOSE_OUT_DTYPE).reshape(-1)
-
-        def result(given, size, what):
-            if given is None:
-                return np.zeros(max(size, 0))
-            if given.dtype != np.float64 or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError(f"{what}: a contiguous one-dimensional float64 array")
-            return given
-
+        jobs = _rows(jobs, dtype=COV_JOB_DTYPE)
+        x = _rows(data)
+        tr = None if transforms is None else _rows(transforms, dtype=SUPERPOSE_OUT_DTYPE)
         wanted = jobs["s_first"] >= 0
-        mean = result(mean, int((jobs["mean_first"] + jobs["D"]).max()) if len(jobs) else 0, "mean")
-        scatter = result(scatter, int((jobs["s_first"] + jobs["D"] * jobs["D"])[wanted].max()) if wanted.any() else 0, "scatter")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), None if tr is None else tr.ctypes.data,
-                0 if tr is None else len(tr), mean.ctypes.data, len(mean), scatter.ctypes.data, len(scatter)]
+        mean = _result(mean, np.float64, "mean", _furthest(jobs["mean_first"] + jobs["D"]))
+        scatter = _result(scatter, np.float64, "scatter", _furthest((jobs["s_first"] + jobs["D"] * jobs["D"])[wanted]))
+        args = [self._h] + _pls(jobs, x, tr, mean, scatter)
         if workspace_bytes is None and kernel_ms is None:
             _stat_call("pw_covariance", *args)
         else:
-            ms = ctypes.c_float(0.0)
-            _stat_call("pw_internal_covariance", *args, int(workspace_bytes or 0), ctypes.byref(ms))
-            if kernel_ms is not None:
-                kernel_ms.append(float(ms.value))
+            _measured("covariance", args, [int(workspace_bytes or 0)], kernel_ms)
         return mean, scatter
 
     def project(self, jobs, data, mean, vectors, transforms=None, proj=None, kernel_ms=None):
@@ -1255,24 +1282,16 @@ class Context:
         ``data``, ``transforms``, ``mean`` and ``vectors`` as :meth:`covariance` does) on their ``k`` vectors: ``proj``,
         float64, with the ``T * k`` entries from ``p_first`` of every job filled in -- given, or zeros up to the furthest
         entry of a job.  Whatever the library refuses raises ``ValueError``."""
-        jobs = np.ascontiguousarray(jobs, dtype=PROJECT_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(data, dtype=np.float64).reshape(-1)
-        m = np.ascontiguousarray(mean, dtype=np.float64).reshape(-1)
-        v = np.ascontiguousarray(vectors, dtype=np.float64).reshape(-1)
-        tr = None if transforms is None else np.ascontiguousarray(transforms, dtype=SUPERPOSE_OUT_DTYPE).reshape(-1)
-        if proj is None:
-            ok = (jobs["T"] > 0) & (jobs["k"] > 0) & (jobs["p_first"] >= 0)
-            proj = np.zeros(int((jobs["p_first"] + jobs["T"] * jobs["k"])[ok].max()) if ok.any() else 0)
-        elif proj.dtype != np.float64 or not proj.flags.c_contiguous or proj.ndim != 1:
-            raise ValueError("proj: a contiguous one-dimensional float64 array")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), None if tr is None else tr.ctypes.data,
-                0 if tr is None else len(tr), m.ctypes.data, len(m), v.ctypes.data, len(v), proj.ctypes.data, len(proj)]
+        jobs = _rows(jobs, dtype=PROJECT_JOB_DTYPE)
+        x, m, v = _rows(data), _rows(mean), _rows(vectors)
+        tr = None if transforms is None else _rows(transforms, dtype=SUPERPOSE_OUT_DTYPE)
+        ok = (jobs["T"] > 0) & (jobs["k"] > 0) & (jobs["p_first"] >= 0)
+        proj = _result(proj, np.float64, "proj", _furthest((jobs["p_first"] + jobs["T"] * jobs["k"])[ok]))
+        args = [self._h] + _pls(jobs, x, tr, m, v, proj)
         if kernel_ms is None:
             _stat_call("pw_project", *args)
         else:
-            ms = ctypes.c_float(0.0)
-            _stat_call("pw_internal_project", *args, ctypes.byref(ms))
-            kernel_ms.append(float(ms.value))
+            _measured("project", args, [], kernel_ms)
         return proj
 
     def cavity(self, jobs, xyz, radii, planes=None, out=None, mask=None, open_words=None, open_first=None,
@@ -1286,35 +1305,16 @@ class Context:
         an array, jobs that share outputs --: ``ValueError`` with the library's message.  ``open_words`` /
         ``open_first`` / ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the
         device work by HIP events) go through the library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=CAVITY_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
-        p = np.zeros((0, 4)) if planes is None else np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
-        rows = int(jobs["out"].max()) + 1 if len(jobs) else 0
-        if out is None:
-            out = np.zeros(max(rows, 0), dtype=CAVITY_OUT_DTYPE)
-        elif out.dtype != CAVITY_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
-            raise ValueError("out: a C-contiguous CAVITY_OUT_DTYPE array")
-        with_mask = jobs[jobs["mask_first"] >= 0]
-        if mask is None and len(with_mask):
-            size = (with_mask["mask_first"] + with_mask["ny"].astype(np.int64) * with_mask["nz"]).max()
-            mask = np.zeros(int(size), dtype=np.uint64)
-        elif mask is not None and (mask.dtype != np.uint64 or not mask.flags.c_contiguous or mask.ndim != 1):
-            raise ValueError("mask: a C-contiguous uint64 array")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), r.ctypes.data, len(r), p.ctypes.data, len(p),
-                out.ctypes.data, len(out), None if mask is None else mask.ctypes.data, 0 if mask is None else len(mask)]
+        jobs = _rows(jobs, dtype=CAVITY_JOB_DTYPE)
+        x, r, p = _rows(xyz, 3), _rows(radii), _rows(planes, 4, optional=True)
+        out = _result(out, CAVITY_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        mask = _result_if_any(mask, np.uint64, "mask", jobs["mask_first"], jobs["ny"].astype(np.int64) * jobs["nz"])
+        args = [self._h] + _pls(jobs, x, r, p, out, mask)
         if open_words is None and workspace_bytes is None and kernel_ms is None:
             _stat_call("pw_cavity", *args)
-            return out, mask
-        w = None if open_words is None else np.ascontiguousarray(open_words, dtype=np.uint64).reshape(-1)
-        f = None if open_first is None else np.ascontiguousarray(open_first, dtype=np.int64).reshape(-1)
-        if (w is None) != (f is None) or (f is not None and len(f) != len(jobs)):
-            raise ValueError("open_words and open_first: both, with one entry of open_first per job")
-        ms = ctypes.c_float(0.0)
-        _stat_call("pw_internal_cavity", *args, None if w is None else w.ctypes.data, None if f is None else f.ctypes.data,
-                   0 if w is None else len(w), int(workspace_bytes or 0), ctypes.byref(ms))
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
+        else:
+            w, f = _open_words(open_words, open_first, len(jobs))
+            _measured("cavity", args, [_pl(w)[0], _pl(f)[0], _pl(w)[1], int(workspace_bytes or 0)], kernel_ms)
         return out, mask
 
     def sasa(self, jobs, xyz, radii, directions, words=None, out=None, exposed=None, inside=None, list_capacity=None,
@@ -1329,36 +1329,20 @@ class Context:
         unit vector to ``1e-9``, a range outside an array, jobs that share outputs --: ``ValueError`` with the
         library's message.  ``list_capacity`` / ``lds_words`` / ``block_atoms`` / ``kernel_ms`` (a list that receives
         the time of the kernel by HIP events) go through the library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=SASA_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
-        u = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
-        w = np.zeros(0, dtype=np.uint64) if words is None else np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
-        if out is None:
-            out = np.zeros(int(jobs["out"].max()) + 1 if len(jobs) else 0, dtype=SASA_OUT_DTYPE)
-        elif out.dtype != SASA_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
-            raise ValueError("out: a C-contiguous SASA_OUT_DTYPE array")
-        size = int(max((jobs["count_first"] + jobs["n"]).max(), 0)) if len(jobs) else 0
-        counts = []
-        for given in (exposed, inside):
-            if given is None:
-                given = np.zeros(size, dtype=np.int32)
-            elif given.dtype != np.int32 or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError("exposed and inside: C-contiguous int32 arrays")
-            counts.append(given)
-        if len(counts[0]) != len(counts[1]):
+        jobs = _rows(jobs, dtype=SASA_JOB_DTYPE)
+        x, r, u = _rows(xyz, 3), _rows(radii), _rows(directions, 3)
+        w = _rows(words, dtype=np.uint64, optional=True)
+        out = _result(out, SASA_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        size = _furthest(jobs["count_first"] + jobs["n"])
+        exposed, inside = _result(exposed, np.int32, "exposed", size), _result(inside, np.int32, "inside", size)
+        if len(exposed) != len(inside):
             raise ValueError("exposed and inside: the same length")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), r.ctypes.data, len(r), u.ctypes.data, len(u),
-                w.ctypes.data, len(w), counts[0].ctypes.data, counts[1].ctypes.data, len(counts[0]), out.ctypes.data, len(out)]
+        args = [self._h] + _pls(jobs, x, r, u, w) + [exposed.ctypes.data, inside.ctypes.data, len(exposed)] + _pls(out)
         if list_capacity is None and lds_words is None and block_atoms is None and kernel_ms is None:
             _stat_call("pw_sasa", *args)
-            return out, counts[0], counts[1]
-        ms = ctypes.c_float(0.0)
-        _stat_call("pw_internal_sasa", *args, int(list_capacity or 0), int(lds_words or 0), int(block_atoms or 0),
-                   ctypes.byref(ms))
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
-        return out, counts[0], counts[1]
+        else:
+            _measured("sasa", args, [int(list_capacity or 0), int(lds_words or 0), int(block_atoms or 0)], kernel_ms)
+        return out, exposed, inside
 
     def pore_sizes(self, jobs, xyz, radii, probes, planes=None, levels=None, out=None, mask=None, open_words=None,
                    open_first=None, workspace_bytes=None, kernel_ms=None):
@@ -1374,41 +1358,18 @@ class Context:
         message.  ``open_words`` / ``open_first`` (ready-made open words, ``n_levels * ny * nz`` a job) /
         ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the device work by HIP events) go through
         the library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=PORES_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
-        q = np.ascontiguousarray(probes, dtype=np.float64).reshape(-1)
-        p = np.zeros((0, 4)) if planes is None else np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
-        if out is None:
-            out = np.zeros(max(int(jobs["out"].max()) + 1, 0) if len(jobs) else 0, dtype=PORES_OUT_DTYPE)
-        elif out.dtype != PORES_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
-            raise ValueError("out: a C-contiguous PORES_OUT_DTYPE array")
-        if levels is None:
-            levels = np.zeros(max(int((jobs["level_first"] + jobs["n_levels"]).max()), 0) if len(jobs) else 0,
-                              dtype=PORES_LEVEL_DTYPE)
-        elif levels.dtype != PORES_LEVEL_DTYPE or not levels.flags.c_contiguous or levels.ndim != 1:
-            raise ValueError("levels: a C-contiguous PORES_LEVEL_DTYPE array")
-        with_mask = jobs[jobs["mask_first"] >= 0]
-        if mask is None and len(with_mask):
-            size = (with_mask["mask_first"] + with_mask["n_levels"] * with_mask["ny"].astype(np.int64) * with_mask["nz"]).max()
-            mask = np.zeros(max(int(size), 0), dtype=np.uint64)
-        elif mask is not None and (mask.dtype != np.uint64 or not mask.flags.c_contiguous or mask.ndim != 1):
-            raise ValueError("mask: a C-contiguous uint64 array")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), r.ctypes.data, len(r), p.ctypes.data, len(p),
-                q.ctypes.data, len(q), levels.ctypes.data, len(levels), out.ctypes.data, len(out),
-                None if mask is None else mask.ctypes.data, 0 if mask is None else len(mask)]
+        jobs = _rows(jobs, dtype=PORES_JOB_DTYPE)
+        x, r, q, p = _rows(xyz, 3), _rows(radii), _rows(probes), _rows(planes, 4, optional=True)
+        out = _result(out, PORES_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        levels = _result(levels, PORES_LEVEL_DTYPE, "levels", _furthest(jobs["level_first"] + jobs["n_levels"]))
+        mask = _result_if_any(mask, np.uint64, "mask", jobs["mask_first"],
+                              jobs["n_levels"] * jobs["ny"].astype(np.int64) * jobs["nz"])
+        args = [self._h] + _pls(jobs, x, r, p, q, levels, out, mask)
         if open_words is None and workspace_bytes is None and kernel_ms is None:
             _stat_call("pw_pore_sizes", *args)
-            return levels, out, mask
-        w = None if open_words is None else np.ascontiguousarray(open_words, dtype=np.uint64).reshape(-1)
-        f = None if open_first is None else np.ascontiguousarray(open_first, dtype=np.int64).reshape(-1)
-        if (w is None) != (f is None) or (f is not None and len(f) != len(jobs)):
-            raise ValueError("open_words and open_first: both, with one entry of open_first per job")
-        ms = ctypes.c_float(0.0)
-        _stat_call("pw_internal_pore_sizes", *args, None if w is None else w.ctypes.data,
-                   None if f is None else f.ctypes.data, 0 if w is None else len(w), int(workspace_bytes or 0), ctypes.byref(ms))
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
+        else:
+            w, f = _open_words(open_words, open_first, len(jobs))
+            _measured("pore_sizes", args, [_pl(w)[0], _pl(f)[0], _pl(w)[1], int(workspace_bytes or 0)], kernel_ms)
         return levels, out, mask
 
     def affinity(self, jobs, xyz, coef, betas, words=None, edges=None, out=None, levels=None, hist=None, energies=None,
@@ -1425,35 +1386,18 @@ class Context:
         bounds, a count or a dimension outside its range, a range outside an array, jobs that share outputs --:
         ``ValueError`` with the library's message.  ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time
         of the device work by HIP events) go through the library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=AFFINITY_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
-        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
-        w = np.zeros(0, dtype=np.uint64) if words is None else np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
-        e = np.zeros(0) if edges is None else np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
-
-        def result(given, dtype, size, name):
-            if given is None:
-                return np.zeros(max(int(size), 0), dtype=dtype)
-            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError(f"{name}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
-            return given
-
-        some = len(jobs) > 0
-        out = result(out, AFFINITY_OUT_DTYPE, jobs["out"].max() + 1 if some else 0, "out")
-        levels = result(levels, AFFINITY_LEVEL_DTYPE, (jobs["level_first"] + jobs["n_betas"]).max() if some else 0, "levels")
-        hist = result(hist, np.int64, (jobs["hist_first"] + jobs["n_edges"]).max() if some else 0, "hist")
-        energies = result(energies, np.float64, 0, "energies")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), w.ctypes.data, len(w),
-                b.ctypes.data, len(b), e.ctypes.data, len(e), energies.ctypes.data, len(energies), levels.ctypes.data,
-                len(levels), hist.ctypes.data, len(hist), out.ctypes.data, len(out)]
+        jobs = _rows(jobs, dtype=AFFINITY_JOB_DTYPE)
+        x, c, b = _rows(xyz, 3), _rows(coef, 2), _rows(betas)
+        w, e = _rows(words, dtype=np.uint64, optional=True), _rows(edges, optional=True)
+        out = _result(out, AFFINITY_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        levels = _result(levels, AFFINITY_LEVEL_DTYPE, "levels", _furthest(jobs["level_first"] + jobs["n_betas"]))
+        hist = _result(hist, np.int64, "hist", _furthest(jobs["hist_first"] + jobs["n_edges"]))
+        energies = _result(energies, np.float64, "energies", 0)
+        args = [self._h] + _pls(jobs, x, c, w, b, e, energies, levels, hist, out)
         if workspace_bytes is None and kernel_ms is None:
             _stat_call("pw_affinity", *args)
-            return out, levels, hist, energies
-        ms = ctypes.c_float(0.0)
-        _stat_call("pw_internal_affinity", *args, int(workspace_bytes or 0), ctypes.byref(ms))
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
+        else:
+            _measured("affinity", args, [int(workspace_bytes or 0)], kernel_ms)
         return out, levels, hist, energies
 
     def rigid_affinity(self, jobs, xyz, coef, offsets, dirs, betas, words=None, out=None, levels=None, maps=None,
@@ -1469,35 +1413,35 @@ class Context:
         region).  Whatever the entry refuses: ``ValueError`` with the library's message.  ``workspace_bytes`` /
         ``kernel_ms`` (a list that receives the time of the device work by HIP events) go through the library's
         measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=RIGID_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 3)
-        t = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
-        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
-        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
-        w = np.zeros(0, dtype=np.uint64) if words is None else np.ascontiguousarray(words, dtype=np.uint64).reshape(-1)
-
-        def result(given, dtype, size, name):
-            if given is None:
-                return np.zeros(max(int(size), 0), dtype=dtype)
-            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError(f"{name}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
-            return given
-
-        some = len(jobs) > 0
-        out = result(out, RIGID_OUT_DTYPE, jobs["out"].max() + 1 if some else 0, "out")
-        levels = result(levels, AFFINITY_LEVEL_DTYPE, (jobs["level_first"] + jobs["n_betas"]).max() if some else 0, "levels")
-        maps = result(maps, np.float64, 0, "maps")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), t.ctypes.data, len(t),
-                d.ctypes.data, len(d), w.ctypes.data, len(w), b.ctypes.data, len(b), maps.ctypes.data, len(maps),
-                levels.ctypes.data, len(levels), out.ctypes.data, len(out)]
+        jobs = _rows(jobs, dtype=RIGID_JOB_DTYPE)
+        x, c, t, d, b = _rows(xyz, 3), _rows(coef, 3), _rows(offsets), _rows(dirs, 3), _rows(betas)
+        w = _rows(words, dtype=np.uint64, optional=True)
+        out = _result(out, RIGID_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        levels = _result(levels, AFFINITY_LEVEL_DTYPE, "levels", _furthest(jobs["level_first"] + jobs["n_betas"]))
+        maps = _result(maps, np.float64, "maps", 0)
+        args = [self._h] + _pls(jobs, x, c, t, d, w, b, maps, levels, out)
         if workspace_bytes is None and kernel_ms is None:
             _stat_call("pw_rigid_affinity", *args)
+        else:
+            _measured("rigid_affinity", args, [int(workspace_bytes or 0)], kernel_ms)
+        return out, levels, maps
+
+    def _rigid_cell(self, name, jobs, cell, inputs, out, levels, maps, workspace_bytes, kernel_ms, diagnostics, skip):
+        """What :meth:`rigid_cell` and :meth:`rigid_cell_ewald` share: the results sized on ``cell``, the ``pw_rigid_cell``
+        records of the jobs, the call of ``pw_<name>`` or of its measurement entry, and the diagnostics."""
+        voxels = np.int64(1) * cell["nx"] * cell["ny"] * cell["nz"]
+        out = _result(out, RIGID_OUT_DTYPE, "out", _furthest(cell["out"] + 1))
+        levels = _result(levels, AFFINITY_LEVEL_DTYPE, "levels", _furthest(cell["level_first"] + cell["n_betas"]))
+        maps = _result_if_any(maps, np.float64, "maps", cell["map_first"], (cell["n_betas"] + 1) * voxels)
+        args = [self._h] + _pls(jobs, *inputs, maps, levels, out)
+        if workspace_bytes is None and kernel_ms is None and diagnostics is None and skip:
+            _stat_call("pw_" + name, *args)
             return out, levels, maps
-        ms = ctypes.c_float(0.0)
-        _stat_call("pw_internal_rigid_affinity", *args, int(workspace_bytes or 0), ctypes.byref(ms))
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
+        n_pairs, instances = np.zeros(len(jobs), dtype=np.int64), np.zeros(1, dtype=np.int32)
+        _measured(name, args, [int(workspace_bytes or 0)], kernel_ms,
+                  [n_pairs.ctypes.data, 1 if skip else 0, instances.ctypes.data])
+        if diagnostics is not None:
+            diagnostics.append((n_pairs, int(instances[0])))
         return out, levels, maps
 
     def rigid_cell(self, jobs, xyz, coef, offsets, dirs, betas, out=None, levels=None, maps=None, workspace_bytes=None,
@@ -1514,43 +1458,9 @@ class Context:
         HIP events) / ``diagnostics`` (a list that receives ``(n_pairs, instances)``: the pair terms evaluated per job
         and a bit per instance of the main kernel that was launched; no part of the defined result) / ``skip=False`` (no
         atom is left out: the same bytes) go through the library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=RIGID_CELL_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
-        t = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
-        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
-        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
-        some = len(jobs) > 0
-        voxels = np.int64(1) * jobs["nx"] * jobs["ny"] * jobs["nz"]
-
-        def made(given, dtype, what, size):
-            if given is None:
-                return np.zeros(max(int(size), 0), dtype=dtype)
-            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
-            return given
-
-        out = made(out, RIGID_OUT_DTYPE, "out", (jobs["out"] + 1).max() if some else 0)
-        levels = made(levels, AFFINITY_LEVEL_DTYPE, "levels", (jobs["level_first"] + jobs["n_betas"]).max() if some else 0)
-        has = jobs["map_first"] >= 0
-        if maps is not None or has.any():
-            maps = made(maps, np.float64, "maps",
-                        (jobs["map_first"][has] + (jobs["n_betas"][has] + 1) * voxels[has]).max() if has.any() else 0)
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), t.ctypes.data, len(t),
-                d.ctypes.data, len(d), b.ctypes.data, len(b), None if maps is None else maps.ctypes.data,
-                0 if maps is None else len(maps), levels.ctypes.data, len(levels), out.ctypes.data, len(out)]
-        if workspace_bytes is None and kernel_ms is None and diagnostics is None and skip:
-            _stat_call("pw_rigid_cell", *args)
-            return out, levels, maps
-        ms = ctypes.c_float(0.0)
-        n_pairs, instances = np.zeros(len(jobs), dtype=np.int64), np.zeros(1, dtype=np.int32)
-        _stat_call("pw_internal_rigid_cell", *args, int(workspace_bytes or 0), ctypes.byref(ms), n_pairs.ctypes.data,
-                   1 if skip else 0, instances.ctypes.data)
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
-        if diagnostics is not None:
-            diagnostics.append((n_pairs, int(instances[0])))
-        return out, levels, maps
+        jobs = _rows(jobs, dtype=RIGID_CELL_JOB_DTYPE)
+        inputs = [_rows(xyz, 3), _rows(coef, 2), _rows(offsets), _rows(dirs, 3), _rows(betas)]
+        return self._rigid_cell("rigid_cell", jobs, jobs, inputs, out, levels, maps, workspace_bytes, kernel_ms, diagnostics, skip)
 
     def rigid_cell_ewald(self, jobs, xyz, coef, offsets, dirs, betas, site_q, cell, kvecs, out=None, levels=None, maps=None,
                          workspace_bytes=None, kernel_ms=None, diagnostics=None, skip=True):
@@ -1558,48 +1468,11 @@ class Context:
         whose ``cell`` is the ``pw_rigid_cell`` job): the rows of ``coef`` are ``(A, B, C)``; ``site_q`` the site charges,
         ``cell`` rows ``(x, y, z, q)`` of the primary cell's atoms and ``kvecs`` rows ``(h, k, l, w)`` of the reciprocal
         sum (:func:`pywindow_amd.ewald_parameters`).  The results and the measurement arguments are :meth:`rigid_cell`'s."""
-        jobs = np.ascontiguousarray(jobs, dtype=RIGID_CELL_EWALD_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        c = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 3)
-        t = np.ascontiguousarray(offsets, dtype=np.float64).reshape(-1)
-        d = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
-        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
-        q = np.ascontiguousarray(site_q, dtype=np.float64).reshape(-1)
-        ca = np.ascontiguousarray(cell, dtype=np.float64).reshape(-1, 4)
-        kv = np.ascontiguousarray(kvecs, dtype=np.float64).reshape(-1, 4)
-        inner = jobs["cell"]
-        some = len(jobs) > 0
-        voxels = np.int64(1) * inner["nx"] * inner["ny"] * inner["nz"]
-
-        def made(given, dtype, what, size):
-            if given is None:
-                return np.zeros(max(int(size), 0), dtype=dtype)
-            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
-            return given
-
-        out = made(out, RIGID_OUT_DTYPE, "out", (inner["out"] + 1).max() if some else 0)
-        levels = made(levels, AFFINITY_LEVEL_DTYPE, "levels", (inner["level_first"] + inner["n_betas"]).max() if some else 0)
-        has = inner["map_first"] >= 0
-        if maps is not None or has.any():
-            maps = made(maps, np.float64, "maps",
-                        (inner["map_first"][has] + (inner["n_betas"][has] + 1) * voxels[has]).max() if has.any() else 0)
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), t.ctypes.data, len(t),
-                d.ctypes.data, len(d), b.ctypes.data, len(b), q.ctypes.data, len(q), ca.ctypes.data, len(ca), kv.ctypes.data,
-                len(kv), None if maps is None else maps.ctypes.data, 0 if maps is None else len(maps), levels.ctypes.data,
-                len(levels), out.ctypes.data, len(out)]
-        if workspace_bytes is None and kernel_ms is None and diagnostics is None and skip:
-            _stat_call("pw_rigid_cell_ewald", *args)
-            return out, levels, maps
-        ms = ctypes.c_float(0.0)
-        n_pairs, instances = np.zeros(len(jobs), dtype=np.int64), np.zeros(1, dtype=np.int32)
-        _stat_call("pw_internal_rigid_cell_ewald", *args, int(workspace_bytes or 0), ctypes.byref(ms), n_pairs.ctypes.data,
-                   1 if skip else 0, instances.ctypes.data)
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
-        if diagnostics is not None:
-            diagnostics.append((n_pairs, int(instances[0])))
-        return out, levels, maps
+        jobs = _rows(jobs, dtype=RIGID_CELL_EWALD_JOB_DTYPE)
+        inputs = [_rows(xyz, 3), _rows(coef, 3), _rows(offsets), _rows(dirs, 3), _rows(betas), _rows(site_q), _rows(cell, 4),
+                  _rows(kvecs, 4)]
+        return self._rigid_cell("rigid_cell_ewald", jobs, jobs["cell"], inputs, out, levels, maps, workspace_bytes, kernel_ms,
+                                diagnostics, skip)
 
     def erfc(self, x):
         """The library's ``pw_erfc`` (pw_math.hpp) element by element on this context (test instrumentation): float64."""
@@ -1627,30 +1500,31 @@ class Context:
         job may read).  Whatever the entry refuses: ``ValueError`` with the library's message.  ``workspace_bytes`` /
         ``kernel_ms`` (a list that receives the time of the kernels by HIP events) go through the library's
         measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=CHARGES_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 2)
-        some = len(jobs) > 0
-        rows = max(int(jobs["out"].max()) + 1, 0) if some else 0
-        if out is None:
-            out = np.zeros(rows, dtype=CHARGES_OUT_DTYPE)
-        elif out.dtype != CHARGES_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1 or len(out) < rows:
-            raise ValueError("out: a contiguous CHARGES_OUT_DTYPE array with a row for every job")
-        size = max(int((jobs["charge_first"] + jobs["n"]).max()), 0) if some else 0
+        return self._charges("charges", _rows(jobs, dtype=CHARGES_JOB_DTYPE), xyz, params, None, out, CHARGES_OUT_DTYPE,
+                             workspace_bytes, kernel_ms, 1)
+
+    def _charges(self, name, jobs, xyz, params, kvecs, out, out_dtype, workspace_bytes, kernel_ms, n_ms):
+        """What :meth:`charges` and :meth:`charges_cell` share: ``xyz``, ``params`` and the charges brought to one length,
+        the rows of ``out`` and the call of ``pw_<name>`` (with the rows of ``kvecs``, if any) or of its measurement
+        entry, which has ``n_ms`` timers."""
+        x, p = _rows(xyz, 3), _rows(params, 2)
+        rows = max(_furthest(jobs["out"] + 1), 0)
+        out = _result(out, out_dtype, "out", rows)
+        if len(out) < rows:
+            raise ValueError("out: a row for every job")
+        size = max(_furthest(jobs["charge_first"] + jobs["n"]), 0)
         n_points = max(len(x), len(p), size)
         if len(x) < n_points:
             x = np.concatenate([x, np.zeros((n_points - len(x), 3))])
         if len(p) < n_points:
             p = np.concatenate([p, np.zeros((n_points - len(p), 2))])
         q = np.zeros(n_points)
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, p.ctypes.data, n_points, q.ctypes.data, out.ctypes.data]
+        args = [self._h, *_pl(jobs), x.ctypes.data, p.ctypes.data, n_points, *(() if kvecs is None else _pl(kvecs)),
+                q.ctypes.data, out.ctypes.data]
         if workspace_bytes is None and kernel_ms is None:
-            _stat_call("pw_charges", *args)
+            _stat_call("pw_" + name, *args)
         else:
-            ms = ctypes.c_float(0.0)
-            _stat_call("pw_internal_charges", *args, int(workspace_bytes or 0), ctypes.byref(ms))
-            if kernel_ms is not None:
-                kernel_ms.append(float(ms.value))
+            _measured(name, args, [int(workspace_bytes or 0)], kernel_ms, n_ms=n_ms)
         return q[:size], out
 
     def charges_cell(self, jobs, xyz, params, kvecs, out=None, workspace_bytes=None, kernel_ms=None):
@@ -1661,33 +1535,8 @@ class Context:
         ``out`` a ``CHARGES_CELL_OUT_DTYPE`` array.  Whatever the entry refuses: ``ValueError`` with the library's message.
         ``workspace_bytes`` / ``kernel_ms`` (a list that receives ``(count, rows, solver)``, the times of the three kinds
         of kernel in ms by HIP events) go through the library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=CHARGES_CELL_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        p = np.ascontiguousarray(params, dtype=np.float64).reshape(-1, 2)
-        kv = np.ascontiguousarray(kvecs, dtype=np.float64).reshape(-1, 4)
-        some = len(jobs) > 0
-        rows = max(int(jobs["out"].max()) + 1, 0) if some else 0
-        if out is None:
-            out = np.zeros(rows, dtype=CHARGES_CELL_OUT_DTYPE)
-        elif out.dtype != CHARGES_CELL_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1 or len(out) < rows:
-            raise ValueError("out: a contiguous CHARGES_CELL_OUT_DTYPE array with a row for every job")
-        size = max(int((jobs["charge_first"] + jobs["n"]).max()), 0) if some else 0
-        n_points = max(len(x), len(p), size)
-        if len(x) < n_points:
-            x = np.concatenate([x, np.zeros((n_points - len(x), 3))])
-        if len(p) < n_points:
-            p = np.concatenate([p, np.zeros((n_points - len(p), 2))])
-        q = np.zeros(n_points)
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, p.ctypes.data, n_points, kv.ctypes.data, len(kv),
-                q.ctypes.data, out.ctypes.data]
-        if workspace_bytes is None and kernel_ms is None:
-            _stat_call("pw_charges_cell", *args)
-        else:
-            ms = (ctypes.c_float * 3)()
-            _stat_call("pw_internal_charges_cell", *args, int(workspace_bytes or 0), ctypes.addressof(ms))
-            if kernel_ms is not None:
-                kernel_ms.append(tuple(float(v) for v in ms))
-        return q[:size], out
+        return self._charges("charges_cell", _rows(jobs, dtype=CHARGES_CELL_JOB_DTYPE), xyz, params, _rows(kvecs, 4), out,
+                             CHARGES_CELL_OUT_DTYPE, workspace_bytes, kernel_ms, 3)
 
     def channels(self, jobs, xyz, radii, out=None, comps=None, mask=None, labels=None, open_words=None, open_first=None,
                  workspace_bytes=None, kernel_ms=None):
@@ -1703,42 +1552,21 @@ class Context:
         array, jobs that share outputs --: ``ValueError`` with the library's message.  ``open_words`` / ``open_first``
         / ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the device work by HIP events) go
         through the library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=CHANNELS_JOB_DTYPE).reshape(-1)
-        x = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        r = np.ascontiguousarray(radii, dtype=np.float64).reshape(-1)
-        some = len(jobs) > 0
+        jobs = _rows(jobs, dtype=CHANNELS_JOB_DTYPE)
+        x, r = _rows(xyz, 3), _rows(radii)
         rows = np.int64(1) * jobs["ny"] * jobs["nz"]
-
-        def made(given, dtype, what, first, count):
-            """`given`, checked, or zeros up to the furthest entry of the jobs that write some"""
-            if given is not None:
-                if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
-                    raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
-                return given
-            has = (jobs[first] >= 0) & (count > 0) if some else np.zeros(0, dtype=bool)
-            return np.zeros(int((jobs[first][has] + count[has]).max()), dtype=dtype) if has.any() else None
-
-        out = made(out, CHANNELS_OUT_DTYPE, "out", "out", np.ones(len(jobs), dtype=np.int64))
-        if out is None:
-            out = np.zeros(0, dtype=CHANNELS_OUT_DTYPE)
-        comps = made(comps, CHANNELS_COMP_DTYPE, "comps", "comp_first", jobs["c_max"].astype(np.int64))
-        mask = made(mask, np.uint64, "mask", "mask_first", rows)
-        labels = made(labels, np.uint8, "labels", "label_first", rows * jobs["nx"])
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), r.ctypes.data, len(r), out.ctypes.data, len(out)]
-        for a in (comps, mask, labels):
-            args += [None if a is None else a.ctypes.data, 0 if a is None else len(a)]
+        c_max, voxels = jobs["c_max"].astype(np.int64), rows * jobs["nx"]
+        out = _result(out, CHANNELS_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        # (a job that would write nothing of a result counts as having none)
+        comps = _result_if_any(comps, CHANNELS_COMP_DTYPE, "comps", np.where(c_max > 0, jobs["comp_first"], -1), c_max)
+        mask = _result_if_any(mask, np.uint64, "mask", np.where(rows > 0, jobs["mask_first"], -1), rows)
+        labels = _result_if_any(labels, np.uint8, "labels", np.where(voxels > 0, jobs["label_first"], -1), voxels)
+        args = [self._h] + _pls(jobs, x, r, out, comps, mask, labels)
         if open_words is None and workspace_bytes is None and kernel_ms is None:
             _stat_call("pw_channels", *args)
-            return out, comps, mask, labels
-        w = None if open_words is None else np.ascontiguousarray(open_words, dtype=np.uint64).reshape(-1)
-        f = None if open_first is None else np.ascontiguousarray(open_first, dtype=np.int64).reshape(-1)
-        if (w is None) != (f is None) or (f is not None and len(f) != len(jobs)):
-            raise ValueError("open_words and open_first: both, with one entry of open_first per job")
-        ms = ctypes.c_float(0.0)
-        _stat_call("pw_internal_channels", *args, None if w is None else w.ctypes.data, None if f is None else f.ctypes.data,
-                   0 if w is None else len(w), int(workspace_bytes or 0), ctypes.byref(ms))
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
+        else:
+            w, f = _open_words(open_words, open_first, len(jobs))
+            _measured("channels", args, [_pl(w)[0], _pl(f)[0], _pl(w)[1], int(workspace_bytes or 0)], kernel_ms)
         return out, comps, mask, labels
 
     def percolation(self, jobs, xyz=None, coef=None, field=None, levels=None, out=None, maps=None, workspace_bytes=None,
@@ -1755,37 +1583,18 @@ class Context:
         HIP events) / ``diagnostics`` (a list that receives ``(n_evaluations, n_fills)``, two int32 arrays over the
         jobs; they are no part of the defined result and differ between device and host) go through the library's
         measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=PERCOLATION_JOB_DTYPE).reshape(-1)
-        x = np.zeros((0, 3)) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        c = np.zeros((0, 2)) if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
-        f = np.zeros(0) if field is None else np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
-        some = len(jobs) > 0
+        jobs = _rows(jobs, dtype=PERCOLATION_JOB_DTYPE)
+        x, c, f = _rows(xyz, 3, optional=True), _rows(coef, 2, optional=True), _rows(field, optional=True)
         voxels = np.int64(1) * jobs["nx"] * jobs["ny"] * jobs["nz"]
-
-        def made(given, dtype, what, size):
-            if given is None:
-                return np.zeros(max(int(size), 0), dtype=dtype)
-            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
-            return given
-
-        levels = made(levels, PERCOLATION_LEVEL_DTYPE, "levels", (jobs["level_first"] + PERC_CRITERIA).max() if some else 0)
-        out = made(out, PERCOLATION_OUT_DTYPE, "out", (jobs["out"] + 1).max() if some else 0)
-        has = jobs["map_first"] >= 0
-        if maps is not None or has.any():
-            maps = made(maps, np.float64, "maps", (jobs["map_first"][has] + voxels[has]).max() if has.any() else 0)
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), f.ctypes.data, len(f),
-                None if maps is None else maps.ctypes.data, 0 if maps is None else len(maps), levels.ctypes.data, len(levels),
-                out.ctypes.data, len(out)]
+        levels = _result(levels, PERCOLATION_LEVEL_DTYPE, "levels", _furthest(jobs["level_first"] + PERC_CRITERIA))
+        out = _result(out, PERCOLATION_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        maps = _result_if_any(maps, np.float64, "maps", jobs["map_first"], voxels)
+        args = [self._h] + _pls(jobs, x, c, f, maps, levels, out)
         if workspace_bytes is None and kernel_ms is None and diagnostics is None:
             _stat_call("pw_percolation", *args)
             return levels, out, maps
-        ms = ctypes.c_float(0.0)
         n_eval, n_fill = np.zeros(len(jobs), dtype=np.int32), np.zeros(len(jobs), dtype=np.int32)
-        _stat_call("pw_internal_percolation", *args, int(workspace_bytes or 0), ctypes.byref(ms), n_eval.ctypes.data,
-                   n_fill.ctypes.data)
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
+        _measured("percolation", args, [int(workspace_bytes or 0)], kernel_ms, [n_eval.ctypes.data, n_fill.ctypes.data])
         if diagnostics is not None:
             diagnostics.append((n_eval, n_fill))
         return levels, out, maps
@@ -1806,42 +1615,20 @@ class Context:
         library's message.  ``workspace_bytes`` / ``kernel_ms`` (a list that receives the time of the device work by HIP
         events) / ``diagnostics`` (a list that receives ``(n_rounds, n_faces)``, two int32 arrays over the jobs; they
         are no part of the defined result) go through the library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=BASINS_JOB_DTYPE).reshape(-1)
-        x = np.zeros((0, 3)) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        c = np.zeros((0, 2)) if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
-        f = np.zeros(0) if field is None else np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
-        some = len(jobs) > 0
+        jobs = _rows(jobs, dtype=BASINS_JOB_DTYPE)
+        x, c, f = _rows(xyz, 3, optional=True), _rows(coef, 2, optional=True), _rows(field, optional=True)
         voxels = np.int64(1) * jobs["nx"] * jobs["ny"] * jobs["nz"]
-
-        def made(given, dtype, what, size):
-            if given is None:
-                return np.zeros(max(int(size), 0), dtype=dtype)
-            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError(f"{what}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
-            return given
-
-        out = made(out, BASINS_OUT_DTYPE, "out", (jobs["out"] + 1).max() if some else 0)
-        basins = made(basins, BASINS_BASIN_DTYPE, "basins", (jobs["basin_first"] + jobs["b_cap"]).max() if some else 0)
-        edges = made(edges, BASINS_EDGE_DTYPE, "edges", (jobs["edge_first"] + jobs["e_cap"]).max() if some else 0)
-        has = jobs["map_first"] >= 0
-        if maps is not None or has.any():
-            maps = made(maps, np.float64, "maps", (jobs["map_first"][has] + voxels[has]).max() if has.any() else 0)
-        lab = jobs["label_first"] >= 0
-        if labels is not None or lab.any():
-            labels = made(labels, BASINS_LABEL_DTYPE, "labels", (jobs["label_first"][lab] + voxels[lab]).max() if lab.any() else 0)
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), f.ctypes.data, len(f),
-                None if maps is None else maps.ctypes.data, 0 if maps is None else len(maps), basins.ctypes.data, len(basins),
-                edges.ctypes.data, len(edges), None if labels is None else labels.ctypes.data, 0 if labels is None else len(labels),
-                out.ctypes.data, len(out)]
+        out = _result(out, BASINS_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        basins = _result(basins, BASINS_BASIN_DTYPE, "basins", _furthest(jobs["basin_first"] + jobs["b_cap"]))
+        edges = _result(edges, BASINS_EDGE_DTYPE, "edges", _furthest(jobs["edge_first"] + jobs["e_cap"]))
+        maps = _result_if_any(maps, np.float64, "maps", jobs["map_first"], voxels)
+        labels = _result_if_any(labels, BASINS_LABEL_DTYPE, "labels", jobs["label_first"], voxels)
+        args = [self._h] + _pls(jobs, x, c, f, maps, basins, edges, labels, out)
         if workspace_bytes is None and kernel_ms is None and diagnostics is None:
             _stat_call("pw_basins", *args)
             return out, basins, edges, maps, labels
-        ms = ctypes.c_float(0.0)
         n_rounds, n_faces = np.zeros(len(jobs), dtype=np.int32), np.zeros(len(jobs), dtype=np.int32)
-        _stat_call("pw_internal_basins", *args, int(workspace_bytes or 0), ctypes.byref(ms), n_rounds.ctypes.data,
-                   n_faces.ctypes.data)
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
+        _measured("basins", args, [int(workspace_bytes or 0)], kernel_ms, [n_rounds.ctypes.data, n_faces.ctypes.data])
         if diagnostics is not None:
             diagnostics.append((n_rounds, n_faces))
         return out, basins, edges, maps, labels
@@ -1859,28 +1646,17 @@ class Context:
         receives the number of flood fills of every row) / ``grids`` (3: the kernel without its fourth bit grid, for
         the measurement of what that grid buys; the result does not depend on it) go through the library's measurement
         entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=PASSAGE_JOB_DTYPE).reshape(-1)
-        x = np.zeros((0, 3)) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        c = np.zeros((0, 2)) if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
-        p = np.zeros((0, 4)) if planes is None else np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
-        f = np.zeros(0) if field is None else np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
-        if out is None:
-            rows = int((jobs["out_first"] + np.maximum(jobs["m"], 1)).max()) if len(jobs) else 0
-            out = np.zeros(max(rows, 0), dtype=PASSAGE_OUT_DTYPE)
-        elif out.dtype != PASSAGE_OUT_DTYPE or not out.flags.c_contiguous or out.ndim != 1:
-            raise ValueError("out: a C-contiguous PASSAGE_OUT_DTYPE array")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), p.ctypes.data, len(p),
-                f.ctypes.data, len(f), out.ctypes.data, len(out)]
+        jobs = _rows(jobs, dtype=PASSAGE_JOB_DTYPE)
+        x, c = _rows(xyz, 3, optional=True), _rows(coef, 2, optional=True)
+        p, f = _rows(planes, 4, optional=True), _rows(field, optional=True)
+        out = _result(out, PASSAGE_OUT_DTYPE, "out", _furthest(jobs["out_first"] + np.maximum(jobs["m"], 1)))
+        args = [self._h] + _pls(jobs, x, c, p, f, out)
         if workspace_bytes is None and kernel_ms is None and fills is None and grids is None:
             _stat_call("pw_passage", *args)
             return out
         if fills is not None and (fills.dtype != np.int32 or not fills.flags.c_contiguous or fills.shape != out.shape):
             raise ValueError("fills: a C-contiguous int32 array as long as out")
-        ms = ctypes.c_float(0.0)
-        _stat_call("pw_internal_passage", *args, int(workspace_bytes or 0), ctypes.byref(ms),
-                   None if fills is None else fills.ctypes.data, int(grids or 0))
-        if kernel_ms is not None:
-            kernel_ms.append(float(ms.value))
+        _measured("passage", args, [int(workspace_bytes or 0)], kernel_ms, [_pl(fills)[0], int(grids or 0)])
         return out
 
     def hop(self, jobs, betas, xyz=None, coef=None, planes=None, field=None, slabs=None, sums=None, out=None, words=None,
@@ -1897,41 +1673,19 @@ class Context:
         array, jobs that share outputs --: ``ValueError`` with the library's message.  ``workspace_bytes`` /
         ``kernel_ms`` (a list that receives ``(total, field kernels, slab kernels)`` in ms by HIP events) go through the
         library's measurement entry."""
-        jobs = np.ascontiguousarray(jobs, dtype=HOP_JOB_DTYPE).reshape(-1)
-        b = np.ascontiguousarray(betas, dtype=np.float64).reshape(-1)
-        x = np.zeros((0, 3)) if xyz is None else np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-        c = np.zeros((0, 2)) if coef is None else np.ascontiguousarray(coef, dtype=np.float64).reshape(-1, 2)
-        p = np.zeros((0, 4)) if planes is None else np.ascontiguousarray(planes, dtype=np.float64).reshape(-1, 4)
-        f = np.zeros(0) if field is None else np.ascontiguousarray(field, dtype=np.float64).reshape(-1)
-
-        def result(given, dtype, size, name):
-            if given is None:
-                return np.zeros(max(int(size), 0), dtype=dtype)
-            if given.dtype != dtype or not given.flags.c_contiguous or given.ndim != 1:
-                raise ValueError(f"{name}: a C-contiguous one-dimensional {np.dtype(dtype).name} array")
-            return given
-
-        some = len(jobs) > 0
+        jobs = _rows(jobs, dtype=HOP_JOB_DTYPE)
+        b, x, c = _rows(betas), _rows(xyz, 3, optional=True), _rows(coef, 2, optional=True)
+        p, f = _rows(planes, 4, optional=True), _rows(field, optional=True)
         nz = jobs["nz"].astype(np.int64)
-        slabs = result(slabs, HOP_SLAB_DTYPE, (jobs["slab_first"] + nz).max() if some else 0, "slabs")
-        sums = result(sums, AFFINITY_LEVEL_DTYPE, (jobs["sum_first"] + nz * jobs["n_betas"]).max() if some else 0, "sums")
-        out = result(out, HOP_OUT_DTYPE, jobs["out"].max() + 1 if some else 0, "out")
-        with_words = jobs[jobs["word_first"] >= 0]
-        if words is None and len(with_words):
-            size = (with_words["word_first"] + with_words["ny"].astype(np.int64) * with_words["nz"]).max()
-            words = np.zeros(max(int(size), 0), dtype=np.uint64)
-        elif words is not None:
-            words = result(words, np.uint64, 0, "words")
-        args = [self._h, jobs.ctypes.data, len(jobs), x.ctypes.data, len(x), c.ctypes.data, len(c), p.ctypes.data, len(p),
-                f.ctypes.data, len(f), b.ctypes.data, len(b), slabs.ctypes.data, len(slabs), sums.ctypes.data, len(sums),
-                out.ctypes.data, len(out), None if words is None else words.ctypes.data, 0 if words is None else len(words)]
+        slabs = _result(slabs, HOP_SLAB_DTYPE, "slabs", _furthest(jobs["slab_first"] + nz))
+        sums = _result(sums, AFFINITY_LEVEL_DTYPE, "sums", _furthest(jobs["sum_first"] + nz * jobs["n_betas"]))
+        out = _result(out, HOP_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        words = _result_if_any(words, np.uint64, "words", jobs["word_first"], jobs["ny"].astype(np.int64) * jobs["nz"])
+        args = [self._h] + _pls(jobs, x, c, p, f, b, slabs, sums, out, words)
         if workspace_bytes is None and kernel_ms is None:
             _stat_call("pw_hop", *args)
-            return slabs, sums, out, words
-        ms = (ctypes.c_float * 3)()
-        _stat_call("pw_internal_hop", *args, int(workspace_bytes or 0), ms)
-        if kernel_ms is not None:
-            kernel_ms.append((float(ms[0]), float(ms[1]), float(ms[2])))
+        else:
+            _measured("hop", args, [int(workspace_bytes or 0)], kernel_ms, n_ms=3)
         return slabs, sums, out, words
 
     def circumcircle(self, coordinates, atom_sets):
