@@ -189,8 +189,6 @@ struct ClusterCopy {
     long host, dev, count;
 };
 
-inline unsigned cluster_grid(long blocks, long cap) { return (unsigned)(blocks < 1 ? 1 : blocks < cap ? blocks : cap); }
-
 // workspace_bytes: the budget of a slab of the matrix, and a quarter of the budget of the bit matrices of a launch
 // group (0: CLUSTER_SLAB_BYTES and CLUSTER_BITS_BYTES; at 1 every slab is one row and every job a group of its own);
 // rounds_per_check: count + pick pairs between two looks at the done flags (0: CLUSTER_ROUNDS); kernel_ms: when not
@@ -308,7 +306,8 @@ int cluster_gromos(pw_context* ctx, const pw_cluster_job* jobs, int64_t n_jobs, 
                            d_done, d_centres, d_sizes);
         STAT_TRY(hipGetLastError());
         // (groups follow one another on the stream, so the next one may take the workspace and the slab over; every
-        // kernel strides over its work, so the launch geometry is free)
+        // kernel strides over its work along x -- tests/test_gpu_launch_cap.py sends them round again -- and a group
+        // has a job with a frame, so no count is zero; y is the job)
         for (const ClusterGroup& G : groups) {
             const unsigned count = (unsigned)(G.last - G.first);
             const ClusterJobDev* gj = d_jobs + G.first;
@@ -325,19 +324,19 @@ int cluster_gromos(pw_context* ctx, const pw_cluster_job* jobs, int64_t n_jobs, 
                     const long rows = n - r0 < slab_rows ? n - r0 : slab_rows;
                     STAT_TRY(hipMemcpyAsync(d_slab, dist + mats[m].d_first + r0 * n, sizeof(double) * (size_t)(rows * n),
                                                hipMemcpyHostToDevice, st));
-                    hipLaunchKernelGGL(pw_cluster_pack_kernel, dim3(cluster_grid((rows * S + 3) / 4, 1l << 16), count), dim3(256),
+                    hipLaunchKernelGGL(pw_cluster_pack_kernel, dim3((unsigned)launch_blocks((rows * S + 3) / 4, 1l << 16), count), dim3(256),
                                        0, st, gj, m, d_slab, r0, rows, d_bits);
                     STAT_TRY(hipGetLastError());
                 }
             }
             const long T = cluster_words(G.n_max);
-            hipLaunchKernelGGL(pw_cluster_mirror_kernel, dim3(cluster_grid((T * T + 3) / 4, 1l << 16), count), dim3(256), 0, st,
+            hipLaunchKernelGGL(pw_cluster_mirror_kernel, dim3((unsigned)launch_blocks((T * T + 3) / 4, 1l << 16), count), dim3(256), 0, st,
                                gj, d_bits);
             STAT_TRY(hipGetLastError());
             // a job takes one round a cluster and one more to find no frame active
             for (long queued = 0;;) {
                 for (int r = 0; r < rounds; ++r) {
-                    hipLaunchKernelGGL(pw_cluster_count_kernel, dim3(cluster_grid((G.n_max + 3) / 4, 2048), count), dim3(256), 0,
+                    hipLaunchKernelGGL(pw_cluster_count_kernel, dim3((unsigned)launch_blocks((G.n_max + 3) / 4, 2048), count), dim3(256), 0,
                                        st, gj, d_bits, d_active, d_keys, d_done);
                     STAT_TRY(hipGetLastError());
                     hipLaunchKernelGGL(pw_cluster_pick_kernel, dim3(count), dim3(256), 0, st, gj, d_bits, d_active, d_keys, d_ncl,

@@ -45,8 +45,6 @@ constexpr int COV_PROJ_WAVES = 4;                    // waves of a workgroup of 
 constexpr int COV_PROJ_VECTORS = 8;                  // vectors a wave takes in one pass over a row
 static_assert(COV_TILE == 16 * COV_R && COV_LANES == 2 * COV_TILE && COV_CHUNK % COV_STAGE == 0, "the lane layout");
 
-inline unsigned cov_grid(long blocks) { return (unsigned)(blocks < (1l << 16) ? (blocks < 1 ? 1 : blocks) : (1l << 16)); }
-
 // ws[q * D + a]: the sum of column a over chunk c0 + q
 __global__ void __launch_bounds__(COV_LANES)
 pw_cov_colsum_kernel(const double* __restrict__ x, const double* __restrict__ tr, long T, int D, long c0, long chunks,
@@ -346,14 +344,15 @@ int covariance(pw_context* ctx, const pw_cov_job* jobs, int64_t n_jobs, const do
             STAT_TRY(poison_scratch(poison, d_S, s_bytes, st));
             STAT_TRY(ev.start(st));
             // (launches follow one another on the stream, so the next one may take the workspace over; every kernel
-            // strides over its work, so the launch geometry is free)
+            // strides over its work -- tests/test_gpu_launch_cap.py sends them round again -- and T, D >= 1 and a range
+            // has a chunk and a tile, so no count is zero)
             const long col_blocks = (D + COV_LANES - 1) / COV_LANES;
             for (long c0 = 0; c0 < chunks_all; c0 += mean_range) {
                 const long chunks = std::min(mean_range, chunks_all - c0);
-                hipLaunchKernelGGL(pw_cov_colsum_kernel, dim3(cov_grid(chunks * col_blocks)), dim3(COV_LANES), 0, st, in.x, in.tr,
+                hipLaunchKernelGGL(pw_cov_colsum_kernel, dim3((unsigned)launch_blocks(chunks * col_blocks, 1l << 16)), dim3(COV_LANES), 0, st, in.x, in.tr,
                                    T, (int)D, c0, chunks, d_ws);
                 STAT_TRY(hipGetLastError());
-                hipLaunchKernelGGL(pw_cov_mean_kernel, dim3(cov_grid(col_blocks)), dim3(COV_LANES), 0, st, d_ws, T, (int)D, c0,
+                hipLaunchKernelGGL(pw_cov_mean_kernel, dim3((unsigned)launch_blocks(col_blocks, 1l << 16)), dim3(COV_LANES), 0, st, d_ws, T, (int)D, c0,
                                    chunks, c0 + chunks == chunks_all ? 1 : 0, d_total, d_mean);
                 STAT_TRY(hipGetLastError());
             }
@@ -361,11 +360,11 @@ int covariance(pw_context* ctx, const pw_cov_job* jobs, int64_t n_jobs, const do
                 const long tiles = std::min(slab, tiles_all - tile0);
                 for (long c0 = 0; c0 < chunks_all; c0 += part_range) {
                     const long chunks = std::min(part_range, chunks_all - c0);
-                    hipLaunchKernelGGL(pw_cov_partial_kernel, dim3(cov_grid(chunks * tiles)), dim3(COV_LANES), 0, st, in.x, in.tr,
+                    hipLaunchKernelGGL(pw_cov_partial_kernel, dim3((unsigned)launch_blocks(chunks * tiles, 1l << 16)), dim3(COV_LANES), 0, st, in.x, in.tr,
                                        d_mean, T, (int)D, tile0, tiles, c0, chunks, d_ws);
                     STAT_TRY(hipGetLastError());
-                    hipLaunchKernelGGL(pw_cov_reduce_kernel, dim3(cov_grid(tiles * COV_TILE_DOUBLES / COV_LANES)), dim3(COV_LANES),
-                                       0, st, d_ws, (int)D, tile0, tiles, c0, chunks, d_S);
+                    hipLaunchKernelGGL(pw_cov_reduce_kernel, dim3((unsigned)launch_blocks(tiles * COV_TILE_DOUBLES / COV_LANES, 1l << 16)),
+                                       dim3(COV_LANES), 0, st, d_ws, (int)D, tile0, tiles, c0, chunks, d_S);
                     STAT_TRY(hipGetLastError());
                 }
             }
@@ -434,7 +433,7 @@ int project(pw_context* ctx, const pw_project_job* jobs, int64_t n_jobs, const d
             STAT_TRY(hipMemcpyAsync(d_mean, mean + J.mean_first, sizeof(double) * (size_t)D, hipMemcpyHostToDevice, st));
             STAT_TRY(hipMemcpyAsync(d_V, vectors + J.v_first, sizeof(double) * (size_t)(K * D), hipMemcpyHostToDevice, st));
             STAT_TRY(ev.start(st));
-            hipLaunchKernelGGL(pw_cov_project_kernel, dim3(cov_grid((T + COV_PROJ_WAVES - 1) / COV_PROJ_WAVES)),
+            hipLaunchKernelGGL(pw_cov_project_kernel, dim3((unsigned)launch_blocks((T + COV_PROJ_WAVES - 1) / COV_PROJ_WAVES, 1l << 16)),
                                dim3(64 * COV_PROJ_WAVES), 0, st, in.x, in.tr, d_mean, d_V, T, (int)D, (int)K, d_P);
             STAT_TRY(hipGetLastError());
             STAT_TRY(ev.stop(st));

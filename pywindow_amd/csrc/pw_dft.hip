@@ -259,8 +259,6 @@ void dft_plan(const pw_dft_job* jobs, long n_jobs, long s_lo, long budget, std::
     if (cur.last > cur.first) launches.push_back(cur);
 }
 
-inline unsigned dft_grid(long blocks) { return (unsigned)(blocks < (1l << 20) ? (blocks < 1 ? 1 : blocks) : (1l << 20)); }
-
 // workspace_bytes: the budget of twiddles and partial sums (0: DFT_WORKSPACE_BYTES); kernel_ms: when not null, the
 // time of all kernels of the call by HIP events on the context's stream
 int dft_sums(pw_context* ctx, const pw_dft_job* jobs, int64_t n_jobs, const double* series, double* re, double* im,
@@ -323,16 +321,17 @@ int dft_sums(pw_context* ctx, const pw_dft_job* jobs, int64_t n_jobs, const doub
         STAT_TRY(hipMemcpyAsync(d_x, series + s_lo, sizeof(double) * (size_t)(s_hi - s_lo), hipMemcpyHostToDevice, st));
         STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one may take the workspace over; all three kernels
-        // stride over their work, so the launch geometry is free)
+        // stride over their work -- tests/test_gpu_launch_cap.py sends them round again -- and a launch has a slab, so
+        // none of the three counts is zero)
         for (const DftLaunch& L : launches) {
             const int count = (int)(L.last - L.first);
-            hipLaunchKernelGGL(pw_dft_twiddle_kernel, dim3(dft_grid((L.tw_items + 255) / 256)), dim3(256), 0, st,
+            hipLaunchKernelGGL(pw_dft_twiddle_kernel, dim3((unsigned)launch_blocks((L.tw_items + 255) / 256, 1l << 20)), dim3(256), 0, st,
                                d_slabs + L.first, count, L.tw_items, d_ws);
             STAT_TRY(hipGetLastError());
-            hipLaunchKernelGGL(pw_dft_partial_kernel, dim3(dft_grid(L.items)), dim3(DFT_THREADS), 0, st, d_slabs + L.first,
+            hipLaunchKernelGGL(pw_dft_partial_kernel, dim3((unsigned)launch_blocks(L.items, 1l << 20)), dim3(DFT_THREADS), 0, st, d_slabs + L.first,
                                count, L.items, d_x, d_ws);
             STAT_TRY(hipGetLastError());
-            hipLaunchKernelGGL(pw_dft_reduce_kernel, dim3(dft_grid(L.red_items)), dim3(256), 0, st, d_slabs + L.first, count,
+            hipLaunchKernelGGL(pw_dft_reduce_kernel, dim3((unsigned)launch_blocks(L.red_items, 1l << 20)), dim3(256), 0, st, d_slabs + L.first, count,
                                L.red_items, outs, d_ws, d_out);
             STAT_TRY(hipGetLastError());
         }
@@ -388,7 +387,7 @@ extern "C" int pw_internal_dft_twiddles(pw_context* ctx, int64_t j, int64_t M, c
         STAT_TRY(buf.alloc(&d_k, sizeof(long) * (size_t)n));
         STAT_TRY(buf.alloc(&d_cs, sizeof(double) * (size_t)n * 2));
         STAT_TRY(hipMemcpyAsync(d_k, k, sizeof(long) * (size_t)n, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(pw_dft_phase_kernel, dim3(dft_grid((n + 255) / 256)), dim3(256), 0, st, (long)j, (long)M, d_k,
+        hipLaunchKernelGGL(pw_dft_phase_kernel, dim3((unsigned)launch_blocks((n + 255) / 256, 1l << 20)), dim3(256), 0, st, (long)j, (long)M, d_k,
                            (long)n, d_cs, d_cs + n);
         STAT_TRY(hipGetLastError());
         STAT_TRY(hipMemcpyAsync(c, d_cs, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));

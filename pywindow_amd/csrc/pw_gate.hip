@@ -188,8 +188,6 @@ void gate_plan(const pw_gate_job* jobs, long n_jobs, long s_lo, long d_lo, long 
     if (cur.last > cur.first) launches.push_back(cur);
 }
 
-inline unsigned gate_grid(long blocks) { return (unsigned)(blocks < (1l << 20) ? (blocks < 1 ? 1 : blocks) : (1l << 20)); }
-
 // workspace_bytes: the budget of summaries (0: GATE_WORKSPACE_BYTES); kernel_ms: when not null, the time of all
 // kernels of the call (the zeroing of the result included) by HIP events on the context's stream
 int gate_counts(pw_context* ctx, const pw_gate_job* jobs, int64_t n_jobs, const double* series, const double* thresholds,
@@ -267,13 +265,14 @@ int gate_counts(pw_context* ctx, const pw_gate_job* jobs, int64_t n_jobs, const 
         STAT_TRY(hipMemsetAsync(d_counts, 0, count_bytes, st));
         if (hist_bytes) STAT_TRY(hipMemsetAsync(d_hist, 0, hist_bytes, st));
         // (launches follow one another on the stream, so the next one may take the workspace over; both kernels
-        // stride over their work, so the launch geometry is free)
+        // stride over their work -- tests/test_gpu_launch_cap.py sends them round again -- and a launch has a slab, so
+        // neither count is zero)
         for (const GateLaunch& L : launches) {
             const int count = (int)(L.last - L.first);
-            hipLaunchKernelGGL(pw_gate_chunk_kernel, dim3(gate_grid(L.items)), dim3(GATE_TILE), 0, st, d_slabs + L.first, count,
+            hipLaunchKernelGGL(pw_gate_chunk_kernel, dim3((unsigned)launch_blocks(L.items, 1l << 20)), dim3(GATE_TILE), 0, st, d_slabs + L.first, count,
                                L.items, d_x, d_thr, d_ws, d_counts, d_hist, (long)n_bins);
             STAT_TRY(hipGetLastError());
-            hipLaunchKernelGGL(pw_gate_merge_kernel, dim3(gate_grid((L.lanes + 255) / 256)), dim3(256), 0, st, d_slabs + L.first,
+            hipLaunchKernelGGL(pw_gate_merge_kernel, dim3((unsigned)launch_blocks((L.lanes + 255) / 256, 1l << 20)), dim3(256), 0, st, d_slabs + L.first,
                                count, L.lanes, d_ws, d_counts, d_hist, (long)n_bins);
             STAT_TRY(hipGetLastError());
         }

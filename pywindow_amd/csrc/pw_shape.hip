@@ -9,6 +9,7 @@
 #include "../../include/pywindow_amd.h"
 #include "pw_host.hpp"
 #include "pw_shape.hpp"
+#include "pw_stat_host.hpp"   // (launch_blocks only: this file keeps its own buffers and SH_TRY)
 #include "pw_team.hpp"
 
 using namespace pw;
@@ -96,8 +97,8 @@ extern "C" int pw_shape_batch(pw_context* ctx, const pw_batch_in* in, pw_shape_o
     SH_TRY(hipMemcpyAsync(d_off, in->atom_offset, sizeof(long) * (U + 1), hipMemcpyHostToDevice, st));
     SH_TRY(hipMemcpyAsync(d_xyz, in->xyz, sizeof(double) * 3 * A, hipMemcpyHostToDevice, st));
     SH_TRY(hipMemcpyAsync(d_mass, in->mass, sizeof(double) * (TA > 0 ? TA : A), hipMemcpyHostToDevice, st));
-    long grid = U < 4096 ? U : 4096;
-    hipLaunchKernelGGL(pw_shape_kernel, dim3((unsigned)grid), dim3(SH_WAVES * 64), 0, st, U, d_off, d_xyz, d_mass, d_out,
+    // (the kernel strides over the units -- tests/test_gpu_launch_cap.py sends a workgroup round again -- and U >= 1)
+    hipLaunchKernelGGL(pw_shape_kernel, dim3((unsigned)launch_blocks(U, 4096)), dim3(SH_WAVES * 64), 0, st, U, d_off, d_xyz, d_mass, d_out,
                        TA > 0 ? 0 : 1);
     SH_TRY(hipGetLastError());
     SH_TRY(hipMemcpyAsync(out, d_out, sizeof(pw_shape_out) * U, hipMemcpyDeviceToHost, st));

@@ -34,9 +34,15 @@ inline hipError_t poison_scratch(bool on, void* p, size_t bytes, hipStream_t st)
 }
 
 // The grid of a capped launch: the kernels whose workgroups walk their work items with
-// `for (item = blockIdx.x; item < total; item += gridDim.x)` are launched with min(items, cap) workgroups, `cap` being the
-// launch site's own (65536, or 2^20 for the partial kernels of pw_kde.hip, pw_kdew.hip and pw_corr.hip); the guard for
-// zero items stays with the site.  Plain C++.  Test hook (pw_kde.hip: pw_internal_launch_cap(blocks)): while blocks > 0
+// `for (item = blockIdx.x; item < total; item += gridDim.x)` -- or by wave or by thread, `items` then being the
+// workgroups that would take one turn each -- are launched with min(items, cap) workgroups, `cap` being the launch
+// site's own; the guard for zero items stays with the site.  The caps: 65536 at every site of the grid and crystal
+// entries, at the reduce kernels of pw_kde.hip, pw_kdew.hip and pw_corr.hip, at the probes, at the three kernels of
+// pw_superpose.hip, the five of pw_cov.hip and the pack and mirror kernels of pw_cluster.hip (x; y is the job); 2^20 at
+// the partial kernels of pw_kde.hip, pw_kdew.hip and pw_corr.hip and at every kernel of pw_dft.hip (its phase probe
+// included), pw_gate.hip and pw_trans.hip; 2048 at pw_cluster_count_kernel; 4096 at pw_shape_kernel.  Not through here:
+// the launches of one workgroup a job (pw_cluster_init_kernel, pw_cluster_pick_kernel) and pw_circumcircle_kernel, which
+// do not stride.  Plain C++.  Test hook (pw_kde.hip: pw_internal_launch_cap(blocks)): while blocks > 0
 // every site gets min(items, blocks) instead, so that a batch of a few dozen items sends every workgroup round its loop
 // again -- the second item of a workgroup is otherwise met only beyond the cap -- and 0 gives every site its own cap
 // back.  Off at start; read on the host at the launch site only, never by a kernel or by the host path (device -1).

@@ -164,8 +164,6 @@ pw_superpose_residual_kernel(const SupJobDev* __restrict__ jobs, long count, con
     }
 }
 
-inline unsigned sup_grid(long blocks) { return (unsigned)(blocks < (1l << 16) ? (blocks < 1 ? 1 : blocks) : (1l << 16)); }
-
 // Everything is checked before anything is launched or written.  The entries a call reads are found once, by a
 // difference array over the rows and one over the weights, so that an all-pairs batch -- millions of jobs over a few
 // thousand frames -- is checked in the time of one pass over the arrays and one over the jobs.
@@ -283,17 +281,18 @@ int superpose(pw_context* ctx, const pw_superpose_job* jobs, int64_t n_jobs, con
             STAT_TRY(hipMemcpyAsync(d_w, weights + w_lo, sizeof(double) * (size_t)(w_hi - w_lo), hipMemcpyHostToDevice, st));
         STAT_TRY(ev.start(st));
         // (launches follow one another on the stream, so the next one may take the workspace over; all three kernels
-        // stride over their jobs, so the launch geometry is free)
+        // stride over their jobs -- tests/test_gpu_launch_cap.py sends them round again -- and count >= 1; each launch
+        // asks for its own grid, so that the test hook counts launches)
         for (long first = 0; first < N; first += per) {
             const long count = N - first < per ? N - first : per;
-            const unsigned waves = sup_grid((count + SUP_WAVES - 1) / SUP_WAVES);
-            hipLaunchKernelGGL(pw_superpose_moments_kernel, dim3(waves), dim3(64 * SUP_WAVES), 0, st, d_jobs + first, count,
-                               d_x, d_w, d_ws);
+            const long wave_blocks = (count + SUP_WAVES - 1) / SUP_WAVES;
+            hipLaunchKernelGGL(pw_superpose_moments_kernel, dim3((unsigned)launch_blocks(wave_blocks, 1l << 16)), dim3(64 * SUP_WAVES), 0, st,
+                               d_jobs + first, count, d_x, d_w, d_ws);
             STAT_TRY(hipGetLastError());
-            hipLaunchKernelGGL(pw_superpose_solve_kernel, dim3(sup_grid((count + 63) / 64)), dim3(64), 0, st, count, d_ws);
+            hipLaunchKernelGGL(pw_superpose_solve_kernel, dim3((unsigned)launch_blocks((count + 63) / 64, 1l << 16)), dim3(64), 0, st, count, d_ws);
             STAT_TRY(hipGetLastError());
-            hipLaunchKernelGGL(pw_superpose_residual_kernel, dim3(waves), dim3(64 * SUP_WAVES), 0, st, d_jobs + first, count,
-                               d_x, d_w, d_ws, d_out + first);
+            hipLaunchKernelGGL(pw_superpose_residual_kernel, dim3((unsigned)launch_blocks(wave_blocks, 1l << 16)), dim3(64 * SUP_WAVES), 0, st,
+                               d_jobs + first, count, d_x, d_w, d_ws, d_out + first);
             STAT_TRY(hipGetLastError());
         }
         STAT_TRY(ev.stop(st));

@@ -248,17 +248,15 @@ void trans_plan(const pw_trans_job* jobs, long n_jobs, long s_lo, long e_lo, lon
     if (cur.last > cur.first) launches.push_back(cur);
 }
 
-inline unsigned trans_grid(long blocks) { return (unsigned)(blocks < (1l << 20) ? (blocks < 1 ? 1 : blocks) : (1l << 20)); }
-
 template <int P, int BI>
 hipError_t trans_launch(const TransLaunch& L, const TransSlabDev* d_slabs, const double* d_x, const double* d_e, unsigned* d_ws,
                         long* d_counts, int S, hipStream_t st) {
     const int count = (int)(L.last - L.first);
-    hipLaunchKernelGGL((pw_trans_pack_kernel<P>), dim3(trans_grid((L.waves + 3) / 4)), dim3(256), 0, st, d_slabs + L.first, count,
+    hipLaunchKernelGGL((pw_trans_pack_kernel<P>), dim3((unsigned)launch_blocks((L.waves + 3) / 4, 1l << 20)), dim3(256), 0, st, d_slabs + L.first, count,
                        L.waves, d_x, d_e, d_ws);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((pw_trans_count_kernel<P, BI>), dim3(trans_grid(L.items)), dim3(TRANS_TILE), 0, st, d_slabs + L.first,
+    hipLaunchKernelGGL((pw_trans_count_kernel<P, BI>), dim3((unsigned)launch_blocks(L.items, 1l << 20)), dim3(TRANS_TILE), 0, st, d_slabs + L.first,
                        count, L.items, d_ws, d_counts, S);
     return hipGetLastError();
 }
@@ -352,7 +350,8 @@ int trans_counts(pw_context* ctx, const pw_trans_job* jobs, int64_t n_jobs, cons
         STAT_TRY(ev.start(st));
         STAT_TRY(hipMemsetAsync(d_counts, 0, count_bytes, st));
         // (launches follow one another on the stream, so the next one may take the workspace over; both kernels
-        // stride over their work, so the launch geometry is free)
+        // stride over their work -- tests/test_gpu_launch_cap.py sends them round again -- and a launch has a job with
+        // a term and a lag, so neither count is zero)
         for (const TransLaunch& L : launches) {
             hipError_t e = P == 2   ? trans_launch<2, trans_block(2)>(L, d_slabs, d_x, d_e, d_ws, d_counts, S, st)
                            : P == 4 ? trans_launch<4, trans_block(4)>(L, d_slabs, d_x, d_e, d_ws, d_counts, S, st)

@@ -12,18 +12,31 @@ a barrier -- follows its opposite at least once.  Every entry is built from its 
 C.first_difference); tile sizes come from the sources (`_stat_edges.constant`).
 
 `Entry.kernels` lists the capped kernels the batch launches, one name a launch of its one launch group: the hook's
-counter must reach their number at every cap, since every one of them has at least 2 x 5 items."""
+counter must reach their number at every cap, since every one of them has at least 2 x 5 items.
+
+The second half of the file has the trajectory entries (`TrajEntry`: pw_trans_counts, pw_superpose, pw_cluster_gromos,
+pw_covariance, pw_project; `Shape`; the sweeps of pw_dft_sums and pw_gate_counts through `STAT_ENTRIES`), whose kernels
+stride by workgroup, by wave or by thread behind caps of their own, and the two batches that pass a real cap with the
+hook off (8200 frames, 4 x 65536 + 5 projected rows)."""
 import functools
+import itertools
 
 import numpy as np
 
 import _affinity_cases as A
 import _basins_cases as BA
+import _cluster_cases as CL
+import _cov_cases as CV
+import _dft_cases as DF
+import _gate_cases as GA
 import _hop_cases as HO
 import _passage_cases as PA
 import _percolation_cases as PC
 import _rigid_cases as R
+import _shape_cases as SH
 import _stat_edges as S
+import _superpose_cases as SU
+import _trans_cases as TR
 
 CAPS = (1, 2, 3, 5)
 STAT_CAPS = (1, 3)
@@ -538,10 +551,12 @@ class ChargesCell(Charges):
 
 
 # ---- the statistical entries that clamp a grid: the edge batch of tests/test_gpu_stat_edges.py ----------------------------
-STAT_ENTRIES = tuple(e for e in S.ENTRIES if e.name in ("kde", "kde2", "kdew", "corr"))
-#: the capped kernels of one launch of each (partial, reduce)
+STAT_ENTRIES = S.ENTRIES                                             # (kde, kde2, kdew, corr, dft and gate with 0 and 5 bins)
+#: the capped kernels of one launch of each (partial, reduce; dft: twiddle, partial, reduce; gate: chunk, merge)
 STAT_KERNELS = {"kde": ("pw_kde_partial_kernel", "pw_kde_reduce_kernel"), "kde2": ("pw_kde2_partial_kernel", "pw_kde2_reduce_kernel"),
-                "kdew": ("pw_kdew_partial_kernel", "pw_kdew_reduce_kernel"), "corr": ("pw_corr_partial_kernel", "pw_corr_reduce_kernel")}
+                "kdew": ("pw_kdew_partial_kernel", "pw_kdew_reduce_kernel"), "corr": ("pw_corr_partial_kernel", "pw_corr_reduce_kernel"),
+                "dft": ("pw_dft_twiddle_kernel", "pw_dft_partial_kernel", "pw_dft_reduce_kernel")}
+STAT_KERNELS.update({e.name: ("pw_gate_chunk_kernel", "pw_gate_merge_kernel") for e in S.ENTRIES if e.name.startswith("gate")})
 
 
 GRID_ENTRIES = (Affinity(), Passage(), Hop(), Percolation(), Basins(), Rigid(), RigidCell(), RigidCellEwald(), Charges(), ChargesCell())
@@ -557,3 +572,541 @@ def past_the_cap_jobs():
     d = (3, 2, 2)
     jobs.append(A.Case("the-17th", d, *A.shell_atoms(5, d, 1.0, 999), words=A.words_with(d, 7, 998), betas=(0.4, 1.0), edges=(-0.5, 0.5)))
     return jobs
+
+
+# ---- the trajectory entries: pw_dft_sums, pw_gate_counts, pw_trans_counts, pw_superpose, pw_cluster_gromos,
+# ---- pw_covariance, pw_project, pw_shape_batch ------------------------------------------------------------------------------
+# Their kernels stride by workgroup, by wave or by thread; `items` is what the launch site hands to launch_blocks: the
+# workgroups that would take one turn each.  Where an entry makes several launches of a kernel, `items` is the LARGEST of
+# them -- the launch the batch is built for -- and `properties` says what lies next to what inside it.
+def budget_constant(name: str, source: str) -> int:
+    """A workspace budget written as `<a>l << <b>` in the sources."""
+    import re
+
+    from _util import ROOT
+
+    m = re.search(rf"constexpr long {name} = (\d+)l? << (\d+)", (ROOT / "pywindow_amd" / "csrc" / source).read_text())
+    return int(m.group(1)) << int(m.group(2))
+
+
+def ceil_div(a, b):
+    return -(-int(a) // int(b))
+
+
+def dft_launches(rec):
+    """pw_dft.hip: dft_plan at the default budget -- [(workgroups of the twiddle kernel, items of the partial kernel, items
+    of the reduce kernel)] a launch."""
+    k = S.dft_constants()
+    C, T, GC = k["C"], k["W"] * k["F"], k["GW"] * k["WC"]
+    RF = S.constant("DFT_RED_FREQS", "pw_dft.hip")
+    budget = budget_constant("DFT_WORKSPACE_BYTES", "pw_dft.hpp") // 16
+    launches, cur = [], None
+    for J in rec:
+        n, nf = int(J["n"]), int(J["n_freq"])
+        if n == 0 or nf == 0:
+            continue
+        chunks = ceil_div(n, C)
+        each = C + chunks
+        slab = nf if each <= budget // nf else max(budget // each // T * T, T)
+        for q0 in range(0, nf, slab):
+            m = min(nf - q0, slab)
+            if cur is not None and cur[0] + each * m > budget:
+                launches.append(cur)
+                cur = None
+            cur = cur or [0, 0, 0, 0]
+            cur[0] += each * m
+            cur[1] += C * m
+            cur[2] += ceil_div(m, T) * ceil_div(chunks, GC)
+            cur[3] += ceil_div(m, RF)
+    if cur is not None:
+        launches.append(cur)
+    return [(ceil_div(tw, 256), items, red) for _, tw, items, red in launches]
+
+
+def gate_launches(rec):
+    """pw_gate.hip: gate_plan at the default budget -- [(items of the chunk kernel, workgroups of the merge kernel)]."""
+    C, T = GA.CHUNK, GA.TILE
+    budget = budget_constant("GATE_WORKSPACE_BYTES", "pw_gate.hpp") // 4
+    launches, cur = [], None
+    for J in rec:
+        n, nt = int(J["n"]), int(J["n_thr"])
+        if n == 0 or nt == 0:
+            continue
+        chunks = ceil_div(n, C)
+        slab = nt if chunks <= budget // nt else max(budget // chunks // T * T, T)
+        for q0 in range(0, nt, slab):
+            m = min(nt - q0, slab)
+            if cur is not None and cur[0] + chunks * m > budget:
+                launches.append(cur)
+                cur = None
+            cur = cur or [0, 0, 0]
+            cur[0] += chunks * m
+            cur[1] += ceil_div(m, T) * chunks
+            cur[2] += m
+    if cur is not None:
+        launches.append(cur)
+    return [(items, ceil_div(lanes, 256)) for _, items, lanes in launches]
+
+
+def stat_items(entry, packed):
+    """{kernel: the fewest work items of a launch of it} for the sweeps of pw_dft_sums and pw_gate_counts, which are one
+    launch each at the default budget (asserted by tests/test_launch_cap.py)."""
+    launches = dft_launches(packed[0]) if entry.name == "dft" else gate_launches(packed[0])
+    return len(launches), {k: min(l[i] for l in launches) for i, k in enumerate(STAT_KERNELS[entry.name])}
+
+
+#: the arguments of the twiddle hook (pw_dft_phase_kernel, thread-strided, 256 a workgroup): more than 2 x 256 x 5, not a
+#: multiple of 256, with the edge arguments of _dft_cases.twiddle_cases among them
+def twiddle_batch():
+    rng = np.random.default_rng(41)
+    j, period, k = DF.twiddle_cases()[-3]
+    count = 2 * 256 * max(CAPS) + 77
+    return j, period, np.concatenate([k, rng.integers(0, 1 << 32, count - len(k))]).astype(np.int64)
+
+
+class TrajEntry:
+    """One trajectory entry under the hook.  `packed()` the batch with rows nobody owns; `run(ctx, packed, budget)` -> a
+    tuple of arrays (a failure raises); `untouched(got)` whether the rows nobody owns still hold the sentinel;
+    `exact(got)` whether the independent exact reference holds (None: the entry has none); `items`, `properties` as for
+    the grid entries.  `budgets`: the workspace budgets the batch runs at (None: the entry's default), the first with every
+    kernel of `kernels` cut, the others with at least `cut_small` launches cut."""
+    caps = CAPS
+    budgets = (None,)
+    cut_small = 1
+
+    def same(self, got, want):
+        return S.same(got, want)
+
+    def exact(self, got):
+        return None
+
+
+def host_context():
+    from pywindow_amd import _lib
+
+    return _lib.Context(-1, host_threads=4)
+
+
+# ---- pw_trans_counts ------------------------------------------------------------------------------------------------------
+def trans_instance(n_states):
+    """pw_trans.hpp: trans_padded and pw_trans.hip: trans_block -- (P, BI) of the instance a call of n_states runs."""
+    P = 2 if n_states <= 2 else 4 if n_states <= 4 else 8 if n_states <= 8 else 16
+    return P, (4 if P == 16 else P)
+
+
+def trans_work(rec, n_states):
+    """pw_trans_count_kernel's work items of one launch in order, as (job, chunk, tile, block of origin states, skipped,
+    in_lds, wn, lanes): the restatement of the kernel's own arithmetic."""
+    CW, WINW, TILE = TR.CHUNK // 32, TR.WINDOW // 32, TR.TILE
+    _, BI = trans_instance(n_states)
+    nob = ceil_div(n_states, BI)
+    out = []
+    for q, J in enumerate(rec):
+        n, nl, first, step = int(J["n"]), int(J["n_lags"]), int(J["lag_first"]), int(J["lag_step"])
+        if n == 0 or nl == 0:
+            continue
+        nw = ceil_div(n, 32)
+        for ch in range(ceil_div(nw, CW)):
+            for tile in range(ceil_div(nl, TILE)):
+                for b in range(nob):
+                    wn = min(nw - ch * CW, CW)
+                    lanes = min(nl - tile * TILE, TILE)
+                    k_lo = first + tile * TILE * step
+                    k_hi = min(first + (tile * TILE + lanes - 1) * step, n)
+                    skipped = k_lo >= n
+                    out.append((q, ch, tile, b, skipped, (not skipped) and wn + (k_hi >> 5) - (k_lo >> 5) + 1 <= WINW, wn, lanes))
+    return out
+
+
+class Trans(TrajEntry):
+    """One call of pw_trans_counts at one n_states: A, a chunk and a word with 40 lags (idle lanes, the window in LDS);
+    B, two chunks and a word with TILE lags FAR_STEP apart -- the window does not fit LDS in the two full chunks and does
+    in the short last one --; B2, the same series with fewer edges and one lag more: its tile 1 is skipped (every lag
+    >= n) between worked items; D, a chunk and a word with TILE + 3 lags (a full tile, then idle lanes; a full chunk after
+    B2's short one); E, 40 entries (less than a wave of the pack kernel after jobs of many)."""
+    def __init__(self, n_states):
+        self.n_states = n_states
+        self.name = f"pw_trans_counts-{n_states}-states"
+        P, BI = trans_instance(n_states)
+        self.kernels = (f"pw_trans_pack_kernel<{P}>", f"pw_trans_count_kernel<{P}, {BI}>")
+
+    @functools.lru_cache(maxsize=None)
+    def jobs(self):
+        S_ = self.n_states
+        mid, long, short = TR.noise(TR.CHUNK + 1, 8), TR.noise(2 * TR.CHUNK + 1, 7), TR.noise(40, 9)
+        full, fewer = TR.edges_for(S_ - 1), TR.edges_for(max(S_ - 2, 0))
+        return [(mid, full, (0, 1, 40)), (long, full, (3, TR.FAR_STEP, TR.TILE)), (long, fewer, (3, TR.FAR_STEP, TR.TILE + 1)),
+                (mid, full, (0, 1, TR.TILE + 3)), (short, full, (2, 3, 5))]
+
+    @functools.lru_cache(maxsize=None)
+    def packed(self):
+        return TR.pack(self.jobs(), hole=1)
+
+    def run(self, ctx, packed, budget=None):
+        rc, counts = TR.raw_counts(ctx, *packed, self.n_states, workspace_bytes=budget)
+        assert rc == 0
+        return (counts,)
+
+    def owned(self, packed):
+        rec = packed[0]
+        return S._spans(int((rec["out_first"] + rec["n_lags"]).max()), rec["out_first"], rec["n_lags"])
+
+    def untouched(self, got):
+        return bool((got[0][~self.owned(self.packed())] == TR.SENTINEL).all())
+
+    def exact(self, got):
+        return bool(np.array_equal(got[0][self.owned(self.packed())], TR.reference_rows(self.jobs(), self.n_states)))
+
+    def items(self, packed):
+        rec = packed[0]
+        waves = sum(ceil_div(int(n), 32) // 2 + 1 for n in rec["n"])
+        return {self.kernels[0]: ceil_div(waves, 4), self.kernels[1]: len(trans_work(rec, self.n_states))}
+
+    def properties(self, packed):
+        rec = packed[0]
+        work = trans_work(rec, self.n_states)
+        CW, TILE = TR.CHUNK // 32, TR.TILE
+        lds = [(w[5], not w[4] and not w[5]) for w in work]          # (in LDS, worked from global memory)
+        skip = [w[4] for w in work]
+        wn = [None if w[4] else w[6] for w in work]
+        lanes = [None if w[4] else w[7] for w in work]
+        return {
+            "a window that does not fit LDS follows one that does": follows(lds, lambda a: a[0], lambda b: b[1]),
+            "a window in LDS follows one that does not fit": follows(lds, lambda a: a[1], lambda b: b[0]),
+            "a skipped tile between two worked ones": "wsw" in "".join(k for k, _ in itertools.groupby("s" if v else "w" for v in skip)),
+            "a short last chunk follows a full one": follows([v for v in wn if v], lambda a: a == CW, lambda b: b < CW),
+            "a full chunk follows a short one": follows([v for v in wn if v], lambda a: a < CW, lambda b: b == CW),
+            "a tile with idle lanes follows a full tile": follows([v for v in lanes if v], lambda a: a == TILE, lambda b: b < TILE),
+            "jobs of other n_edges follow each other": any(a != b for a, b in zip(rec["n_edges"][:-1], rec["n_edges"][1:])),
+            "the pack kernel: n < 64 after a job of several waves": follows(rec["n"].tolist(), lambda a: a > 4 * 64, lambda b: b < 64),
+        }
+
+
+TRANS_STATES = (2, 4, 5, 16)                                         # P = 2, 4, 8, 16
+
+
+# ---- pw_superpose -----------------------------------------------------------------------------------------------------------
+class Superpose(TrajEntry):
+    """391 jobs (6 x 64 + 7: no multiple of SUP_WAVES or of 64) that cycle through the case list of _superpose_cases --
+    every size of SIZES, unsorted, weighted next to unweighted, the degenerate cases (identical, mirror image, collinear,
+    planar, by 180 degrees) beside the random ones in every 64 consecutive jobs -- with `random n=1` moved behind
+    `random n=4097`.  Caps 1 and 3: the solve kernel takes 64 jobs a workgroup, so that 2 x 5 workgroups of it would be
+    more than 576 jobs where seven workgroups show the same second turn.  Runs again with a workspace of 100 jobs: four
+    launches of each kernel."""
+    name = "pw_superpose"
+    caps = STAT_CAPS
+    kernels = ("pw_superpose_moments_kernel", "pw_superpose_solve_kernel", "pw_superpose_residual_kernel")
+    COUNT = 391
+
+    @property
+    def budgets(self):
+        return (0, 100 * S.constant("SUP_MOMENT_FIELDS", "pw_superpose.hpp") * 8 + 100 * S.constant("SUP_SOLVE_FIELDS", "pw_superpose.hpp") * 8)
+
+    cut_small = 2 * 4                                                # (four launches of the two wave-a-job kernels; the solve kernel's have two workgroups' worth)
+
+    @functools.lru_cache(maxsize=None)
+    def names(self):
+        names = [c[0] for c in SU.cases()]
+        names.remove("random n=1")
+        names.insert(names.index(f"random n={max(SU.SIZES)}") + 1, "random n=1")
+        return [names[k % len(names)] for k in range(self.COUNT)]
+
+    @functools.lru_cache(maxsize=None)
+    def jobs(self):
+        by_name = {c[0]: c[1:] for c in SU.cases()}
+        return [by_name[n] for n in self.names()]
+
+    @functools.lru_cache(maxsize=None)
+    def packed(self):
+        return SU.pack(self.jobs(), hole=1)
+
+    def run(self, ctx, packed, budget=None):
+        rc, rows = SU.raw(ctx, *packed, workspace_bytes=budget)
+        assert rc == 0
+        return (rows,)
+
+    def same(self, got, want):
+        return SU.same_bytes(got[0], want[0])
+
+    def untouched(self, got):
+        rec = self.packed()[0]
+        mask = np.ones(len(got[0]), dtype=bool)
+        mask[rec["out"]] = False
+        return bool(SU.untouched(got[0][mask]).all()) and int(mask.sum()) == len(rec)
+
+    def items(self, packed):
+        count = len(packed[0])
+        waves = S.constant("SUP_WAVES", "pw_superpose.hip")
+        return {self.kernels[0]: ceil_div(count, waves), self.kernels[1]: ceil_div(count, 64), self.kernels[2]: ceil_div(count, waves)}
+
+    def properties(self, packed):
+        rec = packed[0]
+        n, weighted = rec["n"].tolist(), (rec["weight_first"] >= 0).tolist()
+        sweeps = self.run(host_context(), packed)[0]["sweeps"][rec["out"]]
+        degenerate = [any(w in name for w in ("identical", "mirror", "collinear", "planar", "180 degrees")) for name in self.names()]
+        groups = [slice(g, g + 64) for g in range(0, len(rec), 64)]
+        return {
+            "no multiple of SUP_WAVES or of 64": len(rec) % S.constant("SUP_WAVES", "pw_superpose.hip") != 0 and len(rec) % 64 != 0,
+            "a weighted job follows an unweighted one": follows(weighted, lambda a: not a, lambda b: b),
+            "an unweighted job follows a weighted one": follows(weighted, lambda a: a, lambda b: not b),
+            "n = 1 follows the largest": follows(n, lambda a: a == max(SU.SIZES), lambda b: b == 1),
+            "every size, unsorted": set(SU.SIZES) <= set(n) and n != sorted(n) and n != sorted(n, reverse=True),
+            "a degenerate job beside others in every workgroup of the solve kernel": all(any(degenerate[g]) and not all(degenerate[g]) for g in groups),
+            "sweeps differ within every workgroup of the solve kernel": all(int(sweeps[g].max()) > int(sweeps[g].min()) for g in groups),
+        }
+
+
+# ---- pw_cluster_gromos ----------------------------------------------------------------------------------------------------------
+class Cluster(TrajEntry):
+    """Seven jobs in one launch group (jobs lie on blockIdx.y, the x grid is sized by the largest): n = 65; a 257-frame
+    matrix at a middling cutoff; n = 1025, the largest, neither first nor last; the 257-frame matrix again at the cutoff
+    that makes one cluster (done after one round; the pack kernel returns for it when the other matrices are packed);
+    n = 129 with every frame a cluster of its own (130 rounds while the others return on done[]; four words a row for
+    three that hold frames); n = 3; n = 64.  The number handed to launch_blocks is that of the launch for the largest job."""
+    name = "pw_cluster_gromos"
+    kernels = ("pw_cluster_pack_kernel", "pw_cluster_mirror_kernel", "pw_cluster_count_kernel")
+
+    @functools.lru_cache(maxsize=None)
+    def jobs(self):
+        by_name = {c[0]: c[1:] for c in CL.cases()}
+        shared = by_name["n=257-middling"][0]
+        return [by_name["n=65-middling"], (shared, by_name["n=257-middling"][1]), by_name["n=1025-middling"],
+                (shared, by_name["n=257-one-cluster"][1]), by_name["n=129-all-singletons"], by_name["n=3-middling"], by_name["n=64-middling"]]
+
+    @functools.lru_cache(maxsize=None)
+    def packed(self):
+        return CL.pack(self.jobs(), hole=1)
+
+    def run(self, ctx, packed, budget=None):
+        rc, out = CL.raw(ctx, *packed, workspace_bytes=budget)
+        assert rc == 0
+        return out
+
+    def same(self, got, want):
+        return CL.same(got, want)
+
+    def untouched(self, got):
+        rec = self.packed()[0]
+        mask = ~S._spans(len(got[0]), rec["out_first"], rec["n"])
+        return int(mask.sum()) == len(rec) and all(bool((a[mask] == CL.SENTINEL).all()) for a in got[:3])
+
+    def exact(self, got):
+        return CL.same(got, CL.expected(self.jobs(), hole=1))
+
+    def items(self, packed):
+        n = int(packed[0]["n"].max())
+        words = ceil_div(n, 64)
+        stride = (words + 1) & ~1
+        assert 8 * n * n <= budget_constant("CLUSTER_SLAB_BYTES", "pw_cluster.hpp")   # (the largest matrix is one slab)
+        return {self.kernels[0]: ceil_div(n * stride, 4), self.kernels[1]: ceil_div(words * words, 4), self.kernels[2]: ceil_div(n, 4)}
+
+    def properties(self, packed):
+        rec = packed[0]
+        n, first = rec["n"].tolist(), rec["d_first"].tolist()
+        found = CL.expected(self.jobs(), hole=1)[3].tolist()
+        words = sum(v * ((ceil_div(v, 64) + 1) & ~1) for v in n)
+        return {
+            "one launch group": 8 * words <= budget_constant("CLUSTER_BITS_BYTES", "pw_cluster.hpp"),
+            "jobs of different n, the largest neither first nor last": len(set(n)) >= 5 and 0 < n.index(max(n)) < len(n) - 1,
+            "sizes from NS up to 1025": set(n) <= set(CL.NS) and max(n) == 1025,
+            "two jobs share a matrix at different cutoffs beside a job on another": any(
+                first[a] == first[c] and first[b] != first[a] and rec["cutoff"][a] != rec["cutoff"][c]
+                for a, b, c in zip(range(len(n) - 2), range(1, len(n) - 1), range(2, len(n)))),
+            "a job done after one round beside the all-singletons job": follows(list(zip(n, found)), lambda a: a[1] == 1 and a[0] > 1,
+                                                                                lambda b: b[1] == b[0] and b[0] > 64),
+            "a row padded by a word": any(((ceil_div(v, 64) + 1) & ~1) > ceil_div(v, 64) for v in n),
+            "every job but the smallest has frames for a second turn of a wave at cap 1": sum(v > 4 for v in n) >= len(n) - 1,
+        }
+
+
+PAST_THE_CAP_FRAMES = 8200
+PAST_THE_CAP_CENTRE = 8195
+
+
+def past_the_cap_cluster():
+    """(the job record, the matrix): the distances of 8200 points on a line (broadcast from 1-D: no (n, n, k)
+    intermediate) at the cutoff 1.0 -- four tight groups in shuffled order at 0, 1.5, 10 and 20, each one clique and none
+    a neighbour of another, and frame PAST_THE_CAP_CENTRE = 8195 at 0.75, a neighbour of the first two groups and so
+    the frame with the most neighbours: the first centre is a row that a wave of workgroup 0 meets on its second turn,
+    larger than the `best` it carries from its first, and in the later rounds that row is inactive.  Three clusters:
+    three rounds and one more.  540 MB of doubles: the caller builds it once, hands it on as it is and frees it."""
+    from pywindow_amd import _lib
+
+    rng = np.random.default_rng(8200)
+    n = PAST_THE_CAP_FRAMES
+    x = np.array([0.0, 1.5, 10.0, 20.0])[rng.integers(0, 4, n)] + rng.uniform(-0.05, 0.05, n)
+    x[PAST_THE_CAP_CENTRE] = 0.75
+    d = x[:, None] - x[None, :]
+    np.abs(d, out=d)
+    rec = np.zeros(1, dtype=_lib.CLUSTER_JOB_DTYPE)
+    rec[0] = (0, n, 1.0, 0)
+    return rec, d
+
+
+# ---- pw_covariance and pw_project ------------------------------------------------------------------------------------------------
+def cov_tiles(D):
+    """pw_cov.hpp: cov_tile_of -- the tiles on or above the diagonal, row-major."""
+    nt = ceil_div(D, CV.TILE)
+    return [(a, b) for a in range(nt) for b in range(a, nt)]
+
+
+class Covariance(TrajEntry):
+    """Four jobs, each with launches of its own.  0: T = 2 CHUNK + 5, D = 2 TILE + 1 -- three chunks, the last of 5 rows
+    (fewer than COV_STAGE) after full ones, and six tiles of which (0, 2) has one live column after the live (0, 1) and
+    before the diagonal (1, 1): 18 items of the partial kernel.  1: moved, T = CHUNK + 1, D = 2 TILE - 1 (just under whole
+    tiles).  2: the mean only, D = 2305 on two chunks: ten workgroups' worth of the mean kernel, twenty items of the
+    column-sum kernel.  3: moved, T = 40, D = 3.  Runs again at a budget of two tiles of partials (the reduce kernel's
+    c0 != 0 under the cap) and of one byte (every range one chunk, one tile: c0 != 0 in the mean kernel too)."""
+    name = "pw_covariance"
+    kernels = ("pw_cov_colsum_kernel", "pw_cov_mean_kernel", "pw_cov_partial_kernel", "pw_cov_reduce_kernel")
+    cut_small = 1
+
+    @property
+    def budgets(self):
+        return (None, 2 * 8 * CV.TILE * CV.TILE, 1)
+
+    @functools.lru_cache(maxsize=None)
+    def jobs(self):
+        rng = np.random.default_rng(1207)
+        shapes = [(2 * CV.CHUNK + 5, 2 * CV.TILE + 1, False, True), (CV.CHUNK + 1, 2 * CV.TILE - 1, True, True),
+                  (CV.CHUNK + 3, 9 * 256 + 1, False, False), (40, 3, True, True)]
+        return [(np.ascontiguousarray(2.0 * rng.standard_normal((T, D)) + rng.uniform(-5, 5, D)), CV.transforms(rng, T) if mv else None, sc)
+                for T, D, mv, sc in shapes]
+
+    @functools.lru_cache(maxsize=None)
+    def packed(self):
+        return CV.pack(self.jobs(), hole=1)
+
+    def run(self, ctx, packed, budget=None):
+        jobs, data, tr, mean, scatter, _ = packed
+        mean, scatter = mean.copy(), scatter.copy()
+        ctx.covariance(jobs, data, tr, mean=mean, scatter=scatter, workspace_bytes=budget)
+        return mean, scatter
+
+    def untouched(self, got):
+        spans = self.packed()[5]
+        m = ~CV.owned(len(got[0]), [s[0] for s in spans])
+        s = ~CV.owned(len(got[1]), [s[1] for s in spans])
+        return bool(CV.untouched(got[0][m]).all() and CV.untouched(got[1][s]).all()) and int(m.sum()) == len(spans) + 1
+
+    def items(self, packed):
+        rec = packed[0]
+        lanes = S.constant("COV_LANES", "pw_cov.hip")
+        chunks = [ceil_div(T, CV.CHUNK) for T in rec["T"]]
+        tiles = [len(cov_tiles(D)) if s >= 0 else 0 for D, s in zip(rec["D"], rec["s_first"])]
+        return {self.kernels[0]: max(c * ceil_div(D, lanes) for c, D in zip(chunks, rec["D"])),
+                self.kernels[1]: max(ceil_div(D, lanes) for D in rec["D"]),
+                self.kernels[2]: max(c * t for c, t in zip(chunks, tiles)),
+                self.kernels[3]: max(t * CV.TILE * CV.TILE // lanes for t in tiles)}
+
+    def properties(self, packed):
+        rec = packed[0]
+        stage = S.constant("COV_STAGE", "pw_cov.hip")
+        T, D = int(rec["T"][0]), int(rec["D"][0])
+        tiles = cov_tiles(D)
+        dead = [(a + 1) * CV.TILE > D or (b + 1) * CV.TILE > D for a, b in tiles]
+        budget = budget_constant("COV_WORKSPACE_BYTES", "pw_cov.hpp") // 8
+        return {
+            "job 0 is one launch of the partial kernel at the default budget": ceil_div(T, CV.CHUNK) * len(tiles) * CV.TILE * CV.TILE <= budget and rec["s_first"][0] >= 0,
+            "D just over and just under whole tiles": any(d % CV.TILE == 1 for d in rec["D"]) and any(d % CV.TILE == CV.TILE - 1 for d in rec["D"]),
+            "a tile with dead columns follows a live one": follows(dead, lambda a: not a, lambda b: b),
+            "a live tile follows one with dead columns": follows(dead, lambda a: a, lambda b: not b),
+            "a diagonal tile follows an off-diagonal one": follows(tiles, lambda a: a[0] != a[1], lambda b: b[0] == b[1]),
+            "a last chunk shorter than COV_STAGE rows after full chunks": T > 2 * CV.CHUNK and 0 < T % CV.CHUNK < stage,
+            "with and without transforms": {True, False} <= set((rec["transform_first"] >= 0).tolist()),
+            "with and without the scatter matrix": {True, False} <= set((rec["s_first"] >= 0).tolist()),
+        }
+
+
+class Project(TrajEntry):
+    """Four jobs, a launch each: k = 1, 8 and 9 (a second pass of COV_PROJ_VECTORS) and T = 41, 43, 42 and 45 rows -- no
+    multiple of COV_PROJ_WAVES, eleven workgroups' worth and more -- with and without transforms, D = 3 .. 129."""
+    name = "pw_project"
+    kernels = ("pw_cov_project_kernel",)
+
+    @functools.lru_cache(maxsize=None)
+    def jobs(self):
+        rng = np.random.default_rng(1208)
+        out = []
+        for T, D, mv, k in ((41, CV.TILE + 1, False, 9), (43, 3, True, 1), (42, 2 * 63, True, 8), (45, 65, False, 9)):
+            V = rng.standard_normal((k, D))
+            out.append((np.ascontiguousarray(rng.standard_normal((T, D))), CV.transforms(rng, T) if mv else None, rng.standard_normal(D),
+                        V / np.linalg.norm(V, axis=1, keepdims=True)))
+        return out
+
+    def packed(self):
+        return tuple(self.jobs())
+
+    def run(self, ctx, packed, budget=None):
+        return (CV.project_batch(ctx, list(packed), hole=1)[1],)
+
+    def spans(self):
+        at, out = 0, []
+        for X, _, _, V in self.jobs():
+            out.append(slice(at + 1, at + 1 + len(X) * len(V)))
+            at = out[-1].stop
+        return out
+
+    def untouched(self, got):
+        mask = ~CV.owned(len(got[0]), self.spans())
+        return int(mask.sum()) == len(self.jobs()) + 1 and bool(CV.untouched(got[0][mask]).all())
+
+    def items(self, packed):
+        return {self.kernels[0]: max(ceil_div(len(X), S.constant("COV_PROJ_WAVES", "pw_cov.hip")) for X, _, _, _ in packed)}
+
+    def properties(self, packed):
+        waves, vectors = S.constant("COV_PROJ_WAVES", "pw_cov.hip"), S.constant("COV_PROJ_VECTORS", "pw_cov.hip")
+        ks = [len(V) for _, _, _, V in packed]
+        return {
+            "k of 1, COV_PROJ_VECTORS and one more": {1, vectors, vectors + 1} <= set(ks),
+            "no T is a multiple of COV_PROJ_WAVES": all(len(X) % waves != 0 for X, _, _, _ in packed),
+            "every launch has the items": all(ceil_div(len(X), waves) >= MIN_ITEMS for X, _, _, _ in packed),
+            "with and without transforms": {True, False} <= {tr is not None for _, tr, _, _ in packed},
+        }
+
+
+PAST_THE_CAP_ROWS = 4 * 65536 + 5
+
+
+def past_the_cap_projection():
+    """pw_project past its real cap: T = 4 x 65536 + 5 rows of D = 3 on k = 2 vectors -- 65538 workgroups' worth."""
+    rng = np.random.default_rng(65536)
+    V = rng.standard_normal((2, 3))
+    return [(np.ascontiguousarray(rng.standard_normal((PAST_THE_CAP_ROWS, 3))), None, rng.standard_normal(3), V / np.linalg.norm(V, axis=1, keepdims=True))]
+
+
+# ---- pw_shape_batch (no host path: the reference is the host build of pw_shape.hpp, as in tests/test_gpu_shape.py) ----------------
+class Shape:
+    """Twelve of the edge units of _shape_cases in an order where a unit of one, two or three 8192-term buffers (90, 91
+    and 127 .. 129 atoms: the leaf tables of ShapeScratch for a whole buffer and for the tail) is followed by a unit of
+    one, two or three atoms and back: ShapeScratch is reused.  The units of 8191 atoms and more fill the same tables and
+    cost the one-thread host reference seconds each: they stay with tests/test_gpu_shape.py."""
+    name = "pw_shape_batch"
+    caps = CAPS
+    kernels = ("pw_shape_kernel",)
+    ORDER = (129, 1, 129, 2, 128, 3, 127, 1, 91, 2, 90, 1)
+
+    @functools.lru_cache(maxsize=None)
+    def jobs(self):
+        return [SH.sized_molecule(n) for n in self.ORDER]
+
+    @functools.lru_cache(maxsize=None)
+    def packed(self):
+        return SH.pack(self.jobs())
+
+    def items(self, packed):
+        return {self.kernels[0]: len(packed[0]) - 1}
+
+    def properties(self, packed):
+        n = np.diff(packed[0]).tolist()
+        return {
+            "only sizes of _shape_cases.SIZES": set(n) <= set(SH.SIZES),
+            "a one-atom unit follows the largest": follows(n, lambda a: a == max(n) and a * a > 2 * 8192, lambda b: b == 1),
+            "a unit of three buffers follows a one-atom unit": follows(n, lambda a: a == 1, lambda b: b * b > 2 * 8192),
+            "units of one, two and three buffers": {1, 2, 3} <= {-(-a * a // 8192) for a in n},
+            "units of at most three atoms and of 90 and more in turn": all((a <= 3) != (b <= 3) for a, b in zip(n[:-1], n[1:])),
+        }
+
+
+TRAJ_ENTRIES = tuple(Trans(s) for s in TRANS_STATES) + (Superpose(), Cluster(), Covariance(), Project())
+SHAPE = Shape()
