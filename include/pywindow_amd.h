@@ -1189,6 +1189,47 @@ int pw_rigid_affinity(pw_context *ctx, const pw_rigid_job *jobs, int64_t n_jobs,
                       int64_t n_dirs, const uint64_t *words, int64_t n_words, const double *betas, int64_t n_betas,
                       double *maps, int64_t n_maps, pw_affinity_level *levels, int64_t n_levels, pw_rigid_out *out,
                       int64_t n_out);
+/* ---- rigid non-linear guests (H2O, CH4, SF6): pose tables ---------------------------------------------------------
+ * pw_rigid_affinity for a guest that is a rigid body, not a line.  The text of record is
+ * pywindow_amd/csrc/pw_rigid_body.hpp; in short, job k is a pw_rigid_affinity job without offsets and directions.  It
+ * carries a pose table instead: M * S rows of three doubles poses[pose_first .. + n_dirs*n_sites), M = n_dirs,
+ * S = n_sites, 1 <= M <= PW_RIGID_MAX_DIRS, 1 <= S <= PW_RIGID_MAX_SITES; row o*S + s is the displacement of site s
+ * from the guest's centre in pose o, every component finite with |component| <= 16.  The rows are data: nothing
+ * orthogonalises, checks or rotates them.
+ * POSE (v, o).  Site s sits at px = x + p.x, likewise py and pz: one rounded sum a coordinate.  Everything after that
+ * -- the pair term, charged or not, BLOCKED, COUNTS, the per-site accumulators, WEIGHT, VOXEL, SUMS and what is written
+ * -- is pw_rigid_affinity's word for word; min_dir of the row of out is the pose index o.
+ * With the table p = (t_s * dx, t_s * dy, t_s * dz), one rounded product each, every output is pw_rigid_affinity's
+ * bytes for the offsets t and the directions d.  The same bytes on every device, launch geometry and run and on a
+ * device == -1 context.
+ * All pointers are host memory; n_pose_rows is the rows of poses (three doubles), the other counts are
+ * pw_rigid_affinity's.  Refused (PW_E_BAD_ARG, pw_last_error reads "pw_rigid_body_affinity: job k: ..." and names
+ * the later of two jobs that share; nothing is launched or written): what pw_rigid_affinity refuses of the fields the
+ * two share, poses outside their array, and a pose component that is not finite or beyond 16. */
+typedef struct pw_rigid_body_job {
+    int64_t atom_first, n;          /* atoms = xyz[atom_first .. +n), n >= 0 */
+    int64_t coef_first;             /* rows (A, B, C) = coef[coef_first .. + n_sites*n), row s*n + a */
+    int64_t word_first;             /* the region = words[word_first .. + ny*nz), or -1: every voxel */
+    int64_t beta_first, n_betas;    /* betas[beta_first .. +n_betas) */
+    int64_t pose_first;             /* poses[pose_first .. + n_dirs*n_sites), rows of three, row o*n_sites + s */
+    int64_t n_sites, n_dirs;        /* S and M */
+    int64_t level_first;            /* levels[level_first .. +n_betas) is written */
+    int64_t map_first;              /* maps[map_first .. + 2*V) is written when map_level >= 0 */
+    int64_t out;                    /* the job's row of out */
+    double  origin[3];              /* the centre of voxel (0, 0, 0) */
+    double  spacing;                /* h > 0 */
+    double  core2;                  /* >= 1e-6 */
+    double  cutoff2;                /* 0.0: none; otherwise > core2 */
+    int32_t nx, ny, nz;             /* 1 .. PW_CAVITY_MAX_G */
+    int32_t charged;                /* 0 or 1 */
+    int32_t map_level;              /* -1: no map; otherwise the beta whose zbar is written */
+    int32_t reserved;               /* padding to a multiple of 8 bytes; not read */
+} pw_rigid_body_job;
+int pw_rigid_body_affinity(pw_context *ctx, const pw_rigid_body_job *jobs, int64_t n_jobs, const double *xyz,
+                           int64_t n_points, const double *coef, int64_t n_coef, const double *poses,
+                           int64_t n_pose_rows, const uint64_t *words, int64_t n_words, const double *betas,
+                           int64_t n_betas, double *maps, int64_t n_maps, pw_affinity_level *levels, int64_t n_levels,
+                           pw_rigid_out *out, int64_t n_out);
 /* ---- rigid linear guests in a crystal: the orientation-averaged Boltzmann factor over a periodic cell --------------
  * pw_rigid_affinity's pose, weight and fold at every voxel of the skewed grid of a periodic cell, so that the free energy
  * -ln(zbar) / beta of a rigid guest's centre can feed pw_percolation and pw_basins as a caller's field.  The reference

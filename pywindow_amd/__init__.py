@@ -43,6 +43,15 @@ from .rigid import (  # noqa: E402
     rigid_guest_affinity,
     rigid_guest_affinity_batch,
 )
+from .rigid_body import (  # noqa: E402
+    RIGID_BODIES,
+    RIGID_BODY_MASSES,
+    RigidBody,
+    body_poses,
+    rigid_body_affinity,
+    rigid_body_affinity_batch,
+    rotation_set,
+)
 from .charges import QEQ_PARAMETERS, Charges, equilibrate_charges, equilibrate_charges_batch  # noqa: E402
 from .channels import Channels, channel_network, channel_network_batch  # noqa: E402
 from .passage import Passage, guest_passage, guest_passage_batch, passage_field  # noqa: E402
@@ -139,6 +148,13 @@ __all__ = [
     "rigid_coefficients",
     "rigid_guest_affinity",
     "rigid_guest_affinity_batch",
+    "RIGID_BODIES",
+    "RIGID_BODY_MASSES",
+    "RigidBody",
+    "body_poses",
+    "rotation_set",
+    "rigid_body_affinity",
+    "rigid_body_affinity_batch",
     "QEQ_PARAMETERS",
     "Charges",
     "equilibrate_charges",

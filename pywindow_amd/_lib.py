@@ -352,6 +352,17 @@ assert RIGID_JOB_DTYPE.itemsize == 176 and RIGID_OUT_DTYPE.itemsize == 56
 RIGID_MAX_SITES = 8
 RIGID_MAX_DIRS = 1024
 
+#: numpy mirror of ``pw_rigid_body_job``; the result rows are ``RIGID_OUT_DTYPE`` and ``AFFINITY_LEVEL_DTYPE``
+RIGID_BODY_JOB_DTYPE = np.dtype(
+    [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("word_first", np.int64),
+     ("beta_first", np.int64), ("n_betas", np.int64), ("pose_first", np.int64), ("n_sites", np.int64), ("n_dirs", np.int64),
+     ("level_first", np.int64), ("map_first", np.int64), ("out", np.int64),
+     ("origin", np.float64, (3,)), ("spacing", np.float64), ("core2", np.float64), ("cutoff2", np.float64),
+     ("nx", np.int32), ("ny", np.int32), ("nz", np.int32), ("charged", np.int32), ("map_level", np.int32),
+     ("reserved", np.int32)]
+)
+assert RIGID_BODY_JOB_DTYPE.itemsize == 168
+
 #: numpy mirror of ``pw_rigid_cell_job``; the result rows are ``RIGID_OUT_DTYPE`` and ``AFFINITY_LEVEL_DTYPE``
 RIGID_CELL_JOB_DTYPE = np.dtype(
     [("atom_first", np.int64), ("n", np.int64), ("coef_first", np.int64), ("beta_first", np.int64), ("n_betas", np.int64),
@@ -600,6 +611,7 @@ EXPORTED_SYMBOLS = [
     "pw_passage",
     "pw_hop",
     "pw_rigid_affinity",
+    "pw_rigid_body_affinity",
     "pw_rigid_cell",
     "pw_rigid_cell_ewald",
     "pw_charges",
@@ -736,7 +748,8 @@ def load():
     open_words, counters, pair_counts = [vp, vp, i64, i64, fp], [i64, fp, vp, vp], [i64, fp, vp, ctypes.c_int, vp]
     for name, n, tail in (("covariance", 4, [i64, fp]), ("project", 5, [fp]), ("cavity", 5, open_words),
                           ("pore_sizes", 7, open_words), ("affinity", 9, [i64, fp]), ("passage", 5, [i64, fp, vp, ctypes.c_int]),
-                          ("hop", 9, [i64, fp]), ("rigid_affinity", 9, [i64, fp]), ("rigid_cell", 8, pair_counts),
+                          ("hop", 9, [i64, fp]), ("rigid_affinity", 9, [i64, fp]), ("rigid_body_affinity", 8, [i64, fp]),
+                          ("rigid_cell", 8, pair_counts),
                           ("rigid_cell_ewald", 11, pair_counts), ("channels", 6, open_words), ("percolation", 6, counters),
                           ("basins", 8, counters)):
         getattr(L, "pw_" + name).argtypes = [vp, vp, i64] + [vp, i64] * n
@@ -1424,6 +1437,26 @@ class Context:
             _stat_call("pw_rigid_affinity", *args)
         else:
             _measured("rigid_affinity", args, [int(workspace_bytes or 0)], kernel_ms)
+        return out, levels, maps
+
+    def rigid_body_affinity(self, jobs, xyz, coef, poses, betas, words=None, out=None, levels=None, maps=None,
+                            workspace_bytes=None, kernel_ms=None):
+        """``pw_rigid_body_affinity``: :meth:`rigid_affinity` for a guest that is a rigid body
+        (``RIGID_BODY_JOB_DTYPE`` records): instead of offsets and directions the jobs index the rows of ``poses`` (rows of
+        three), ``n_dirs * n_sites`` a job from its ``pose_first``, row ``o * n_sites + s`` the displacement of site ``s``
+        from the guest's centre in pose ``o``.  The rows are data.  The results, the refusals (``ValueError`` with the
+        library's message) and the measurement arguments are :meth:`rigid_affinity`'s."""
+        jobs = _rows(jobs, dtype=RIGID_BODY_JOB_DTYPE)
+        x, c, p, b = _rows(xyz, 3), _rows(coef, 3), _rows(poses, 3), _rows(betas)
+        w = _rows(words, dtype=np.uint64, optional=True)
+        out = _result(out, RIGID_OUT_DTYPE, "out", _furthest(jobs["out"] + 1))
+        levels = _result(levels, AFFINITY_LEVEL_DTYPE, "levels", _furthest(jobs["level_first"] + jobs["n_betas"]))
+        maps = _result(maps, np.float64, "maps", 0)
+        args = [self._h] + _pls(jobs, x, c, p, w, b, maps, levels, out)
+        if workspace_bytes is None and kernel_ms is None:
+            _stat_call("pw_rigid_body_affinity", *args)
+        else:
+            _measured("rigid_body_affinity", args, [int(workspace_bytes or 0)], kernel_ms)
         return out, levels, maps
 
     def _rigid_cell(self, name, jobs, cell, inputs, out, levels, maps, workspace_bytes, kernel_ms, diagnostics, skip):

@@ -14,7 +14,7 @@ import sys
 PKG = pathlib.Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 OUT = PKG / "libpywindow_hip.so"
-SOURCES = ["pw_kernels.hip", "pw_kernels_big.hip", "pw_rebuild.hip", "pw_shape.hip", "pw_kde.hip", "pw_kdew.hip", "pw_corr.hip", "pw_dft.hip", "pw_gate.hip", "pw_trans.hip", "pw_superpose.hip", "pw_cluster.hip", "pw_cov.hip", "pw_cavity.hip", "pw_sasa.hip", "pw_pores.hip", "pw_affinity.hip", "pw_rigid.hip", "pw_rigid_cell.hip", "pw_ewald.hip", "pw_passage.hip", "pw_hop.hip", "pw_charges.hip", "pw_charges_cell.hip", "pw_channels.hip", "pw_percolate.hip", "pw_basins.hip", "pw_lb_probe.hip", "pw_history.cpp", "pw_hostpath.cpp"]
+SOURCES = ["pw_kernels.hip", "pw_kernels_big.hip", "pw_rebuild.hip", "pw_shape.hip", "pw_kde.hip", "pw_kdew.hip", "pw_corr.hip", "pw_dft.hip", "pw_gate.hip", "pw_trans.hip", "pw_superpose.hip", "pw_cluster.hip", "pw_cov.hip", "pw_cavity.hip", "pw_sasa.hip", "pw_pores.hip", "pw_affinity.hip", "pw_rigid.hip", "pw_rigid_body.hip", "pw_rigid_cell.hip", "pw_ewald.hip", "pw_passage.hip", "pw_hop.hip", "pw_charges.hip", "pw_charges_cell.hip", "pw_channels.hip", "pw_percolate.hip", "pw_basins.hip", "pw_lb_probe.hip", "pw_history.cpp", "pw_hostpath.cpp"]
 # -ffp-contract=off: the numerical core relies on explicit fma() only (pw_common.hpp)
 
 

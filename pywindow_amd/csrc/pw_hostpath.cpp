@@ -21,6 +21,7 @@
 #include "pw_cov.hpp"
 #include "pw_affinity.hpp"
 #include "pw_rigid.hpp"
+#include "pw_rigid_body.hpp"
 #include "pw_rigid_cell.hpp"
 #include "pw_ewald.hpp"
 #include "pw_cavity.hpp"
@@ -1145,17 +1146,19 @@ extern "C" int pw_hostpath_affinity(const pw_affinity_job* jobs, long n_jobs, co
 // device == -1 contexts here): the site position, the charged pair term and the fold over the orientations of
 // pw_rigid.hpp on the pair term, the tests, the weight, the chunk tree and the search of a rank's voxel of
 // pw_affinity.hpp.  The threads share out (job, chunk) pieces, each of which leaves the partial of pw_rigid.hpp; then one
-// ordered reduce a job.
-extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const long* voxels, const double* xyz,
-                                 const double* coef, const double* offsets, const double* dirs,
-                                 const unsigned long long* words, const double* betas, double* maps,
-                                 pw_affinity_level* levels, pw_rigid_out* out, int threads) {
+// ordered reduce a job.  pw_rigid_body_affinity (pw_rigid_body.hip) is the same walk with the site position read from
+// the job's pose table (pw_rigid_body.hpp), so both entries go through rigid_on_host: `site(J, o, s, x, y, z, px, py,
+// pz)` places site s of pose o of job J at the voxel centre (x, y, z).
+template <class Job, class Site>
+static int rigid_on_host(const Job* jobs, long n_jobs, const long* voxels, const double* xyz, const double* coef,
+                         const unsigned long long* words, const double* betas, double* maps, pw_affinity_level* levels,
+                         pw_rigid_out* out, int threads, Site site) {
     typedef cavity_word u64;
     struct Plan { long piece_first, part_first, prefix_first; };
     std::vector<Plan> plan((size_t)n_jobs + 1);
     long pieces = 0, part_words = 0, prefix_ints = 0;
     for (long k = 0; k < n_jobs; ++k) {
-        const pw_rigid_job& J = jobs[k];
+        const Job& J = jobs[k];
         plan[k] = Plan{pieces, part_words, prefix_ints};
         const long chunks = (voxels[k] + AFF_CHUNK - 1) / AFF_CHUNK;
         pieces += chunks;
@@ -1166,7 +1169,7 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
     std::vector<u64> part((size_t)part_words);
     std::vector<int> prefix((size_t)prefix_ints);
     for (long k = 0; k < n_jobs; ++k) {
-        const pw_rigid_job& J = jobs[k];
+        const Job& J = jobs[k];
         if (J.word_first < 0) continue;
         int* p = prefix.data() + plan[k].prefix_first;
         const int rows = J.ny * J.nz;
@@ -1174,7 +1177,7 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
         for (int r = 0; r < rows; ++r) p[r + 1] = p[r] + cavity_popcount(words[(long)J.word_first + r] & cavity_row_mask(J.nx));
     }
     auto voxel_of = [&](long k, long rank, int& i, int& row) {
-        const pw_rigid_job& J = jobs[k];
+        const Job& J = jobs[k];
         const u64* w = J.word_first >= 0 ? words + (long)J.word_first : nullptr;
         const int* p = prefix.data() + plan[k].prefix_first;
         aff_voxel(rank, J.word_first >= 0, J.nx, J.ny * J.nz, [&](int r) { return w[r]; }, [&](int r) { return p[r]; }, i, row);
@@ -1185,14 +1188,12 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
             const long mid = (k + hi) / 2;
             if (plan[mid].piece_first <= piece) k = mid; else hi = mid;
         }
-        const pw_rigid_job& J = jobs[k];
+        const Job& J = jobs[k];
         const int L = (int)J.n_betas, S = (int)J.n_sites, M = (int)J.n_dirs, stride = rigid_part_words(L);
         const long chunk = piece - plan[k].piece_first, V = voxels[k], n = (long)J.n;
         const bool charged = J.charged != 0;
         const double* atoms = xyz + 3 * (long)J.atom_first;
         const double* abc = coef + 3 * (long)J.coef_first;
-        const double* ts = offsets + (long)J.site_first;
-        const double* dd = dirs + 3 * (long)J.dir_first;
         const double inv_M = rigid_inv(M);
         double slot_z[AFF_MAX_LEVELS][AFF_CHUNK], slot_e[AFF_MAX_LEVELS][AFF_CHUNK];
         double m = aff_inf();
@@ -1213,8 +1214,8 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
                 bool blocked = false;
                 double U = 0.0;
                 for (int s = 0; s < S && !blocked; ++s) {
-                    const double px = rigid_site(x, ts[s], dd[3 * o]), py = rigid_site(y, ts[s], dd[3 * o + 1]),
-                                 pz = rigid_site(z, ts[s], dd[3 * o + 2]);
+                    double px, py, pz;
+                    site(J, o, s, x, y, z, px, py, pz);
                     const double* rows = abc + 3 * (long)s * n;
                     double Us = 0.0;
                     for (long a = 0; a < n && !blocked; ++a) {
@@ -1262,7 +1263,7 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
         P[2 * L + 5] = clamped ? (u64)AFF_CLAMPED : 0ull;
     });
     host_share(n_jobs, threads, [&](long k) {
-        const pw_rigid_job& J = jobs[k];
+        const Job& J = jobs[k];
         const int L = (int)J.n_betas, stride = rigid_part_words(L);
         const long chunks = plan[k + 1].piece_first - plan[k].piece_first;
         const u64* P = part.data() + plan[k].part_first;
@@ -1297,6 +1298,33 @@ extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const lo
         out[(long)J.out] = o;
     });
     return PW_OK;
+}
+
+extern "C" int pw_hostpath_rigid(const pw_rigid_job* jobs, long n_jobs, const long* voxels, const double* xyz,
+                                 const double* coef, const double* offsets, const double* dirs,
+                                 const unsigned long long* words, const double* betas, double* maps,
+                                 pw_affinity_level* levels, pw_rigid_out* out, int threads) {
+    return rigid_on_host(jobs, n_jobs, voxels, xyz, coef, words, betas, maps, levels, out, threads,
+                         [&](const pw_rigid_job& J, int o, int s, double x, double y, double z, double& px, double& py, double& pz) {
+                             const double t = offsets[(long)J.site_first + s];
+                             const double* d = dirs + 3 * ((long)J.dir_first + o);
+                             px = rigid_site(x, t, d[0]);
+                             py = rigid_site(y, t, d[1]);
+                             pz = rigid_site(z, t, d[2]);
+                         });
+}
+
+extern "C" int pw_hostpath_rigid_body(const pw_rigid_body_job* jobs, long n_jobs, const long* voxels, const double* xyz,
+                                      const double* coef, const double* poses, const unsigned long long* words,
+                                      const double* betas, double* maps, pw_affinity_level* levels, pw_rigid_out* out,
+                                      int threads) {
+    return rigid_on_host(jobs, n_jobs, voxels, xyz, coef, words, betas, maps, levels, out, threads,
+                         [&](const pw_rigid_body_job& J, int o, int s, double x, double y, double z, double& px, double& py, double& pz) {
+                             const double* p = poses + 3 * ((long)J.pose_first + (long)o * (long)J.n_sites + s);
+                             px = rigid_body_site(x, p[0]);
+                             py = rigid_body_site(y, p[1]);
+                             pz = rigid_body_site(z, p[2]);
+                         });
 }
 
 // pw_rigid_cell on the host (pw_rigid_cell.hip checks the arguments and sends device == -1 contexts here): the pose, the

@@ -288,7 +288,7 @@ class Molecule:
         return af
 
     def calculate_rigid_guest_affinity(self, guest="CO2", temperature: float = 298.0, spacing: float = 0.5, close="windows",
-                                       directions=None, charges=None, device=None):
+                                       directions=None, charges=None, device=None, rotations=None):
         """How strongly the cage holds a rigid linear guest -- N2, CO2, O2 -- averaged over its orientations
         (``pywindow_amd.rigid_guest_affinity``, on the GPU): the guest's centre at every voxel of the cavity of
         ``calculate_cavity(probe=0)`` -- seeded, boxed and closed as in :meth:`calculate_guest_affinity` --, in every
@@ -300,18 +300,30 @@ class Molecule:
         ``properties["rigid_guest_affinity"]``: ``guest``, ``temperature``, ``boltzmann_volume``, ``henry``,
         ``mean_energy``, ``heat``, ``min_energy``, ``min_position``, ``min_direction``, ``closed``, ``spacing``;
         ``self.rigid_affinity`` keeps the :class:`pywindow_amd.RigidAffinity`, which is returned.  ``full_analysis``
-        does not call it."""
+        does not call it.  A rigid body -- a name of ``pywindow_amd.RIGID_BODIES`` (H2O, CH4, SF6) or a
+        :class:`pywindow_amd.RigidBody` -- goes through ``pywindow_amd.rigid_body_affinity`` instead, averaged over
+        ``rotations`` (``None``: ``pywindow_amd.rotation_set()``); the properties then also hold ``min_rotation``."""
         from . import rigid as RG
+        from . import rigid_body as RB
 
+        body = RB.is_body(guest)
+        if (directions is not None and body) or (rotations is not None and not body):
+            raise ValueError("calculate_rigid_guest_affinity: directions for a linear guest, rotations for a rigid body")
         self.calculate_cavity(probe=0.0, spacing=spacing, close=close, device=device, mask=True)
-        af = RG.rigid_guest_affinity(self.coordinates, self.elements, guest, [temperature], cavity=self.cavity,
-                                     directions=directions, charges=charges, core2=0.25, device=device)
+        if body:
+            af = RB.rigid_body_affinity(self.coordinates, self.elements, guest, [temperature], cavity=self.cavity,
+                                        rotations=rotations, charges=charges, core2=0.25, device=device)
+        else:
+            af = RG.rigid_guest_affinity(self.coordinates, self.elements, guest, [temperature], cavity=self.cavity,
+                                         directions=directions, charges=charges, core2=0.25, device=device)
         self.rigid_affinity = af
         self.properties["rigid_guest_affinity"] = {
             "guest": guest, "temperature": float(temperature), "boltzmann_volume": float(af.boltzmann_volume[0]),
             "henry": float(af.henry[0]), "mean_energy": float(af.mean_energy[0]), "heat": float(af.heat[0]),
             "min_energy": float(af.min_energy), "min_position": af.min_position, "min_direction": af.min_direction,
             "closed": bool(af.closed), "spacing": float(spacing)}
+        if body:
+            self.properties["rigid_guest_affinity"]["min_rotation"] = af.min_rotation
         return af
 
     def calculate_charges(self, total_charge: float = 0.0, device=None):

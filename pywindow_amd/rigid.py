@@ -11,7 +11,8 @@ the device and the explicit host path (``device=-1``) return the same bytes.  Fr
 ``boltzmann_volume``, ``henry``, ``mean_energy``, ``heat``, ``min_energy`` with its position and direction, and
 ``selectivity`` -- "CO2 over N2?".
 
-What is left out.  Linear guests only (all sites on one axis).  No guest-guest term: infinite dilution.  The bundled
+What is left out.  This module's guests are linear (all sites on one axis); rigid bodies -- H2O, CH4, SF6 -- are
+:mod:`pywindow_amd.rigid_body`, which returns the same :class:`RigidAffinity`.  No guest-guest term: infinite dilution.  The bundled
 cage model (UFF) carries no partial charges, so without ``charges`` the job is uncharged and the guest's own charges do
 nothing; ``charges`` are the caller's, one set for all frames or one a frame, or ``"qeq"``: the library equilibrates them
 itself, frame by frame (:mod:`pywindow_amd.charges`).  Passage and hopping of a rigid guest go through
@@ -71,14 +72,16 @@ RIGID_GUESTS = {
 _SERIES = ("boltzmann_volume", "henry", "mean_energy", "heat", "min_energy", "n_voxels", "n_dead")
 
 
-def _guest(guest) -> RigidGuest:
-    return guest if isinstance(guest, RigidGuest) else RIGID_GUESTS[guest]
+def _guest(guest):
+    """The model of a guest: a name of ``RIGID_GUESTS``, or a model as it is (a :class:`RigidGuest`, or a
+    :class:`pywindow_amd.RigidBody`, which has the same ``sigma``, ``eps_k`` and ``charges``)."""
+    return RIGID_GUESTS[guest] if isinstance(guest, str) else guest
 
 
 def rigid_coefficients(elements, guest, charges=None) -> np.ndarray:
-    """Rows ``(A, B, C)`` ``(S, n, 3)`` between every site of ``guest`` (a name of ``RIGID_GUESTS`` or a
-    :class:`RigidGuest`) and every framework atom: ``A = 4 eps sigma^12`` and ``B = 4 eps sigma^6`` from UFF,
-    Lorentz-Berthelot mixed as :func:`pywindow_amd.lj_coefficients` does (a site with ``eps = 0`` gets ``A = B = 0``; it
+    """Rows ``(A, B, C)`` ``(S, n, 3)`` between every site of ``guest`` (a name of ``RIGID_GUESTS``, a
+    :class:`RigidGuest` or a :class:`pywindow_amd.RigidBody`) and every framework atom: ``A = 4 eps sigma^12`` and
+    ``B = 4 eps sigma^6`` from UFF, Lorentz-Berthelot mixed as :func:`pywindow_amd.lj_coefficients` does (a site with ``eps = 0`` gets ``A = B = 0``; it
     still blocks within the core), and ``C = COULOMB q_a q_s`` with ``charges`` the ``(n,)`` framework charges in e.
     With ``charges=None`` the column is zero and a job made from the rows is uncharged: the guest's charges do
     nothing, because the bundled cage model carries no charges.  ``charges`` ``(F, n)``, one row a frame, gives
@@ -87,14 +90,14 @@ def rigid_coefficients(elements, guest, charges=None) -> np.ndarray:
     if charges is not None and np.ndim(charges) == 2:
         per_frame = np.asarray(charges, dtype=np.float64)
         return np.stack([rigid_coefficients(elements, guest, row) for row in per_frame]) if len(per_frame) else \
-            np.zeros((0, len(_guest(guest).offsets), len(list(elements)), 3))
+            np.zeros((0, len(_guest(guest).sigma), len(list(elements)), 3))
     g = _guest(guest)
     rows = np.array([UFF[str(e).upper()] for e in elements], dtype=np.float64).reshape(-1, 2)
     n = len(rows)
     q = np.zeros(n) if charges is None else np.asarray(charges, dtype=np.float64).reshape(-1)
     if len(q) != n:
         raise ValueError("charges: one per atom")
-    out = np.zeros((len(g.offsets), n, 3))
+    out = np.zeros((len(g.sigma), n, 3))
     for s, (sigma_s, eps_k, q_s) in enumerate(zip(g.sigma, g.eps_k, g.charges)):
         sigma = (rows[:, 0] / 2.0 ** (1.0 / 6.0) + float(sigma_s)) / 2.0
         eps = np.sqrt(4.184 * rows[:, 1] * (R * float(eps_k)))
@@ -127,6 +130,8 @@ class RigidAffinity:
     charged: bool = False
     frames: np.ndarray | None = None
     charges_converged: object = None      # with charges="qeq": whether the frame's charge equilibration converged
+    rotations: object = None              # of a rigid body (pywindow_amd.rigid_body): the (M, 3, 3) rotations of its poses
+    poses: object = None                  # of a rigid body: the (M, S, 3) displacements of the sites, pose by pose
 
     @property
     def n_voxels(self):
@@ -185,6 +190,26 @@ class RigidAffinity:
         d = self.directions[np.maximum(o, 0)]
         return np.where((o < 0)[..., None], np.nan, d)
 
+    @property
+    def min_rotation(self):
+        """The rotation ``(3, 3)`` of the pose of ``min_energy`` of a rigid body; NaN without one, and for a result that
+        has no ``rotations``."""
+        o = np.asarray(self.raw["min_dir"])
+        if self.rotations is None:
+            return np.full(o.shape + (3, 3), np.nan)
+        return np.where((o < 0)[..., None, None], np.nan, np.asarray(self.rotations)[np.maximum(o, 0)])
+
+    @property
+    def min_sites(self):
+        """The positions ``(S, 3)`` of the guest's sites in the pose of ``min_energy``, for looking at it; NaN without
+        one."""
+        o = np.asarray(self.raw["min_dir"])
+        if self.poses is not None:
+            p = np.asarray(self.poses)[np.maximum(o, 0)]
+        else:
+            p = np.asarray(self.guest.offsets, dtype=np.float64)[:, None] * self.directions[np.maximum(o, 0)][..., None, :]
+        return np.where((o < 0)[..., None, None], np.nan, self.min_position[..., None, :] + p)
+
     def selectivity(self, other):
         """The ratio of this guest's Henry coefficient to ``other``'s, a :class:`RigidAffinity` or an
         :class:`pywindow_amd.Affinity` (same frames, region and temperatures)."""
@@ -238,12 +263,24 @@ def rigid_guest_affinity_batch(xyz, elements_or_coef, guest, temperatures, cavit
     (:func:`pywindow_amd.equilibrate_charges_batch`, total charge 0), and a frame whose charges did not converge is not
     valid in :meth:`RigidAffinity.series`.  ``kernel_ms``: a list that receives the time of the device work by HIP
     events."""
+    d = sphere_directions(M_DEFAULT) if directions is None else np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
+    if not 1 <= len(d) <= _lib.RIGID_MAX_DIRS:
+        raise ValueError(f"directions: 1 .. {_lib.RIGID_MAX_DIRS} rows of three")
+    return _batch(xyz, elements_or_coef, _guest(guest), temperatures, cavity, grid, d, None, None, charges, maps, level, core2,
+                  cutoff2, device, frames, kernel_ms)
+
+
+def _batch(xyz, elements_or_coef, g, temperatures, cavity, grid, d, poses, rotations, charges, maps, level, core2, cutoff2,
+           device, frames, kernel_ms) -> RigidAffinity:
+    """What :func:`rigid_guest_affinity_batch` and :func:`pywindow_amd.rigid_body_affinity_batch` share: the coefficient
+    rows, the charges, the jobs over the cavities or the grid, the call and the result.  ``poses`` ``None``: the linear
+    guest ``g`` in the directions ``d`` through ``pw_rigid_affinity``; otherwise the ``(M, S, 3)`` pose table of the
+    body ``g`` through ``pw_rigid_body_affinity``, with ``d`` and ``rotations`` kept for the result."""
     x = np.ascontiguousarray(xyz, dtype=np.float64)
     if x.ndim != 3 or x.shape[2] != 3:
         raise ValueError("xyz: (T, n, 3)")
     T, n = x.shape[:2]
-    g = _guest(guest)
-    S = len(g.offsets)
+    S = len(g.sigma)
     charges_converged = None
     coef = np.asarray(elements_or_coef)
     if coef.dtype.kind in "fiu" and coef.ndim == 3 and coef.shape[2] == 3:
@@ -268,21 +305,18 @@ def rigid_guest_affinity_batch(xyz, elements_or_coef, guest, temperatures, cavit
     temps = np.atleast_1d(np.asarray(temperatures, dtype=np.float64))
     if temps.ndim != 1 or not 1 <= len(temps) <= _lib.AFF_MAX_LEVELS or not (np.isfinite(temps) & (temps > 0.0)).all():
         raise ValueError(f"temperatures: 1 .. {_lib.AFF_MAX_LEVELS} positive numbers")
-    d = sphere_directions(M_DEFAULT) if directions is None else np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
-    if not 1 <= len(d) <= _lib.RIGID_MAX_DIRS:
-        raise ValueError(f"directions: 1 .. {_lib.RIGID_MAX_DIRS} rows of three")
     if maps and not 0 <= int(level) < len(temps):
         raise ValueError("level: one of the temperatures")
     if (cavity is None) == (grid is None):
         raise ValueError("one of cavity and grid")
-    jobs = np.zeros(T, dtype=_lib.RIGID_JOB_DTYPE)
+    jobs = np.zeros(T, dtype=_lib.RIGID_JOB_DTYPE if poses is None else _lib.RIGID_BODY_JOB_DTYPE)
     jobs["atom_first"] = np.arange(T) * n
     if per_frame_coef:
         jobs["coef_first"] = np.arange(T) * (S * n)
     jobs["n"] = n
     jobs["n_betas"] = len(temps)
     jobs["n_sites"] = S
-    jobs["n_dirs"] = len(d)
+    jobs["n_dirs"] = len(d) if poses is None else len(poses)
     jobs["level_first"] = np.arange(T) * len(temps)
     jobs["out"] = np.arange(T)
     jobs["core2"], jobs["cutoff2"] = float(core2), float(cutoff2)
@@ -315,14 +349,28 @@ def rigid_guest_affinity_batch(xyz, elements_or_coef, guest, temperatures, cavit
         jobs["map_level"] = int(level)
         jobs["map_first"] = 2 * np.concatenate([[0], np.cumsum(voxels)[:-1]]) if T else 0
         buf = np.zeros(2 * int(voxels.sum()))
-    out, levels, buf = engine.context(device).rigid_affinity(jobs, x.reshape(-1, 3), coef.reshape(-1, 3), np.asarray(g.offsets),
-                                                             d, 1.0 / (R * temps), words, maps=buf, kernel_ms=kernel_ms)
+    ctx, betas = engine.context(device), 1.0 / (R * temps)
+    if poses is None:
+        out, levels, buf = ctx.rigid_affinity(jobs, x.reshape(-1, 3), coef.reshape(-1, 3), np.asarray(g.offsets), d, betas, words,
+                                              maps=buf, kernel_ms=kernel_ms)
+    else:
+        out, levels, buf = ctx.rigid_body_affinity(jobs, x.reshape(-1, 3), coef.reshape(-1, 3), poses.reshape(-1, 3), betas, words,
+                                                   maps=buf, kernel_ms=kernel_ms)
     per_frame = None
     if maps:
         per_frame = [buf[int(f):int(f) + 2 * int(v)].reshape(-1, 2) for f, v in zip(jobs["map_first"], voxels)]
     return RigidAffinity(out, levels.reshape(T, len(temps)), temps, jobs["origin"].copy(), np.array(shape, dtype=np.int64),
                          spacing, d, g, closed, per_frame, int(level) if maps else -1, charged,
-                         None if frames is None else np.array(frames, dtype=np.int64).reshape(-1), charges_converged)
+                         None if frames is None else np.array(frames, dtype=np.int64).reshape(-1), charges_converged, rotations,
+                         poses)
+
+
+def _one(many: RigidAffinity) -> RigidAffinity:
+    """The only frame of a result over one frame."""
+    return dataclasses.replace(many, raw=many.raw[0], levels=many.levels[0], origin=many.origin[0], shape=many.shape[0],
+                               closed=None if many.closed is None else many.closed[0],
+                               maps=None if many.maps is None else many.maps[0], frames=None,
+                               charges_converged=None if many.charges_converged is None else many.charges_converged[0])
 
 
 def rigid_guest_affinity(xyz, elements_or_coef, guest, temperatures, cavity=None, grid=None, directions=None, charges=None,
@@ -345,9 +393,5 @@ def rigid_guest_affinity(xyz, elements_or_coef, guest, temperatures, cavity=None
     if x.ndim == 3:
         return rigid_guest_affinity_batch(x, elements_or_coef, guest, temperatures, cavity, grid, directions, charges, maps,
                                           level, core2, cutoff2, device)
-    many = rigid_guest_affinity_batch(x.reshape(1, -1, 3), elements_or_coef, guest, temperatures, cavity, grid, directions,
-                                      charges, maps, level, core2, cutoff2, device)
-    return RigidAffinity(many.raw[0], many.levels[0], many.temperatures, many.origin[0], many.shape[0], many.spacing,
-                         many.directions, many.guest, None if many.closed is None else many.closed[0],
-                         None if many.maps is None else many.maps[0], many.map_level, many.charged, None,
-                         None if many.charges_converged is None else many.charges_converged[0])
+    return _one(rigid_guest_affinity_batch(x.reshape(1, -1, 3), elements_or_coef, guest, temperatures, cavity, grid, directions,
+                                           charges, maps, level, core2, cutoff2, device))

@@ -44,7 +44,8 @@ from .affinity import _PER_BAR, R
 from .diffusion import Diffusion, _basins_jobs, _frame, _one as _one_diffusion, _run
 from .ewald import ewald_parameters, framework_charges
 from .percolation import _one as _one_percolation, _result as _percolation_result, plan_jobs
-from .rigid import COULOMB, M_DEFAULT, _guest, rigid_coefficients
+from .rigid import COULOMB, M_DEFAULT, _guest as _linear_guest, rigid_coefficients
+from .rigid_body import is_body
 from .surface import sphere_directions
 
 __all__ = ["RIGID_GUEST_MASSES", "RigidField", "rigid_guest_field", "rigid_guest_field_batch", "rigid_guest_percolation",
@@ -184,6 +185,14 @@ class RigidField:
         if self.charges_converged is not None:
             valid &= np.atleast_1d(np.asarray(self.charges_converged, dtype=bool))
         return values, valid
+
+
+def _guest(guest):
+    """The model of a linear guest.  A rigid body (:mod:`pywindow_amd.rigid_body`) is refused: the cell's proved atom
+    skip (pw_rigid_cell.hpp) states its reach for offsets along directions, not for pose tables."""
+    if is_body(guest):
+        raise ValueError("rigid_guest_field: rigid bodies are not built for the cell yet")
+    return _linear_guest(guest)
 
 
 def _free_energy(zbar, temperature):
@@ -354,6 +363,7 @@ def rigid_guest_field_batch(xyz, elements_or_coef, lattice, guest="CO2", tempera
     by HIP events; ``diagnostics``: a list that receives ``(n_pairs, instances)``.  ``charges`` ``(n,)`` or ``(T, n)``: the
     framework's point charges, one ``pw_rigid_cell_ewald`` call (``None``: ``pw_rigid_cell`` as before); ``"qeq-cell"``: ONE
     ``pw_charges_cell`` call over the same frames makes them first (:func:`_cell_charges`)."""
+    _guest(guest)                                                    # (a rigid body is refused before any charges are made)
     if charges is None:
         planned = plan_field(xyz, elements_or_coef, lattice, guest, temperatures, spacing, cutoff, core2, directions)
         return _field(planned, engine.context(device), spacing, frames, kernel_ms, diagnostics)

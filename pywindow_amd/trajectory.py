@@ -528,18 +528,28 @@ class DLPOLY:
                                        edges=edges, energies=energies, core2=0.25, device=device, frames=sel)
 
     def rigid_affinity(self, guest="CO2", temperatures=298.0, spacing: float = 0.5, frames=None, close="windows",
-                       directions=None, charges=None, device=None, swap_atoms=None, forcefield=None):
+                       directions=None, charges=None, device=None, swap_atoms=None, forcefield=None, rotations=None):
         """The orientation-averaged affinity of the cage for a rigid linear guest (N2, CO2, O2) in every frame analysed
         so far (``frames``: a selection of them): one ``pw_cavity`` call for the probe-0 cavities, seeded, boxed and
         closed exactly as :meth:`cavity`, then ALL frames in ONE ``pw_rigid_affinity`` call on the GPU
         (``pywindow_amd.rigid_guest_affinity_batch``, UFF atoms, ``core2 = 0.25``; ``charges``: the framework's partial
         charges, one set or one row a frame, ``"qeq"``: :meth:`charges` of the same frames, ``None``: no electrostatics) -- a :class:`pywindow_amd.RigidAffinity` whose fields are arrays over the
-        frames and whose ``frames`` are the trajectory's frame numbers.  Non-modular, non-periodic analyses only."""
+        frames and whose ``frames`` are the trajectory's frame numbers.  Non-modular, non-periodic analyses only.  A rigid
+        body -- a name of ``pywindow_amd.RIGID_BODIES`` (H2O, CH4, SF6) or a :class:`pywindow_amd.RigidBody` -- goes
+        through ONE ``pw_rigid_body_affinity`` call instead (``pywindow_amd.rigid_body_affinity_batch``), averaged over
+        ``rotations`` (``None``: ``pywindow_amd.rotation_set()``)."""
         from . import cavity as CV
         from . import rigid as RG
+        from . import rigid_body as RB
 
+        body = RB.is_body(guest)
+        if (directions is not None and body) or (rotations is not None and not body):
+            raise ValueError("rigid_affinity: directions for a linear guest, rotations for a rigid body")
         sel, coords, radii, seeds, half_widths, planes = self._cavity_inputs("rigid_affinity", frames, close, swap_atoms, forcefield)
         cav = CV.cavity_grid_batch(coords, radii, seeds, 0.0, spacing, half_widths, planes, True, device, frames=sel)
+        if body:
+            return RB.rigid_body_affinity_batch(coords, self.elements(swap_atoms, forcefield), guest, temperatures, cavity=cav,
+                                                rotations=rotations, charges=charges, core2=0.25, device=device, frames=sel)
         return RG.rigid_guest_affinity_batch(coords, self.elements(swap_atoms, forcefield), guest, temperatures, cavity=cav,
                                              directions=directions, charges=charges, core2=0.25, device=device, frames=sel)
 
